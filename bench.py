@@ -6,11 +6,20 @@ dequant+CfL+LLF+IDCT, Gaborish, EPF1, EPF2) over one synthetic 8192x8192 VarDCT 
 (BASELINE.json configs[2]) whose inputs -- 805 MB of i32 coefficients, the HfMetadata maps,
 the quantised LF, the dequant tables -- are resident in HBM before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--cpu-sample 8192]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--dump-outputs DIR] [--full] [--cpu-sample 8192]
 
-N > 1 (launched by torch.distributed.run, one rank per GPU) measures BOTH multi-GPU forms in one run:
-  * weak (the top-level `value`): frames are independent units, every rank reconstructs its own frame of the
-    same shape with no data-path collective; value = all ranks' pixels / max-over-ranks time;
+A plain run sets up, warms up with W steps, times exactly K steps (one repetition), writes the planes of its last step
+if --dump-outputs is given, and prints the result line; `roofline`, `cpu_baseline`, `e2e_pcie_inclusive`, `secondary`,
+`strong_scaling*` and the counter-traffic fractions are null there.  Everything else it measures runs with --full only
+(the timed region then repeated --reps times, default 5, median reported).
+
+--dump-outputs DIR: the three f32 planes of the last timed step (what jxlh_frame_read_planes hands a caller) as
+DIR/planes.npy (3 x H x W) when they fit in 64 MB, else a fixed, seeded sample of 2^21 positions (the same for every
+plane) as DIR/planes_sample.npy (3 x n) with the flat positions in DIR/planes_sample_index.npy (float64).
+
+With --full, N > 1 (launched by torch.distributed.run, one rank per GPU) measures BOTH multi-GPU forms in one run:
+  * weak (the top-level `value`, also in a plain run): frames are independent units, every rank reconstructs its own
+    frame of the same shape with no data-path collective; value = all ranks' pixels / max-over-ranks time;
   * strong (`strong_scaling`): ONE frame cut into bands of group rows, one band per rank -- transforms on the
     own band, halo exchange of the edge block rows (ncclSend/ncclRecv), filters, in-place ncclAllGather of
     the finished planes so that every rank holds the whole frame (the layout north_star describes).  The
@@ -19,7 +28,7 @@ N > 1 (launched by torch.distributed.run, one rank per GPU) measures BOTH multi-
     sharded legs have not come back after JXLH_BENCH_STRONG_TIMEOUT_S seconds (default 240) rank 0 prints the weak
     line with them marked as timed out and every rank leaves.
 
-Rank 0 prints ONE JSON line: metric/value/... + "roofline" (every kernel of the chain with its own
+Rank 0 prints ONE JSON line: metric/value/... and, with --full, + "roofline" (every kernel of the chain with its own
 algorithmic bytes and fraction, HIP-event timed on the kernels' own stream; the chain against the
 fused-ideal numerator; the all-blocks-filtered EPF population next to the spec one; measured copy
 ceilings) + "cpu_baseline" (the CPU oracle, a C port of the reference, on the same frame size).
@@ -474,6 +483,24 @@ def slot_content_sweep(jxl_rs_amd, synth, np, ectx, wl, size, steps, reps, cores
     return res
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_POSITIONS = 1 << 21
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_planes(planes, out_dir, np):
+    """--dump-outputs: the three f32 planes whole when they fit in DUMP_LIMIT_BYTES, else the same fixed, seeded sample
+    of positions from each (positions depend on the plane size only, so two builds' dumps compare value for value)."""
+    os.makedirs(out_dir, exist_ok=True)
+    planes = [np.ascontiguousarray(p, dtype=np.float32) for p in planes]
+    if sum(p.nbytes for p in planes) <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "planes.npy"), np.stack(planes))
+        return
+    idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, planes[0].size, DUMP_SAMPLE_POSITIONS))
+    np.save(os.path.join(out_dir, "planes_sample.npy"), np.stack([p.reshape(-1)[idx] for p in planes]))
+    np.save(os.path.join(out_dir, "planes_sample_index.npy"), idx.astype(np.float64))
+
+
 def usable_cores():
     """Host cores this process may actually use: the affinity mask capped by the container's CPU quota
     (cgroup v2 cpu.max / v1 cfs quota).  os.cpu_count() reports the machine (256 on the GPU boxes) while the
@@ -499,6 +526,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: timed-region repetitions, roofline / per-kernel "
+                         "tables, CPU baseline, PCIe-inclusive legs, secondary configs, the sharded legs of N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the planes of the last timed step (or a fixed, seeded sample of them) to DIR as .npy")
     ap.add_argument("--placement-trials", type=int, default=12,
                     help="candidate buffer placements a VarDCT context picks from at setup (jxlh_ctx_tune_placement); 1 = off")
     ap.add_argument("--size", type=int, default=8192)
@@ -506,21 +538,23 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the sharded-frame (strong scaling) leg")
     ap.add_argument("--strong-at-1", action="store_true",
-                    help="run the sharded-frame leg with a single rank too (validation of the RCCL path on a 1-GPU box; "
-                         "needs a torch.distributed.run launch)")
+                    help="with --full: run the sharded-frame leg with a single rank too (validation of the RCCL path on a "
+                         "1-GPU box; needs a torch.distributed.run launch)")
     ap.add_argument("--no-active", action="store_true",
                     help="skip the all-blocks-filtered EPF population (profiling runs: one population per kernel name)")
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip the PCIe-inclusive legs (pinned host coefficients -> finished planes)")
     ap.add_argument("--strip", action="store_true",
-                    help="also run the strip-kernel A/B block (roofline.strip_kernel; opt-in since round 6: a closed negative result)")
+                    help="with --full: also run the strip-kernel A/B block (roofline.strip_kernel; opt-in since round 6: a "
+                         "closed negative result)")
     ap.add_argument("--no-sweep", action="store_true",
                     help="skip e2e_pcie_inclusive.slot_form_content_sweep (outliers / density / one dense group on the slot form)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the `secondary` block (BASELINE configs 2, 4 and 5, one frame in flight each)")
-    ap.add_argument("--reps", type=int, default=5,
-                    help="repetitions of the timed region of K steps: `value` / `ms_per_step` are the MEDIAN repetition, "
-                         "min and max are reported beside it (boxes and runs differ by several per cent)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed region of K steps (default 1, with --full 5): `value` / `ms_per_step` "
+                         "are the MEDIAN repetition, min and max are reported beside it (boxes and runs differ by several "
+                         "per cent)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--inflight", type=int, default=2,
                     help="frames in flight per GPU (contexts with their own stream and buffers, used round-robin)")
@@ -533,11 +567,14 @@ def main():
     ap.add_argument("--mix", default="d1", choices=["d1", "dct8", "all"],
                     help="transform-type mix of the synthetic frame (d1 = BASELINE config 3)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
     PLACEMENT_TRIALS[0] = max(1, args.placement_trials)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: one rank per GPU under torch.distributed.run (what the driver's command
-        # line does explicitly).  Never a silent single-rank measurement labelled N.
+        # line does explicitly), in a child process: this one has opened the runtime to count the devices.  Never a
+        # silent single-rank measurement labelled N.
         import torch
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
         if have < args.gpus:
@@ -549,7 +586,8 @@ def main():
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.exit(subprocess.call(cmd))
 
     import numpy as np
     import torch
@@ -627,8 +665,8 @@ def main():
         return float(t.item())
 
     # ---- weak leg (N = 1: THE measurement): K steps of whole frames, one frame per rank; the timed region is
-    # repeated --reps times (barrier + synchronize on both sides of each, max over ranks of each) and the MEDIAN
-    # repetition is what `value` / `ms_per_step` report
+    # repeated --reps times (once in a plain run; barrier + synchronize on both sides of each, max over ranks of each)
+    # and the MEDIAN repetition is what `value` / `ms_per_step` report
     for _ in range(args.warmup):
         step()
     sync_all()
@@ -653,7 +691,13 @@ def main():
     ev_ms = rep_ev[mid]
     value = size * size * n_gpus / 1e6 / (ms_per_step / 1e3)
 
-    chain_bytes, chain_file = chain_traffic("8192 d1") if size == 8192 and args.mix == "d1" else (None, None)
+    if args.dump_outputs and rank == 0:
+        # the planes of the last timed step, read from the context that ran it (outside every timed region)
+        dump_planes(ctxs[(step_no[0] - 1) % len(ctxs)].read_planes(), args.dump_outputs, np)
+
+    full = args.full
+    chain_bytes, chain_file = (chain_traffic("8192 d1") if full and size == 8192 and args.mix == "d1"
+                               else (None, None))
 
     def result_line(strong, strong_modular, roofline, cpu, e2e, secondary):
         return {
@@ -703,7 +747,7 @@ def main():
     # seconds (a rank that failed, a transport that hangs), rank 0 prints the weak line with the legs marked as timed
     # out and every rank leaves -- the driver gets its line instead of a hung job.
     watchdog = None
-    if (world > 1 or (args.strong_at_1 and dist is not None)) and not args.no_strong:
+    if full and (world > 1 or (args.strong_at_1 and dist is not None)) and not args.no_strong:
         import threading
         limit_s = float(os.environ.get("JXLH_BENCH_STRONG_TIMEOUT_S", "240"))
 
@@ -719,7 +763,7 @@ def main():
 
     # ---- strong leg (N > 1): one frame sharded by bands of group rows, halo exchange + all-gather in the timed region
     strong = None
-    if (world > 1 or (args.strong_at_1 and dist is not None)) and not args.no_strong:
+    if full and (world > 1 or (args.strong_at_1 and dist is not None)) and not args.no_strong:
         try:
             from jxl_rs_amd import lib as jl
             swl = wl if rank == 0 else synth.make_vardct(size, size, mix=mix, seed=args.seed, unique_groups=24,
@@ -857,7 +901,7 @@ def main():
     # all-gather"): the squeeze chain replicated on every rank (its recurrence is serial along whole lines), the RCT
     # and the palette expansion on the rank's own sample share, six in-place all-gathers over the library's communicator
     strong_modular = None
-    if (world > 1 or (args.strong_at_1 and dist is not None)) and not args.no_strong:
+    if full and (world > 1 or (args.strong_at_1 and dist is not None)) and not args.no_strong:
         try:
             from jxl_rs_amd import lib as jl
             from jxl_rs_amd.modular import ModularChain
@@ -906,7 +950,7 @@ def main():
 
     # ---- per-kernel HIP-event timing (separate steps; not part of the timed region)
     roofline = None
-    if rank == 0:
+    if rank == 0 and full:
         npx = size * size
 
         def kernel_table():
@@ -1069,7 +1113,7 @@ def main():
 
     # ---- CPU baseline: the oracle (C port of the reference path) on the same frame size
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu:  # reported baseline: single-GPU runs only
+    if rank == 0 and n_gpus == 1 and full and not args.no_cpu:  # reported baseline: single-GPU runs only
         from oracle.oracle import Oracle
         o = Oracle(fused=True)
         cs = min(args.cpu_sample, size)
@@ -1129,7 +1173,7 @@ def main():
     # beside `value`, never as `value`.  Two transports: the reference's dense i32 slabs
     # (jxlh_submit_group) and (position, value) pairs (jxlh_submit_groups_sparse).
     e2e = None
-    if rank == 0 and n_gpus == 1 and not args.no_e2e and torch.cuda.is_available():
+    if rank == 0 and n_gpus == 1 and full and not args.no_e2e and torch.cuda.is_available():
         e2e = {}
         ng = wl.coeffs.shape[0]
         # slot streams per context: the slot-bucketed legs (and the resident ones) run on contexts with ONE, the older
@@ -1507,7 +1551,7 @@ def main():
     # ---- the other BASELINE configurations, driver-visible: config 2 (4096^2, EPF off), config 4 (Modular 8192^2),
     # config 5 (16384^2, all 27 types; + epf_iters = 3).  Not `value`: one frame in flight each, a few steps.
     secondary = None
-    if rank == 0 and n_gpus == 1 and not args.no_secondary and torch.cuda.is_available():
+    if rank == 0 and n_gpus == 1 and full and not args.no_secondary and torch.cuda.is_available():
         secondary = {}
         for key, fn in (
                 ("config2_4096_d1_epf0", lambda: time_vardct_config(jxl_rs_amd, synth, np, local_rank, 4096, synth.MIX_D1, 0,

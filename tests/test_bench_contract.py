@@ -46,6 +46,33 @@ def test_chain_traffic_resolves_for_both_resident_forms():
     assert b.chain_traffic("no such workload") == (None, None)
 
 
+def test_dump_outputs_stays_under_64_mb_and_samples_the_same_positions(tmp_path):
+    """--dump-outputs: planes too large for 64 MB are written as a fixed, seeded sample of positions, identical from run
+    to run; small planes whole"""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(1)
+    big = [rng.random((2400, 2400), dtype=np.float32) for _ in range(3)]
+    dumps = []
+    for run in ("a", "b"):
+        b.dump_planes(big, str(tmp_path / run), np)
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["planes_sample.npy", "planes_sample_index.npy"], files
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64_000_000
+        dumps.append([np.load(tmp_path / run / f) for f in files])
+    sample, idx = dumps[0]
+    assert sample.dtype == np.float32 and idx.dtype == np.float64 and sample.shape == (3, idx.size) > (3, 1 << 20)
+    assert np.array_equal(idx, dumps[1][1]) and np.array_equal(sample, dumps[1][0])
+    pos = idx.astype(np.int64)
+    assert np.all(np.diff(pos) > 0) and pos[0] >= 0 and pos[-1] < 2400 * 2400
+    for c in range(3):
+        assert np.array_equal(sample[c], big[c].reshape(-1)[pos])
+    small = [p[:512, :640] for p in big]
+    b.dump_planes(small, str(tmp_path / "small"), np)
+    assert os.listdir(tmp_path / "small") == ["planes.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "planes.npy"), np.stack(small))
+
+
 def test_gpus_n_without_devices_refuses_instead_of_measuring_one_rank():
     """`python bench.py --gpus 2` on a box without two devices must die naming what is missing, not
     print an n_gpus: 1 line"""

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 modes=${MODES:-"spec passthrough"}
 for lib in jxl_rs_amd/libjxl_hip.so $(ls jxl_rs_amd/variants/*.so 2>/dev/null); do
   for m in $modes; do
-    JXLH_LIBRARY=$PWD/$lib timeout 200 python bench.py --no-cpu --inflight 1 --epf $m ${BENCH_ARGS} 2>&1 | tail -1 | python -c "
+    JXLH_LIBRARY=$PWD/$lib timeout 200 python bench.py --full --no-cpu --inflight 1 --epf $m ${BENCH_ARGS} 2>&1 | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['roofline']['all_kernels_ms_per_step']
