@@ -53,6 +53,15 @@ jxlh_status jxlh_frame_path(jxlh_ctx* ctx, int32_t* strip, int32_t* tiles, int32
  * (29 for everything).  Synchronises the context's stream. */
 jxlh_status jxlh_frame_k1_counters(jxlh_ctx* ctx, int32_t* out, int32_t n);
 
+/* Layout of the transform stage's work-list memory for a frame of xblocks x yblocks 8x8 blocks (host only: no context,
+ * no device).  out[0] = bytes allocated; out[1 + 2 r], out[2 + 2 r] = byte offset and length of region r, in memory
+ * order: the two counter sets; the lists of the 11 transform classes (DCT8, 16x8, 8x16, 16x16, 32x8, 8x32, 32x16, 16x32,
+ * 32x32, special, large; 16 bytes per varblock); the entry side items, then the dense-route lists, of the 9 DCT classes
+ * (16 bytes each); the fallback flag words of the 9 DCT classes (4 bytes per batch); the fallback launch's summary
+ * words; the large transforms' unit lists; their LLF planes (3 x nblocks floats).  n = values `out` holds (85 for
+ * everything). */
+jxlh_status jxlh_worklist_layout(int32_t xblocks, int32_t yblocks, uint64_t* out, int32_t n);
+
 /* Device self-test of the EPF weight normalisation: the filters compute 1/(1 + sum of weights)
  * (epf0.rs:208, epf1.rs:140, epf2.rs:130 divide) with rcp + two FMA refinement steps.  Counts the
  * floats whose bit pattern lies in [lo_bits, hi_bits) for which that differs from the IEEE

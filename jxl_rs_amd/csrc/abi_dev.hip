@@ -52,6 +52,19 @@ jxlh_status jxlh_kernel_timing_reset(jxlh_ctx* ctx) {
   return JXLH_OK;
 }
 
+jxlh_status jxlh_worklist_layout(int32_t xblocks, int32_t yblocks, uint64_t* out, int32_t n) {
+  if (xblocks <= 0 || yblocks <= 0 || !out || n < 0) return JXLH_ERR_INVALID_ARGUMENT;
+  const WorklistLayout L = vardct_worklist_layout((size_t)xblocks * (size_t)yblocks);
+  uint64_t v[1 + 2 * kWlRegions];
+  v[0] = L.bytes;
+  for (int r = 0; r < kWlRegions; r++) {
+    v[1 + 2 * r] = L.off[r];
+    v[2 + 2 * r] = L.len[r];
+  }
+  for (int i = 0; i < n && i < 1 + 2 * kWlRegions; i++) out[i] = v[i];
+  return JXLH_OK;
+}
+
 jxlh_status jxlh_frame_path(jxlh_ctx* ctx, int32_t* strip, int32_t* tiles, int32_t* tiles_by_class_kernels) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;

@@ -401,7 +401,17 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   if ((st = ensure(ctx, ctx->ytox, ncmap)) != JXLH_OK) return st;
   if ((st = ensure(ctx, ctx->ytob, ncmap)) != JXLH_OK) return st;
   if ((st = ensure(ctx, ctx->error_flag, 1)) != JXLH_OK) return st;
-  if ((st = ensure(ctx, ctx->worklist, vardct_worklist_bytes(f))) != JXLH_OK) return st;
+  {
+    // a new allocation starts out as whatever the memory held, and a new layout puts the fallback flags on bytes of other
+    // regions: either could equal a launch's epoch (launch_vardct_groups)
+    const uint8_t* const wl_p = ctx->worklist.p;
+    const size_t wl_n = ctx->worklist.n;
+    if ((st = ensure(ctx, ctx->worklist, vardct_worklist_bytes(f))) != JXLH_OK) return st;
+    if (ctx->worklist.p != wl_p || ctx->worklist.n != wl_n || ctx->worklist_nblocks != nblocks) {
+      vardct_worklist_clear_flags(ctx->stream, ctx->worklist.p, nblocks);
+      ctx->worklist_nblocks = nblocks;
+    }
+  }
   vardct_worklist_reset(ctx->stream, ctx->worklist.p, &ctx->k1_launches);
   HIPCHK(ctx, hipMemsetAsync(ctx->error_flag.p, 0, sizeof(int), ctx->stream));
   // rects the caller never sets read as "not the first block of a varblock" (no work item, no stale map bytes of

@@ -234,6 +234,23 @@ void launch_check_tables(hipStream_t s, const float* tables, size_t n, int* ok);
 // other set for launch n + 1 (whose last readers, the kernels of launch n - 1, are behind it in stream order) -- no
 // memset launch inside K1's serial sequence.  *launch_parity is the caller's per-context launch counter.
 size_t vardct_worklist_bytes(const FrameDev& f);
+// The work-list memory's layout for a frame of nblocks 8x8 blocks, the one source of both its size and its carve: byte
+// offset and length of every region from the start of the allocation, in memory order (kWlCounts: the two counter
+// sets; then the 11 class lists, the entry side items and the dense-route lists of the 9 DCT classes, the fallback flag
+// words of those classes, the fallback launch's summary words, the large transforms' unit lists and their LLF planes,
+// the last aligned to 64 bytes), and the bytes to allocate.
+enum : int {
+  kWlCounts = 0, kWlItems0 = 1, kWlEItems0 = kWlItems0 + 11, kWlDItems0 = kWlEItems0 + 9, kWlFallback0 = kWlDItems0 + 9,
+  kWlFbAny = kWlFallback0 + 9, kWlLargeUnits, kWlLlf, kWlRegions
+};
+struct WorklistLayout {
+  size_t off[kWlRegions], len[kWlRegions];
+  size_t bytes;
+};
+WorklistLayout vardct_worklist_layout(size_t nblocks);
+// zero the fallback flag words and the summary words (a fresh allocation, or a layout that moved them onto bytes other
+// regions wrote)
+void vardct_worklist_clear_flags(hipStream_t s, void* worklist_mem, size_t nblocks);
 void vardct_worklist_reset(hipStream_t s, void* worklist_mem, uint32_t* launch_parity);
 // the counter set launch number `launch` counted in: *bytes = its size, *lines = counters in it (one per `*bytes / *lines`)
 const void* vardct_worklist_counters(const void* worklist_mem, uint32_t launch, size_t* bytes, int* lines);

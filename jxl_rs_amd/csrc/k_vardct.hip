@@ -627,9 +627,10 @@ __device__ __forceinline__ void direct_stage_channel(const FrameDev& f, float* _
   for (int k = 0; k < D; k++) {
     if (sum[k] != kClaimed) {
       // dequant_lane (group.rs:100-133) for one coefficient, the operations of dequant4t
-      const int q = sum[k], aq = q < 0 ? -q : q;
-      float am = adj->v[CH][min(aq, kAdjN - 1)];
-      if (aq >= kAdjN)
+      const int q = sum[k];
+      const uint32_t aq = wrapping_abs(q);
+      float am = adj->v[CH][min(aq, (uint32_t)kAdjN - 1u)];
+      if (aq >= (uint32_t)kAdjN)
         am = __uint_as_float(__float_as_uint(adjust_quant_bias(q, f.quant_biases[CH], f.quant_biases[3])) ^ ((uint32_t)q & 0x80000000u));
       const float a = __uint_as_float(__float_as_uint(am) ^ ((uint32_t)q & 0x80000000u));
       const float mul = w[k] * sd;
@@ -673,7 +674,7 @@ __device__ __forceinline__ int4 tile_q4(const float* __restrict__ buf, int b, in
 // in the reference's slab, frame/group.rs:521-524), so the loads are skipped and read as zero, and nothing is stored.
 // SPARSE: 0 = dense slabs, 1 = bucketed pair words + slot tables (sp_sorted), 2 = slot-bucketed entries in place (se_*)
 // with the dense dequantisation pass, 3 = the same input, direct path only: batches it cannot take are flagged in
-// WorkLists::fallback[class] (one word per batch, written with the launch's epoch: no atomics, nothing to clear) and the
+// WorkLists::fallback[class] (one word per batch, written with the launch's epoch: no atomics, no clear per launch) and the
 // fallback launch (LISTED) runs the flagged ones through mode 2.  CLS: the class id.
 // INLINE_FB (mode 3): a batch the direct path cannot take runs through the dense dequantisation pass right here instead
 // of going to the fallback list -- for the 8x8 class, whose generic body costs a handful of registers: a frame denser
@@ -1378,19 +1379,44 @@ static size_t large_unit_capacity(size_t nblocks) { return nblocks / 8 + 64; }
 void launch_vardct_large(hipStream_t s, const FrameDev& f, const WorkLists& wl, int nblk, uint32_t* large_units,
                          size_t unit_capacity, size_t nblocks);
 
+static_assert(kWlEItems0 - kWlItems0 == kNumClasses && kWlDItems0 - kWlEItems0 == kClsSpecial &&
+              kWlFallback0 - kWlDItems0 == kClsSpecial && kWlFbAny - kWlFallback0 == kClsSpecial, "work-list regions");
+
+WorklistLayout vardct_worklist_layout(size_t nblocks) {
+  WorklistLayout L{};
+  size_t p = 0;
+  auto put = [&](int r, size_t len) {
+    L.off[r] = p;
+    L.len[r] = len;
+    p += len;
+  };
+  put(kWlCounts, 2 * kCountBytes);  // two sets of counters, one 128-byte line each
+  for (int c = 0; c < kNumClasses; c++) put(kWlItems0 + c, (nblocks / class_min_area(c) + 1) * sizeof(WorkItem));
+  // entry side items of the DCT classes + their dense-route lists
+  for (int c = 0; c < kClsSpecial; c++) put(kWlEItems0 + c, (nblocks / class_min_area(c) + 1) * sizeof(EntryItem));
+  for (int c = 0; c < kClsSpecial; c++) put(kWlDItems0 + c, (nblocks / class_min_area(c) + 1) * sizeof(WorkItem));
+  // the fallback flags: one word per batch of the class (at least 2 varblocks per batch)
+  for (int c = 0; c < kClsSpecial; c++) put(kWlFallback0 + c, (nblocks / (2 * class_min_area(c)) + 16) * sizeof(uint32_t));
+  put(kWlFbAny, (size_t)kFbAny * kFbAnyPitch * sizeof(uint32_t));  // the fallback launch's summary words
+  // the unit lists of the large transforms: one u32 per 4096 samples of a 256-pixel varblock (two-pass units) and one
+  // per varblock of the smaller types (three lists by slabs per channel; worst case one entry per 32 blocks)
+  put(kWlLargeUnits, large_unit_capacity(nblocks) * sizeof(uint32_t));
+  // the LLF planes of the large transforms (3 x nblocks floats, k1_large_llf): launch_vardct_large aligns their pointer
+  // to 64 bytes, which is this offset on a hipMalloc'ed (256-byte aligned) base
+  p = (p + 63) & ~(size_t)63;
+  put(kWlLlf, 3 * nblocks * sizeof(float));
+  L.bytes = p;
+  return L;
+}
+
 size_t vardct_worklist_bytes(const FrameDev& f) {
-  const size_t nblocks = (size_t)f.xblocks * f.yblocks;
-  size_t items = 0;
-  for (int c = 0; c < kNumClasses; c++) items += nblocks / class_min_area(c) + 1;
-  for (int c = 0; c < kClsSpecial; c++) items += 2 * (nblocks / class_min_area(c) + 1);  // entry side items of the DCT
-                                                                                         // classes + their dense-route lists
-  for (int c = 0; c < kClsSpecial; c++) items += nblocks / (8 * class_min_area(c)) + 4;  // the fallback flags (u32 per batch)
-  // + the unit lists of the large transforms: one u32 per 4096 samples of a 256-pixel varblock (two-pass units) and
-  //   one per varblock of the smaller types (three lists by slabs per channel; worst case one entry per 32 blocks)
-  // + the LLF planes of the large transforms (3 x nblocks floats, k1_large_llf)
-  // + the fallback launch's summary words
-  return items * sizeof(WorkItem) + 2 * kCountBytes + large_unit_capacity(nblocks) * sizeof(uint32_t) + 64 +
-         3 * nblocks * sizeof(float) + (size_t)kFbAny * kFbAnyPitch * sizeof(uint32_t);
+  return vardct_worklist_layout((size_t)f.xblocks * f.yblocks).bytes;
+}
+
+void vardct_worklist_clear_flags(hipStream_t s, void* worklist_mem, size_t nblocks) {
+  const WorklistLayout L = vardct_worklist_layout(nblocks);
+  (void)hipMemsetAsync(reinterpret_cast<char*>(worklist_mem) + L.off[kWlFallback0], 0,
+                       L.off[kWlFbAny] + L.len[kWlFbAny] - L.off[kWlFallback0], s);
 }
 
 void vardct_worklist_reset(hipStream_t s, void* worklist_mem, uint32_t* launch_parity) {
@@ -1412,40 +1438,29 @@ void launch_vardct_groups(hipStream_t s, const FrameDev& f_in, int group_row0, i
   const int ngroups = group_list ? n_list : (group_row1 - group_row0) * f_in.xgroups;
   if (ngroups <= 0) return;
   // The value that flags a batch for the fallback launch: unique per launch across the process, never 0.  The flag words
-  // are never cleared and start out as whatever the allocation held: a word that happens to equal the epoch sends an
-  // already reconstructed batch through the dense pass once more, which writes the same pixels (the two passes are
-  // bit-identical, tests/test_gpu_parity.py) behind the direct kernel in stream order.
+  // are zeroed when the work list is allocated or its layout moves (vardct_worklist_clear_flags), so a stale word holds an
+  // earlier launch's epoch and never this one's.
   static std::atomic<uint32_t> epoch_counter{0};
   FrameDev f = f_in;
   uint32_t epoch = ++epoch_counter;
   if (epoch == 0) epoch = ++epoch_counter;
   f.fb_epoch = (int)epoch;
-  // carve the work-list memory: [two sets of counters, one 128-byte line each] [class 0 items] [class 1 items] ...
+  // carve the work-list memory (vardct_worklist_layout): [two sets of counters, one 128-byte line each] [class 0 items] ...
   WorkLists wl;
   const uint32_t set = (*launch_parity)++ & 1u;
   wl.counts = reinterpret_cast<int*>(reinterpret_cast<char*>(worklist_mem) + set * kCountBytes);
   int* next_counts = reinterpret_cast<int*>(reinterpret_cast<char*>(worklist_mem) + (set ^ 1u) * kCountBytes);
-  char* p = reinterpret_cast<char*>(worklist_mem) + 2 * kCountBytes;
+  char* const base = reinterpret_cast<char*>(worklist_mem);
   const size_t nblocks = (size_t)f.xblocks * f.yblocks;
-  for (int c = 0; c < kNumClasses; c++) {
-    wl.items[c] = reinterpret_cast<WorkItem*>(p);
-    p += (nblocks / class_min_area(c) + 1) * sizeof(WorkItem);
-  }
+  const WorklistLayout L = vardct_worklist_layout(nblocks);
+  for (int c = 0; c < kNumClasses; c++) wl.items[c] = reinterpret_cast<WorkItem*>(base + L.off[kWlItems0 + c]);
   for (int c = 0; c < kClsSpecial; c++) {
-    wl.eitems[c] = reinterpret_cast<EntryItem*>(p);
-    p += (nblocks / class_min_area(c) + 1) * sizeof(EntryItem);
+    wl.eitems[c] = reinterpret_cast<EntryItem*>(base + L.off[kWlEItems0 + c]);
+    wl.ditems[c] = reinterpret_cast<WorkItem*>(base + L.off[kWlDItems0 + c]);
+    wl.fallback[c] = reinterpret_cast<uint32_t*>(base + L.off[kWlFallback0 + c]);
   }
-  for (int c = 0; c < kClsSpecial; c++) {
-    wl.ditems[c] = reinterpret_cast<WorkItem*>(p);
-    p += (nblocks / class_min_area(c) + 1) * sizeof(WorkItem);
-  }
-  for (int c = 0; c < kClsSpecial; c++) {  // one word per batch of the class (at least 2 varblocks per batch)
-    wl.fallback[c] = reinterpret_cast<uint32_t*>(p);
-    p += (nblocks / (2 * class_min_area(c)) + 16) * sizeof(uint32_t);
-  }
-  wl.fb_any = reinterpret_cast<uint32_t*>(p);
-  p += (size_t)kFbAny * kFbAnyPitch * sizeof(uint32_t);
-  uint32_t* large_units = reinterpret_cast<uint32_t*>(p);  // behind the last list
+  wl.fb_any = reinterpret_cast<uint32_t*>(base + L.off[kWlFbAny]);
+  uint32_t* large_units = reinterpret_cast<uint32_t*>(base + L.off[kWlLargeUnits]);  // behind the last list
   const dim3 gscan((ngroups + kScanGroups - 1) / kScanGroups);
   if (f.strip_desc)
     hipLaunchKernelGGL(k1_scan<true>, gscan, dim3(kScanThreads), 0, s, f, wl, group_row0, error_flag, group_list, ngroups,

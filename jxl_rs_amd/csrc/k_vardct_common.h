@@ -105,7 +105,7 @@ struct WorkLists {
   uint32_t* fb_any;                 // kFbAny summary words (kFbAnyPitch apart): == fb_epoch = some batch was left
   uint32_t* fallback[kClsSpecial];  // entries form, direct kernels: per class one word per batch; == FrameDev::fb_epoch
                                     // of the launch = left to the fallback launch (varblocks with more entries than a
-                                    // lane holds, raw_quant == 0).  Never cleared: see launch_vardct_groups.
+                                    // lane holds, raw_quant == 0).  Zeroed with the allocation: see launch_vardct_groups.
   int* counts;  // kCountLines counters at kCountPitch ints, zeroed before k1_scan: the classes, then the large
                 // transforms' unit lists (k_vardct_large.hip: two-pass slab units, fused lists of 1 / 2 / 4 slabs)
 };
@@ -143,11 +143,15 @@ __device__ __forceinline__ void decode_item(const FrameDev& f, const WorkItem& i
   bi->b_cc = f.base_b + (float)(int8_t)((it.cc >> 8) & 0xffu) / f.color_factor;
 }
 
-// group.rs:85-96
+// |q| as the reference's I32Vec::abs computes it, wrapping (i32::abs of the scalar release build, _mm_abs_epi32,
+// _mm256_abs_epi32, _mm512_abs_epi32, vabsq_s32): i32::MIN stays 0x80000000, every other value its magnitude
+__device__ __forceinline__ uint32_t wrapping_abs(int q) { return q < 0 ? 0u - (uint32_t)q : (uint32_t)q; }
+
+// group.rs:85-96: the bias branch when 2 > quant_i.abs() as an i32 -- q in {-1, 0, 1} and i32::MIN
 __device__ __forceinline__ float adjust_quant_bias(int q, float bias_c, float bias3) {
   const float quant = (float)q;
   const float adjusted = quant - bias3 / quant;
-  return (q > -2 && q < 2) ? quant * bias_c : adjusted;
+  return (int)wrapping_abs(q) < 2 ? quant * bias_c : adjusted;
 }
 
 // Dequantise four consecutive coefficients of channel CH (0 = X, 1 = Y, 2 = B); dy = the
@@ -219,18 +223,19 @@ __device__ __forceinline__ float4 dequant4t(const FrameDev& f, const int4 q, con
   if constexpr (CH == 2) sd = bi.sdy * f.b_dm;
   const int qq[4] = {q.x, q.y, q.z, q.w};
   const float tt[4] = {t.x, t.y, t.z, t.w};
-  int aq[4];
+  // (unsigned magnitudes: i32::MIN clamps to the table's last entry and takes the expression below, like any |q| >= kAdjN)
+  uint32_t aq[4];
   float am[4];
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    aq[i] = qq[i] < 0 ? -qq[i] : qq[i];
-    am[i] = tab[min(aq[i], kAdjN - 1)];
+    aq[i] = wrapping_abs(qq[i]);
+    am[i] = tab[min(aq[i], (uint32_t)kAdjN - 1u)];
   }
   // kAdjN is a power of two: the OR of the four magnitudes is below it iff each is
-  if (__builtin_expect(nofast || __any(((uint32_t)aq[0] | (uint32_t)aq[1] | (uint32_t)aq[2] | (uint32_t)aq[3]) >= (uint32_t)kAdjN), 0)) {
+  if (__builtin_expect(nofast || __any((aq[0] | aq[1] | aq[2] | aq[3]) >= (uint32_t)kAdjN), 0)) {
 #pragma unroll
     for (int i = 0; i < 4; i++)
-      if (nofast || aq[i] >= kAdjN)
+      if (nofast || aq[i] >= (uint32_t)kAdjN)
         am[i] = __uint_as_float(__float_as_uint(adjust_quant_bias(qq[i], f.quant_biases[CH], f.quant_biases[3])) ^
                                 ((uint32_t)qq[i] & 0x80000000u));
   }

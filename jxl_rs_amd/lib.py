@@ -64,7 +64,7 @@ ABI_SYMBOLS = [
 DEV_SYMBOLS = [
     "jxlh_timer_start", "jxlh_timer_stop", "jxlh_kernel_timing_enable", "jxlh_kernel_timing_get",
     "jxlh_kernel_timing_reset", "jxlh_selftest_recip", "jxlh_probe_copy_bandwidth", "jxlh_frame_path",
-    "jxlh_flow_profile", "jxlh_frame_k1_counters", "jxlh_probe_placement",
+    "jxlh_flow_profile", "jxlh_frame_k1_counters", "jxlh_probe_placement", "jxlh_worklist_layout",
 ]
 
 
@@ -263,6 +263,20 @@ def load():
         getattr(L, name).argtypes = [i32]
         getattr(L, name).restype = i32
     return L
+
+
+WORKLIST_REGIONS = 42  # jxlh_worklist_layout: counters, 11 class lists, 9 + 9 + 9 DCT-class regions, fb_any, units, LLF
+
+
+def worklist_layout(xblocks, yblocks):
+    """jxlh_worklist_layout (jxl_hip_dev.h, host only): (bytes allocated, [(offset, length)] of the 42 regions of the
+    transform stage's work-list memory in memory order)"""
+    L = _lib()
+    out = np.zeros(1 + 2 * WORKLIST_REGIONS, np.uint64)
+    st = L.jxlh_worklist_layout(C.c_int32(xblocks), C.c_int32(yblocks), _addr(out), C.c_int32(out.size))
+    if st != 0:
+        raise JxlHipError(st, "worklist_layout")
+    return int(out[0]), [(int(out[1 + 2 * r]), int(out[2 + 2 * r])) for r in range(WORKLIST_REGIONS)]
 
 
 def host_pack_slots(group_coeffs, group_id=0, bits12=False, entries=None, slot_counts=None, wide_capacity=4096):

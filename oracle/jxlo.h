@@ -124,6 +124,9 @@ void jxlo_adaptive_lf_smoothing(const JxloFrameParams* p, const float* const in[
 /* K3sigma SigmaSource::new (features/epf.rs:35-87): inv-sigma image, stride = xsize_blocks */
 void jxlo_sigma_map(const JxloFrameParams* p, const int32_t* raw_quant, const uint8_t* epf_map,
                     float* inv_sigma);
+/* adjust_quant_bias of channel c (0 = X, 1 = Y, 2 = B) for n quantised values (frame/group.rs:85-96): what K1
+ * multiplies by the dequant weight.  biases: the four quant biases of the frame. */
+void jxlo_adjust_quant_bias(const int32_t* q, size_t n, int c, const float biases[4], float* out);
 /* K1 dequant + LLF + IDCT for one group (frame/group.rs:85-253, :454-613).
  * coeffs: 3 * group_dim^2 i32 (X,Y,B), varblocks back to back.
  * maps are whole-frame, stride xsize_blocks (cmap stride = ceil(xsize_blocks/8)).

@@ -174,8 +174,15 @@ void jxlo_sigma_map(const JxloFrameParams* p, const int32_t* raw_quant, const ui
 /* ---------------- K1 ---------------- */
 static inline float adjust_quant_bias(int32_t q, float bias_c, float bias3) { /* group.rs:85-96 */
   const float quant = (float)q;
-  if ((q < 0 ? -q : q) < 2) return quant * bias_c;
+  /* 2 > quant_i.abs(): the reference's abs wraps (scalar release build, SSE4.2 / AVX2 / AVX-512 / NEON), so
+   * i32::MIN, whose abs is itself, takes the bias branch like -1, 0 and 1.  (-q on i32::MIN would be UB here.) */
+  const uint32_t aq = q < 0 ? 0u - (uint32_t)q : (uint32_t)q;
+  if (aq < 2u || aq == 0x80000000u) return quant * bias_c;
   return quant - bias3 / quant;
+}
+
+void jxlo_adjust_quant_bias(const int32_t* q, size_t n, int c, const float biases[4], float* out) {
+  for (size_t i = 0; i < n; i++) out[i] = adjust_quant_bias(q[i], biases[c], biases[3]);
 }
 
 void jxlo_decode_group(const JxloFrameParams* p, int group, const int32_t* coeffs,

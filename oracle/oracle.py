@@ -105,6 +105,8 @@ class Oracle:
         pf3 = C.POINTER(fp)
         L.jxlo_adaptive_lf_smoothing.argtypes = [C.POINTER(FrameParams), pf3, C.c_int, C.c_int, pf3]
         L.jxlo_sigma_map.argtypes = [C.POINTER(FrameParams), ip, C.POINTER(C.c_uint8), fp]
+        L.jxlo_adjust_quant_bias.argtypes = [ip, C.c_size_t, C.c_int, fp, fp]
+        L.jxlo_adjust_quant_bias.restype = None
         L.jxlo_decode_group.argtypes = [C.POINTER(FrameParams), C.c_int, ip, C.POINTER(C.c_uint8), ip,
                                         C.POINTER(C.c_int8), C.POINTER(C.c_int8), pf3, pf3, pf3, C.c_size_t]
         L.jxlo_gaborish.argtypes = [fp, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_float, fp]
@@ -298,6 +300,14 @@ class Oracle:
         em = np.ascontiguousarray(epf_map, dtype=np.uint8)
         out = np.zeros(rq.shape, dtype=np.float32)
         self.lib.jxlo_sigma_map(C.byref(p), _ptr(rq, C.c_int32), _ptr(em, C.c_uint8), _ptr(out, C.c_float))
+        return out
+
+    def adjust_quant_bias(self, q, c, biases):
+        """adjust_quant_bias (group.rs:85-96) of channel c for every value of q, with the frame's four quant biases"""
+        q = np.ascontiguousarray(q, dtype=np.int32)
+        b = _f32(biases)
+        out = np.empty(q.shape, np.float32)
+        self.lib.jxlo_adjust_quant_bias(_ptr(q, C.c_int32), q.size, c, _ptr(b, C.c_float), _ptr(out, C.c_float))
         return out
 
     def decode_group(self, p, group, coeffs, transform_map, raw_quant, ytox, ytob, lf, tables, planes):

@@ -1089,8 +1089,21 @@ def test_epf_fast_reciprocal_is_ieee_exact_on_weight_range():
 
 
 # ---------------------------------------------------------------- sparse coefficient transport
+def _dense_equals_oracle(planes, wl, coeffs=None):
+    """the dense submission's planes a sparse form is compared with are the oracle's, bit for bit"""
+    import copy
+    from oracle.oracle import Oracle
+    w2 = copy.copy(wl)
+    if coeffs is not None:
+        w2.coeffs = coeffs
+    want, _ = run_oracle_frame(Oracle(fused=True), w2)
+    for c in range(3):
+        assert bit_equal(planes[c], want[c]), f"dense submission vs oracle, plane {c}: {diff_report(planes[c], want[c])}"
+
+
 def _sparse_frame_equals_dense(ctx, wl, mutate=None, frame_flags=0):
-    """Runs the frame twice -- dense submit vs sparse submit -- and checks identical planes."""
+    """Runs the frame twice -- dense submit vs sparse submit -- and checks identical planes (the dense ones equal to
+    the oracle's)."""
     from jxl_rs_amd import synth
     coeffs = wl.coeffs.copy()
     if mutate is not None:
@@ -1129,6 +1142,7 @@ def _sparse_frame_equals_dense(ctx, wl, mutate=None, frame_flags=0):
         ctx.frame_run()
         ctx.sync()
         outs.append(ctx.read_planes())
+    _dense_equals_oracle(outs[0], wl, coeffs)
     for a, b in zip(outs[0], outs[1]):
         assert bit_equal(a, b), diff_report(a, b)
 
@@ -1221,6 +1235,7 @@ def test_sparse_duplicates_accumulate(ctx):
         ctx.frame_run()
         ctx.sync()
         outs.append(ctx.read_planes())
+    _dense_equals_oracle(outs[0], wl)
     for a, b in zip(outs[0], outs[1]):
         assert bit_equal(a, b), diff_report(a, b)
 
@@ -1404,6 +1419,9 @@ def test_entries_form_direct_path_and_its_fallbacks(ctx, oracle, mix, size, dens
         m = rng.random(wl.coeffs[g].shape) < 0.5
         wl.coeffs[g] = np.where(m, rng.integers(-9, 10, size=wl.coeffs[g].shape), wl.coeffs[g]).astype(np.int32)
     want, _ = run_gpu_frame(ctx, wl)
+    oref, _ = run_oracle_frame(oracle, wl)
+    for c in range(3):
+        assert bit_equal(want[c], oref[c]), f"dense submission vs oracle, plane {c}: {diff_report(want[c], oref[c])}"
     ng = wl.coeffs.shape[0]
     # duplicates: c = a + b with overlapping supports; where b == -a' the two updates cancel
     split = rng.random(wl.coeffs.shape) < 0.3

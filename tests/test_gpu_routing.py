@@ -8,8 +8,8 @@
   - varblocks with more than 1023 entries per channel (legal: repeated positions, u8 counts per slot; ADVICE r05);
   - coefficient densities far from d1: every batch beyond the direct path's depth takes the dense dequantisation pass.
 
-Every case is compared bit for bit with the dense-slab submission of the same coefficients (which the other test files
-compare with the oracle), and the first one with the oracle itself."""
+Every case is compared bit for bit with the dense-slab submission of the same coefficients, and that submission's
+planes with the oracle's."""
 import numpy as np
 import pytest
 
@@ -48,6 +48,13 @@ def _submit_slots(ctx, groups, parts, flags=None, slot=0):
                             np.concatenate([parts[g][1].reshape(-1) for g in groups]),
                             np.concatenate([parts[g][2] for g in groups]), np.concatenate(wide) if wide else None,
                             slot=slot, flags=jl.GROUP_COMPLETE if flags is None else flags)
+
+
+def _hold_to_oracle(oracle, wl, planes, what):
+    """the dense submission's planes a case compares with are themselves the oracle's, bit for bit"""
+    want, _ = run_oracle_frame(oracle, wl)
+    for c in range(3):
+        assert bit_equal(planes[c], want[c]), f"{what} vs oracle, plane {c}: {diff_report(planes[c], want[c])}"
 
 
 def _check(ctx, want, what):
@@ -111,7 +118,7 @@ def test_per_group_routing(ctx, oracle, mix, size, seed):
     _check(ctx, want2, "clean frame after a routed one")
 
 
-def test_added_pass_routes_only_its_groups(ctx):
+def test_added_pass_routes_only_its_groups(ctx, oracle):
     """JXLH_GROUP_ACCUMULATE on some groups of a frame that is resident in place: those groups' earlier content is
     expanded from the live set, the new pass added on top, and they are read from their slabs; the other groups
     (resubmitted whole) stay in place.  A third epoch then leaves the bucketed form altogether (dense slabs for a few
@@ -126,8 +133,10 @@ def test_added_pass_routes_only_its_groups(ctx):
     part_b = np.where(split, rng.integers(-3, 4, size=full.shape), 0).astype(np.int32)
     part_a = (full - part_b).astype(np.int32)
     want_full, _ = run_gpu_frame(ctx, wl)
+    _hold_to_oracle(oracle, wl, want_full, "full frame, dense submission")
     wl.coeffs = part_a
     want_a, _ = run_gpu_frame(ctx, wl)
+    _hold_to_oracle(oracle, wl, want_a, "first pass, dense submission")
     _begin(ctx, wl)
     ids = list(range(ng))
     _submit_slots(ctx, ids, {g: jl.host_pack_slots(part_a[g], group_id=g) for g in ids})
@@ -157,12 +166,13 @@ def test_added_pass_routes_only_its_groups(ctx):
     ctx.sync()
     got = ctx.read_planes()
     want_mixed, _ = run_gpu_frame(ctx, wl)
+    _hold_to_oracle(oracle, wl, want_mixed, "mixed frame, dense submission")
     for c in range(3):
         assert bit_equal(got[c], want_mixed[c]), f"leaving the routed form, plane {c}: {diff_report(got[c], want_mixed[c])}"
 
 
 @pytest.mark.parametrize("bits12", [False, True])
-def test_split_wide_values_stay_in_place(ctx, bits12):
+def test_split_wide_values_stay_in_place(ctx, oracle, bits12):
     """values far outside the entries' range, split by jxlh_host_pack_slots into repeated in-range entries: no `wide`
     list, no expansion, the frame is read in place (the varblocks that hold them take the dense dequantisation pass)"""
     from jxl_rs_amd import lib as jl
@@ -175,6 +185,7 @@ def test_split_wide_values_stay_in_place(ctx, bits12):
     hi = 1800 if bits12 else 30000
     wl.coeffs.reshape(-1)[sel] = rng.integers(hi // 15, hi, size=len(sel)) * rng.choice([-1, 1], size=len(sel))
     want, _ = run_gpu_frame(ctx, wl)
+    _hold_to_oracle(oracle, wl, want, "dense submission")
     parts = {g: jl.host_pack_slots(wl.coeffs[g], group_id=g, bits12=bits12) for g in range(ng)}
     assert all(len(parts[g][3]) == 0 for g in range(ng))
     assert sum(int(parts[g][2].sum()) for g in range(ng)) > len(nz) + 5 * len(sel)
@@ -206,7 +217,7 @@ def _merge(a, b):
 
 
 @pytest.mark.parametrize("dense_dequant", [False, True])
-def test_more_than_1023_entries_in_a_varblock(ctx, dense_dequant):
+def test_more_than_1023_entries_in_a_varblock(ctx, oracle, dense_dequant):
     """16x32 / 32x16 / 32x32 varblocks may legally hold 8-16 x 255 entries per channel (repeated positions).
     Dense 32-point varblocks submitted as TWO passes in one list: up to 2048 entries per channel in a 32x32."""
     from jxl_rs_amd import lib as jl
@@ -224,6 +235,7 @@ def test_more_than_1023_entries_in_a_varblock(ctx, dense_dequant):
     b[:, :, tail] = 0
     wl.coeffs = (a + b).astype(np.int32)
     want, _ = run_gpu_frame(ctx, wl)
+    _hold_to_oracle(oracle, wl, want, "dense submission")
     parts = {g: _merge(synth.to_slots(a[g]), synth.to_slots(b[g])) for g in range(ng)}
     assert max(int(parts[g][1].astype(np.int64).reshape(3, 64, 16).sum(axis=2).max()) for g in range(ng)) > 1023
     _begin(ctx, wl, flags=jl.FRAME_DENSE_DEQUANT if dense_dequant else 0)
@@ -234,7 +246,7 @@ def test_more_than_1023_entries_in_a_varblock(ctx, dense_dequant):
 
 @pytest.mark.parametrize("mix", ["d1", "all"])
 @pytest.mark.parametrize("density", [0.02, 0.11, 0.15, 0.25, 0.35, 0.6])
-def test_coefficient_density_far_from_d1(ctx, density, mix):
+def test_coefficient_density_far_from_d1(ctx, oracle, density, mix):
     """the direct path holds 3-6 entries per lane and channel; a frame of another density falls back batch by batch
     (the fallback launch; from 0.125 entries per coefficient on the 16..32-point classes take the dense pass outright,
     from 0.25 on the 8x8 class runs its over-depth batches inline) and gives the dense submission's bits; `all`: with
@@ -247,6 +259,7 @@ def test_coefficient_density_far_from_d1(ctx, density, mix):
     m = rng.random(wl.coeffs.shape) < density
     wl.coeffs = np.where(m, rng.integers(-30, 31, size=wl.coeffs.shape), 0).astype(np.int32)
     want, _ = run_gpu_frame(ctx, wl)
+    _hold_to_oracle(oracle, wl, want, f"density {density}, dense submission")
     _begin(ctx, wl)
     _submit_slots(ctx, list(range(ng)), {g: jl.host_pack_slots(wl.coeffs[g], group_id=g) for g in range(ng)})
     ctx.slot_wait(0)

@@ -659,3 +659,48 @@ def test_squeeze_forms_agree_up_to_2_28_and_the_reference_splits_beyond(oracle):
         res = rng.integers(-lim, lim, size=(h, w // 2), dtype=np.int64).astype(np.int32)
         split = np.mean(oracle.unsqueeze_h(avg, res, w) != oracle.unsqueeze_h(avg, res, w, simd_form=True))
         assert split > least, (bits, split)
+
+
+# adjust_quant_bias (group.rs:85-96) restated in numpy float32 from the reference's own operations: the I32Vec abs of
+# every back-end wraps (jxl_simd scalar.rs:247 `Wrapping(self.0.abs())` in a release build, _mm_abs_epi32 sse42.rs:756,
+# _mm256_abs_epi32 avx.rs:821, _mm512_abs_epi32 avx512.rs:1004, vabsq_s32 neon.rs:635), so `2 > abs(i32::MIN)` holds
+# and i32::MIN takes the bias branch.
+def _ref_adjust_quant_bias(q, c, biases):
+    q = np.asarray(q, dtype=np.int32)
+    b = np.asarray(biases, dtype=np.float32)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        quant = q.astype(np.float32)
+        adjusted = quant - b[3] / quant
+        return np.where(np.int32(2) > np.abs(q), quant * b[c], adjusted).astype(np.float32)
+
+
+_QB_EDGES = np.array([-2**31, -2**31 + 1, -2, -1, 0, 1, 2, 2**31 - 1], dtype=np.int64).astype(np.int32)
+
+
+@pytest.mark.parametrize("biases", [
+    (1.0 - 0.05465007, 1.0 - 0.07005449, 1.0 - 0.049935103, 0.145),  # the library default (headers/transform_data.rs)
+    (0.5, 1e-6, 1e6, -3.25),
+    (0.0, -0.75, 65504.0, 4.0),
+], ids=["default", "custom_a", "custom_b"])
+def test_oracle_adjust_quant_bias_at_i32_edges(oracle_any, biases):
+    """The oracle's dequantised value at q in {MIN, MIN+1, -2, -1, 0, 1, 2, MAX} equals the reference expression
+    bit for bit -- i32::MIN included, where a plain `-q` is undefined behaviour in C and a non-wrapping |q| picks
+    the other branch (the adjusted value, -2.1474836e9 instead of MIN * bias_c)."""
+    assert np.abs(np.int32(-2**31)) == np.int32(-2**31)  # numpy's abs wraps like the reference's
+    for c in range(3):
+        got = oracle_any.adjust_quant_bias(_QB_EDGES, c, biases)
+        want = _ref_adjust_quant_bias(_QB_EDGES, c, biases)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (c, got, want)
+        # MIN takes the bias branch: exactly (f32)MIN * bias_c
+        assert got[0].view(np.uint32) == (np.float32(-2**31) * np.float32(biases[c])).view(np.uint32)
+
+
+def test_oracle_adjust_quant_bias_wide_sweep(oracle):
+    """Every |q| < 2^12 and a random sample of the whole i32 range, default biases, all three channels."""
+    rng = np.random.default_rng(85)
+    q = np.concatenate([np.arange(-4096, 4097), rng.integers(-2**31, 2**31, size=1 << 16, dtype=np.int64),
+                        _QB_EDGES]).astype(np.int32)
+    b = (0.94534993, 0.9299455, 0.9500649, 0.145)
+    for c in range(3):
+        assert np.array_equal(oracle.adjust_quant_bias(q, c, b).view(np.uint32),
+                              _ref_adjust_quant_bias(q, c, b).view(np.uint32)), c
