@@ -32,7 +32,9 @@ extern "C" {
 #endif
 
 #define JXLH_ABI_VERSION 6  /* additions only since 6: round 6 added the jxlh_host_*, jxlh_slot_writer_* and
-                               jxlh_ctx_wait_* / _record_event entry points */
+                               jxlh_ctx_wait_* / _record_event entry points; then the reference-frame slots and the
+                               patch dictionary (jxlh_ctx_*_reference, jxlh_frame_save_reference,
+                               jxlh_frame_set_patches, jxlh_stage_patches) */
 #define JXLH_NUM_TRANSFORMS 27   /* HfTransformType::CARDINALITY, transform_map.rs:59-61 */
 #define JXLH_NUM_QUANT_TABLES 17 /* NUM_QUANT_TABLES, quantizer.rs:11 */
 #define JXLH_GROUP_DIM 256       /* GROUP_DIM, jxl/src/lib.rs:24-26 */
@@ -452,6 +454,71 @@ jxlh_status jxlh_frame_device_planes(jxlh_ctx* ctx, float* planes[3], size_t* st
 jxlh_status jxlh_frame_set_extra_channel(jxlh_ctx* ctx, uint32_t ec, const int32_t* samples, size_t stride, uint32_t w,
                                          uint32_t h, uint32_t bits_per_sample, uint32_t ec_upsampling);
 jxlh_status jxlh_frame_read_extra_channel(jxlh_ctx* ctx, uint32_t ec, const jxlh_plane* out);
+
+/* ---------------------------------------------------------------- patches (features/patches.rs)
+ * REFERENCE FRAMES.  DecoderState::reference_frames (4 slots of 3 + num_ec f32 planes, frame/mod.rs:77-80), held on the
+ * device by the context: they survive jxlh_frame_begin and are freed by jxlh_ctx_clear_reference / jxlh_ctx_destroy.
+ *   jxlh_ctx_set_reference     copies n_channels caller planes (w x h, row stride `stride` floats, host or device) into
+ *                              `slot` -- a reference decoded elsewhere (a Modular reference-only frame, another
+ *                              context's planes after jxlh_ctx_wait_event).  Returns when the copy has completed.
+ *   jxlh_frame_save_reference  the save_before_ct save stage (frame/render.rs:711-722): the current frame's finished
+ *                              result -- the colour planes after patches, upsampling and noise, and the patched extra
+ *                              channels -- copied device to device, ordered on the context's stream.  Needs a
+ *                              whole-frame render first (JXLH_ERR_BAD_STATE otherwise); every extra channel must have the
+ *                              result's size (JXLH_ERR_UNSUPPORTED otherwise).
+ * THE PATCH DICTIONARY of the current frame: PatchesDictionary (features/patches.rs:127-170) flattened.  patches[i] in
+ * definition order, which is the order of application (set_patches_for_row's final sort, :676-679); blendings holds
+ * n * (1 + num_ec) entries, entry i * (1 + num_ec) the colour blending of patch i, then one per extra channel (the
+ * reference's blendings_stride layout); ec_flags[k] = JXLH_EC_* of extra channel k (the parts of ExtraChannelInfo that
+ * perform_blending reads).  Checked like PatchesDictionary::read (:362-620), JXLH_ERR_INVALID_ARGUMENT with nothing
+ * launched: the slot is set; num_ec == the slot's n_channels - 3 and == the number of extra channels the frame has been
+ * handed so far (if any); the reference rectangle lies in the slot; mode < 8; alpha_channel < num_ec when the mode uses
+ * alpha and num_ec > 1 (the reference reads it only then and leaves 0 otherwise: it is ignored); the patch rectangle
+ * lies within the frame's PADDED size in its VarDCT form (FrameHeader::size_padded, headers/frame_header.rs:572-581:
+ * whole 8x8 blocks of the coded size, as frame/decode.rs:317-323 passes it for a VarDCT frame), drawing is clipped at
+ * the frame's edge.  A Modular frame's bound is its coded size (frame_header.rs:574-575), which is never larger: its
+ * dictionary, as PatchesDictionary::read accepted it, always passes here, but a patch reaching into the VarDCT padding
+ * is NOT rejected -- a caller using the Modular seam (jxlh_stage_patches) checks that bound itself.  The dictionary
+ * needs a begun frame (jxlh_frame_begin with the frame's size).  n = 0 clears the dictionary; jxlh_frame_begin clears
+ * it too.
+ * Position in the frame: PatchesStage (frame/render.rs:644-650) -- after the filters and the extra channels' own
+ * upsampling, BEFORE the colour upsampling and noise -- so patches are drawn at the coded size.  Extra channels are
+ * drawn into a patched copy (jxlh_frame_read_extra_channel returns it); an upsampled frame may carry patches only
+ * without extra channels, and every extra channel must cover the whole frame (JXLH_ERR_UNSUPPORTED / BAD_STATE from
+ * jxlh_frame_set_patches / jxlh_frame_run otherwise).  A band run (jxlh_frame_run with a group-row range) of a frame
+ * whose result lives in the planes the transforms write and whose transforms rewrite a group row beyond the band
+ * (chroma-subsampled frames without a filter stage, stage lists that end in those planes) renders the whole frame
+ * instead: the band's halo would undo the neighbouring band's patches.  Sharded runs of a frame with patches:
+ * JXLH_ERR_UNSUPPORTED. */
+#define JXLH_MAX_REFERENCE_FRAMES 4
+enum { JXLH_EC_ALPHA = 1u << 0, JXLH_EC_ALPHA_ASSOCIATED = 1u << 1 };
+/* PatchBlendMode (features/patches.rs:41-74) */
+enum {
+  JXLH_PATCH_NONE = 0, JXLH_PATCH_REPLACE = 1, JXLH_PATCH_ADD = 2, JXLH_PATCH_MUL = 3, JXLH_PATCH_BLEND_ABOVE = 4,
+  JXLH_PATCH_BLEND_BELOW = 5, JXLH_PATCH_ALPHA_WEIGHTED_ADD_ABOVE = 6, JXLH_PATCH_ALPHA_WEIGHTED_ADD_BELOW = 7
+};
+typedef struct jxlh_patch {
+  uint32_t x, y;            /* PatchPosition: top-left corner in the frame */
+  uint32_t ref_slot;        /* PatchReferencePosition::reference */
+  uint32_t ref_x0, ref_y0;  /* ... x0, y0 */
+  uint32_t xsize, ysize;    /* ... xsize, ysize */
+} jxlh_patch;
+typedef struct jxlh_patch_blending {
+  uint32_t mode;           /* JXLH_PATCH_* */
+  uint32_t alpha_channel;  /* extra channel index */
+  uint32_t clamp;          /* 0 / 1 */
+} jxlh_patch_blending;
+jxlh_status jxlh_ctx_set_reference(jxlh_ctx* ctx, uint32_t slot, uint32_t n_channels, uint32_t w, uint32_t h,
+                                   const float* const* planes, size_t stride);
+jxlh_status jxlh_frame_save_reference(jxlh_ctx* ctx, uint32_t slot);
+jxlh_status jxlh_ctx_clear_reference(jxlh_ctx* ctx, uint32_t slot);
+jxlh_status jxlh_frame_set_patches(jxlh_ctx* ctx, const jxlh_patch* patches, uint32_t n,
+                                   const jxlh_patch_blending* blendings, uint32_t num_ec, const uint32_t* ec_flags);
+/* The context's current dictionary applied to caller planes in place (3 colour + num_ec extra channels, w x h, row
+ * stride `stride` floats, host or device), with the frame path's kernel: the Modular seam and tests. */
+jxlh_status jxlh_stage_patches(jxlh_ctx* ctx, float* const planes[], uint32_t n_channels, uint32_t w, uint32_t h,
+                               size_t stride);
+
 /* smoothed LF image as used by K1 (tests) */
 jxlh_status jxlh_frame_read_lf(jxlh_ctx* ctx, float* x, float* y, float* b, size_t stride);
 

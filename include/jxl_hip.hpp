@@ -52,6 +52,15 @@ class Context {
     return p;
   }
   void free_pinned(void* p) { check(jxlh_free_pinned(c_, p), "jxlh_free_pinned"); }
+  // DecoderState::reference_frames[slot] <- n_channels planes (w x h, row stride `stride` floats, host or device)
+  void set_reference(uint32_t slot, const std::vector<const float*>& planes, uint32_t w, uint32_t h, size_t stride) {
+    check(jxlh_ctx_set_reference(c_, slot, (uint32_t)planes.size(), w, h, planes.data(), stride), "jxlh_ctx_set_reference");
+  }
+  void clear_reference(uint32_t slot) { check(jxlh_ctx_clear_reference(c_, slot), "jxlh_ctx_clear_reference"); }
+  // the current frame's patch dictionary on caller planes (3 + num_ec), in place
+  void stage_patches(const std::vector<float*>& planes, uint32_t w, uint32_t h, size_t stride) {
+    check(jxlh_stage_patches(c_, planes.data(), (uint32_t)planes.size(), w, h, stride), "jxlh_stage_patches");
+  }
 
  private:
   jxlh_ctx* c_ = nullptr;
@@ -105,6 +114,18 @@ class VarDctFrame {
                "jxlh_submit_group_sparse");
   }
   void slot_wait(int slot = 0) { ctx_.check(jxlh_slot_wait(ctx_.raw(), slot), "jxlh_slot_wait"); }
+  // PatchesDictionary::read's result (decode_lf_global, frame/decode.rs:315-324), flattened: blendings holds
+  // patches.size() * (1 + ec_flags.size()) entries, ec_flags the JXLH_EC_* of each extra channel
+  void decode_patches(const std::vector<jxlh_patch>& patches, const std::vector<jxlh_patch_blending>& blendings,
+                      const std::vector<uint32_t>& ec_flags) {
+    if (blendings.size() != patches.size() * (1 + ec_flags.size()))
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "VarDctFrame::decode_patches", "blendings != patches * (1 + num_ec)");
+    ctx_.check(jxlh_frame_set_patches(ctx_.raw(), patches.data(), (uint32_t)patches.size(), blendings.data(),
+                                      (uint32_t)ec_flags.size(), ec_flags.data()),
+               "jxlh_frame_set_patches");
+  }
+  // the save_before_ct save stage: the rendered frame becomes reference frame `slot`
+  void save_reference(uint32_t slot) { ctx_.check(jxlh_frame_save_reference(ctx_.raw(), slot), "jxlh_frame_save_reference"); }
   // finalize_lf + SigmaSource::new + transforms + the frame's stage list, for group rows [row0, row1)
   void finalize_and_render(uint32_t group_row0 = 0, uint32_t group_row1 = 0xFFFFFFFFu) {
     ctx_.check(jxlh_frame_run(ctx_.raw(), group_row0, group_row1), "jxlh_frame_run");

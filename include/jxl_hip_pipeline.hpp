@@ -153,7 +153,18 @@ struct ConvertModularXYBToF32Stage {  // convert.rs:284, :309-310; quant_factors
   std::string display() const { return "convert modular xyb data to F32 in channels 0..3"; }
   bool uses_channel(int c) const { return c >= first_channel && c < first_channel + 3; }
 };
-// A stage of the reference this path does not run on the device (patches, splines, blending, extend, spot colour,
+// PatchesStage (render/stages/patches.rs, added at frame/render.rs:644-650): the frame's dictionary flattened as
+// jxlh_frame_set_patches takes it -- blendings = patches.size() * (1 + ec_flags.size()) -- and the alpha flags of
+// the extra channels.  In place on every channel; the reference frames it reads are the context's slots.
+struct PatchesStage {
+  std::vector<jxlh_patch> patches;
+  std::vector<jxlh_patch_blending> blendings;
+  std::vector<uint32_t> ec_flags;
+  static constexpr Border BORDER{0, 0}, SHIFT{0, 0};
+  std::string display() const { return "patches"; }
+  bool uses_channel(int) const { return true; }
+};
+// A stage of the reference this path does not run on the device (patches by name, splines, blending, extend, spot colour,
 // premultiplied alpha, extra-channel conversions ...): adding one makes build() fail with JXLH_ERR_UNSUPPORTED.
 struct CpuOnlyStage {
   std::string name;
@@ -176,7 +187,7 @@ struct SaveStage {
 
 using Stage = std::variant<ConvertModularToF32Stage, ConvertModularXYBToF32Stage, HorizontalChromaUpsample, VerticalChromaUpsample, GaborishStage, Epf0Stage, Epf1Stage, Epf2Stage,
                            Upsample2x, Upsample4x, Upsample8x, ConvolveNoiseStage, AddNoiseStage, XybStage, YcbcrToRgbStage,
-                           FromLinearStage, ConvertF32ToU8Stage, ConvertF32ToU16Stage, CpuOnlyStage, SaveStage>;
+                           FromLinearStage, ConvertF32ToU8Stage, ConvertF32ToU16Stage, CpuOnlyStage, SaveStage, PatchesStage>;
 
 inline std::string stage_display(const Stage& s) {
   return std::visit([](const auto& st) { return st.display(); }, s);
@@ -203,6 +214,9 @@ struct LoweredPipeline {
     uint32_t bits = 0, upsampling = 1;
   };
   std::array<Extra, JXLH_MAX_EXTRA_CHANNELS> extra{};
+  // PatchesStage: the dictionary build() hands to jxlh_frame_set_patches
+  bool has_patches = false;
+  PatchesStage patches;
   std::vector<std::string> stages;  // Display strings, in order (diagnostics; what `info!("adding stage")` logs)
 };
 
@@ -281,6 +295,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   const float*(&ec_weights)[3] = lp.weights_by_factor;  // index n >> 2: factor 2, 4, 8
   uint32_t convert_bits = 0;
   bool have_colour = false, have_tf = false, have_save = false, pre_upsample = true, epf1_seen = false, epf2_seen = false;
+  bool patches_seen = false;
   Border border{0, 0};
   auto add_border = [&](Border b) {
     if (pre_upsample) {
@@ -372,6 +387,9 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
         const int ec = ch - 3;
         if (ec >= JXLH_MAX_EXTRA_CHANNELS || !lp.extra[ec].bits) fail(JXLH_ERR_INVALID_ARGUMENT, "upsampling of an extra channel the list never converted to f32");
         if (lp.extra[ec].upsampling != 1) fail(JXLH_ERR_INVALID_ARGUMENT, "an extra channel is upsampled once");
+        // an extra channel's own upsampling comes before the patches (frame/render.rs:624-650); only the late form,
+        // together with the colour channels, may follow them
+        if (patches_seen && ups_seen == 0) fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "' after the patches stage");
         if (ups_seen != 0 && (ups_seen != 3 || n != ups_factor)) fail(JXLH_ERR_INVALID_ARGUMENT, "extra channels upsampled with the colour channels use the frame's factor, after channel 2");
         if (ec_weights[n >> 2] && ec_weights[n >> 2] != w) fail(JXLH_ERR_INVALID_ARGUMENT, "one weight table per upsampling factor (CustomTransformData)");
         ec_weights[n >> 2] = w;
@@ -387,6 +405,19 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       ec_weights[n >> 2] = w;
       p.upsampling = (uint32_t)n;
       pre_upsample = false;
+    } else if (const auto* ps = std::get_if<PatchesStage>(&s)) {
+      // the reference's position: after the filters and the extra channels' own upsampling, before the colour
+      // upsampling, noise and the colour stage (frame/render.rs:624-683)
+      if (phase > kUpsample || ups_seen != 0 || patches_seen)
+        fail(JXLH_ERR_UNSUPPORTED, "stage 'patches' out of the order of Frame::build_render_pipeline");
+      if (lp.modular != LoweredPipeline::Modular::kNone)
+        fail(JXLH_ERR_UNSUPPORTED, "patches on a Modular frame (jxlh_stage_patches on the planes instead)");
+      if (ps->blendings.size() != ps->patches.size() * (1 + ps->ec_flags.size()))
+        fail(JXLH_ERR_INVALID_ARGUMENT, "patches: blendings != patches * (1 + num_ec)");
+      phase = kUpsample;
+      patches_seen = true;
+      lp.has_patches = true;
+      lp.patches = *ps;
     } else if (const auto* cn = std::get_if<ConvolveNoiseStage>(&s)) {
       enter(kNoiseConvolve, s);
       if (cn->channel != (int)num_channels_ - 3 + conv_seen) fail(JXLH_ERR_INVALID_ARGUMENT, "noise convolution: the three temporaries behind the image channels");
@@ -504,6 +535,7 @@ class GpuRenderPipeline {
     const float* const* w = lp_.weights_by_factor;
     if (w[0] || w[1] || w[2])  // CustomTransformData::weights{2,4,8} of the factors in use; the others keep their state
       ctx_.check(jxlh_set_upsampling_weights(ctx_.raw(), w[0], w[1], w[2]), "jxlh_set_upsampling_weights");
+    if (lp_.has_patches) frame_.decode_patches(lp_.patches.patches, lp_.patches.blendings, lp_.patches.ec_flags);
   }
   VarDctFrame& frame() { return frame_; }  // decode_hf_global / decode_lf_group / decode_hf_metadata go here
   const LoweredPipeline& lowered() const { return lp_; }

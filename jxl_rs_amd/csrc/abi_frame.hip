@@ -221,6 +221,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   release(ctx->strip_flags);
   for (auto& b : ctx->hook_f) release(b);
   for (auto& b : ctx->hook_i) release(b);
+  patches_release(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -468,7 +469,12 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   ctx->has_special = ctx->has_large = false;
   ctx->strip_all_closed = true;
   ctx->strip_ran = false;
-  for (auto& e : ctx->extra) e.set = e.done = false;
+  for (auto& e : ctx->extra) e.set = e.done = e.pat_ready = false;
+  // the patch dictionary is per frame (the reference slots are not)
+  ctx->patch_n = ctx->patch_nec = 0;
+  ctx->patch_slots_used = 0;
+  ctx->patch_ec_stale = true;
+  ctx->patch_desc_host.clear();
   for (auto& s : ctx->slots) s.used = false;
   for (int c = 0; c < 3; c++) ctx->result[c] = nullptr;
   ctx->chroma_lazy = false;
@@ -1010,7 +1016,8 @@ jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan, int gr0, int gr1) {
   if (f.subsampled) {
     // ... and brought to full resolution into planes[c] before any filter (frame/render.rs:569-576) -- or, when no
     // stage follows at all, only when the planes are asked for (materialise_chroma)
-    const bool stages_follow = f.gab || f.epf_iters > 0 || p.upsampling > 1 || (p.noise && !noise_lut_is_zero(p.noise_lut));
+    const bool stages_follow = f.gab || f.epf_iters > 0 || p.upsampling > 1 || (p.noise && !noise_lut_is_zero(p.noise_lut)) ||
+                               ctx->patch_n > 0;
     ctx->lazy_gr0 = gr0;
     ctx->lazy_gr1 = gr1;
     // A sharded frame gathers planes[c] band by band (jxlh_frame_allgather): the full-resolution chroma must exist
@@ -1176,7 +1183,7 @@ jxlh_status run_stages_rows(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_
   return run_post_stages(ctx, cur, y_lo, y_hi, whole_frame);
 }
 
-// what follows the filters: upsampling and noise on the finished planes `cur` (rows [y_lo, y_hi))
+// what follows the filters: patches, upsampling and noise on the finished planes `cur` (rows [y_lo, y_hi))
 jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
@@ -1184,6 +1191,18 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
   ctx->res_w = f.xsize;
   ctx->res_h = f.ysize;
   ctx->res_stride = f.plane_stride;
+  bool extra_run = false;
+  if (ctx->patch_n > 0) {
+    // PatchesStage (frame/render.rs:644-650): after the extra channels' own upsampling, before the colour upsampling
+    // and noise, at the coded size.  The extra channels must be converted before the patches read them.
+    bool pending = whole_frame;
+    for (uint32_t i = 0; i < ctx->patch_nec; i++) pending |= !ctx->extra[i].done;
+    if (ctx->patch_nec > 0 && pending) {
+      if (jxlh_status st = run_extra_channels(ctx)) return st;
+      extra_run = true;
+    }
+    if (jxlh_status st = run_patches(ctx, cur, f.plane_stride, y_lo, y_hi)) return st;
+  }
   if (p.upsampling > 1) {
     // Upsample2x/4x/8x on the three colour channels (frame/render.rs:655-671).  The 5x5 window crosses band
     // edges, so an upsampled frame is run whole.
@@ -1230,7 +1249,7 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
   // (a partial re-render still picks up a channel that was handed over after the last whole-frame run)
   bool pending_extra = false;
   for (int i = 0; i < JXLH_MAX_EXTRA_CHANNELS; i++) pending_extra |= ctx->extra[i].set && !ctx->extra[i].done;
-  if (whole_frame || pending_extra)
+  if ((whole_frame || pending_extra) && !extra_run)
     if (jxlh_status st = run_extra_channels(ctx)) return st;
   HIPCHK(ctx, hipGetLastError());
   return JXLH_OK;
@@ -1244,6 +1263,8 @@ jxlh_status run_extra_channels(jxlh_ctx* ctx) {
     if (!e.set) continue;
     const size_t n = (size_t)e.w * e.h;
     e.done = false;
+    e.pat_ready = false;  // a new base: the patched copy is rebuilt by the next patches launch
+    ctx->patch_ec_stale = true;
     if (jxlh_status st = ensure(ctx, e.f32, n)) return st;
     {
       ScopedKernelTimer t(ctx, "k_modular_to_f32");
@@ -1282,10 +1303,19 @@ jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_ro
   FrameDev& f = ctx->fd;
   if (group_row1 > (uint32_t)f.ygroups) group_row1 = (uint32_t)f.ygroups;
   if (group_row0 >= group_row1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = patches_check_run(ctx)) return st;
   RunPlan plan;
-  const bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
+  bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
   plan.want_strip = whole && strip_eligible(ctx);
   if (jxlh_status st = run_prologue(ctx, &plan)) return st;
+  // Patches are drawn in place on the result.  When the result lives in the planes K1 writes and K1 rewrites a group
+  // row beyond the band (the filters' or the chroma upsampling's halo), a band run would overwrite the neighbouring
+  // band's patched pixels with unpatched ones: such a frame is rendered whole.
+  if (!whole && ctx->patch_n > 0 && (plan.halo_px > 0 || f.subsampled) && result_in_tmp(ctx) == 0) {
+    group_row0 = 0;
+    group_row1 = (uint32_t)f.ygroups;
+    whole = true;
+  }
   ctx->strip_ran = false;
   if (plan.want_strip) {
     const jxlh_status st = run_strip(ctx, plan);
@@ -1311,6 +1341,7 @@ jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids,
   for (uint32_t i = 0; i < count; i++)
     if (group_ids[i] >= ctx->ngroups) return JXLH_ERR_INVALID_ARGUMENT;
   if (count == 0) return JXLH_OK;
+  if (jxlh_status st = patches_check_run(ctx)) return st;
   const jxlh_frame_params& p = ctx->params;
   if (p.upsampling > 1) return JXLH_ERR_UNSUPPORTED;  // like a band run: the 5x5 upsampling window crosses groups
   // a rank of a sharded frame holds only its band: progressive re-renders run on unsharded contexts
@@ -1324,7 +1355,8 @@ jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids,
   const bool unfiltered_kept = !ctx->strip_ran && (ns == 0 || (per_stage ? ns == 1 : result_in_tmp(ctx) != 0));
   // Noise is added IN PLACE to the result planes.  Without a filter stage the result lives in `planes`, the planes K1
   // writes: the groups that are not re-transformed would receive their noise a second time.
-  const bool noise_in_place = ns == 0 && p.noise && !noise_lut_is_zero(p.noise_lut);
+  // The same holds for patches: they are drawn in place (an Add would reach the other groups twice).
+  const bool noise_in_place = ns == 0 && ((p.noise && !noise_lut_is_zero(p.noise_lut)) || ctx->patch_n > 0);
   if (!ctx->rendered || !unfiltered_kept || f.subsampled || noise_in_place) return jxlh_frame_run(ctx, 0, UINT32_MAX);
   RunPlan plan;
   if (jxlh_status st = run_prologue(ctx, &plan)) return st;
@@ -1401,7 +1433,7 @@ jxlh_status jxlh_frame_read_extra_channel(jxlh_ctx* ctx, uint32_t ec, const jxlh
   if (!out->ptr || out->bytes_per_row < (size_t)e.out_w * sizeof(float) || out->num_rows < e.out_h ||
       out->bytes_between_rows < out->bytes_per_row)
     return JXLH_ERR_INVALID_ARGUMENT;
-  const float* src = e.up > 1 ? e.out.p : e.f32.p;
+  const float* src = e.pat_ready ? e.pat.p : e.up > 1 ? e.out.p : e.f32.p;  // (with the frame's patches drawn in)
   if (jxlh_status st = copy2d(ctx, out->ptr, out->bytes_between_rows, src, e.out_stride * sizeof(float),
                               (size_t)e.out_w * sizeof(float), e.out_h, ctx->stream))
     return st;

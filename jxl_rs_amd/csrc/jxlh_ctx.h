@@ -172,8 +172,37 @@ struct jxlh_ctx {
     size_t out_stride = 0;
     DevBuf<int32_t> raw;
     DevBuf<float> f32, out;
+    // the channel with the frame's patches drawn in (abi_patches.hip); `pat_ready`: it holds the current dictionary's
+    // result for the current conversion (read-outs then return it)
+    DevBuf<float> pat;
+    bool pat_ready = false;
   };
   ExtraChannel extra[JXLH_MAX_EXTRA_CHANNELS];
+  // reference frames (DecoderState::reference_frames): n_channels planes of w x h at `stride`, channel c at c * stride * h
+  struct RefSlot {
+    bool set = false;
+    uint32_t n_channels = 0, w = 0, h = 0;
+    size_t stride = 0;
+    DevBuf<float> buf;
+  };
+  RefSlot refs[JXLH_MAX_REFERENCE_FRAMES];
+  // the frame's patch dictionary (jxlh_frame_set_patches), binned into 64 x 4 tiles: words = tile ids | starts | patch
+  // indices; row_first[r] = first listed tile of tile row r
+  struct PatchBins {
+    int w = 0, h = 0, ntx = 0, nty = 0;
+    uint32_t ntiles = 0;
+    std::vector<uint32_t> words, row_first;
+    DevBuf<uint32_t> dev;
+  };
+  uint32_t patch_n = 0, patch_nec = 0;  // 0 patches: no dictionary
+  uint32_t patch_ec_alpha = 0, patch_ec_assoc = 0;
+  std::vector<PatchDev> patch_desc_host;
+  DevBuf<PatchDev> patch_desc;
+  uint32_t patch_need_w[JXLH_MAX_REFERENCE_FRAMES] = {}, patch_need_h[JXLH_MAX_REFERENCE_FRAMES] = {};
+  uint32_t patch_slots_used = 0;  // bit s: the dictionary reads slot s
+  PatchBins patch_bins, patch_hook_bins;
+  bool patch_ec_stale = true;  // the patched extra channels must be rebuilt from their base planes on all rows
+  DevBuf<float> patch_hook;    // jxlh_stage_patches staging
   // strip path (k_strip.hip): block descriptors / tile modes written by k1_scan, the strips' edge-column exchange
   // buffer, progress flags + ticket.  strip_all_closed: every rect of the transform map came from host memory and
   // every varblock in it is a small DCT inside its 64x64 tile (jxlh_frame_set_hf_meta); strip_ran: the last
@@ -316,6 +345,11 @@ jxlh_status run_stages(jxlh_ctx* ctx, const RunPlan& plan, uint32_t group_row0, 
 jxlh_status run_stages_rows(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsample of the channels handed over
+// abi_patches.hip: the patches stage on the colour planes `cur` (rows [y_lo, y_hi)) and, when stale, on every row of
+// the patched extra channels; the check a run makes before it launches anything; release of the context's buffers
+jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y_lo, int y_hi);
+jxlh_status patches_check_run(const jxlh_ctx* ctx);
+void patches_release(jxlh_ctx* ctx);
 bool strip_eligible(const jxlh_ctx* ctx);
 jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan);
 // Where run_stages leaves the finished planes (1 = f.tmp, 0 = f.planes): a property of the frame's stage list, so a

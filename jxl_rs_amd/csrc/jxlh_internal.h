@@ -409,4 +409,30 @@ bool launch_unsqueeze_levels(hipStream_t s, int n_planes, int n_levels, const in
 void launch_smooth_unsqueeze(hipStream_t s, int kind, const int32_t* in, size_t in_stride, int in_w, int in_h, int x0,
                              int y0, int32_t* out, size_t out_stride, int out_w, int out_h, bool cvt_rne);
 
+// patches stage (k_patches.hip): one patch as the kernel reads it (wave-uniform, scalar loads)
+struct PatchDev {
+  int x, y, w, h;    // target rectangle (not clipped: the kernel tests each pixel)
+  int rx, ry, slot;  // top-left corner in reference slot `slot`
+  int pad;
+  uint32_t blend[1 + JXLH_MAX_EXTRA_CHANNELS];  // pack_blending (blend_device.h): colour, then extra channel i
+  uint32_t pad2[3];
+};
+struct PatchLaunch {
+  float* col[3];  // colour planes, patched in place
+  size_t col_stride;
+  const float* ec_in[JXLH_MAX_EXTRA_CHANNELS];  // extra channels: base values read ...
+  float* ec_out[JXLH_MAX_EXTRA_CHANNELS];       // ... patched values written (may alias ec_in)
+  uint32_t ec_stride[JXLH_MAX_EXTRA_CHANNELS];
+  const float* ref[JXLH_MAX_REFERENCE_FRAMES];  // slot planes: channel c at ref[s] + c * ref_plane[s]
+  size_t ref_plane[JXLH_MAX_REFERENCE_FRAMES];
+  uint32_t ref_stride[JXLH_MAX_REFERENCE_FRAMES];
+  int w, h, ntx;         // clip size, tiles per row (64 x 4 px tiles)
+  int cy0, cy1, ey0, ey1;  // rows whose colour / extra channel values are stored
+  uint32_t ec_alpha, ec_assoc;
+  uint32_t tile0;        // first entry of the compact tile list this launch covers
+};
+// tiles[t] = tile id (ty * ntx + tx), start[t] .. start[t + 1] = its entries of `list` (patch indices, ascending)
+void launch_patches(hipStream_t s, int num_ec, const PatchLaunch& a, uint32_t ntiles, const uint32_t* tiles,
+                    const uint32_t* start, const uint32_t* list, const PatchDev* desc);
+
 }  // namespace jxlh

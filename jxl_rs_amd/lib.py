@@ -59,6 +59,8 @@ ABI_SYMBOLS = [
     "jxlh_frame_allgather_output", "jxlh_frames_allgather_output_local",
     "jxlh_host_pack_slots", "jxlh_host_pack_slots_many", "jxlh_slot_writer_create", "jxlh_slot_writer_destroy", "jxlh_slot_writer_begin_group",
     "jxlh_slot_writer_begin_varblock", "jxlh_slot_writer_add", "jxlh_slot_writer_add_many", "jxlh_slot_writer_end_group",
+    "jxlh_ctx_set_reference", "jxlh_frame_save_reference", "jxlh_ctx_clear_reference", "jxlh_frame_set_patches",
+    "jxlh_stage_patches",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
@@ -112,6 +114,20 @@ class Plane(C.Structure):
     """jxlh_plane == RawImageBuffer."""
     _fields_ = [("ptr", C.c_void_p), ("bytes_per_row", C.c_size_t), ("num_rows", C.c_size_t),
                 ("bytes_between_rows", C.c_size_t)]
+
+
+# patches (jxlh_frame_set_patches): PatchBlendMode values, ExtraChannelInfo flags
+PATCH_NONE, PATCH_REPLACE, PATCH_ADD, PATCH_MUL, PATCH_BLEND_ABOVE, PATCH_BLEND_BELOW, PATCH_AWA_ABOVE, PATCH_AWA_BELOW = range(8)
+EC_ALPHA = 1
+EC_ALPHA_ASSOCIATED = 2
+
+
+class Patch(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("x", "y", "ref_slot", "ref_x0", "ref_y0", "xsize", "ysize")]
+
+
+class PatchBlending(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "alpha_channel", "clamp")]
 
 
 class JxlHipError(RuntimeError):
@@ -235,6 +251,11 @@ def load():
         L.jxlh_frame_set_extra_channel.argtypes = [vp, u32, vp, sz, u32, u32, u32, u32]
         L.jxlh_frame_read_extra_channel.argtypes = [vp, u32, C.POINTER(Plane)]
     L.jxlh_frame_rerender_groups.argtypes = [vp, vp, u32]
+    L.jxlh_ctx_set_reference.argtypes = [vp, u32, u32, u32, u32, C.POINTER(vp), sz]
+    L.jxlh_frame_save_reference.argtypes = [vp, u32]
+    L.jxlh_ctx_clear_reference.argtypes = [vp, u32]
+    L.jxlh_frame_set_patches.argtypes = [vp, vp, u32, vp, u32, vp]
+    L.jxlh_stage_patches.argtypes = [vp, C.POINTER(vp), u32, u32, u32, sz]
     L.jxlh_comm_allgather_local.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), sz]
     L.jxlh_palette_strided.argtypes = [vp, vp, sz, vp, i32, sz, i32, i32, vp, sz]
     L.jxlh_modular_frame_filters.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32, sz]
@@ -753,6 +774,54 @@ class Context:
         pl = Plane(out.ctypes.data, out_w * 4, out_h, out_w * 4)
         self._chk(self.L.jxlh_frame_read_extra_channel(self._ctx, ec, C.byref(pl)), "frame_read_extra_channel")
         return out
+
+    # ---- patches ----
+    def set_reference(self, slot, planes):
+        """jxlh_ctx_set_reference: reference slot `slot` <- the 3 + num_ec f32 planes [h, w] (host arrays)"""
+        pl = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+        h, w = pl[0].shape
+        assert all(a.shape == (h, w) for a in pl)
+        pp = (C.c_void_p * len(pl))(*[a.ctypes.data for a in pl])
+        self._chk(self.L.jxlh_ctx_set_reference(self._ctx, slot, len(pl), w, h, pp, w), "ctx_set_reference")
+
+    def save_reference(self, slot):
+        self._chk(self.L.jxlh_frame_save_reference(self._ctx, slot), "frame_save_reference")
+
+    def clear_reference(self, slot):
+        self._chk(self.L.jxlh_ctx_clear_reference(self._ctx, slot), "ctx_clear_reference")
+
+    @staticmethod
+    def _patch_arrays(patches, blendings, ec_flags):
+        n = len(patches)
+        pa = (Patch * max(n, 1))()
+        for i, p in enumerate(patches):
+            pa[i] = Patch(*[int(v) for v in p])
+        bl = list(blendings)
+        ba = (PatchBlending * max(len(bl), 1))()
+        for i, b in enumerate(bl):
+            ba[i] = PatchBlending(*[int(v) for v in b])
+        fl = (C.c_uint32 * max(len(ec_flags), 1))(*[int(v) for v in ec_flags])
+        return n, pa, ba, fl
+
+    def set_patches(self, patches, blendings, ec_flags=(), num_ec=None):
+        """jxlh_frame_set_patches.  patches: (x, y, ref_slot, ref_x0, ref_y0, xsize, ysize) each, in order of
+        application; blendings: len(patches) * (1 + num_ec) (mode, alpha_channel, clamp) triples, the colour blending of
+        each patch first; ec_flags: EC_ALPHA / EC_ALPHA_ASSOCIATED per extra channel (try_set_patches: the same,
+        returning the status instead of raising)"""
+        self._chk(self.try_set_patches(patches, blendings, ec_flags, num_ec), "frame_set_patches")
+
+    def try_set_patches(self, patches, blendings, ec_flags=(), num_ec=None):
+        n, pa, ba, fl = self._patch_arrays(patches, blendings, ec_flags)
+        nec = len(ec_flags) if num_ec is None else num_ec
+        return self.L.jxlh_frame_set_patches(self._ctx, C.byref(pa), n, C.byref(ba), nec, C.byref(fl))
+
+    def stage_patches(self, planes):
+        """jxlh_stage_patches: the current dictionary applied to copies of the 3 + num_ec f32 planes [h, w]"""
+        pl = [np.ascontiguousarray(a, dtype=np.float32).copy() for a in planes]
+        h, w = pl[0].shape
+        pp = (C.c_void_p * len(pl))(*[a.ctypes.data for a in pl])
+        self._chk(self.L.jxlh_stage_patches(self._ctx, pp, len(pl), w, h, w), "stage_patches")
+        return pl
 
     def tune_placement(self, trials=0):
         """jxlh_ctx_tune_placement: trials > 0 sets the number of candidate sets the next first allocation of the large
