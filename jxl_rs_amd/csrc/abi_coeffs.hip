@@ -5,6 +5,30 @@
 
 #include "jxlh_ctx.h"
 
+namespace {
+// the slot's device staging, grown to `bytes` (5/4 + 4 KiB of headroom)
+jxlh_status grow_stage(jxlh_ctx* ctx, Slot& s, size_t bytes) {
+  if (s.stage8_cap >= bytes) return JXLH_OK;
+  HIPCHK(ctx, hipStreamSynchronize(s.stream));  // the old staging may still be read by a queued kernel
+  if (s.stage8) (void)hipFree(s.stage8);
+  s.stage8 = nullptr;
+  s.stage8_cap = 0;
+  const size_t cap = bytes * 5 / 4 + 4096;
+  if (hipMalloc(reinterpret_cast<void**>(&s.stage8), cap) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
+  s.stage8_cap = cap;
+  return JXLH_OK;
+}
+
+// the end of every submission: `done` behind its work on the slot's stream; `copied` (already recorded) when device
+// work follows the copies
+jxlh_status submitted(jxlh_ctx* ctx, Slot& s, bool copied = false) {
+  s.copied_valid = copied;
+  HIPCHK(ctx, hipEventRecord(s.done, s.stream));
+  s.used = true;
+  return JXLH_OK;
+}
+}  // namespace
+
 extern "C" {
 
 jxlh_status jxlh_submit_group(jxlh_ctx* ctx, int32_t slot, uint32_t group_id, const int32_t* coeffs, uint32_t flags) {
@@ -19,16 +43,7 @@ jxlh_status jxlh_submit_group(jxlh_ctx* ctx, int32_t slot, uint32_t group_id, co
   Slot& s = ctx->slots[slot];
   {
     std::lock_guard<std::mutex> lock(ctx->sp_mutex);
-    if (ctx->touched[group_id] == 2) {
-      // submitted as pairs earlier in this epoch: the dense slab replaces that submission
-      for (size_t i = 0; i < ctx->sp_pending.size();) {
-        if (ctx->sp_pending[i].group == group_id) ctx->sp_pending.erase(ctx->sp_pending.begin() + i);
-        else i++;
-      }
-    }
-    ctx->touched[group_id] = 1;
-    if (group_id < ctx->bucketed.size()) ctx->bucketed[group_id] = 0;
-    ctx->epoch_dirty = true;
+    ctx->epoch.record(group_id, Sub::kDense, false);
   }
   int32_t* dst = ctx->coeffs.p + (size_t)group_id * 3 * kGroupArea;
   // the previous jxlh_frame_run's transforms may still be reading the slab (callers that use the *_async reads
@@ -37,18 +52,16 @@ jxlh_status jxlh_submit_group(jxlh_ctx* ctx, int32_t slot, uint32_t group_id, co
   if (dst != coeffs) {
     HIPCHK(ctx, hipMemcpyAsync(dst, coeffs, (size_t)3 * kGroupArea * sizeof(int32_t), hipMemcpyDefault, s.stream));
   }
-  s.copied_valid = false;
-  HIPCHK(ctx, hipEventRecord(s.done, s.stream));
-  s.used = true;
-  return JXLH_OK;
+  return submitted(ctx, s);
 }
 
 namespace {
-// bookkeeping shared by the sparse submission forms: validates, reserves `total` pairs in the frame's pair buffer
-// (offset returned) and records the groups / wide entries for the next jxlh_frame_run
+// bookkeeping shared by the sparse submission forms: validates (`data`: the caller has the pairs / entries to copy),
+// reserves `total` pairs in the frame's pair buffer (offset returned) and records the groups (as `kind`) / wide entries
+// for the next jxlh_frame_run.  A failed call reserves nothing: the epoch stays as it was.
 jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const uint32_t* group_ids, const uint32_t* n,
-                           const jxlh_coeff32* wide, uint32_t n_wide, uint32_t flags, size_t* offset_out,
-                           size_t* total_out) {
+                           const jxlh_coeff32* wide, uint32_t n_wide, uint32_t flags, Sub kind, bool data,
+                           size_t* offset_out, size_t* total_out) {
   if (!ctx || slot < 0 || (size_t)slot >= ctx->slots.size() || !group_ids || !n || (n_wide && !wide))
     return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
@@ -57,6 +70,7 @@ jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const ui
     if (group_ids[i] >= ctx->ngroups) return JXLH_ERR_INVALID_ARGUMENT;
     total += (size_t)n[3 * i] + n[3 * i + 1] + n[3 * i + 2];
   }
+  if (total && !data) return JXLH_ERR_INVALID_ARGUMENT;
   const size_t wide_limit = ctx->ngroups * 3 * (size_t)kGroupArea;
   for (uint32_t i = 0; i < n_wide; i++)
     if (wide[i].pos >= wide_limit) return JXLH_ERR_INVALID_ARGUMENT;
@@ -64,14 +78,15 @@ jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const ui
   const size_t capacity = ctx->ngroups * 3 * (size_t)kGroupArea;  // one pair per coefficient
   if (jxlh_status st = ensure(ctx, ctx->sp_pairs, capacity)) return st;
   if (!ctx->sp_expanded) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sp_expanded, hipEventDisableTiming));
-  if (ctx->sp_used + total > capacity) return JXLH_ERR_INVALID_ARGUMENT;  // more pairs than coefficients
+  CoeffEpoch& e = ctx->epoch;
+  if (e.pairs_used + total > capacity) return JXLH_ERR_INVALID_ARGUMENT;  // more pairs than coefficients
   for (uint32_t i = 0; i < count; i++) {  // one sparse submission per group between two runs (its list may
-    if (ctx->touched[group_ids[i]] == 2) return JXLH_ERR_BAD_STATE;  // hold several passes' updates)
+    if (e.sparse(group_ids[i])) return JXLH_ERR_BAD_STATE;  // hold several passes' updates)
     for (uint32_t k = 0; k < i; k++)  // ... and not twice inside this batch either
       if (group_ids[k] == group_ids[i]) return JXLH_ERR_BAD_STATE;
   }
-  const size_t offset = ctx->sp_used;
-  ctx->sp_used += total;
+  const size_t offset = e.pairs_used;
+  e.pairs_used += total;
   size_t o = offset;
   for (uint32_t i = 0; i < count; i++) {
     SparseGroup g;
@@ -82,12 +97,12 @@ jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const ui
       o += g.n[c];
     }
     g.flags = (flags & JXLH_GROUP_ACCUMULATE) ? 1u : 0u;
-    ctx->sp_pending.push_back(g);
-    ctx->touched[g.group] = 2;
-    if (g.group < ctx->bucketed.size()) ctx->bucketed[g.group] = 0;  // only jxlh_submit_groups_slots sets it (again)
+    e.pending.push_back(g);
+    e.record(g.group, kind, g.flags != 0);
   }
-  ctx->epoch_dirty = true;
-  for (uint32_t i = 0; i < n_wide; i++) ctx->sp_wide.push_back(make_uint2(wide[i].pos, (uint32_t)wide[i].val));
+  for (uint32_t i = 0; i < n_wide; i++) e.wide.push_back(WideValue{wide[i].pos, (uint32_t)wide[i].val});
+  // the pair buffer is recycled per frame: the previous frame's expansion must have read it
+  if (ctx->sp_expanded_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->slots[slot].stream, ctx->sp_expanded, 0));
   *offset_out = offset;
   *total_out = total;
   return JXLH_OK;
@@ -100,19 +115,13 @@ jxlh_status jxlh_submit_groups_sparse(jxlh_ctx* ctx, int32_t slot, uint32_t coun
   JXLH_ON_DEVICE(ctx);
   if (count == 0 && ctx && ctx->in_frame) return JXLH_OK;
   size_t offset = 0, total = 0;
-  if (!pairs && n && count)  // checked before anything is reserved: a failed call leaves the epoch as it was
-    for (size_t r = 0; r < (size_t)count * 3; r++)
-      if (n[r]) return JXLH_ERR_INVALID_ARGUMENT;
-  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, &offset, &total)) return st;
+  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, Sub::kPairs, pairs != nullptr,
+                                      &offset, &total))
+    return st;
   Slot& s = ctx->slots[slot];
-  // the pair buffer is recycled per frame: the previous frame's expansion must have read it
-  if (ctx->sp_expanded_valid) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->sp_expanded, 0));
   if (total)
     HIPCHK(ctx, hipMemcpyAsync(ctx->sp_pairs.p + offset, pairs, total * sizeof(uint32_t), hipMemcpyDefault, s.stream));
-  s.copied_valid = false;
-  HIPCHK(ctx, hipEventRecord(s.done, s.stream));
-  s.used = true;
-  return JXLH_OK;
+  return submitted(ctx, s);
 }
 
 // 3 bytes per coefficient update on the bus: positions and values as separate arrays (u16 / i8), widened into the
@@ -123,34 +132,21 @@ jxlh_status jxlh_submit_groups_sparse8(jxlh_ctx* ctx, int32_t slot, uint32_t cou
   JXLH_ON_DEVICE(ctx);
   if (count == 0 && ctx && ctx->in_frame) return JXLH_OK;
   size_t offset = 0, total = 0;
-  if ((!pos || !val) && n && count)  // checked before anything is reserved
-    for (size_t r = 0; r < (size_t)count * 3; r++)
-      if (n[r]) return JXLH_ERR_INVALID_ARGUMENT;
-  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, &offset, &total)) return st;
+  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, Sub::kPairs, pos && val,
+                                      &offset, &total))
+    return st;
   Slot& s = ctx->slots[slot];
-  if (ctx->sp_expanded_valid) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->sp_expanded, 0));
   if (total) {
     // staging: [positions | values], reused by the slot (stream-ordered)
     const size_t pos_bytes = (total * sizeof(uint16_t) + 15) & ~(size_t)15;
-    if (s.stage8_cap < pos_bytes + total) {
-      HIPCHK(ctx, hipStreamSynchronize(s.stream));  // the old staging may still be read by a queued kernel
-      if (s.stage8) (void)hipFree(s.stage8);
-      s.stage8 = nullptr;
-      s.stage8_cap = 0;
-      const size_t cap = (pos_bytes + total) * 5 / 4 + 4096;
-      if (hipMalloc(reinterpret_cast<void**>(&s.stage8), cap) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
-      s.stage8_cap = cap;
-    }
+    if (jxlh_status st = grow_stage(ctx, s, pos_bytes + total)) return st;
     HIPCHK(ctx, hipMemcpyAsync(s.stage8, pos, total * sizeof(uint16_t), hipMemcpyDefault, s.stream));
     HIPCHK(ctx, hipMemcpyAsync(s.stage8 + pos_bytes, val, total, hipMemcpyDefault, s.stream));
     launch_pack_pairs8(s.stream, reinterpret_cast<const uint16_t*>(s.stage8),
                        reinterpret_cast<const int8_t*>(s.stage8 + pos_bytes), total, ctx->sp_pairs.p + offset);
     HIPCHK(ctx, hipGetLastError());
   }
-  s.copied_valid = false;
-  HIPCHK(ctx, hipEventRecord(s.done, s.stream));
-  s.used = true;
-  return JXLH_OK;
+  return submitted(ctx, s);
 }
 
 // 2 bytes per coefficient update on the bus: u16 entries = position inside a 4096-coefficient segment | value nibble,
@@ -181,7 +177,9 @@ jxlh_status jxlh_submit_groups_sparse4(jxlh_ctx* ctx, int32_t slot, uint32_t cou
   }
   if ((tot4 && !entries) || (tot8 && (!pos8 || !val8))) return JXLH_ERR_INVALID_ARGUMENT;
   size_t offset = 0, total = 0;
-  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n.data(), wide, n_wide, flags, &offset, &total)) return st;
+  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n.data(), wide, n_wide, flags, Sub::kPairs, true,
+                                      &offset, &total))
+    return st;
   {
     size_t o = 0;
     for (size_t r = 0; r < runs; r++) {
@@ -190,21 +188,11 @@ jxlh_status jxlh_submit_groups_sparse4(jxlh_ctx* ctx, int32_t slot, uint32_t cou
     }
   }
   Slot& s = ctx->slots[slot];
-  if (ctx->sp_expanded_valid) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->sp_expanded, 0));
   if (total) {
     // staging: [entries | seg counts | overflow positions | overflow values | run descriptors], reused by the slot
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t b_ent = up(tot4 * 2), b_cnt = up(runs * 16 * 2), b_pos = up(tot8 * 2), b_val = up(tot8), b_desc = up(runs * 16);
-    const size_t need = b_ent + b_cnt + b_pos + b_val + b_desc;
-    if (s.stage8_cap < need) {
-      HIPCHK(ctx, hipStreamSynchronize(s.stream));  // the old staging may still be read by a queued kernel
-      if (s.stage8) (void)hipFree(s.stage8);
-      s.stage8 = nullptr;
-      s.stage8_cap = 0;
-      const size_t cap = need * 5 / 4 + 4096;
-      if (hipMalloc(reinterpret_cast<void**>(&s.stage8), cap) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
-      s.stage8_cap = cap;
-    }
+    if (jxlh_status st = grow_stage(ctx, s, b_ent + b_cnt + b_pos + b_val + b_desc)) return st;
     uint8_t* d_ent = s.stage8, *d_cnt = d_ent + b_ent, *d_pos = d_cnt + b_cnt, *d_val = d_pos + b_pos, *d_desc = d_val + b_val;
     if (tot4) HIPCHK(ctx, hipMemcpyAsync(d_ent, entries, tot4 * 2, hipMemcpyDefault, s.stream));
     HIPCHK(ctx, hipMemcpyAsync(d_cnt, seg_counts, runs * 16 * 2, hipMemcpyDefault, s.stream));
@@ -219,10 +207,7 @@ jxlh_status jxlh_submit_groups_sparse4(jxlh_ctx* ctx, int32_t slot, uint32_t cou
                        reinterpret_cast<const uint32_t*>(d_desc), (int)runs, ctx->sp_pairs.p + offset);
     HIPCHK(ctx, hipGetLastError());
   }
-  s.copied_valid = false;
-  HIPCHK(ctx, hipEventRecord(s.done, s.stream));
-  s.used = true;
-  return JXLH_OK;
+  return submitted(ctx, s);
 }
 
 // slot-bucketed form: entries, slot counts and run descriptors go to the context's PENDING set as they are (no unpack
@@ -236,15 +221,14 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
   if (!ctx || !slot_counts || !n || !group_ids || slot < 0 || (size_t)slot >= ctx->slots.size()) return JXLH_ERR_INVALID_ARGUMENT;
   const size_t runs = (size_t)count * 3;
   const bool e12 = (flags & JXLH_GROUP_ENTRIES12) != 0;
-  size_t total_check = 0;
   for (size_t r = 0; r < runs; r++) {
     if (n[r] > (uint32_t)kGroupArea) return JXLH_ERR_INVALID_ARGUMENT;
     if (e12 && (n[r] & 1u)) return JXLH_ERR_INVALID_ARGUMENT;  // 12-bit runs are closed to an even number of entries
-    total_check += n[r];
   }
-  if (total_check && !entries) return JXLH_ERR_INVALID_ARGUMENT;
   size_t offset = 0, total = 0;
-  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, &offset, &total)) return st;
+  if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, Sub::kSlots, entries != nullptr,
+                                      &offset, &total))
+    return st;
   int pend;
   {
     std::lock_guard<std::mutex> lock(ctx->sp_mutex);
@@ -253,29 +237,18 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
     if (jxlh_status st = ensure(ctx, ctx->se_entries[pend], ctx->ngroups * 3 * (size_t)kGroupArea + 64)) return st;
     if (jxlh_status st = ensure(ctx, ctx->se_counts[pend], ctx->ngroups * 3 * (size_t)kSlotsPerRun)) return st;
     if (jxlh_status st = ensure(ctx, ctx->se_runs[pend], ctx->ngroups * 3)) return st;
-    if (ctx->bucketed.size() != ctx->ngroups) ctx->bucketed.assign(ctx->ngroups, 0);
-    for (uint32_t i = 0; i < count; i++) ctx->bucketed[group_ids[i]] = 1;
   }
   Slot& s = ctx->slots[slot];
   // the pending set was last read two frames ago (by the transforms of the frame that made it live, or by the previous
   // epoch's widening into the pair buffer): nothing here waits for the frame that is running now
   if (ctx->se_read_valid[pend]) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->se_read[pend], 0));
-  if (ctx->sp_expanded_valid) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->sp_expanded, 0));
   uint16_t* d_ent = ctx->se_entries[pend].p + offset;
   if (total) {
     if (!e12) {
       HIPCHK(ctx, hipMemcpyAsync(d_ent, entries, total * sizeof(uint16_t), hipMemcpyDefault, s.stream));
     } else {
       const size_t bytes = total / 2 * 3;
-      if (s.stage8_cap < bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // the old staging may still be read by a queued kernel
-        if (s.stage8) (void)hipFree(s.stage8);
-        s.stage8 = nullptr;
-        s.stage8_cap = 0;
-        const size_t cap = bytes * 5 / 4 + 4096;
-        if (hipMalloc(reinterpret_cast<void**>(&s.stage8), cap) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
-        s.stage8_cap = cap;
-      }
+      if (jxlh_status st = grow_stage(ctx, s, bytes)) return st;
       HIPCHK(ctx, hipMemcpyAsync(s.stage8, entries, bytes, hipMemcpyDefault, s.stream));
       // (the unpack kernel goes behind the other copies, below: what jxlh_slot_wait / jxlh_slot_after wait for is the
       // copies -- a kernel queued behind another context's transforms would hold the next upload, and the bus, back)
@@ -305,14 +278,8 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
     HIPCHK(ctx, hipEventRecord(s.copied, s.stream));
     launch_unpack_entries12(s.stream, s.stage8, total / 2, d_ent);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(s.done, s.stream));
-    s.copied_valid = true;
-  } else {
-    s.copied_valid = false;
-    HIPCHK(ctx, hipEventRecord(s.done, s.stream));
   }
-  s.used = true;
-  return JXLH_OK;
+  return submitted(ctx, s, total && e12);
 }
 
 jxlh_status jxlh_submit_group_sparse(jxlh_ctx* ctx, int32_t slot, uint32_t group_id, const jxlh_coeff16* pairs,

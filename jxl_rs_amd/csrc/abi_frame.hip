@@ -368,16 +368,7 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   ctx->ngroups = (size_t)f.xgroups * f.ygroups;
   {
     std::lock_guard<std::mutex> lock(ctx->sp_mutex);
-    ctx->sp_pending.clear();
-    ctx->sp_wide.clear();
-    ctx->sp_used = 0;
-    ctx->touched.assign(ctx->ngroups, 0);
-    ctx->bucketed.assign(ctx->ngroups, 0);
-    ctx->epoch_dirty = false;
-    ctx->sp_sorted_valid = false;
-    ctx->se_valid = false;
-    ctx->route_live.clear();
-    ctx->n_route = 0;
+    ctx->epoch.reset(ctx->ngroups);
   }
   const size_t nblocks = (size_t)f.xblocks * f.yblocks;
   const size_t ncmap = (size_t)f.cmap_stride * ((f.yblocks + 7) / 8);
@@ -739,7 +730,89 @@ jxlh_status upload_upsampling_kernels(jxlh_ctx* ctx, int n) {
   return JXLH_OK;
 }
 
-// everything before K1: upload fences, sparse coefficient transport, K0b, K3 sigma
+// The coefficient transport of an epoch: plans it (coeff_epoch.h), issues the plan's copies and launches on the main
+// stream, moves the state on.  *sparse_k1: the transforms read a bucketed form instead of the dense slabs.
+static jxlh_status apply_coeff_epoch(jxlh_ctx* ctx, bool want_strip, bool* sparse_k1) {
+  std::lock_guard<std::mutex> lock(ctx->sp_mutex);
+  CoeffEpoch& e = ctx->epoch;
+  if (e.dirty) {
+    static_assert(sizeof(WideValue) == sizeof(uint2) && kEpochGroupCoeffs == 3u * kGroupArea, "coeff_epoch.h");
+    e.upload.swap(e.pending);  // the descriptors and the plan stay alive until the next run: the H2D copies read them
+    e.wide_upload.swap(e.wide);
+    e.pending.clear();
+    e.wide.clear();
+    const size_t n = ctx->ngroups, ng = e.upload.size(), nw = e.wide_upload.size();
+    if (jxlh_status st = ensure(ctx, ctx->sp_groups_dev, ng)) return st;
+    if (jxlh_status st = ensure(ctx, ctx->sp_wide_dev, nw)) return st;
+    if (jxlh_status st = ensure(ctx, ctx->group_dense, n)) return st;
+    e.plan = plan_coeff_epoch(e.inputs((ctx->params.flags & JXLH_FRAME_EXPAND_SPARSE) != 0, want_strip));
+    const EpochPlan& pl = e.plan;
+    const int live = ctx->se_live, pend = live ^ 1;
+    if (pl.descs == Descs::kAll && ng)
+      HIPCHK(ctx, hipMemcpyAsync(ctx->sp_groups_dev.p, e.upload.data(), ng * sizeof(SparseGroup), hipMemcpyHostToDevice,
+                                 ctx->stream));
+    if (nw)
+      HIPCHK(ctx, hipMemcpyAsync(ctx->sp_wide_dev.p, e.wide_upload.data(), nw * sizeof(uint2), hipMemcpyHostToDevice,
+                                 ctx->stream));
+    if (!pl.rebuild.empty()) {
+      HIPCHK(ctx, hipMemcpyAsync(ctx->group_dense.p, pl.rebuild.data(), n, hipMemcpyHostToDevice, ctx->stream));
+      ScopedKernelTimer t(ctx, "k_expand_sparse");
+      if (e.live.form == Resident::kEntries)
+        launch_expand_entries(ctx->stream, ctx->coeffs.p, ctx->se_entries[live].p, ctx->se_counts[live].p,
+                              ctx->se_runs[live].p, ctx->group_dense.p, (int)n);
+      else
+        launch_expand_sorted(ctx->stream, ctx->coeffs.p, ctx->sp_sorted.p, ctx->sp_slot_start.p, ctx->group_dense.p, (int)n);
+    }
+    if (!pl.widen.empty()) {
+      if (jxlh_status st = ensure(ctx, ctx->bucketed_dev, n)) return st;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->bucketed_dev.p, pl.widen.data(), n, hipMemcpyHostToDevice, ctx->stream));
+      ScopedKernelTimer t(ctx, "k_entries_to_pairs");
+      launch_entries_to_pairs(ctx->stream, ctx->se_entries[pend].p, ctx->se_counts[pend].p, ctx->se_runs[pend].p,
+                              ctx->bucketed_dev.p, (int)n, ctx->sp_pairs.p);
+    }
+    size_t n_expand = ng;
+    if (pl.descs == Descs::kRouted) {
+      if (jxlh_status st = ensure(ctx, ctx->route_dev, n)) return st;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->route_dev.p, pl.after.route.data(), n, hipMemcpyHostToDevice, ctx->stream));
+      // only the routed groups that arrived as pairs / entries have anything to expand: their descriptors go to the
+      // front of the list (a frame whose only routed group is a dense slab launches nothing here)
+      n_expand = 0;
+      for (size_t i = 0; i < ng; i++)
+        if (pl.after.route[e.upload[i].group]) std::swap(e.upload[n_expand++], e.upload[i]);
+      if (n_expand)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->sp_groups_dev.p, e.upload.data(), n_expand * sizeof(SparseGroup),
+                                   hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (pl.sort) {
+      if (jxlh_status st = ensure(ctx, ctx->sp_sorted, n * kEpochGroupCoeffs)) return st;
+      if (jxlh_status st = ensure(ctx, ctx->sp_slot_start, n * 3 * (size_t)kSlotTable)) return st;
+      ScopedKernelTimer t(ctx, "k_sort_sparse");
+      launch_sort_sparse(ctx->stream, ctx->sp_pairs.p, ctx->sp_groups_dev.p, (int)ng, ctx->sp_sorted.p, ctx->sp_slot_start.p);
+    } else if (pl.descs != Descs::kNone && (n_expand || nw)) {
+      // zero-fill + scatter of the pair words (their own, or the ones the widening made of their entries) + the wide
+      // values into the slabs -- or, for an added pass, on top of what the slab holds
+      ScopedKernelTimer t(ctx, "k_expand_sparse");
+      launch_expand_sparse(ctx->stream, ctx->coeffs.p, ctx->sp_pairs.p, ctx->sp_groups_dev.p, (int)n_expand,
+                           ctx->sp_wide_dev.p, (uint32_t)nw, nullptr);
+    }
+    if (pl.pending_read) {
+      if (!ctx->se_read[pend]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->se_read[pend], hipEventDisableTiming));
+      HIPCHK(ctx, hipEventRecord(ctx->se_read[pend], ctx->stream));
+      ctx->se_read_valid[pend] = true;
+    }
+    if (pl.trade_sets()) ctx->se_live = pend;  // the next epoch's uploads go to the set read two frames ago
+    e.reset(n);
+    e.live = pl.after;
+    if (ctx->sp_expanded) {  // the pair buffer has been consumed (bucketed or expanded)
+      HIPCHK(ctx, hipEventRecord(ctx->sp_expanded, ctx->stream));
+      ctx->sp_expanded_valid = true;
+    }
+  }
+  *sparse_k1 = e.live.form != Resident::kDense;
+  return JXLH_OK;
+}
+
+// everything before K1: upload fences, the coefficient transport, K0b, K3 sigma
 jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
@@ -747,191 +820,7 @@ jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan) {
   for (auto& s : ctx->slots) {
     if (s.used) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s.done, 0));
   }
-  // ---- sparse coefficient transport.  Preferred: K1 reads the pairs itself (bucketed by varblock slot
-  // first) -- possible when every group arrived as pairs in this epoch and no value needed the wide
-  // list.  Otherwise everything ends up in the dense slabs: groups whose content so far lived only in
-  // the bucketed form are expanded from it, this epoch's pairs are zero-filled + scattered.
-  bool sparse_k1 = false;
-  {
-    std::lock_guard<std::mutex> lock(ctx->sp_mutex);
-    if (ctx->epoch_dirty) {
-      ctx->sp_upload.swap(ctx->sp_pending);  // stays alive until the next run: the H2D copies read it
-      ctx->sp_wide_upload.swap(ctx->sp_wide);
-      ctx->sp_pending.clear();
-      ctx->sp_wide.clear();
-      const size_t ng = ctx->sp_upload.size(), nw = ctx->sp_wide_upload.size();
-      if (jxlh_status st = ensure(ctx, ctx->sp_groups_dev, ng)) return st;
-      if (jxlh_status st = ensure(ctx, ctx->sp_wide_dev, nw)) return st;
-      if (jxlh_status st = ensure(ctx, ctx->group_dense, ctx->ngroups)) return st;
-      bool all_pairs = nw == 0 && ng == ctx->ngroups && !(p.flags & JXLH_FRAME_EXPAND_SPARSE) && !plan->want_strip;
-      for (size_t g = 0; all_pairs && g < ctx->ngroups; g++) all_pairs = ctx->touched[g] == 2;
-      // pairs that ADD to a group's earlier passes need that group's dense slab
-      std::vector<uint8_t> accum(ctx->ngroups, 0);
-      for (const SparseGroup& sg : ctx->sp_upload) {
-        if (sg.flags & 1u) {
-          accum[sg.group] = 1;
-          all_pairs = false;
-        }
-      }
-      // every group arrived slot-bucketed (jxlh_submit_groups_slots): the pending set holds the frame the way the
-      // transforms read it -- no sort, no unpacking, no copy
-      bool any_bucketed = false, all_bucketed = all_pairs && ctx->bucketed.size() == ctx->ngroups;
-      for (size_t g = 0; g < ctx->bucketed.size(); g++) {
-        any_bucketed |= ctx->bucketed[g] != 0;
-        all_bucketed = all_bucketed && ctx->bucketed[g] != 0;
-      }
-      const int pend = ctx->se_live ^ 1;
-      // Per-group routing (round 6): every group of the frame arrived in this epoch and MOST of them slot-bucketed and
-      // self-contained -- the others (a dense slab, plain pairs, a value outside the entries' 10 bits in `wide`, a pass
-      // added to earlier content) are brought into their dense slabs and read from there (FrameDev::group_route), the
-      // bucketed ones are still read in place.  Round 5 took the whole frame out of the in-place form for one such group.
-      std::vector<uint8_t> route(ctx->ngroups, 1);
-      size_t n_inplace = 0;
-      bool mixed = false;
-      if (any_bucketed && !all_bucketed && ctx->bucketed.size() == ctx->ngroups &&
-          !(p.flags & JXLH_FRAME_EXPAND_SPARSE) && !plan->want_strip) {
-        bool all_touched = true;
-        for (size_t g = 0; g < ctx->ngroups; g++) all_touched = all_touched && ctx->touched[g] != 0;
-        if (all_touched) {
-          std::vector<uint8_t> wide_group(ctx->ngroups, 0);
-          for (const uint2& w : ctx->sp_wide_upload) wide_group[w.x / (3u * kGroupArea)] = 1;  // (validated at submission)
-          for (size_t g = 0; g < ctx->ngroups; g++) {
-            route[g] = !(ctx->touched[g] == 2 && ctx->bucketed[g] && !accum[g] && !wide_group[g]);
-            n_inplace += route[g] ? 0 : 1;
-          }
-          mixed = 2 * n_inplace >= ctx->ngroups;
-        }
-      }
-      // (the group list is read by the sort and by the expansion: a frame that arrived slot-bucketed needs neither)
-      if (ng && !all_bucketed && !mixed)  // (mixed: only the routed groups' descriptors, below)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sp_groups_dev.p, ctx->sp_upload.data(), ng * sizeof(SparseGroup),
-                                   hipMemcpyHostToDevice, ctx->stream));
-      if (nw)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sp_wide_dev.p, ctx->sp_wide_upload.data(), nw * sizeof(uint2),
-                                   hipMemcpyHostToDevice, ctx->stream));
-      if (ctx->sp_sorted_valid && !all_pairs) {
-        // leaving the bucketed form: groups not resubmitted now (or only added to) need their dense slab -- unless
-        // the slab already was where they lived (a dense-route group of a frame with per-group routing)
-        ctx->flag_upload.assign(ctx->ngroups, 0);
-        bool any = false;
-        const bool had_routes = ctx->route_live.size() == ctx->ngroups;
-        for (size_t g = 0; g < ctx->ngroups; g++)
-          any |= (ctx->flag_upload[g] = ((ctx->touched[g] == 0 || accum[g]) && !(had_routes && ctx->route_live[g])) ? 1 : 0) != 0;
-        if (any) {
-          HIPCHK(ctx, hipMemcpyAsync(ctx->group_dense.p, ctx->flag_upload.data(), ctx->ngroups, hipMemcpyHostToDevice,
-                                     ctx->stream));
-          ScopedKernelTimer t(ctx, "k_expand_sparse");
-          if (ctx->se_valid)
-            launch_expand_entries(ctx->stream, ctx->coeffs.p, ctx->se_entries[ctx->se_live].p, ctx->se_counts[ctx->se_live].p,
-                                  ctx->se_runs[ctx->se_live].p, ctx->group_dense.p, (int)ctx->ngroups);
-          else
-            launch_expand_sorted(ctx->stream, ctx->coeffs.p, ctx->sp_sorted.p, ctx->sp_slot_start.p, ctx->group_dense.p,
-                                 (int)ctx->ngroups);
-        }
-      }
-      if (any_bucketed && !all_bucketed) {
-        // a mixed epoch (other groups as plain pairs or dense slabs, a wide entry, an added pass): the slot-bucketed
-        // groups' entries become pair words at their reserved places of the pair buffer and take the general route
-        if (jxlh_status st = ensure(ctx, ctx->bucketed_dev, ctx->ngroups)) return st;
-        ctx->bucketed_upload = ctx->bucketed;  // stays alive until the next epoch: the copy reads it
-        bool any_widened = !mixed;
-        if (mixed)  // only the bucketed groups that leave the in-place form (often none: the routed group is a dense slab)
-          for (size_t g = 0; g < ctx->ngroups; g++) any_widened |= (ctx->bucketed_upload[g] = ctx->bucketed[g] && route[g]) != 0;
-        if (any_widened) {
-          HIPCHK(ctx, hipMemcpyAsync(ctx->bucketed_dev.p, ctx->bucketed_upload.data(), ctx->ngroups, hipMemcpyHostToDevice,
-                                     ctx->stream));
-          ScopedKernelTimer t(ctx, "k_entries_to_pairs");
-          launch_entries_to_pairs(ctx->stream, ctx->se_entries[pend].p, ctx->se_counts[pend].p, ctx->se_runs[pend].p,
-                                  ctx->bucketed_dev.p, (int)ctx->ngroups, ctx->sp_pairs.p);
-        }
-      }
-      if (all_bucketed || mixed) {
-        // entries per coefficient of the groups that are read in place: from about three times d1's share (0.086 on the
-        // synthetic frame) the 8x8 class is better off running its over-depth batches inline (FrameDev::se_dense_hint;
-        // K1 at x1 / x2 / x4 density: 0.301 / 0.412 / 0.582 ms without, 0.320 / 0.424 / 0.557 with: profiles/r06_c_density.txt)
-        uint64_t entries = 0, groups = 0;
-        for (const SparseGroup& sg : ctx->sp_upload) {
-          if (mixed && route[sg.group]) continue;
-          entries += (uint64_t)sg.n[0] + sg.n[1] + sg.n[2];
-          groups++;
-        }
-        // ... and from about 1.5 times d1's share most 16..32-point batches are beyond the direct path's depth: the
-        // dense dequantisation pass for those classes outright instead of a direct launch that rejects them and a
-        // fallback launch that picks them up (level 1; K1 at x2: 0.405 -> see profiles/r06_p_density.txt)
-        const double share = groups ? (double)entries / (double)(groups * 3 * (uint64_t)kGroupArea) : 0.0;
-        ctx->se_dense_hint = share > 0.25 ? 2 : share > 0.125 ? 1 : 0;
-      }
-      if (all_bucketed) {
-        ctx->se_live = pend;  // the sets trade places: the next epoch's uploads go to the set read two frames ago
-        ctx->se_valid = true;
-        ctx->sp_sorted_valid = true;
-        ctx->route_live.clear();
-        ctx->n_route = 0;
-      } else if (mixed) {
-        // the routed groups' slabs: zero-fill + scatter of their pair words (their own, or the ones the widening above
-        // made of their entries) + the wide values -- or, for an added pass, on top of what the slab holds
-        if (jxlh_status st = ensure(ctx, ctx->route_dev, ctx->ngroups)) return st;
-        ctx->route_upload = route;  // stays alive until the next epoch: the copy reads it
-        HIPCHK(ctx, hipMemcpyAsync(ctx->route_dev.p, ctx->route_upload.data(), ctx->ngroups, hipMemcpyHostToDevice, ctx->stream));
-        // (only the routed groups that arrived as pairs / entries have anything to expand: their descriptors are moved to
-        // the front of the list -- a frame whose only routed group is a dense slab launches nothing here)
-        size_t n_expand = 0;
-        for (size_t i = 0; i < ng; i++)
-          if (route[ctx->sp_upload[i].group]) std::swap(ctx->sp_upload[n_expand++], ctx->sp_upload[i]);
-        if (n_expand)
-          HIPCHK(ctx, hipMemcpyAsync(ctx->sp_groups_dev.p, ctx->sp_upload.data(), n_expand * sizeof(SparseGroup),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        if (n_expand || nw) {
-          ScopedKernelTimer t(ctx, "k_expand_sparse");
-          launch_expand_sparse(ctx->stream, ctx->coeffs.p, ctx->sp_pairs.p, ctx->sp_groups_dev.p, (int)n_expand,
-                               ctx->sp_wide_dev.p, (uint32_t)nw, nullptr);
-        }
-        ctx->se_live = pend;
-        ctx->se_valid = true;
-        ctx->sp_sorted_valid = true;
-        ctx->route_live = route;
-        ctx->n_route = (int)(ctx->ngroups - n_inplace);
-      } else if (all_pairs) {
-        const size_t capacity = ctx->ngroups * 3 * (size_t)kGroupArea;
-        if (jxlh_status st = ensure(ctx, ctx->sp_sorted, capacity)) return st;
-        if (jxlh_status st = ensure(ctx, ctx->sp_slot_start, ctx->ngroups * 3 * (size_t)kSlotTable)) return st;
-        {
-          ScopedKernelTimer t(ctx, "k_sort_sparse");
-          launch_sort_sparse(ctx->stream, ctx->sp_pairs.p, ctx->sp_groups_dev.p, (int)ng, ctx->sp_sorted.p,
-                             ctx->sp_slot_start.p);
-        }
-        ctx->se_valid = false;
-        ctx->sp_sorted_valid = true;
-        ctx->route_live.clear();
-        ctx->n_route = 0;
-      } else {
-        ctx->route_live.clear();
-        ctx->n_route = 0;
-        if (ng || nw) {
-          ScopedKernelTimer t(ctx, "k_expand_sparse");
-          launch_expand_sparse(ctx->stream, ctx->coeffs.p, ctx->sp_pairs.p, ctx->sp_groups_dev.p, (int)ng,
-                               ctx->sp_wide_dev.p, (uint32_t)nw, nullptr);
-        }
-        ctx->se_valid = false;
-        ctx->sp_sorted_valid = false;
-      }
-      if (any_bucketed && !all_bucketed && !mixed) {  // the pending set has been read (it stays the pending one)
-        if (!ctx->se_read[pend]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->se_read[pend], hipEventDisableTiming));
-        HIPCHK(ctx, hipEventRecord(ctx->se_read[pend], ctx->stream));
-        ctx->se_read_valid[pend] = true;
-      }
-      ctx->sp_used = 0;
-      ctx->bucketed.assign(ctx->ngroups, 0);
-      ctx->touched.assign(ctx->ngroups, 0);
-      ctx->epoch_dirty = false;
-      if (ctx->sp_expanded) {  // the pair buffer has been consumed (bucketed or expanded)
-        HIPCHK(ctx, hipEventRecord(ctx->sp_expanded, ctx->stream));
-        ctx->sp_expanded_valid = true;
-      }
-    }
-    sparse_k1 = ctx->sp_sorted_valid;
-  }
-  plan->sparse_k1 = sparse_k1;
+  if (jxlh_status st = apply_coeff_epoch(ctx, plan->want_strip, &plan->sparse_k1)) return st;
   // ---- K0b: Frame::finalize_lf (frame/mod.rs:360-378)
   const bool smooth = p.do_lf_smoothing && f.xblocks > 2 && f.yblocks > 2;  // adaptive_lf_smoothing.rs:51-53
   if (smooth) {
@@ -958,32 +847,33 @@ jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan) {
   // K1 writes the 8x8-tiled layout whenever the fused filter kernel is its only consumer
   plan->will_fuse = !(p.flags & JXLH_FRAME_UNFUSED_FILTERS) && (f.gab || f.epf_iters > 0);
   f.tiled = plan->will_fuse ? 1 : 0;
-  plan->want_strip = plan->want_strip && !sparse_k1;
+  plan->want_strip = plan->want_strip && !plan->sparse_k1;
   return JXLH_OK;
 }
 
 // what the transforms read when the frame is resident in a bucketed sparse form: the slot-bucketed entries in place
 // (se_*) or the sorted pair words (sp_sorted); all null = the dense slabs
 static void set_sparse_view(jxlh_ctx* ctx, FrameDev& f, bool sparse_k1) {
-  const bool ent = sparse_k1 && ctx->se_valid;
+  const CoeffEpoch& e = ctx->epoch;
+  const bool ent = sparse_k1 && e.live.form == Resident::kEntries;
   f.sp_sorted = sparse_k1 && !ent ? ctx->sp_sorted.p : nullptr;
   f.sp_slot_start = sparse_k1 && !ent ? ctx->sp_slot_start.p : nullptr;
   f.se_entries = ent ? ctx->se_entries[ctx->se_live].p : nullptr;
   f.se_counts = ent ? ctx->se_counts[ctx->se_live].p : nullptr;
   f.se_runs = ent ? ctx->se_runs[ctx->se_live].p : nullptr;
   f.group_dense = sparse_k1 ? ctx->group_dense.p : nullptr;
-  f.group_route = ent && ctx->n_route > 0 ? ctx->route_dev.p : nullptr;
-  f.se_dense_hint = ent ? ctx->se_dense_hint : 0;
+  f.group_route = ent && e.live.n_route > 0 ? ctx->route_dev.p : nullptr;
+  f.se_dense_hint = ent ? e.live.se_dense_hint : 0;
   f.k1_stats = ctx->timing ? 1 : 0;
 }
-static int dense_route_groups(const jxlh_ctx* ctx, bool sparse_k1) { return sparse_k1 && ctx->se_valid ? ctx->n_route : 0; }
+static int dense_route_groups(const jxlh_ctx* ctx, bool sparse_k1) { return sparse_k1 ? ctx->epoch.live.n_route : 0; }
 // behind the transforms: the coefficient slabs are free again (dense resubmissions of the next frame wait for this,
 // jxlh_submit_group), and so is the live set of the slot-bucketed form once it has become the pending one
 static jxlh_status mark_coefficients_read(jxlh_ctx* ctx, bool sparse_k1) {
   if (!ctx->k1_done) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->k1_done, hipEventDisableTiming));
   HIPCHK(ctx, hipEventRecord(ctx->k1_done, ctx->stream));
   ctx->k1_done_valid = true;
-  if (sparse_k1 && ctx->se_valid) {
+  if (sparse_k1 && ctx->epoch.live.form == Resident::kEntries) {
     const int l = ctx->se_live;
     if (!ctx->se_read[l]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->se_read[l], hipEventDisableTiming));
     HIPCHK(ctx, hipEventRecord(ctx->se_read[l], ctx->stream));
@@ -1104,9 +994,7 @@ jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan) {
   }
   f.strip_desc = nullptr;  // band runs / re-renders of this frame take the two-kernel path
   f.strip_mode = nullptr;
-  if (!ctx->k1_done) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->k1_done, hipEventDisableTiming));
-  HIPCHK(ctx, hipEventRecord(ctx->k1_done, ctx->stream));
-  ctx->k1_done_valid = true;
+  if (jxlh_status st = mark_coefficients_read(ctx, false)) return st;
   ctx->chroma_lazy = false;
   ctx->rendered = true;
   ctx->strip_ran = true;

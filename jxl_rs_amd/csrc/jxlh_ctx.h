@@ -116,54 +116,34 @@ struct jxlh_ctx {
   DevBuf<unsigned long long> flow_prof;
   bool flow_prof_on = false;
   int flow_prof_levels = 0;
-  // sparse coefficient transport (jxlh_submit_group(s)_sparse): pairs land in sp_pairs (bump
-  // allocated, sized for a frame's worst case), are expanded by the next jxlh_frame_run
+  // coefficient transport: what this epoch's submissions were and in which form the frame is resident (coeff_epoch.h);
+  // the device buffers those forms live in.  Pairs land in sp_pairs (bump allocated, sized for a frame's worst case).
   std::mutex sp_mutex;
+  CoeffEpoch epoch;
   DevBuf<uint32_t> sp_pairs;
   DevBuf<SparseGroup> sp_groups_dev;
   DevBuf<uint2> sp_wide_dev;
-  std::vector<SparseGroup> sp_pending, sp_upload;
-  std::vector<uint2> sp_wide, sp_wide_upload;
-  size_t sp_used = 0;
-  hipEvent_t sp_expanded = nullptr;
+  hipEvent_t sp_expanded = nullptr;  // recorded behind what consumed the pair buffer (the next epoch's uploads wait)
   bool sp_expanded_valid = false;
   // recorded behind the transforms of every jxlh_frame_run: dense resubmissions wait for it
   hipEvent_t k1_done = nullptr;
   bool k1_done_valid = false;
   size_t worklist_nblocks = 0;  // the frame size the work list's fallback flags were last zeroed for
   uint32_t k1_launches = 0;  // parity selects the work-list counter set (vardct_worklist_reset / launch_vardct_groups)
-  // K1 reading the pairs directly: the frame's pairs bucketed by varblock slot + slot tables.  Valid
-  // while every group of the frame has been submitted sparse (once) and nothing was resubmitted.
+  // Resident::kSortedPairs: the frame's pairs bucketed by varblock slot + slot tables
   DevBuf<uint32_t> sp_sorted, sp_slot_start;
   DevBuf<uint8_t> group_dense;
-  // Epochs: the submissions between two jxlh_frame_run calls.  touched[g]: 0 not resubmitted (keeps its
-  // content), 1 dense slab, 2 pairs.  sp_sorted_valid: before this epoch every group's content lived in
-  // the bucketed form (and only there).
-  std::vector<uint8_t> touched, flag_upload;
-  // groups submitted in the slot-bucketed form in this epoch (jxlh_submit_groups_slots): their entries, slot counts
-  // and run descriptors sit in se_*[se_live ^ 1] exactly as uploaded.  If that is every group (and nothing is added to
-  // earlier passes), jxlh_frame_run makes that set the live one and the transforms read it in place (round 5; round 4
-  // unpacked it into pair words + slot tables at submission time, overwriting the tables the resident frame was read
-  // through); otherwise the flagged groups' entries are widened into the pair buffer first.
-  std::vector<uint8_t> bucketed, bucketed_upload;
-  DevBuf<uint8_t> bucketed_dev;
-  // The two sets trade places when a frame arrives entirely slot-bucketed, so the uploads of frame i + 1 never touch
-  // what the transforms of frame i read; se_read[i]: recorded behind the last kernels that read set i.
+  DevBuf<uint8_t> bucketed_dev;  // EpochPlan::widen on the device
+  // Resident::kEntries: the transforms read the live set se_*[se_live] as uploaded, the next epoch's entries go to the
+  // pending set se_*[se_live ^ 1]; the two trade places when a frame arrives slot-bucketed, so the uploads of frame i + 1
+  // never touch what the transforms of frame i read.  se_read[i]: recorded behind the last kernels that read set i.
   DevBuf<uint16_t> se_entries[2];
   DevBuf<uint8_t> se_counts[2];
   DevBuf<uint2> se_runs[2];
   hipEvent_t se_read[2] = {nullptr, nullptr};
   bool se_read_valid[2] = {false, false};
   int se_live = 0;
-  bool se_valid = false;  // the resident bucketed form is se_*[se_live] (else, with sp_sorted_valid, the pair words)
-  bool epoch_dirty = false;
-  bool sp_sorted_valid = false;
-  // per-group routing of a frame that is resident in the slot-bucketed form (round 6): route_live[g] != 0 = group g
-  // lives in its dense slab, not in the live set (empty = no routed group); route_dev the device copy the scan reads
-  std::vector<uint8_t> route_live, route_upload;
-  DevBuf<uint8_t> route_dev;
-  int n_route = 0;
-  int se_dense_hint = 0;       // FrameDev::se_dense_hint of the live set
+  DevBuf<uint8_t> route_dev;  // Residence::route on the device (FrameDev::group_route)
   // extra channels inside the frame path (jxlh_frame_set_extra_channel): as handed over, converted, upsampled
   struct ExtraChannel {
     bool set = false, done = false;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/jxl_hip.h"
+#include "coeff_epoch.h"
 
 namespace jxlh {
 // 16-byte global accesses with a selectable cache policy (NT = streamed once: `nt` loads / stores)
@@ -307,13 +308,6 @@ void launch_xyb_to_rgb8(hipStream_t s, const float* const planes[3], size_t stri
                         const XybParamsDev& q, const TfParamsDev& t, int channels, uint8_t* out, size_t out_stride);
 void launch_xyb_to_rgb16(hipStream_t s, const float* const planes[3], size_t stride, int w, int y0, int rows, int mode,
                          const XybParamsDev& q, const TfParamsDev& t, int channels, uint16_t* out, size_t out_stride_elems);
-// sparse coefficient transport (k_coeffs.hip): one descriptor per submitted group
-struct SparseGroup {
-  uint32_t group;   // group id
-  uint32_t offset;  // index of the group's first pair in the pair buffer (X pairs, then Y, then B)
-  uint32_t n[3];    // pairs per channel
-  uint32_t flags;   // bit 0: add the pairs to the group's current slab instead of starting from zero
-};
 // only_flagged (nullable): expand a group only if only_flagged[group] != 0
 void launch_pack_pairs8(hipStream_t s, const uint16_t* pos, const int8_t* val, size_t n, uint32_t* pairs);
 // the 2-byte form (jxlh_submit_groups_sparse4): n_runs = groups of the batch x 3, desc = 4 words per run, see k_coeffs.hip

@@ -220,6 +220,37 @@ def test_group_resubmitted_in_another_form_inside_one_epoch(ctx, oracle):
     check(ctx, oracle_frame(oracle, wl, want), "slots then dense")
 
 
+@pytest.mark.parametrize("form", ["pairs", "slots"])
+def test_dense_slab_drops_the_wide_values_it_replaces(ctx, oracle, form):
+    """a slab always replaces the group's coefficients: sparse pairs (or slot-bucketed entries) with values in `wide`
+    for group 1, then a dense slab of group 1 inside the same epoch -- the slab drops the wide values along with the
+    pairs (pairs: the general expansion; slots: the frame stays in place, group 1 routed to its slab)"""
+    from jxl_rs_amd import synth, lib
+    wl = synth.make_vardct(300, 520, mix=synth.MIX_D1, seed=53, epf_iters=1)  # 2 x 3 groups
+    c1, c2 = split_passes(wl.coeffs, 29)
+    g, ng = 1, wl.coeffs.shape[0]
+    rng = np.random.default_rng(53)
+    flat = c1[g].reshape(-1)
+    sel = rng.choice(np.flatnonzero(flat), size=6, replace=False)
+    flat[sel] = rng.integers(60000, 900000, size=6) * rng.choice([-1, 1], size=6)  # beyond i16 and the entries' split
+    begin(ctx, wl)
+    if form == "pairs":
+        for h in range(ng):
+            ctx.submit_group_sparse(h, *synth.to_sparse(c1[h]))
+    else:
+        parts = [lib.host_pack_slots(c1[h], group_id=h) for h in range(ng)]
+        assert len(parts[g][3]) == 6
+        ctx.submit_groups_slots(np.arange(ng, dtype=np.uint32), np.concatenate([q[0] for q in parts]),
+                                np.concatenate([q[1].reshape(-1) for q in parts]), np.concatenate([q[2] for q in parts]),
+                                np.concatenate([q[3] for q in parts if len(q[3])]))
+    ctx.submit_group(g, c2[g])
+    ctx.slot_wait(0)
+    ctx.frame_run()
+    want = c1.copy()
+    want[g] = c2[g]
+    check(ctx, oracle_frame(oracle, wl, want), f"{form} with wide values, then a dense slab of the group")
+
+
 def test_slots_argument_errors_leave_the_epoch_intact(ctx, oracle):
     """a rejected jxlh_submit_groups_slots call reserves nothing -- the group can be submitted again"""
     from jxl_rs_amd import synth, lib, JxlHipError
