@@ -258,6 +258,14 @@ impl<'a> VarDctFrame<'a> {
     pub fn finalize_and_render(&self) -> Result<()> {
         self.ctx.ok(unsafe { sys::jxlh_frame_run(self.ctx.raw, 0, u32::MAX) })
     }
+    /// The colour stage (`None`: the planes are in the output colour space already), `BlendingStage` and
+    /// `ExtendToImageDimensionsStage` (frame/render.rs:754-771): the rendered frame composed onto the
+    /// `image_w x image_h` image from the context's reference slots.  The image becomes what the read calls and
+    /// `jxlh_frame_save_reference` see, until the next render.
+    pub fn blend(&self, desc: &sys::jxlh_blend_desc, colour: Option<&sys::jxlh_output_desc>) -> Result<()> {
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        self.ctx.ok(unsafe { sys::jxlh_frame_blend(self.ctx.raw, desc, colour) })
+    }
     /// `mark_group_to_rerender` + re-render (render/mod.rs:143-146): after more passes arrived for `groups`
     pub fn rerender_groups(&self, groups: &[u32]) -> Result<()> {
         self.ctx.ok(unsafe { sys::jxlh_frame_rerender_groups(self.ctx.raw, groups.as_ptr(), groups.len() as u32) })

@@ -531,9 +531,9 @@ jxlh_status jxlh_frame_read_lf(jxlh_ctx* ctx, float* x, float* y, float* b, size
  * host or device memory; for host memory the call returns after the copy has completed.
  * The parameters are the reference's XybParams::new(opsin, intensity_target) (xyb.rs:147-163):
  * inverse matrix, cbrt(biases), biases * intensity_scale, intensity_scale = 255 / intensity_target.
- * Frames whose output colour space is not sRGB/D65 with the sRGB transfer function, or that need
- * upsampling / blending / extra channels, keep the reference's CPU stages (JXLH_ERR_UNSUPPORTED is the
- * caller's decision: this entry point does what it says). */
+ * Frames whose output colour space is not sRGB/D65 with the sRGB transfer function go through
+ * jxlh_frame_read_output, frames that need blending through jxlh_frame_blend first (this entry point does
+ * what it says). */
 typedef struct jxlh_xyb_params {
   float opsin_inverse_matrix[9];
   float bias_cbrt[3];
@@ -587,6 +587,63 @@ jxlh_status jxlh_frame_read_output(jxlh_ctx* ctx, const jxlh_output_desc* d, uin
 /* without the final wait, like jxlh_frame_read_rgb8_async: `out` is valid after the next jxlh_ctx_sync */
 jxlh_status jxlh_frame_read_output_async(jxlh_ctx* ctx, const jxlh_output_desc* d, uint32_t y0, uint32_t y1, void* out,
                                          size_t bytes_per_row);
+
+/* ---------------------------------------------------------------- frame blending (render/stages/blending.rs, extend.rs)
+ * How the reference closes a frame that needs_blending() (headers/frame_header.rs:540-552: every cropped frame, every
+ * colour or extra-channel blend mode other than Replace -- animation deltas, layers, alpha compositing), as
+ * frame/render.rs:754-791 orders it: colour stage, BlendingStage, ExtendToImageDimensionsStage, save into the reference
+ * slot, conversion.
+ * jxlh_frame_blend, on the context's stream without host synchronisation, in one pass over the image:
+ *   1. the colour stage named by `colour` (color, transfer, xyb, tf_param, hlg_luminance_rgb; bits / channels are
+ *      ignored; NULL = JXLH_COLOR_NONE) on the frame's three result planes, kept in f32;
+ *   2. BlendingStage::process_row_chunk (blending.rs:97-166): the frame is perform_blending's bg, the slot named by
+ *      `source` its fg, read at image coordinates (x0 + x, y0 + y).  Colour reads channels 0..2 of color.source, extra
+ *      channel i reads channel 3 + i of ec[i].source; a slot that is not set is a row of zeros.  Modes map as
+ *      From<&BlendingInfo> for PatchBlending does (blending.rs:41-56): Replace -> None, Add -> Add, Mul -> Mul,
+ *      Blend -> BlendBelow, AlphaWeightedAdd -> AlphaWeightedAddBelow.  Frame pixels outside the image are dropped;
+ *   3. ExtendToImageDimensionsStage (extend.rs:59-84): every image pixel outside the frame's rectangle takes the value
+ *      of that channel's source slot, or zero.
+ * The image_w x image_h set of 3 + num_ec planes BECOMES THE FRAME'S RESULT: jxlh_frame_read_planes / _rect /
+ * jxlh_frame_device_planes return the composed colour planes, jxlh_frame_read_extra_channel the composed extra channels
+ * (image-sized), jxlh_frame_save_reference saves them (the !save_before_ct save, render.rs:780-791), and the output
+ * calls with JXLH_COLOR_NONE convert them to 8 / 16 bit; an output call with any other colour stage returns
+ * JXLH_ERR_BAD_STATE (the stage has run already).  The frame is the result of the last whole-frame render
+ * (JXLH_ERR_BAD_STATE without one) at the result's size (the upsampled size of an upsampled frame); its extra channels
+ * are the converted / upsampled / patched planes jxlh_frame_save_reference would save, under the same conditions.  The
+ * call reads the frame's own planes and the slots and writes a separate canvas: calling it again gives the same canvas.
+ * A later jxlh_frame_run / jxlh_frame_rerender_groups discards the composition (the result is the frame's own planes
+ * again), jxlh_frame_begin does too.
+ * JXLH_ERR_INVALID_ARGUMENT, checked before anything is launched (an earlier composition stays as it is): mode > 4,
+ * source >= 4, num_ec > 8, num_ec != the number of extra channels handed to the frame, alpha_channel >= num_ec for
+ * Blend / AlphaWeightedAdd when num_ec > 0 (the reference's header check; the field is not read for other modes),
+ * image_w * image_h zero or >= 2^31, a set source slot smaller than the image or with n_channels != 3 + num_ec.
+ * Sharded contexts: JXLH_ERR_UNSUPPORTED.
+ * jxlh_stage_blend: the same kernel on caller planes (host or device): frame[] are n_channels = 3 + num_ec planes of
+ * w x h at row stride `stride` floats, already in the output colour space; out[] as many image_w x image_h planes at
+ * row stride out_stride.  The Modular seam and tests.
+ * Not done here: alpha taken from an extra channel into the interleaved 8 / 16-bit output, premultiplication, spot
+ * colours, splines. */
+/* BlendingMode (headers/frame_header.rs:98-104) */
+enum {
+  JXLH_BLEND_REPLACE = 0, JXLH_BLEND_ADD = 1, JXLH_BLEND_BLEND = 2, JXLH_BLEND_ALPHA_WEIGHTED_ADD = 3, JXLH_BLEND_MUL = 4
+};
+typedef struct jxlh_blending_info { /* BlendingInfo (frame_header.rs:114-140) */
+  uint32_t mode;           /* JXLH_BLEND_* */
+  uint32_t alpha_channel;  /* extra channel index */
+  uint32_t clamp;          /* 0 / 1 */
+  uint32_t source;         /* reference slot */
+} jxlh_blending_info;
+typedef struct jxlh_blend_desc {
+  int32_t x0, y0;             /* FrameHeader::x0, y0: the frame's origin in the image, may be negative */
+  uint32_t image_w, image_h;  /* FileHeader::size */
+  jxlh_blending_info color;   /* FrameHeader::blending_info */
+  uint32_t num_ec;
+  jxlh_blending_info ec[8];   /* FrameHeader::ec_blending_info */
+  uint32_t ec_flags[8];       /* JXLH_EC_* per extra channel, as for jxlh_frame_set_patches */
+} jxlh_blend_desc;
+jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* desc, const jxlh_output_desc* colour);
+jxlh_status jxlh_stage_blend(jxlh_ctx* ctx, const jxlh_blend_desc* desc, const float* const frame[], uint32_t n_channels,
+                             uint32_t w, uint32_t h, size_t stride, float* const out[], size_t out_stride);
 
 /* ---------------------------------------------------------------- stage-level hooks */
 /* Whole-image single stages with the pipeline's mirror edge semantics; the analogue of

@@ -126,8 +126,16 @@ class VarDctFrame {
   }
   // the save_before_ct save stage: the rendered frame becomes reference frame `slot`
   void save_reference(uint32_t slot) { ctx_.check(jxlh_frame_save_reference(ctx_.raw(), slot), "jxlh_frame_save_reference"); }
+  // the colour stage (null: none), BlendingStage and ExtendToImageDimensionsStage (frame/render.rs:754-771): the rendered
+  // frame composed onto the image from the reference slots; the image becomes what the read calls and save_reference see
+  void blend(const jxlh_blend_desc& desc, const jxlh_output_desc* colour = nullptr) {
+    ctx_.check(jxlh_frame_blend(ctx_.raw(), &desc, colour), "jxlh_frame_blend");
+    blend_w_ = desc.image_w;
+    blend_h_ = desc.image_h;
+  }
   // finalize_lf + SigmaSource::new + transforms + the frame's stage list, for group rows [row0, row1)
   void finalize_and_render(uint32_t group_row0 = 0, uint32_t group_row1 = 0xFFFFFFFFu) {
+    blend_w_ = blend_h_ = 0;  // a render discards the composition
     ctx_.check(jxlh_frame_run(ctx_.raw(), group_row0, group_row1), "jxlh_frame_run");
   }
   // tight f32 planes X, Y, B of out_width() x out_height()
@@ -159,10 +167,12 @@ class VarDctFrame {
                "jxlh_frame_read_output");
   }
   uint32_t out_width() const {
+    if (blend_w_) return blend_w_;
     const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;
     return p_.xsize_upsampled ? p_.xsize_upsampled : p_.xsize * n;
   }
   uint32_t out_height() const {
+    if (blend_h_) return blend_h_;
     const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;
     return p_.ysize_upsampled ? p_.ysize_upsampled : p_.ysize * n;
   }
@@ -170,6 +180,7 @@ class VarDctFrame {
  private:
   Context& ctx_;
   jxlh_frame_params p_;
+  uint32_t blend_w_ = 0, blend_h_ = 0;  // the image the frame was blended onto (0: not blended)
 };
 
 }  // namespace jxlh

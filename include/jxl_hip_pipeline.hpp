@@ -164,7 +164,30 @@ struct PatchesStage {
   std::string display() const { return "patches"; }
   bool uses_channel(int) const { return true; }
 };
-// A stage of the reference this path does not run on the device (patches by name, splines, blending, extend, spot colour,
+// BlendingStage (render/stages/blending.rs:17-27, added at frame/render.rs:765-771 when needs_blending()): the fields
+// BlendingStage::new takes from the frame and file headers that matter on the device -- the reference frames it reads
+// are the context's slots.  In place on the colour and extra channels.
+struct BlendingStage {
+  int32_t x0, y0;                                    // frame_origin
+  uint32_t image_w, image_h;                         // image_size
+  jxlh_blending_info blending_info;
+  std::vector<jxlh_blending_info> ec_blending_info;  // one per extra channel
+  std::vector<uint32_t> ec_flags;                    // JXLH_EC_* of each extra channel (extra_channels)
+  static constexpr Border BORDER{0, 0}, SHIFT{0, 0};
+  std::string display() const { return "blending"; }
+  bool uses_channel(int c) const { return c < 3 + (int)ec_blending_info.size(); }
+};
+// ExtendToImageDimensionsStage (render/stages/extend.rs:22-50, add_extend_stage at frame/render.rs:766-771): built from
+// the same headers as the BlendingStage in front of it
+struct ExtendToImageDimensionsStage {
+  int32_t x0, y0;
+  uint32_t image_w, image_h;
+  jxlh_blending_info blending_info;
+  std::vector<jxlh_blending_info> ec_blending_info;
+  std::string display() const { return "extend-to-image-dims"; }
+  bool uses_channel(int) const { return true; }
+};
+// A stage of the reference this path does not run on the device (patches by name, splines, spot colour,
 // premultiplied alpha, extra-channel conversions ...): adding one makes build() fail with JXLH_ERR_UNSUPPORTED.
 struct CpuOnlyStage {
   std::string name;
@@ -187,7 +210,8 @@ struct SaveStage {
 
 using Stage = std::variant<ConvertModularToF32Stage, ConvertModularXYBToF32Stage, HorizontalChromaUpsample, VerticalChromaUpsample, GaborishStage, Epf0Stage, Epf1Stage, Epf2Stage,
                            Upsample2x, Upsample4x, Upsample8x, ConvolveNoiseStage, AddNoiseStage, XybStage, YcbcrToRgbStage,
-                           FromLinearStage, ConvertF32ToU8Stage, ConvertF32ToU16Stage, CpuOnlyStage, SaveStage, PatchesStage>;
+                           FromLinearStage, ConvertF32ToU8Stage, ConvertF32ToU16Stage, CpuOnlyStage, SaveStage, PatchesStage,
+                           BlendingStage, ExtendToImageDimensionsStage>;
 
 inline std::string stage_display(const Stage& s) {
   return std::visit([](const auto& st) { return st.display(); }, s);
@@ -217,6 +241,12 @@ struct LoweredPipeline {
   // PatchesStage: the dictionary build() hands to jxlh_frame_set_patches
   bool has_patches = false;
   PatchesStage patches;
+  // BlendingStage + ExtendToImageDimensionsStage: do_render() ends in jxlh_frame_blend(blend, blend_colour).  The colour
+  // stage of the list runs inside that call (blend_colour), so `output.color` is JXLH_COLOR_NONE
+  bool has_blend = false;
+  jxlh_blend_desc blend{};
+  jxlh_output_desc blend_colour{};
+  uint32_t out_w = 0, out_h = 0;  // what the save stages see: the frame's (upsampled) size, or the image's when blending
   std::vector<std::string> stages;  // Display strings, in order (diagnostics; what `info!("adding stage")` logs)
 };
 
@@ -248,8 +278,13 @@ class RenderPipelineBuilder {
     stages_.emplace_back(SaveStage{std::move(channels), output_buffer_index, color_channels, bits});
     return std::move(*this);
   }
-  RenderPipelineBuilder add_extend_stage() && {
+  RenderPipelineBuilder add_extend_stage() && {  // without the stage's arguments there is nothing to lower
     stages_.emplace_back(CpuOnlyStage{"extend to image dimensions"});
+    return std::move(*this);
+  }
+  // builder.rs add_extend_stage(ExtendToImageDimensionsStage::new(frame_header, file_header, reference_frames))
+  RenderPipelineBuilder add_extend_stage(ExtendToImageDimensionsStage stage) && {
+    stages_.emplace_back(std::move(stage));
     return std::move(*this);
   }
 
@@ -296,6 +331,11 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   uint32_t convert_bits = 0;
   bool have_colour = false, have_tf = false, have_save = false, pre_upsample = true, epf1_seen = false, epf2_seen = false;
   bool patches_seen = false;
+  // BlendingStage must be followed at once by the extend stage (frame/render.rs:765-771)
+  bool blend_seen = false, extend_seen = false, expect_extend = false;
+  auto same_info = [](const jxlh_blending_info& a, const jxlh_blending_info& b) {
+    return a.mode == b.mode && a.alpha_channel == b.alpha_channel && a.clamp == b.clamp && a.source == b.source;
+  };
   Border border{0, 0};
   auto add_border = [&](Border b) {
     if (pre_upsample) {
@@ -309,8 +349,47 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   lp.output.channels = 3;
   for (const Stage& s : stages_) {
     lp.stages.push_back(stage_display(s));
+    if (expect_extend && !std::holds_alternative<ExtendToImageDimensionsStage>(s))
+      fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "' between the blending stage and the extend stage");
+    if (blend_seen && (std::holds_alternative<XybStage>(s) || std::holds_alternative<YcbcrToRgbStage>(s) ||
+                       std::holds_alternative<FromLinearStage>(s)))
+      fail(JXLH_ERR_INVALID_ARGUMENT, "blending / extend stage before the colour stage '" + stage_display(s) + "'");
     if (const auto* st = std::get_if<CpuOnlyStage>(&s)) {
       fail(JXLH_ERR_UNSUPPORTED, "stage '" + st->name + "' is not part of the device path");
+    } else if (const auto* bl = std::get_if<BlendingStage>(&s)) {
+      // the reference's position: behind the colour stage, in front of the conversions (frame/render.rs:754-779)
+      if (blend_seen) fail(JXLH_ERR_INVALID_ARGUMENT, "two blending stages");
+      if (phase > kConvert || convert_seen) fail(JXLH_ERR_INVALID_ARGUMENT, "blending stage behind the conversion / save stages");
+      if (lp.modular != LoweredPipeline::Modular::kNone)
+        fail(JXLH_ERR_UNSUPPORTED, "blending on a Modular frame (jxlh_stage_blend on the planes instead)");
+      const size_t nec = bl->ec_blending_info.size();
+      size_t named = 0;
+      while (named < JXLH_MAX_EXTRA_CHANNELS && lp.extra[named].bits) named++;
+      if (nec > JXLH_MAX_EXTRA_CHANNELS || bl->ec_flags.size() != nec || nec != named)
+        fail(JXLH_ERR_INVALID_ARGUMENT, "blending: one ec_blending_info and one flag word per extra channel of the list");
+      blend_seen = expect_extend = true;
+      lp.has_blend = true;
+      lp.blend = jxlh_blend_desc{};
+      lp.blend.x0 = bl->x0;
+      lp.blend.y0 = bl->y0;
+      lp.blend.image_w = bl->image_w;
+      lp.blend.image_h = bl->image_h;
+      lp.blend.color = bl->blending_info;
+      lp.blend.num_ec = (uint32_t)nec;
+      for (size_t i = 0; i < nec; i++) {
+        lp.blend.ec[i] = bl->ec_blending_info[i];
+        lp.blend.ec_flags[i] = bl->ec_flags[i];
+      }
+      phase = kConvert;
+    } else if (const auto* ex = std::get_if<ExtendToImageDimensionsStage>(&s)) {
+      if (!expect_extend) fail(JXLH_ERR_INVALID_ARGUMENT, extend_seen ? "two extend stages" : "extend stage without a blending stage in front of it");
+      bool same = ex->x0 == lp.blend.x0 && ex->y0 == lp.blend.y0 && ex->image_w == lp.blend.image_w &&
+                  ex->image_h == lp.blend.image_h && same_info(ex->blending_info, lp.blend.color) &&
+                  ex->ec_blending_info.size() == lp.blend.num_ec;
+      for (size_t i = 0; same && i < ex->ec_blending_info.size(); i++) same = same_info(ex->ec_blending_info[i], lp.blend.ec[i]);
+      if (!same) fail(JXLH_ERR_INVALID_ARGUMENT, "blending and extend stages built from different headers");
+      expect_extend = false;
+      extend_seen = true;
     } else if (const auto* m = std::get_if<ConvertModularToF32Stage>(&s)) {
       enter(kModular, s);
       if (m->bit_depth < 1 || m->bit_depth > 31) fail(JXLH_ERR_INVALID_ARGUMENT, "bit depth");
@@ -512,6 +591,12 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   if (convert_seen != 0 && convert_seen != 3) fail(JXLH_ERR_INVALID_ARGUMENT, "integer conversion on some channels only");
   if (!have_save) fail(JXLH_ERR_INVALID_ARGUMENT, "no save stage");
   if (lp.has_output && lp.output.color == JXLH_COLOR_NONE && have_tf) fail(JXLH_ERR_INVALID_ARGUMENT, "transfer function without colour stage");
+  if (expect_extend) fail(JXLH_ERR_INVALID_ARGUMENT, "blending stage without the extend stage behind it");
+  if (lp.has_blend) {  // the colour stage runs inside jxlh_frame_blend; the conversion reads the composed image as it is
+    lp.blend_colour = lp.output;
+    lp.output.color = JXLH_COLOR_NONE;
+    lp.output.transfer = JXLH_TF_LINEAR;
+  }
   // size = FrameHeader::size_upsampled() (builder.rs:70-85): the frame itself is size >> downsampling_shift
   const uint32_t n = p.upsampling;
   if (size_.first == 0 || size_.second == 0) fail(JXLH_ERR_INVALID_ARGUMENT, "empty frame");
@@ -524,6 +609,8 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
     fail(JXLH_ERR_INVALID_ARGUMENT, "pipeline size and frame size disagree");
   }
   lp.input_border = border;
+  lp.out_w = lp.has_blend ? lp.blend.image_w : (uint32_t)size_.first;
+  lp.out_h = lp.has_blend ? lp.blend.image_h : (uint32_t)size_.second;
   return lp;
 }
 
@@ -553,9 +640,9 @@ class GpuRenderPipeline {
   void render_outside_frame() {}
   // render/mod.rs:138: the caller's buffer must hold out_height rows of out_width * channels samples
   void check_buffer_sizes(size_t bytes_per_row, size_t rows) const {
-    const size_t need = lp_.has_output ? (size_t)frame_.out_width() * lp_.output.channels * (lp_.output.bits / 8)
-                                       : (size_t)frame_.out_width() * sizeof(float);
-    if (bytes_per_row < need || rows < frame_.out_height())
+    const size_t need = lp_.has_output ? (size_t)lp_.out_w * lp_.output.channels * (lp_.output.bits / 8)
+                                       : (size_t)lp_.out_w * sizeof(float);
+    if (bytes_per_row < need || rows < lp_.out_h)
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::check_buffer_sizes", "output buffer too small");
   }
   // what the reference does when the last group of a pass has been handed over (frame/decode.rs:547-558, :703-711)
@@ -566,6 +653,8 @@ class GpuRenderPipeline {
     } else {
       frame_.finalize_and_render();
     }
+    // BlendingStage + extend (with the list's colour stage in front): the image becomes what the save stages read
+    if (lp_.has_blend) frame_.blend(lp_.blend, &lp_.blend_colour);
     dirty_first_ = false;
     rerender_.clear();
   }

@@ -1,0 +1,205 @@
+// C ABI of frame blending: BlendingStage + ExtendToImageDimensionsStage (jxl/src/render/stages/blending.rs, extend.rs)
+// behind the frame's colour stage, as frame/render.rs:754-791 chains them.  jxlh_frame_blend composes the current frame's
+// result onto an image-sized canvas that becomes the frame's result; jxlh_stage_blend runs the same kernel (k_blend.hip)
+// on caller planes.
+#include <algorithm>
+
+#include "blend_device.h"
+#include "jxlh_ctx.h"
+
+namespace jxlh_host {
+
+namespace {
+
+// the descriptor's own checks (no frame or plane involved), and the source slots against the image
+jxlh_status check_desc(const jxlh_ctx* ctx, const jxlh_blend_desc* d) {
+  if (!d || d->num_ec > JXLH_MAX_EXTRA_CHANNELS) return JXLH_ERR_INVALID_ARGUMENT;
+  if (d->image_w == 0 || d->image_h == 0 || (uint64_t)d->image_w * d->image_h >= (1ull << 31))
+    return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k <= d->num_ec; k++) {
+    const jxlh_blending_info& b = k == 0 ? d->color : d->ec[k - 1];
+    if (b.mode > JXLH_BLEND_MUL || b.source >= JXLH_MAX_REFERENCE_FRAMES) return JXLH_ERR_INVALID_ARGUMENT;
+    // the reference's header check (frame_header.rs, test_invalid_blending_alpha_channel); not read for other modes
+    const bool alpha_mode = b.mode == JXLH_BLEND_BLEND || b.mode == JXLH_BLEND_ALPHA_WEIGHTED_ADD;
+    if (alpha_mode && d->num_ec > 0 && b.alpha_channel >= d->num_ec) return JXLH_ERR_INVALID_ARGUMENT;
+    const jxlh_ctx::RefSlot& r = ctx->refs[b.source];
+    if (r.set && (r.w < d->image_w || r.h < d->image_h || r.n_channels != 3 + d->num_ec)) return JXLH_ERR_INVALID_ARGUMENT;
+  }
+  return JXLH_OK;
+}
+
+// From<&BlendingInfo> for PatchBlending (blending.rs:41-56)
+uint32_t map_blending(const jxlh_blending_info& b, uint32_t num_ec) {
+  static const uint32_t mode[5] = {kBlendNone, kBlendAdd, kBlendBelow, kBlendAddBelow, kBlendMul};
+  const bool alpha_mode = b.mode == JXLH_BLEND_BLEND || b.mode == JXLH_BLEND_ALPHA_WEIGHTED_ADD;
+  return pack_blending(mode[b.mode], alpha_mode && num_ec > 0 ? b.alpha_channel : 0, b.clamp != 0);
+}
+
+// everything of the launch the descriptor and the slots decide (checked by check_desc)
+void fill_desc(const jxlh_ctx* ctx, const jxlh_blend_desc* d, BlendLaunch& a) {
+  // an origin beyond +-2^30 leaves the frame wholly outside the image, and so does the clamped one
+  a.x0 = std::min(std::max(d->x0, -(1 << 30)), 1 << 30);
+  a.y0 = std::min(std::max(d->y0, -(1 << 30)), 1 << 30);
+  a.iw = (int)d->image_w;
+  a.ih = (int)d->image_h;
+  a.ec_alpha = a.ec_assoc = 0;
+  for (uint32_t k = 0; k <= d->num_ec; k++) a.blend[k] = map_blending(k == 0 ? d->color : d->ec[k - 1], d->num_ec);
+  for (uint32_t i = 0; i < d->num_ec; i++) {
+    if (d->ec_flags[i] & JXLH_EC_ALPHA) a.ec_alpha |= 1u << i;
+    if (d->ec_flags[i] & JXLH_EC_ALPHA_ASSOCIATED) a.ec_assoc |= 1u << i;
+  }
+  for (uint32_t c = 0; c < 3 + d->num_ec; c++) {
+    const jxlh_ctx::RefSlot& r = ctx->refs[c < 3 ? d->color.source : d->ec[c - 3].source];
+    a.src[c] = r.set ? r.buf.p + (size_t)c * r.stride * r.h : nullptr;
+    a.src_stride[c] = r.set ? (uint32_t)r.stride : 0;
+  }
+}
+
+// the kernel works in int: sides up to 2^30 (the codestream's own limit) keep every x0 + w and tile edge below 2^31
+bool sides_ok(const jxlh_blend_desc* d, uint32_t w, uint32_t h) {
+  const uint32_t lim = 1u << 30;
+  return d->image_w <= lim && d->image_h <= lim && w <= lim && h <= lim;
+}
+
+}  // namespace
+
+void blend_release(jxlh_ctx* ctx) {
+  release(ctx->blend_canvas);
+  release(ctx->blend_hook_in);
+  release(ctx->blend_hook_out);
+}
+
+}  // namespace jxlh_host
+
+extern "C" {
+
+jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh_output_desc* colour) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !d) return JXLH_ERR_INVALID_ARGUMENT;
+  if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
+  if (!ctx->in_frame || !ctx->rendered || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (jxlh_status st = check_desc(ctx, d)) return st;
+  BlendLaunch a{};
+  a.mode = kModeNone;
+  if (colour) {
+    switch (colour->color) {
+      case JXLH_COLOR_XYB:
+        if (colour->transfer > JXLH_TF_GAMMA) return JXLH_ERR_INVALID_ARGUMENT;
+        a.mode = (int)colour->transfer;  // JXLH_TF_* share the values of the internal modes
+        for (int i = 0; i < 9; i++) a.xyb.mat[i] = colour->xyb.opsin_inverse_matrix[i];
+        for (int i = 0; i < 3; i++) {
+          a.xyb.bias_cbrt[i] = colour->xyb.bias_cbrt[i];
+          a.xyb.scaled_bias[i] = colour->xyb.scaled_bias[i];
+        }
+        a.xyb.intensity_scale = colour->xyb.intensity_scale;
+        break;
+      case JXLH_COLOR_YCBCR: a.mode = kModeYcbcr; break;
+      case JXLH_COLOR_NONE: break;
+      default: return JXLH_ERR_INVALID_ARGUMENT;
+    }
+    a.tf.param = colour->tf_param;
+    for (int i = 0; i < 3; i++) a.tf.lum[i] = colour->hlg_luminance_rgb[i];
+  }
+  // the frame's own planes: the render's result, also when an earlier composition has taken its place
+  const bool again = blended(ctx);
+  float* fr[3];
+  for (int c = 0; c < 3; c++) fr[c] = again ? ctx->blend_frame[c] : ctx->result[c];
+  const int fw = again ? ctx->blend_fw : ctx->res_w, fh = again ? ctx->blend_fh : ctx->res_h;
+  const size_t fstride = again ? ctx->blend_fstride : ctx->res_stride;
+  if (!sides_ok(d, (uint32_t)fw, (uint32_t)fh)) return JXLH_ERR_UNSUPPORTED;
+  // the extra channels handed over: 0 .. nec - 1, converted, at the frame's size (as jxlh_frame_save_reference)
+  uint32_t nec = 0;
+  while (nec < JXLH_MAX_EXTRA_CHANNELS && ctx->extra[nec].set) nec++;
+  for (uint32_t i = nec; i < JXLH_MAX_EXTRA_CHANNELS; i++)
+    if (ctx->extra[i].set) return JXLH_ERR_UNSUPPORTED;
+  if (d->num_ec != nec) return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < nec; i++) {
+    const jxlh_ctx::ExtraChannel& e = ctx->extra[i];
+    if (!e.done) return JXLH_ERR_BAD_STATE;
+    if (e.out_w != (uint32_t)fw || e.out_h != (uint32_t)fh) return JXLH_ERR_UNSUPPORTED;
+  }
+  // checked: from here on only the device can fail
+  if (!again) materialise_chroma(ctx);
+  fill_desc(ctx, d, a);
+  a.fw = fw;
+  a.fh = fh;
+  for (int c = 0; c < 3; c++) {
+    a.frame[c] = fr[c];
+    a.frame_stride[c] = (uint32_t)fstride;
+  }
+  for (uint32_t i = 0; i < nec; i++) {
+    const jxlh_ctx::ExtraChannel& e = ctx->extra[i];
+    a.frame[3 + i] = e.pat_ready ? e.pat.p : e.up > 1 ? e.out.p : e.f32.p;
+    a.frame_stride[3 + i] = (uint32_t)e.out_stride;
+  }
+  const size_t ostride = round_up(d->image_w, 64), plane = ostride * d->image_h;
+  if (again && ctx->blend_canvas.n < plane * (3 + nec)) {  // the canvas is about to be replaced: un-blend first
+    for (int c = 0; c < 3; c++) ctx->result[c] = fr[c];
+    ctx->res_w = fw;
+    ctx->res_h = fh;
+    ctx->res_stride = fstride;
+  }
+  if (jxlh_status st = ensure(ctx, ctx->blend_canvas, plane * (3 + nec))) return st;
+  for (uint32_t c = 0; c < 3 + nec; c++) a.out[c] = ctx->blend_canvas.p + c * plane;
+  a.out_stride = (uint32_t)ostride;
+  {
+    ScopedKernelTimer t(ctx, "k_blend");
+    launch_blend(ctx->stream, (int)nec, a);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  for (int c = 0; c < 3; c++) {
+    ctx->blend_frame[c] = fr[c];
+    ctx->result[c] = a.out[c];
+  }
+  ctx->blend_fw = fw;
+  ctx->blend_fh = fh;
+  ctx->blend_fstride = fstride;
+  ctx->blend_nec = nec;
+  ctx->res_w = (int)d->image_w;
+  ctx->res_h = (int)d->image_h;
+  ctx->res_stride = ostride;
+  return JXLH_OK;
+}
+
+jxlh_status jxlh_stage_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const float* const frame[], uint32_t n_channels,
+                             uint32_t w, uint32_t h, size_t stride, float* const out[], size_t out_stride) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !d || !frame || !out || w == 0 || h == 0 || stride < w) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_desc(ctx, d)) return st;
+  if (n_channels != 3 + d->num_ec || out_stride < d->image_w) return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t c = 0; c < n_channels; c++)
+    if (!frame[c] || !out[c]) return JXLH_ERR_INVALID_ARGUMENT;
+  if ((uint64_t)w * h >= (1ull << 31) || !sides_ok(d, w, h)) return JXLH_ERR_UNSUPPORTED;
+  const size_t fplane = (size_t)w * h;
+  const size_t ostride = round_up(d->image_w, 64), oplane = ostride * d->image_h;
+  if (jxlh_status st = ensure(ctx, ctx->blend_hook_in, fplane * n_channels)) return st;
+  if (jxlh_status st = ensure(ctx, ctx->blend_hook_out, oplane * n_channels)) return st;
+  BlendLaunch a{};
+  a.mode = kModeNone;
+  fill_desc(ctx, d, a);
+  a.fw = (int)w;
+  a.fh = (int)h;
+  a.out_stride = (uint32_t)ostride;
+  for (uint32_t c = 0; c < n_channels; c++) {
+    float* in = ctx->blend_hook_in.p + c * fplane;
+    if (jxlh_status st = copy2d(ctx, in, (size_t)w * sizeof(float), frame[c], stride * sizeof(float),
+                                (size_t)w * sizeof(float), h, ctx->stream))
+      return st;
+    a.frame[c] = in;
+    a.frame_stride[c] = w;
+    a.out[c] = ctx->blend_hook_out.p + c * oplane;
+  }
+  {
+    ScopedKernelTimer t(ctx, "k_blend");
+    launch_blend(ctx->stream, (int)d->num_ec, a);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  for (uint32_t c = 0; c < n_channels; c++)
+    if (jxlh_status st = copy2d(ctx, out[c], out_stride * sizeof(float), a.out[c], ostride * sizeof(float),
+                                (size_t)d->image_w * sizeof(float), d->image_h, ctx->stream))
+      return st;
+  JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+}  // extern "C"

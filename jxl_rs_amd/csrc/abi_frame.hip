@@ -222,6 +222,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   for (auto& b : ctx->hook_f) release(b);
   for (auto& b : ctx->hook_i) release(b);
   patches_release(ctx);
+  blend_release(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1318,6 +1319,17 @@ jxlh_status jxlh_frame_read_extra_channel(jxlh_ctx* ctx, uint32_t ec, const jxlh
   if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
   const jxlh_ctx::ExtraChannel& e = ctx->extra[ec];
   if (!e.set || !e.done) return JXLH_ERR_BAD_STATE;  // handed over but no jxlh_frame_run since
+  if (blended(ctx)) {  // the composed channel, image-sized (jxlh_frame_blend)
+    if (ec >= ctx->blend_nec) return JXLH_ERR_BAD_STATE;
+    const size_t w = (size_t)ctx->res_w, h = (size_t)ctx->res_h;
+    if (!out->ptr || out->bytes_per_row < w * sizeof(float) || out->num_rows < h ||
+        out->bytes_between_rows < out->bytes_per_row)
+      return JXLH_ERR_INVALID_ARGUMENT;
+    if (jxlh_status st = copy2d(ctx, out->ptr, out->bytes_between_rows, ctx->blend_canvas.p + (3 + ec) * ctx->res_stride * h,
+                                ctx->res_stride * sizeof(float), w * sizeof(float), h, ctx->stream))
+      return st;
+    return jxlh_ctx_sync(ctx);
+  }
   if (!out->ptr || out->bytes_per_row < (size_t)e.out_w * sizeof(float) || out->num_rows < e.out_h ||
       out->bytes_between_rows < out->bytes_per_row)
     return JXLH_ERR_INVALID_ARGUMENT;

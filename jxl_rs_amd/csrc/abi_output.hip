@@ -37,6 +37,7 @@ jxlh_status read_rgb8(jxlh_ctx* ctx, int mode, const jxlh_xyb_params* p, const T
                       uint32_t y0, uint32_t y1, void* out, size_t bytes_per_row, bool wait = true) {
   if (!ctx || !out || (channels != 3 && channels != 4)) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (blended(ctx) && mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   if (y1 > (uint32_t)ctx->res_h) y1 = (uint32_t)ctx->res_h;
   if (y0 >= y1 || bytes_per_row < (size_t)ctx->res_w * channels) return JXLH_ERR_INVALID_ARGUMENT;
   XybParamsDev d = {};
@@ -92,6 +93,7 @@ jxlh_status read_rgb16(jxlh_ctx* ctx, int mode, const jxlh_xyb_params* p, const 
                        uint32_t y0, uint32_t y1, void* out, size_t bytes_per_row, bool wait = true) {
   if (!ctx || !out || (channels != 3 && channels != 4)) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (blended(ctx) && mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   if (y1 > (uint32_t)ctx->res_h) y1 = (uint32_t)ctx->res_h;
   const size_t row_bytes = (size_t)ctx->res_w * channels * sizeof(uint16_t);
   if (y0 >= y1 || bytes_per_row < row_bytes || bytes_per_row % sizeof(uint16_t) != 0 ||

@@ -223,6 +223,19 @@ jxlh_status jxlh_frame_save_reference(jxlh_ctx* ctx, uint32_t slot) {
   if (!ctx->in_frame || !ctx->rendered || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
   materialise_chroma(ctx);
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
+  if (blended(ctx)) {  // the composed image (jxlh_frame_blend): the canvas has the slot's layout, one linear copy
+    jxlh_ctx::RefSlot& r = ctx->refs[slot];
+    const uint32_t nch = 3 + ctx->blend_nec;
+    const size_t n = ctx->res_stride * h * nch;
+    if (jxlh_status st = ensure(ctx, r.buf, n)) return st;
+    HIPCHK(ctx, hipMemcpyAsync(r.buf.p, ctx->blend_canvas.p, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    r.set = true;
+    r.n_channels = nch;
+    r.w = w;
+    r.h = h;
+    r.stride = ctx->res_stride;
+    return JXLH_OK;
+  }
   // the extra channels handed over: 0 .. nec - 1, converted, at the result's size
   uint32_t nec = 0;
   while (nec < JXLH_MAX_EXTRA_CHANNELS && ctx->extra[nec].set) nec++;

@@ -1,6 +1,6 @@
 // perform_blending (jxl/src/features/blending.rs:199-474) restated for ONE pixel: the reference's row functions are
 // pointwise, and its "old alpha" scratch is a per-pixel copy of the extra channels taken before the blend.  Shared by
-// the patches stage (k_patches.hip); frame blending (BlendingStage, frame/render.rs:765-771) calls the same function.
+// the patches stage (k_patches.hip) and frame blending (BlendingStage, frame/render.rs:765-771: k_blend.hip).
 //
 // Every expression keeps the reference's association (the library builds with -ffp-contract=off, so nothing fuses),
 // and 1 / new_a is the IEEE division: new_a is unbounded when clamp is off.

@@ -183,6 +183,14 @@ struct jxlh_ctx {
   PatchBins patch_bins, patch_hook_bins;
   bool patch_ec_stale = true;  // the patched extra channels must be rebuilt from their base planes on all rows
   DevBuf<float> patch_hook;    // jxlh_stage_patches staging
+  // frame blending (abi_blend.hip): the image-sized canvas of 3 + blend_nec planes, channel c at c * res_stride * res_h.
+  // While the frame's result points at it (blended()), blend_frame / blend_f* keep the frame's own planes and geometry.
+  DevBuf<float> blend_canvas;
+  uint32_t blend_nec = 0;
+  float* blend_frame[3] = {nullptr, nullptr, nullptr};
+  int blend_fw = 0, blend_fh = 0;
+  size_t blend_fstride = 0;
+  DevBuf<float> blend_hook_in, blend_hook_out;  // jxlh_stage_blend staging
   // strip path (k_strip.hip): block descriptors / tile modes written by k1_scan, the strips' edge-column exchange
   // buffer, progress flags + ticket.  strip_all_closed: every rect of the transform map came from host memory and
   // every varblock in it is a small DCT inside its 64x64 tile (jxlh_frame_set_hf_meta); strip_ran: the last
@@ -330,6 +338,9 @@ jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsampl
 jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y_lo, int y_hi);
 jxlh_status patches_check_run(const jxlh_ctx* ctx);
 void patches_release(jxlh_ctx* ctx);
+// abi_blend.hip.  blended(): the frame's result is the canvas jxlh_frame_blend composed (any render resets `result`).
+inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
+void blend_release(jxlh_ctx* ctx);
 bool strip_eligible(const jxlh_ctx* ctx);
 jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan);
 // Where run_stages leaves the finished planes (1 = f.tmp, 0 = f.planes): a property of the frame's stage list, so a

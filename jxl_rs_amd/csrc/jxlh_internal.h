@@ -429,4 +429,24 @@ struct PatchLaunch {
 void launch_patches(hipStream_t s, int num_ec, const PatchLaunch& a, uint32_t ntiles, const uint32_t* tiles,
                     const uint32_t* start, const uint32_t* list, const PatchDev* desc);
 
+// frame blending + extension to the image size (k_blend.hip).  Channel c = 0..2 colour, 3 + i extra channel i; the host
+// resolves each channel's source slot, so the kernel sees one plane per channel on every side.
+constexpr int kBlendChannels = 3 + JXLH_MAX_EXTRA_CHANNELS;
+struct BlendLaunch {
+  const float* frame[kBlendChannels];  // the frame's planes (fw x fh), any alignment
+  uint32_t frame_stride[kBlendChannels];
+  const float* src[kBlendChannels];    // the channel's source slot plane (at least iw x ih, rows 256-B aligned with at
+  uint32_t src_stride[kBlendChannels];  // least round_up(iw, 64) floats), or null: the slot is not set, zeros
+  float* out[kBlendChannels];          // canvas planes: iw x ih, rows 256-B aligned, stride round_up(iw, 64) floats
+  uint32_t out_stride;
+  int x0, y0, fw, fh;  // the frame's origin in the image (may be negative) and its size
+  int iw, ih;          // image size
+  uint32_t blend[1 + JXLH_MAX_EXTRA_CHANNELS];  // pack_blending of the mapped modes (blend_device.h)
+  uint32_t ec_alpha, ec_assoc;
+  int mode;  // colour stage on the frame's channels 0..2 before the blend: kTfLinear .. kTfGamma, kModeYcbcr, kModeNone
+  XybParamsDev xyb;
+  TfParamsDev tf;
+};
+void launch_blend(hipStream_t s, int num_ec, const BlendLaunch& a);
+
 }  // namespace jxlh

@@ -60,7 +60,7 @@ ABI_SYMBOLS = [
     "jxlh_host_pack_slots", "jxlh_host_pack_slots_many", "jxlh_slot_writer_create", "jxlh_slot_writer_destroy", "jxlh_slot_writer_begin_group",
     "jxlh_slot_writer_begin_varblock", "jxlh_slot_writer_add", "jxlh_slot_writer_add_many", "jxlh_slot_writer_end_group",
     "jxlh_ctx_set_reference", "jxlh_frame_save_reference", "jxlh_ctx_clear_reference", "jxlh_frame_set_patches",
-    "jxlh_stage_patches",
+    "jxlh_stage_patches", "jxlh_frame_blend", "jxlh_stage_blend",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
@@ -128,6 +128,34 @@ class Patch(C.Structure):
 
 class PatchBlending(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mode", "alpha_channel", "clamp")]
+
+
+# frame blending (jxlh_frame_blend): BlendingMode values
+BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = range(5)
+
+
+class BlendingInfo(C.Structure):
+    """jxlh_blending_info."""
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "alpha_channel", "clamp", "source")]
+
+
+class BlendDesc(C.Structure):
+    """jxlh_blend_desc."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("image_w", C.c_uint32), ("image_h", C.c_uint32),
+                ("color", BlendingInfo), ("num_ec", C.c_uint32), ("ec", BlendingInfo * 8), ("ec_flags", C.c_uint32 * 8)]
+
+
+def blend_desc(x0, y0, image_w, image_h, color, ec=(), ec_flags=(), num_ec=None):
+    """jxlh_blend_desc from (mode, alpha_channel, clamp, source) tuples: `color`, and one per extra channel in `ec`"""
+    d = BlendDesc()
+    d.x0, d.y0, d.image_w, d.image_h = int(x0), int(y0), int(image_w), int(image_h)
+    d.color = BlendingInfo(*[int(v) for v in color])
+    d.num_ec = len(ec) if num_ec is None else int(num_ec)
+    for i, b in enumerate(list(ec)[:8]):
+        d.ec[i] = BlendingInfo(*[int(v) for v in b])
+    for i, f in enumerate(list(ec_flags)[:8]):
+        d.ec_flags[i] = int(f)
+    return d
 
 
 class JxlHipError(RuntimeError):
@@ -256,6 +284,9 @@ def load():
     L.jxlh_ctx_clear_reference.argtypes = [vp, u32]
     L.jxlh_frame_set_patches.argtypes = [vp, vp, u32, vp, u32, vp]
     L.jxlh_stage_patches.argtypes = [vp, C.POINTER(vp), u32, u32, u32, sz]
+    if hasattr(L, "jxlh_frame_blend"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        L.jxlh_frame_blend.argtypes = [vp, C.POINTER(BlendDesc), C.POINTER(OutputDesc)]
+        L.jxlh_stage_blend.argtypes = [vp, C.POINTER(BlendDesc), C.POINTER(vp), u32, u32, u32, sz, C.POINTER(vp), sz]
     L.jxlh_comm_allgather_local.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), sz]
     L.jxlh_palette_strided.argtypes = [vp, vp, sz, vp, i32, sz, i32, i32, vp, sz]
     L.jxlh_modular_frame_filters.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32, sz]
@@ -579,6 +610,7 @@ class Context:
     # ---- frame ----
     def frame_begin(self, params):
         self.params = params
+        self._blend_size = None
         # FrameHeader::size_blocks: whole blocks of the coarsest (sub-sampled) channel
         mh, mv = max(params.hshift), max(params.vshift)
         self.xblocks = -(-params.xsize // (8 << mh)) << mh
@@ -724,10 +756,13 @@ class Context:
         return p.value, n.value
 
     def frame_run(self, group_row0=0, group_row1=0xFFFFFFFF):
+        self._blend_size = None  # a render discards the composition
         self._chk(self.L.jxlh_frame_run(self._ctx, group_row0, group_row1), "frame_run")
 
     def rerender_groups(self, group_ids):
         ids = np.ascontiguousarray(group_ids, dtype=np.uint32)
+        if len(ids):
+            self._blend_size = None
         self._chk(self.L.jxlh_frame_rerender_groups(self._ctx, _addr(ids), len(ids)), "frame_rerender_groups")
 
     def sync(self):
@@ -823,6 +858,34 @@ class Context:
         self._chk(self.L.jxlh_stage_patches(self._ctx, pp, len(pl), w, h, w), "stage_patches")
         return pl
 
+    # ---- frame blending ----
+    def try_blend(self, desc, colour=None):
+        """jxlh_frame_blend, returning the status.  desc: blend_desc(...); colour: output_desc(...) naming the colour
+        stage to run in front (None: the planes are in the output colour space already)"""
+        st = self.L.jxlh_frame_blend(self._ctx, C.byref(desc), None if colour is None else C.byref(colour))
+        if st == OK:
+            self._blend_size = (desc.image_w, desc.image_h)
+        return st
+
+    def blend(self, desc, colour=None):
+        """jxlh_frame_blend: the rendered frame composed onto the image from the reference slots; the image becomes what
+        read_planes / read_extra_channel / save_reference / read_output(COLOR_NONE) see"""
+        self._chk(self.try_blend(desc, colour), "frame_blend")
+
+    def try_stage_blend(self, desc, planes):
+        pl = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+        h, w = pl[0].shape
+        out = [np.zeros((desc.image_h, desc.image_w), dtype=np.float32) for _ in pl]
+        pp = (C.c_void_p * len(pl))(*[a.ctypes.data for a in pl])
+        po = (C.c_void_p * len(pl))(*[a.ctypes.data for a in out])
+        return self.L.jxlh_stage_blend(self._ctx, C.byref(desc), pp, len(pl), w, h, w, po, desc.image_w), out
+
+    def stage_blend(self, desc, planes):
+        """jxlh_stage_blend: the 3 + num_ec f32 planes [h, w] blended onto the image; returns the image's planes"""
+        st, out = self.try_stage_blend(desc, planes)
+        self._chk(st, "stage_blend")
+        return out
+
     def tune_placement(self, trials=0):
         """jxlh_ctx_tune_placement: trials > 0 sets the number of candidate sets the next first allocation of the large
         buffers is picked from; returns (ratings [(k1-like ms, filter-like ms), ...] of the last pick, index taken)"""
@@ -881,7 +944,10 @@ class Context:
 
     @property
     def out_size(self):
-        """(width, height) of what the jxlh_frame_read_* calls return: the frame, or its upsampled image"""
+        """(width, height) of what the jxlh_frame_read_* calls return: the frame, or its upsampled image, or the image
+        the frame was blended onto"""
+        if getattr(self, "_blend_size", None):
+            return self._blend_size
         p = self.params
         n = max(1, p.upsampling)
         return (p.xsize_upsampled or p.xsize * n, p.ysize_upsampled or p.ysize * n)
