@@ -85,8 +85,13 @@ typedef struct {
  *                           (frame/modular/mod.rs:1058-1060; JXLH_ERR_INVALID_BLOCK_SIZE otherwise), their size
  *                           in blocks is rounded up to whole blocks of the coarsest channel
  *                           (FrameHeader::size_blocks, :564-569), the LF samples of a sub-sampled channel
- *                           sit in the top-left corner of each LF group's rectangle (frame/group.rs:485-504,
- *                           modular/mod.rs:877-893) and the LF dequantisation skips chroma-from-luma.
+ *                           sit in the top-left (w >> hshift) x (h >> vshift) corner of each LF group's rectangle
+ *                           (frame/group.rs:485-504, modular/mod.rs:877-893) and the LF dequantisation skips
+ *                           chroma-from-luma.  The setters store the whole rectangle of every channel.  What a
+ *                           caller passes outside that corner is never read by the transforms; adaptive LF
+ *                           smoothing (do_lf_smoothing) does read it, as the reference's does, whose LF image is
+ *                           zero there (dequant_lf writes the corner only): pass zeros outside the corner to get
+ *                           the reference's smoothed LF, anything at all when smoothing is off.
  *                           The transforms reconstruct every channel at its own resolution
  *                           (frame/group.rs:223-250) and the chroma upsampling stages
  *                           (render/stages/chroma_upsample.rs, frame/render.rs:569-576) run before Gaborish /
@@ -182,18 +187,33 @@ jxlh_status jxlh_frame_set_dequant_tables(jxlh_ctx* ctx, const float* const tabl
                                           const size_t n[JXLH_NUM_QUANT_TABLES]);
 
 /* decode_vardct_lf -> dequant_lf (frame/modular/mod.rs:837-929), one LF-group rect at a time.
- * Rect in blocks.  qy/qx/qb are the three modular channels in coded order (Y, X, B), row stride
- * `stride` samples.  Runs K0a on the device. */
+ * Rect in blocks, anywhere inside the frame (any origin, any size, zero-sized included; rects may arrive in
+ * any order, between the other setters and the submissions, and a later call replaces an earlier one's samples,
+ * also after a jxlh_frame_run: the next render smooths again from the stored LF).  qy/qx/qb are the three
+ * modular channels in coded order (Y, X, B), host or device memory, row stride `stride` >= w samples; what lies
+ * between w and stride is not read.  extra_precision (0..3) is the LF group's: the rect is dequantised with
+ * (factor * inv_quant_lf) * (1 / (1 << extra_precision)).  Runs K0a on the device.
+ * JXLH_ERR_INVALID_ARGUMENT: a null plane, stride < w, extra_precision > 3, a rect that leaves the frame;
+ * JXLH_ERR_BAD_STATE outside a frame.  A refused call changes nothing.
+ * Sub-sampled frames: see hshift / vshift above for what the samples outside each LF group's corner mean. */
 jxlh_status jxlh_frame_set_lf_quantized(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                         const int32_t* qy, const int32_t* qx, const int32_t* qb,
                                         size_t stride, uint32_t extra_precision);
-/* Alternative: LF already dequantised by the host (lf_image, frame/mod.rs). */
+/* Alternative: LF already dequantised by the host (lf_image, frame/mod.rs), channels X, Y, B; rects, strides,
+ * ordering and errors as above.  Both setters may be mixed rect by rect inside one frame. */
 jxlh_status jxlh_frame_set_lf(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                               const float* x, const float* y, const float* b, size_t stride);
 
 /* decode_hf_metadata (frame/modular/mod.rs:984-1081): HfMetadata maps for a rect in blocks
  * (frame/mod.rs:169-176).  ytox/ytob cover ceil(w/8) x ceil(h/8) colour tiles starting at
- * (x0/8, y0/8); x0, y0 must be multiples of 8. */
+ * (x0/8, y0/8); x0, y0 must be multiples of 8, w and h need not be: a rect that ends inside a colour tile
+ * sets that whole tile, so a neighbouring rect that delivers the tile again must carry the same value.
+ * transform_map, raw_quant and epf_map share the row stride map_stride >= w (in elements of each map), ytox and
+ * ytob cmap_stride >= ceil(w/8); host or device memory.  Which transform families the frame holds (and whether
+ * the strip kernel may take every tile) is gathered over all rects of the frame from the host-resident maps; a
+ * map in device memory is not inspected and every family is assumed present.  Any order, any number of calls.
+ * JXLH_ERR_INVALID_ARGUMENT: a null map, map_stride < w, cmap_stride < ceil(w/8), x0 or y0 off the 8-block grid,
+ * a rect that leaves the frame; JXLH_ERR_BAD_STATE outside a frame.  A refused call changes nothing. */
 jxlh_status jxlh_frame_set_hf_meta(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                    const uint8_t* transform_map, const int32_t* raw_quant,
                                    const uint8_t* epf_map, size_t map_stride, const int8_t* ytox,

@@ -566,6 +566,55 @@ class DeviceArray:
             self.ptr = 0
 
 
+def _is_pointer(a):
+    return isinstance(a, (int, np.integer, DeviceArray)) or hasattr(a, "data_ptr")
+
+
+def _row_pitch(a):
+    """Row pitch in elements of a 2-D array whose rows are contiguous, or None when it cannot be passed as it is (rows
+    not contiguous, wrong byte order, negative or unaligned pitch)."""
+    isz = a.dtype.itemsize
+    if a.ndim != 2 or not a.dtype.isnative:
+        return None
+    h, w = a.shape
+    if w > 1 and a.strides[1] != isz:
+        return None
+    if h <= 1:
+        return max(w, 1)
+    st = a.strides[0]
+    if st < w * isz or st % isz:
+        return None
+    return st // isz
+
+
+def _rect_planes_mixed(arrs, dtypes):
+    """Host planes of one rect that share a row pitch in elements (their element types may differ).  Returns
+    (arrays, w, h, pitch): the arrays as they are when every one has contiguous rows and they agree on the pitch,
+    tight copies otherwise."""
+    arrs = [np.asarray(a) for a in arrs]
+    arrs = [a if a.dtype == np.dtype(dt) else a.astype(dt) for a, dt in zip(arrs, dtypes)]
+    if any(a.ndim != 2 for a in arrs) or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError("the planes of a rect are 2-D arrays of one shape: " + ", ".join(str(a.shape) for a in arrs))
+    h, w = arrs[0].shape
+    pitches = [_row_pitch(a) for a in arrs]
+    if None in pitches or len(set(pitches)) != 1:
+        arrs = [np.ascontiguousarray(a) for a in arrs]
+        pitches = [max(w, 1)]
+    return arrs, w, h, pitches[0]
+
+
+def _rect_planes(arrs, dtype, w, h, stride):
+    """Three planes of one element type: host arrays (see _rect_planes_mixed) or device pointers with explicit
+    w, h, stride."""
+    if any(_is_pointer(a) for a in arrs):
+        if not all(_is_pointer(a) for a in arrs) or None in (w, h, stride):
+            raise ValueError("device pointers need all three planes as pointers and explicit w, h, stride")
+        return list(arrs), int(w), int(h), int(stride)
+    if not (w is None and h is None and stride is None):
+        raise ValueError("w, h and stride of host arrays come from the arrays themselves")
+    return _rect_planes_mixed(arrs, (dtype,) * len(arrs))
+
+
 class SqueezeLevel(C.Structure):  # jxlh_squeeze_level
     _fields_ = [("horizontal", C.c_int32), ("out_w", C.c_uint32), ("out_h", C.c_uint32), ("res", C.c_void_p * 3),
                 ("res_stride", C.c_size_t)]
@@ -623,26 +672,35 @@ class Context:
         sizes = (C.c_size_t * NUM_QUANT_TABLES)(*[t.size // 3 for t in tabs])
         self._chk(self.L.jxlh_frame_set_dequant_tables(self._ctx, ptrs, sizes), "set_dequant_tables")
 
-    def set_lf_quantized(self, qy, qx, qb, x0=0, y0=0, extra_precision=0):
-        qy, qx, qb = [np.ascontiguousarray(a, dtype=np.int32) for a in (qy, qx, qb)]
-        h, w = qy.shape
-        self._chk(self.L.jxlh_frame_set_lf_quantized(self._ctx, x0, y0, w, h, _addr(qy), _addr(qx), _addr(qb), w,
+    def set_lf_quantized(self, qy, qx, qb, x0=0, y0=0, extra_precision=0, w=None, h=None, stride=None):
+        """One rect of the quantised LF (coded order Y, X, B).  Host arrays: 2-D, rows contiguous, any row pitch (a slice
+        `big[y0:y1, x0:x1]` is passed as it is).  DeviceArrays / raw device pointers: give w, h and stride (samples)."""
+        (qy, qx, qb), w, h, stride = _rect_planes((qy, qx, qb), np.int32, w, h, stride)
+        self._chk(self.L.jxlh_frame_set_lf_quantized(self._ctx, x0, y0, w, h, _addr(qy), _addr(qx), _addr(qb), stride,
                                                      extra_precision), "set_lf_quantized")
 
-    def set_lf(self, x, y, b, x0=0, y0=0):
-        x, y, b = [np.ascontiguousarray(a, dtype=np.float32) for a in (x, y, b)]
-        h, w = x.shape
-        self._chk(self.L.jxlh_frame_set_lf(self._ctx, x0, y0, w, h, _addr(x), _addr(y), _addr(b), w), "set_lf")
+    def set_lf(self, x, y, b, x0=0, y0=0, w=None, h=None, stride=None):
+        """One rect of the LF the host has already dequantised (X, Y, B); arrays and pointers as in set_lf_quantized."""
+        (x, y, b), w, h, stride = _rect_planes((x, y, b), np.float32, w, h, stride)
+        self._chk(self.L.jxlh_frame_set_lf(self._ctx, x0, y0, w, h, _addr(x), _addr(y), _addr(b), stride), "set_lf")
 
-    def set_hf_meta(self, transform_map, raw_quant, epf_map, ytox, ytob, x0=0, y0=0):
-        tm = np.ascontiguousarray(transform_map, dtype=np.uint8)
-        rq = np.ascontiguousarray(raw_quant, dtype=np.int32)
-        em = np.ascontiguousarray(epf_map, dtype=np.uint8)
-        yx = np.ascontiguousarray(ytox, dtype=np.int8)
-        yb = np.ascontiguousarray(ytob, dtype=np.int8)
-        h, w = tm.shape
-        self._chk(self.L.jxlh_frame_set_hf_meta(self._ctx, x0, y0, w, h, _addr(tm), _addr(rq), _addr(em), w,
-                                                _addr(yx), _addr(yb), yx.shape[1]), "set_hf_meta")
+    def set_hf_meta(self, transform_map, raw_quant, epf_map, ytox, ytob, x0=0, y0=0, w=None, h=None, map_stride=None,
+                    cmap_stride=None):
+        """One rect of the HfMetadata maps.  The three block maps share one row pitch (in elements), ytox and ytob
+        another; host arrays as in set_lf_quantized.  DeviceArrays / raw device pointers: give w, h, map_stride and
+        cmap_stride."""
+        maps = (transform_map, raw_quant, epf_map)
+        if any(_is_pointer(a) for a in maps + (ytox, ytob)):
+            if not all(_is_pointer(a) for a in maps + (ytox, ytob)) or None in (w, h, map_stride, cmap_stride):
+                raise ValueError("device pointers need all five maps as pointers and explicit w, h, map_stride, cmap_stride")
+            tm, rq, em, yx, yb = maps + (ytox, ytob)
+        else:
+            if not (w is None and h is None and map_stride is None and cmap_stride is None):
+                raise ValueError("w, h and the strides of host arrays come from the arrays themselves")
+            (tm, rq, em), w, h, map_stride = _rect_planes_mixed(maps, (np.uint8, np.int32, np.uint8))
+            (yx, yb), cw, ch, cmap_stride = _rect_planes_mixed((ytox, ytob), (np.int8, np.int8))
+        self._chk(self.L.jxlh_frame_set_hf_meta(self._ctx, x0, y0, w, h, _addr(tm), _addr(rq), _addr(em), map_stride,
+                                                _addr(yx), _addr(yb), cmap_stride), "set_hf_meta")
 
     def submit_group(self, group_id, coeffs, slot=0, flags=GROUP_COMPLETE):
         if isinstance(coeffs, np.ndarray):

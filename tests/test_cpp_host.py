@@ -40,6 +40,17 @@ def test_cpp_host_frame_parity(tmp_path, args):
     assert "0 differing rows" in r.stdout and "error path ok" in r.stdout
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("args", [("300", "270", "2"), ("515", "133", "3")])
+def test_cpp_host_frame_parity_per_rect(tmp_path, args):
+    """the same frames fed through VarDctFrame::decode_lf_group / decode_hf_metadata one rect at a time: padded row
+    strides, LF rects at odd origins with a non-zero extra_precision, maps before LF (the wrapper's argument order)"""
+    exe = _build(tmp_path)
+    r = subprocess.run([exe, *args, "rects"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+    assert "per rect: 0 differing rows" in r.stdout and "error path ok" in r.stdout
+
+
 def test_pipeline_builder_lowering_and_rejections(tmp_path):
     """host logic of the RenderPipelineBuilder mirror: the reference's stage lists lower onto the frame parameters the
     device path takes (accumulated border 4 for Gaborish + EPF1 + EPF2, render/mod.rs:28-36), lists outside the path
