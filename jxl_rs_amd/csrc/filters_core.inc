@@ -76,15 +76,11 @@ __device__ __forceinline__ void load10g(const float* __restrict__ strip, bool ed
 // Correctly rounded 1/w for w in [1, 16) (1 + up to 12 weights in [0,1]); equals the IEEE
 // quotient 1.0f / w bit for bit on that range -- jxlh_selftest_recip checks every float.
 __device__ __forceinline__ float recip_weight_sum(float w) {
-#if JXLH_FAST_RECIP
   float r = __builtin_amdgcn_rcpf(w);
   float e = __builtin_fmaf(-w, r, 1.0f);
   r = __builtin_fmaf(e, r, r);
   e = __builtin_fmaf(-w, r, 1.0f);
   return __builtin_fmaf(e, r, r);
-#else
-  return 1.0f / w;
-#endif
 }
 
 // sigma * sad_mul for the four pixels of a strip in frame row fy (common.rs:31-41): the border
@@ -153,11 +149,7 @@ __device__ __forceinline__ void epf1_pair(const float* __restrict__ p0, Regeom&&
 
   // one channel at a time (a rolled loop): unrolled, the scheduler interleaves the three
   // channels' loads and difference maps and triples the live registers
-#if JXLH_E1_ROLLED
 #pragma unroll 1
-#else
-#pragma unroll
-#endif
   for (int c = 0; c < 3; c++) {
     const float* p = p0 + c * kPlane;
     const float scale = a.scale[c];
@@ -336,76 +328,6 @@ __device__ __forceinline__ void epf1_strip_g(const float* __restrict__ p0, int f
       o[i] = pass ? M[i + 2] : acc * inv_w[i];
     }
     emit(c, make_float4(o[0], o[1], o[2], o[3]));
-  }
-}
-
-// ---- EPF2 on a 4x2 micro-tile (epf2.rs:84-136)
-template <class Emit>
-__device__ __forceinline__ void epf2_pair(const float* __restrict__ p0, int fx0, int fy, float sigma0, float sigma1,
-                                          const FusedArgs& a, Emit&& emit) {
-  float T[3][4], M0[3][8], M1[3][8], Bt[3][4];  // rows y-1, y, y+1, y+2
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const float* p = p0 + c * kPlane;
-    load4(p - kBW, T[c]);
-    load8(p, M0[c]);
-    load8(p + kBW, M1[c]);
-    load4(p + 2 * kBW, Bt[c]);
-  }
-  const float s0 = a.scale[0], s1 = a.scale[1], s2 = a.scale[2];
-  // the SAD of epf2.rs:103-109 between two pixels (symmetric in its arguments)
-  auto sad3 = [&](float ax, float ay, float ab, float bx, float by, float bb) {
-    return __builtin_fmaf(FAD(ax, bx), s0, __builtin_fmaf(FAD(ay, by), s1, FAD(ab, bb) * s2));
-  };
-  float dv[3][4];  // between rows (y-1,y), (y,y+1), (y+1,y+2)
-  float dh[2][4];  // between columns x+i and x+i+1, rows y and y+1
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int j = i + 2;
-    dv[0][i] = sad3(T[0][i], T[1][i], T[2][i], M0[0][j], M0[1][j], M0[2][j]);
-    dv[1][i] = sad3(M1[0][j], M1[1][j], M1[2][j], M0[0][j], M0[1][j], M0[2][j]);
-    dv[2][i] = sad3(Bt[0][i], Bt[1][i], Bt[2][i], M1[0][j], M1[1][j], M1[2][j]);
-    dh[0][i] = sad3(M0[0][j + 1], M0[1][j + 1], M0[2][j + 1], M0[0][j], M0[1][j], M0[2][j]);
-    dh[1][i] = sad3(M1[0][j + 1], M1[1][j + 1], M1[2][j + 1], M1[0][j], M1[1][j], M1[2][j]);
-  }
-  // per row: the four weights of each pixel, then the channels.  The outer rows (y-1, y+2) are
-  // only needed once more, as N / S neighbours: re-read them instead of holding 24 registers.
-#pragma unroll
-  for (int r = 0; r < 2; r++) {
-    const float sigma = r ? sigma1 : sigma0;
-    const bool pass = sigma < kMinSigma;
-    float is[4], wgt[4][4], inv_w[4];
-    strip_inv_sigma(sigma, fx0, fy + r, a.sm2, a.bsm2, is);
-    const float from_left = dpp_from_left(dh[r][3]);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      // neighbour order N, W, E, S (epf2.rs:95)
-      const float sad[4] = {dv[r][i], i ? dh[r][i - 1] : from_left, dh[r][i], dv[r + 1][i]};
-      float wacc = 1.0f;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        wgt[i][k] = fmaxf(__builtin_fmaf(sad[k], is[i], 1.0f), 0.0f);
-        wacc += wgt[i][k];
-      }
-      inv_w[i] = recip_weight_sum(wacc);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float(&M)[8] = r ? M1[c] : M0[c];
-      float outer[4];
-      load4(p0 + c * kPlane + (r ? 2 : -1) * kBW, outer);
-      float o[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int j = i + 2;
-        const float n[4] = {r ? M0[c][j] : outer[i], M[j - 1], M[j + 1], r ? outer[i] : M1[c][j]};
-        float acc = M[j];
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc = __builtin_fmaf(wgt[i][k], n[k], acc);
-        o[i] = pass ? M[j] : acc * inv_w[i];
-      }
-      emit(r, c, make_float4(o[0], o[1], o[2], o[3]));
-    }
   }
 }
 

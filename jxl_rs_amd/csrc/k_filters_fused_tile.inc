@@ -6,7 +6,6 @@ constexpr int kBH = kTH + 2 * kB;
 constexpr int kStrips = kBW / 4;   // 16
 constexpr int kPlane = kBW * kBH;  // floats per channel
 constexpr int kThreadsDefault = JXLH_TILE_THREADS;
-constexpr int kBandRows = JXLH_FUSED_BAND;  // tile rows of an XCD's band (the blockIdx -> tile map of k23_fused_filters)
 static_assert(kStrips == 16, "lane <-> strip mapping relies on 16-lane DPP rows");
 static_assert(kTH % 4 == 0 && kThreadsDefault % 64 == 0, "tiled staging fetches 4-row groups");
 constexpr int kSigW = kBW / 8 + 2, kSigH = kBH / 8 + 2;
@@ -37,53 +36,36 @@ __device__ __forceinline__ void mirror_fill(float* __restrict__ buf, int m, int 
 template <bool E0>
 constexpr int fused_threads() { return E0 ? JXLH_FUSED_E0_THREADS : kThreadsDefault; }
 
-// NC: tiles a workgroup works through, top to bottom (a column strip of NC * kTH output rows).  Round 6: with NC > 1 the
-// 2 * border input rows two consecutive tiles share stay in LDS (s_halo: saved before the first stage overwrites them in
-// place, put back as the next tile's top rows) instead of being fetched again -- the reference streams every input row
-// through its ring buffers exactly once (render/low_memory_pipeline/render_group.rs:21-63, :447-476); round 5's tiles
-// fetched (kTH + 8) / kTH = 1.33 rows per output row (counter fetch 1.083 GB against 0.809 compulsory at 8K).
-template <bool GAB, bool E0, bool E1, bool E2, int NC>
-__global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 1 ? JXLH_FUSED_STRIP_WPE : JXLH_FUSED_WAVES_PER_EU) void k23_fused_filters(const FusedArgs a) {
+// One workgroup, one tile.  (A workgroup walking a column strip of tiles with the shared input rows kept in LDS measured
+// slower: profiles/r06_e_filter_strips.txt.)
+template <bool GAB, bool E0, bool E1, bool E2>
+__global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : JXLH_FUSED_WAVES_PER_EU) void k23_fused_filters(const FusedArgs a) {
   constexpr int kT = fused_threads<E0>();
   __shared__ __attribute__((aligned(16))) float s_buf[3 * kPlane];
-  __shared__ __attribute__((aligned(16))) float s_halo[NC > 1 ? 3 * 2 * kB * kBW : 4];
   // 1/sigma of the 8x8 blocks this tile touches (block columns/rows relative to the tile's first block)
   __shared__ float s_sigma[kSigH * kSigW];
   // compacted EPF items of the current stage (see run_stage) and the number of wavefronts free to take them
   __shared__ uint16_t s_list[(kTH + 2 * kB) * kStrips];
   __shared__ int s_cnt, s_nsw;
   const int tid_kernel = threadIdx.x, tid = tid_kernel;
-  // blockIdx.x enumerates tiles (column strips of NC tiles) so that the workgroups one XCD receives (ids congruent
-  // mod 8) walk along a tile row (kBandRows == 1): neighbouring tiles share 128-byte output lines and halo input
-  // columns, which then meet in the same (non-coherent) L2.  kBandRows > 1: bands of that many tile rows walked column
-  // by column, so that the halo ROWS could meet there too -- measured slower, see JXLH_FUSED_BAND.
+  // blockIdx.x enumerates tiles so that the workgroups one XCD receives (ids congruent mod 8) walk along a tile row:
+  // neighbouring tiles share 128-byte output lines and halo input columns, which then meet in the same (non-coherent)
+  // L2.  (Bands of several tile rows per XCD, walked column by column, measured slower: profiles/r06_e_filter_bands.txt.)
   const int tiles_x = (a.w + kTW - 1) / kTW;
   const int tiles_y = (a.y1 - a.y0 + kTH - 1) / kTH;
-  int tile_x, strip_y;
-  {
-    constexpr int R = kBandRows;
-    const int b = blockIdx.x, k = b & 7, j = b >> 3;
-    const int band = j / (tiles_x * R), in_band = j % (tiles_x * R);
-    strip_y = (band * 8 + k) * R + in_band % R;
-    tile_x = in_band / R;
-  }
+  const int b = blockIdx.x, k = b & 7, j = b >> 3;
+  const int tile_y = (j / tiles_x) * 8 + k, tile_x = j % tiles_x;
+  if (tile_y >= tiles_y) return;  // the grid rounds the tile rows up to a multiple of 8
   constexpr int kBorder = (GAB ? 1 : 0) + (E0 ? 3 : 0) + (E1 ? 2 : 0) + (E2 ? 1 : 0);
   static_assert(kBorder >= 1 && kBorder <= kB, "at least one stage");
   static_assert(!(E0 && (E1 || E2)), "EPF0 closes its kernel; EPF1/EPF2 follow in a second launch");
   const int tx0 = tile_x * kTW;
-  bool halo_saved = false;  // s_halo holds the previous tile's bottom input rows (workgroup-uniform)
-#pragma unroll 1
-  for (int ci = 0; ci < NC; ci++) {
-  const int tile_y = strip_y * NC + ci;
-  if (tile_y >= tiles_y) break;
   const int ty0 = a.y0 + tile_y * kTH;
   const bool edge = tx0 - kB < 0 || ty0 - kB < 0 || tx0 + kTW + kB > a.w || ty0 + kTH + kB > a.h;
-  if (ci > 0) __syncthreads();  // the previous tile's last stage has read s_buf, s_sigma and the lists
   if (tid_kernel == 0) {
     s_cnt = 0;
     s_nsw = 0;
   }
-  const bool reuse = NC > 1 && halo_saved && !edge;  // the top 2 * kBorder input rows are in s_halo
 
   const int sbx0 = max(tx0 - kB, 0) >> 3, sby0 = max(ty0 - kB, 0) >> 3;
   if constexpr (E0 || E1 || E2) {
@@ -103,11 +85,6 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
       // the values scatter into the raster LDS tile with conflict-free ds_write_b32.
       constexpr int yg0 = (kB - m) / 4, ygn = (rows + 2 * ((kB - m) % 4) + 3) / 4;  // 4-row groups touched
       constexpr int items = kBW * ((ygn + 1) / 2) * 2;
-      // (reuse: the groups that lie wholly inside the rows s_halo brings -- two of them with the full border of 4 --
-      // are not fetched)
-      constexpr int kSkip = (kB + m) / 4 - yg0;
-      const int ygs = reuse ? yg0 + kSkip : yg0;
-      const int items_r = reuse ? kBW * ((ygn - kSkip + 1) / 2) * 2 : items;
 #pragma unroll
       for (int it = 0; it < (items + kT - 1) / kT; it++) {
         // idx -> (pair of row groups, half of the columns): lanes 0-31 / 32-63 = the two 4-row
@@ -115,8 +92,8 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
         const int idx = it * kT + tid;
         const int w64 = idx >> 6, l = idx & 63;
         const int xh = w64 % 2, ypair = w64 / 2;
-        const int bx = xh * 32 + (l & 31), yg = ygs + ypair * 2 + (l >> 5);
-        if (idx >= items_r || yg * 4 >= kBH) continue;
+        const int bx = xh * 32 + (l & 31), yg = yg0 + ypair * 2 + (l >> 5);
+        if (idx >= items || yg * 4 >= kBH) continue;
         const int by = yg * 4;
         const uint32_t off = in_offset(a, tx0 - kB + bx, ty0 - kB + by);
 #pragma unroll
@@ -130,8 +107,7 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
         }
       }
     } else if (!edge) {  // interior tile, raster input: pure 16-byte coalesced rows
-      const int r0 = reuse ? 2 * m : 0;  // (reuse: the first 2 * m rows of the region come from s_halo)
-      for (int idx = r0 * kStrips + tid; idx < kStrips * rows; idx += kT) {
+      for (int idx = tid; idx < kStrips * rows; idx += kT) {
         const int by = kB - m + idx / kStrips, bx0 = (idx % kStrips) * 4;
         const uint32_t off = in_offset(a, tx0 - kB + bx0, ty0 - kB + by);
 #pragma unroll
@@ -154,30 +130,8 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
         }
       }
     }
-    if constexpr (NC > 1) {
-      // rows [kB - m, kB + m) <- the previous tile's rows [kTH + kB - m, kTH + kB + m), saved before its stages ran
-      if (reuse)
-        for (int idx = tid; idx < 3 * 2 * m * kStrips; idx += kT) {
-          const int c = idx / (2 * m * kStrips), rem = idx % (2 * m * kStrips);
-          lds_store4(s_buf + c * kPlane + (kB - m + rem / kStrips) * kBW + (rem % kStrips) * 4,
-                     lds_load4(s_halo + (c * 2 * kB + rem / kStrips) * kBW + (rem % kStrips) * 4));
-        }
-    }
   }
   __syncthreads();
-  if constexpr (NC > 1) {
-    // the input rows the NEXT tile of the strip shares with this one, before the first stage overwrites them in place
-    // (an edge tile's rows hold mirrored values: the next tile then fetches its own)
-    halo_saved = !edge && ci + 1 < NC && tile_y + 1 < tiles_y;
-    if (halo_saved) {
-      constexpr int m = kBorder;
-      for (int idx = tid; idx < 3 * 2 * m * kStrips; idx += kT) {
-        const int c = idx / (2 * m * kStrips), rem = idx % (2 * m * kStrips);
-        lds_store4(s_halo + (c * 2 * kB + rem / kStrips) * kBW + (rem % kStrips) * 4,
-                   lds_load4(s_buf + c * kPlane + (kTH + kB - m + rem / kStrips) * kBW + (rem % kStrips) * 4));
-      }
-    }
-  }
 
   // One stage, in place: margin = the output region's margin around the tile (the input region's
   // minus the stage's border).  Every 4x2 item of the region is computed into registers, then
@@ -204,7 +158,8 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
     int tid = tid_kernel;
     asm volatile("" : "+v"(tid));
     static_assert(STAGE != 3 || last, "EPF0 runs as the last stage");
-    if constexpr ((STAGE == 2 && last && JXLH_E2_STRIPS) || STAGE == 3) {
+    static_assert(STAGE != 2 || last, "EPF2 runs as the last stage");
+    if constexpr (STAGE == 2 || STAGE == 3) {
       constexpr int ns = rows * kStrips;
       auto strip_geom = [&](int t, int& by, int& bx0, int& fy, int& fx0, float& sigma) {
         by = kB + t / kStrips;
@@ -326,8 +281,7 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
         const bool act0 = g.live && !(g.sigma0 < kMinSigma), act1 = g.live && !(g.sigma1 < kMinSigma);
         const unsigned long long m0 = __ballot(act0), m1 = __ballot(act1);
         const int cnt = __popcll(m0) + __popcll(m1);  // active strips of this wavefront
-        // EPF2 as an in-place stage has no compacted form: any active strip makes the wavefront dense
-        dense = STAGE == 1 ? cnt > kSparseMax : cnt > 0;
+        dense = cnt > kSparseMax;
         if (!dense) {
           int slot = 0, base = 0;
           if ((tid & 63) == 0) {
@@ -360,8 +314,7 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
           if constexpr (last) put_global(gg, r, c, o);
           else held[0][r][c] = o;
         };
-        if constexpr (STAGE == 1) epf1_pair(g.p, geom, a, put);
-        else epf2_pair(g.p, g.fx0, g.fy, g.sigma0, g.sigma1, a, [&](int r, int c, float4 o) { put(g, r, c, o); });
+        epf1_pair(g.p, geom, a, put);
         held_e = tid;
       } else if constexpr (STAGE == 1) {
         const int cnt = s_cnt;
@@ -428,14 +381,12 @@ __global__ __launch_bounds__(fused_threads<E0>(), E0 ? JXLH_FUSED_E0_WPE : NC > 
   if constexpr (E0) run_stage(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{});
   if constexpr (E1) run_stage(std::integral_constant<int, 1>{}, std::integral_constant<int, kMe1>{});
   if constexpr (E2) run_stage(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{});
-  }  // tiles of the strip
 }
 
-template <bool GAB, bool E0, bool E1, bool E2, int NC = 1>
+template <bool GAB, bool E0, bool E1, bool E2>
 void launch_variant(hipStream_t s, const FusedArgs& a) {
   const int tiles_x = (a.w + kTW - 1) / kTW, tiles_y = (a.y1 - a.y0 + kTH - 1) / kTH;
-  const int strips_y = (tiles_y + NC - 1) / NC;
-  const dim3 grid(tiles_x * ((strips_y + 8 * kBandRows - 1) / (8 * kBandRows)) * 8 * kBandRows);
-  hipLaunchKernelGGL((k23_fused_filters<GAB, E0, E1, E2, NC>), grid, dim3(fused_threads<E0>()), 0, s, a);
+  const dim3 grid(tiles_x * ((tiles_y + 7) / 8) * 8);  // see the blockIdx -> tile map of k23_fused_filters
+  hipLaunchKernelGGL((k23_fused_filters<GAB, E0, E1, E2>), grid, dim3(fused_threads<E0>()), 0, s, a);
 }
 

@@ -63,12 +63,6 @@
 #ifndef JXLH_STRIP_ABLATE
 #define JXLH_STRIP_ABLATE 0
 #endif
-#ifndef JXLH_FAST_RECIP
-#define JXLH_FAST_RECIP 1
-#endif
-#ifndef JXLH_E1_ROLLED
-#define JXLH_E1_ROLLED 1
-#endif
 #ifndef JXLH_SPARSE_MAX
 #define JXLH_SPARSE_MAX 62
 #endif
@@ -789,8 +783,8 @@ __global__ __launch_bounds__(kNT, JXLH_STRIP_WPE) void k123_strip(const FrameDev
                   held[r][c] = o;
                 }
               };
-              if constexpr (STAGE == 1) epf1_pair(g.p, geom, a, put);
-              else epf2_pair(g.p, g.fx0, g.fy, g.sigma0, g.sigma1, a, [&](int r, int c, float4 o) { put(g, r, c, o); });
+              static_assert(STAGE != 2 || last, "EPF2 runs as the last stage");
+              epf1_pair(g.p, geom, a, put);
               if (owner && g.live) held_e = item(tid);
             } else if constexpr (STAGE == 1) {
               const int cnt = s_cnt;

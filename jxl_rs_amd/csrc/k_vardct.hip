@@ -1082,14 +1082,6 @@ __global__ __launch_bounds__(kThreads, SPARSE == 3 ? (INLINE ? JXLH_K1_INLINE_WP
 // of a batch ahead of the coefficients (through an LDS scratch) measured flat as well
 // exclusive slot-count prefixes of a batch's varblocks (entries form): NB * (N / 64) words, at most 40 (8 x 32)
 constexpr int kExclWords = 40;
-#ifndef JXLH_K1_MERGED
-// Dense slabs, frames of >= 512 groups: every DCT class in ONE launch (k1_dct16_32<0, false, true>).  Built in round 6,
-// -1.7 % on K1's own time with one frame in flight on one box -- and 4-5 % SLOWER on the pipelined headline (two frames
-// in flight: 0.718 against 0.691 ms per frame; three boxes' worth of alternating runs): one long launch at three waves
-// per SIMD leaves the other frame's kernels nothing to overlap with.  Off; the one-launch form still runs the
-// dense-route lists of a routed frame (a handful of groups).  profiles/r06_f_k1_merged.txt
-#define JXLH_K1_MERGED 0
-#endif
 #ifndef JXLH_K1_DIRECT_WPE
 #define JXLH_K1_DIRECT_WPE 3  // waves per SIMD the direct form of k1_dct16_32 is compiled for
 #endif
@@ -1185,7 +1177,7 @@ __global__ __launch_bounds__(kThreads, SPARSE == 3 ? JXLH_K1_DIRECT_WPE : SPARSE
   // (the 8x8 class: only when its kernel ran without the inline fallback; the list stays empty otherwise)
   if constexpr (FB) run(ShapeTag<S8x8>{}, std::true_type{}, std::integral_constant<int, kClsDct8>{}, 0, 8);
   // ALL: the 8x8 class too -- every DCT class in one launch (the dense-route lists of a routed frame; as the form of
-  // whole dense frames it lost on the pipelined headline: JXLH_K1_MERGED)
+  // whole dense frames it lost on the pipelined headline: profiles/r06_f_k1_merged.txt)
   if constexpr (ALL) run(ShapeTag<S8x8>{}, std::true_type{}, std::integral_constant<int, kClsDct8>{}, 0);
 }
 
@@ -1527,12 +1519,8 @@ void launch_vardct_groups(hipStream_t s, const FrameDev& f_in, int group_row0, i
       hipLaunchKernelGGL(k1_dct8<1>, g8, dim3(kThreads), 0, s, f, wl);
       hipLaunchKernelGGL(k1_dct16_32<1>, g1632, dim3(kThreads), 0, s, f, wl);
     } else {
-      if (JXLH_K1_MERGED && ngroups >= 512) {
-        hipLaunchKernelGGL((k1_dct16_32<0, false, true>), dim3(std::min(8192u, g8.x + g1632.x)), dim3(kThreads), 0, s, f, wl);
-      } else {
-        hipLaunchKernelGGL(k1_dct8<0>, g8, dim3(kThreads), 0, s, f, wl);
-        hipLaunchKernelGGL(k1_dct16_32<0>, g1632, dim3(kThreads), 0, s, f, wl);
-      }
+      hipLaunchKernelGGL(k1_dct8<0>, g8, dim3(kThreads), 0, s, f, wl);
+      hipLaunchKernelGGL(k1_dct16_32<0>, g1632, dim3(kThreads), 0, s, f, wl);
     }
   }
   // what the direct form of k1_dct16_32 left (usually next to nothing: the workgroups read one counter and leave)
@@ -1556,7 +1544,7 @@ void launch_vardct_groups(hipStream_t s, const FrameDev& f_in, int group_row0, i
     if (f.subsampled) {
       hipLaunchKernelGGL((k1_dct8<0, true>), d8, dim3(kThreads), 0, s, fd, wd);
     } else {
-      // (one launch for every DCT class of the routed groups: the form big dense frames take)
+      // (one launch for every DCT class of the routed groups)
       hipLaunchKernelGGL((k1_dct16_32<0, false, true>), dim3(std::min(8192u, d8.x + (unsigned)grid_for(dblk / 2, kWaves * 8 * 2, 4096))),
                          dim3(kThreads), 0, s, fd, wd);
     }

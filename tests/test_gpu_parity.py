@@ -101,6 +101,8 @@ FRAME_CASES = [
     (256, 256, "MIX_DCT8", dict(epf_iters=2, gab=True, lf_smoothing=True)),     # BASELINE config 1
     (520, 300, "MIX_D1", dict(epf_iters=0, gab=True, lf_smoothing=True)),       # config-2 style
     (520, 300, "MIX_D1", dict(epf_iters=2, gab=True, lf_smoothing=True)),       # config-3 style
+    # Gaborish alone (56-row tiles): 9 tile rows, the last one partial -- a second block of 8 in the blockIdx -> tile map
+    (130, 470, "MIX_D1", dict(epf_iters=0, gab=True, lf_smoothing=True)),
     (777, 513, "MIX_ALL", dict(epf_iters=3, gab=True, lf_smoothing=True)),      # config-5 style, ragged
     (512, 512, "MIX_ALL", dict(epf_iters=1, gab=False, lf_smoothing=False)),
     (9, 9, "MIX_D1", dict(epf_iters=2, gab=True, lf_smoothing=True)),           # tiny: smoothing skipped path
