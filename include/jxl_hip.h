@@ -172,7 +172,16 @@ jxlh_status jxlh_free_pinned(jxlh_ctx* ctx, void* p);
 
 /* ---------------------------------------------------------------- VarDCT frame */
 /* Replaces Frame::from_header_and_toc's LF / HfMetadata allocation
- * (frame/decode.rs:172-204) + prepare_render_pipeline (frame/render.rs:907). */
+ * (frame/decode.rs:172-204) + prepare_render_pipeline (frame/render.rs:907).
+ * SIZES.  xsize and ysize may each be up to 2^20 (JXLH_ERR_INVALID_ARGUMENT beyond), subject to two totals
+ * (JXLH_ERR_UNSUPPORTED beyond): fewer than 2^30 samples in one plane -- whole 8x8 blocks, rows rounded up to 64
+ * samples -- and fewer than 2^31 coefficients (3 * 65536 per 256x256 group).  Inside these bounds every entry point
+ * serves either axis at its full length, and so do the stage and Modular entry points, whose w and h are bounded by
+ * 2^20 where they are bounded at all: a frame 8 pixels wide and 65 544 tall is as good as a square one.  Several
+ * kernels take one image row (or 2 to 8) per workgroup row, so such a frame launches grids of more than 65 535
+ * workgroup rows; gfx950 runs them, and tests/test_gpu_long_axis.py holds frames and planes of more than 65 536 rows
+ * or columns to the oracle through every one of these launches.  No combination of sizes may surface as a HIP launch
+ * error: one that cannot be served is declined by the argument checks, before anything is launched. */
 jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p);
 
 /* CustomTransformData::weights2 / weights4 / weights8 (headers/transform_data.rs:337-344): 15 / 55 / 210 weights

@@ -173,6 +173,100 @@ def test_16k_config5_whole_frame_and_determinism(ctx, oracle):
         assert bit_equal(again[c], got[c])
 
 
+@pytest.mark.parametrize("lf_as", ["quantized", "float"])
+def test_lf_image_of_65537_rows(ctx, oracle, lf_as):
+    """8 x 524 296: an LF image of 65 537 rows, one more than fits gridDim.y on earlier CDNA parts.  The LF
+    dequantisation kernels have no stage hook, so the frame carries LF only: every block an 8x8 DCT, every group
+    submitted as an empty sparse run.  The dequantised and smoothed LF and the planes against the oracle, with the LF
+    given quantised (with and without chroma-from-luma) and, in a second run, as the oracle's floats."""
+    import time
+    from jxl_rs_amd import synth
+    w, h, top = 8, 524296, 65536
+    yb, ng = 65537, 2049
+    rng = np.random.default_rng([0x4C46, 65537])
+    yy = np.arange(yb, dtype=np.float64)[:, None]
+    Y = 0.5 + 0.25 * np.cos(2 * np.pi * yy / 61) + rng.uniform(-0.001, 0.001, (yb, 1))
+    X = 0.01 * np.sin(2 * np.pi * yy / 31) + 0.002
+    B = 0.9 * Y + rng.uniform(-0.001, 0.001, (yb, 1))
+    inv_quant_lf = 65536.0 / (21845.0 * 16.0)
+    lf_q = [np.round(Y / (inv_quant_lf / 512.0)).astype(np.int32), np.round(X / (inv_quant_lf / 4096.0)).astype(np.int32),
+            np.round((B - Y) / (inv_quant_lf / 256.0)).astype(np.int32)]
+    wl = synth.VarDctWorkload(w, h, np.full((yb, 1), 0x80, np.uint8), rng.integers(2, 17, size=(yb, 1)).astype(np.int32),
+                              rng.integers(0, 8, size=(yb, 1), dtype=np.uint8),
+                              rng.integers(-16, 17, size=((yb + 7) // 8, 1)).astype(np.int8),
+                              rng.integers(-16, 17, size=((yb + 7) // 8, 1)).astype(np.int8), lf_q, None,
+                              synth.library_dequant_tables(),
+                              dict(epf_iters=0, gab=False, lf_smoothing=True, hshift=(0, 0, 0), vshift=(0, 0, 0)))
+    assert (wl.yblocks, wl.xblocks, wl.ygroups * wl.xgroups) == (yb, 1, ng)
+    # ---- the oracle: LF, smoothed LF, then the groups one by one from one shared all-zero slab
+    p = oracle_params_from(oracle, wl)
+    want_raw = oracle.dequant_lf(p, *lf_q)
+    want_lf = oracle.adaptive_lf_smoothing(p, want_raw)
+    # (one block wide: every LF sample sits on the image's edge and the smoothing passes it through; the smoothing
+    # kernel at this height is held to the oracle through its stage hook in tests/test_gpu_long_axis.py)
+    zero = np.zeros((3, 65536), dtype=np.int32)
+    want = [np.zeros((yb * 8, 8), dtype=np.float32) for _ in range(3)]
+    for g in range(ng):
+        oracle.decode_group(p, g, zero, wl.transform_map, wl.raw_quant, wl.ytox, wl.ytob, want_lf, wl.tables, want)
+    for a in want_lf + want:  # a wrapped or skipped row index must show: see tests/test_gpu_long_axis.py
+        tail = a[top if a is want_lf[0] or a.shape[0] == yb else top * 8:]
+        assert np.any(tail != 0) and not np.array_equal(tail, a[:len(tail)])
+    # (what lies beyond is one LF row, one flat 8x8 block per plane: not zero, and not what the first row holds)
+    # ---- the device; first the same frame with a constant LF, so that neither the LF images nor the planes hold the
+    # right samples already (the two cases share the context)
+    empty = (np.arange(ng, dtype=np.uint32), np.zeros(1, np.uint32), np.zeros(3 * ng, np.uint32))
+    ctx.frame_begin(helpers.gpu_params_from(ctx, wl))
+    ctx.set_dequant_tables(wl.tables)
+    ctx.set_lf_quantized(*[np.full_like(q, 3) for q in lf_q])
+    ctx.set_hf_meta(wl.transform_map, wl.raw_quant, wl.epf_map, wl.ytox, wl.ytob)
+    ctx.submit_groups_sparse(*empty)
+    ctx.slot_wait(0)
+    ctx.frame_run()
+    ctx.sync()
+    t0 = time.perf_counter()
+    ctx.frame_begin(helpers.gpu_params_from(ctx, wl))
+    ctx.set_dequant_tables(wl.tables)
+    if lf_as == "quantized":
+        ctx.set_lf_quantized(*lf_q)
+    else:
+        ctx.set_lf(*want_raw)
+    ctx.set_hf_meta(wl.transform_map, wl.raw_quant, wl.epf_map, wl.ytox, wl.ytob)
+    ctx.submit_groups_sparse(*empty)
+    ctx.slot_wait(0)
+    ctx.frame_run()
+    ctx.sync()
+    got, got_lf = ctx.read_planes(), ctx.read_lf()
+    print(f"8 x 524296 LF-only frame ({lf_as} LF): {time.perf_counter() - t0:.2f} s on the device side")
+    for c in range(3):
+        assert bit_equal(got_lf[c], want_lf[c]), f"LF ch{c}: {diff_report(got_lf[c], want_lf[c])}"
+    for c in range(3):
+        assert bit_equal(got[c], want[c]), f"plane {c}: {diff_report(got[c], want[c])}"
+    if lf_as == "quantized":
+        # a sub-sampled frame dequantises every channel on its own (no chroma-from-luma): the other LF kernel.  Only the
+        # LF samples each channel holds are compared here (a 4:2:0 frame of this height goes through the whole chain in
+        # tests/test_gpu_long_axis.py)
+        wl2 = synth.VarDctWorkload(16, h, np.full((yb, 2), 0x80, np.uint8), np.repeat(wl.raw_quant, 2, axis=1),
+                                   np.repeat(wl.epf_map, 2, axis=1), wl.ytox, wl.ytob, [np.repeat(q, 2, axis=1) for q in lf_q],
+                                   None, wl.tables, dict(epf_iters=0, gab=False, lf_smoothing=False, hshift=(1, 0, 1),
+                                                         vshift=(0, 0, 0)))
+        p2 = oracle_params_from(oracle, wl2)
+        want2 = [oracle.dequant_lf_channel(p2, 0, wl2.lf_q[1]), oracle.dequant_lf_channel(p2, 1, wl2.lf_q[0]),
+                 oracle.dequant_lf_channel(p2, 2, wl2.lf_q[2])]
+        ctx.frame_begin(helpers.gpu_params_from(ctx, wl2))
+        ctx.set_dequant_tables(wl2.tables)
+        ctx.set_lf_quantized(*wl2.lf_q)
+        ctx.set_hf_meta(wl2.transform_map, wl2.raw_quant, wl2.epf_map, wl2.ytox, wl2.ytob)
+        ctx.submit_groups_sparse(*empty)
+        ctx.slot_wait(0)
+        ctx.frame_run()
+        ctx.sync()
+        got2 = ctx.read_lf()
+        mask = [helpers.subsampled_corner_mask(wl2, c) for c in range(3)]
+        for c in range(3):
+            assert mask[c][top:].any() and np.any(want2[c][top:][mask[c][top:]] != 0)
+            assert np.array_equal(got2[c].view(np.uint32)[mask[c]], want2[c].view(np.uint32)[mask[c]]), f"plain LF ch{c}"
+
+
 def test_8k_modular_chain_vs_oracle(ctx, oracle):
     """BASELINE configs[3] against the ORACLE (not only a round trip): the whole default squeeze chain of an
     8192x8192 image on three channels (residuals as in SURVEY 8(d): Laplacian(b = 3), 8-bit averages), then the
