@@ -18,7 +18,9 @@
 //             are staged channel by channel in the wave's private LDS tile with 16-byte
 //             coalesced loads and run through the wave-level cores of varblock_core.h.  For
 //             the small shapes all three channels' loads are issued up front and the dequant
-//             weights stay in registers across batches.
+//             weights stay in registers across batches; on dense slabs every shape's batch is
+//             sized to 16 coefficients per lane and channel or fewer, and all of them issue
+//             the three channels' loads up front.
 //   k1_special / k1_large  the 8x8 special transforms and the 64..256 transforms.
 //
 // HBM traffic is the compulsory 12 B/px in + 12 B/px out (+ maps, + 32 B per varblock of
@@ -363,8 +365,10 @@ __device__ __forceinline__ void stage4(float* __restrict__ buf, int b, int k, fl
   }
 }
 
-// All batches of one DCT shape assigned to this wave.  PREFETCH: issue the coefficient
-// loads of all three channels before touching any (small shapes; 3*E/4 int4 in flight per lane).
+// All batches of one DCT shape assigned to this wave.  PREFETCH: the dequant weights a lane needs stay in registers
+// across batches, and the coefficient loads of all three channels are issued before any is touched (small shapes;
+// 3*E/4 int4 in flight per lane).  Dense slabs issue the three channels' loads together without PREFETCH too, whenever
+// a lane holds at most 16 coefficients per channel (generic_batch: kQPF).
 // Sparse input: builds the integer coefficients of one channel of the batch in the wave's tile
 // (zero, then ds_add of the varblocks' pairs: duplicates from several passes add up before
 // dequantisation, like `coeffs[i] += v` in the dense slab).  64 / NB lanes per varblock walk its
@@ -760,6 +764,11 @@ __device__ __forceinline__ int run_dct_class(const FrameDev& f, const WorkItem* 
 #endif
   constexpr bool kNextItem = kChain && !LISTED && (JXLH_ITEM_PREFETCH == 2 || (JXLH_ITEM_PREFETCH == 1 && PREFETCH));
   constexpr int kLfPerBlock = 3 * (S::R / 8) * (S::C / 8), kLfIters = (S::NB * kLfPerBlock + 63) / 64;
+  // Dense slabs, the 16..32-point classes (16 coefficients per lane and channel): the three channels are dequantised in
+  // one go, see generic_batch.  (Requesting the next batch's work items while this one is transformed, and the LF samples
+  // together with the coefficients, as the entries form does, measured no better on dense slabs -- K1's 16..32-point
+  // kernel 169.4 against 169.0 us, and 175.7 us with the LF samples ahead: profiles/r07_a_dense_k1_batches.txt.)
+  constexpr bool kEarly = SPARSE == 0 && S::E == 16;
   WorkItem it_next = {};
   EntryItem ei_next = {};
   if constexpr (kNextItem) {
@@ -882,8 +891,11 @@ __device__ __forceinline__ int run_dct_class(const FrameDev& f, const WorkItem* 
     // the dense dequantisation pass: every coefficient position of the batch (GM: 0 dense slabs, 1 pair words, 2 entries)
     auto generic_batch = [&](auto mode_tag) {
       constexpr int GM = decltype(mode_tag)::value;
-      int4 qv[kPF ? 3 : 1][NCH];
-      if constexpr (kPF && !GM) {
+      // dense slabs: all three channels' coefficients are requested together whenever a lane holds at most 16 per channel
+      // (48 registers) -- with or without the weights resident (kPF): the two are separate switches
+      constexpr bool kQPF = !GM && (kPF || S::E <= 16);
+      int4 qv[kQPF ? 3 : 1][NCH];
+      if constexpr (kQPF) {
 #pragma unroll
         for (int c = 0; c < 3; c++)
 #pragma unroll
@@ -895,13 +907,12 @@ __device__ __forceinline__ int run_dct_class(const FrameDev& f, const WorkItem* 
               qv[c][j] = gload_i4<JXLH_NT_COEF>(f.coeffs + binfo[b].coef_off + c * kGroupArea + k);
           }
       }
-      // The dequantised Y the X / B channels' chroma-from-luma needs: kept in registers across the channels -- except for
-      // the shape with 32 of them per lane (32x32, dense input), where they would sit through two 32-point IDCTs
-      // (167 VGPRs + 16 spilled + 68 bytes of scratch for that class alone): there X and B dequantise their Y values again
-      // (the coefficient read hits L2, the table-driven dequantisation is ~10 instructions per value).
-      constexpr bool kRecomputeY = !GM && !PREFETCH && S::E > 16;
+      // The dequantised Y the X / B channels' chroma-from-luma needs is kept in registers across the channels.  (Dense
+      // slabs once ran the shapes with a 32-point side at 32 coefficients per lane, where 32 values of Y would have sat
+      // through two 32-point IDCTs: X and B loaded and dequantised their Y again.  Those shapes now run at half the batch.)
+      static_assert(GM != 0 || S::E <= 16, "dense slabs: at most 16 coefficients per lane and channel");
       constexpr bool kDyLds = GM == 2 && SPARSE == 2 && S::E > 16;  // (callers of mode 2 pass s_dy)
-      float dy[kRecomputeY || kDyLds ? 4 : S::E];
+      float dy[kDyLds ? 4 : S::E];
       auto stage_channel = [&](auto ch_tag) {
         constexpr int CH = decltype(ch_tag)::value;
         if constexpr (GM == 1) sparse_stage_channel<S>(f, CH, buf, lane, sl);
@@ -912,9 +923,7 @@ __device__ __forceinline__ int run_dct_class(const FrameDev& f, const WorkItem* 
           const int b = fl / S::N, k = fl % S::N;
           float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
           float d4[4];
-          if constexpr (kRecomputeY) {
-            d4[0] = d4[1] = d4[2] = d4[3] = 0.0f;
-          } else if constexpr (kDyLds) {
+          if constexpr (kDyLds) {
             d4[0] = d4[1] = d4[2] = d4[3] = 0.0f;
             if constexpr (CH != 1) {
               const float4 t = *reinterpret_cast<const float4*>(s_dy + (j * 64 + lane) * 4);
@@ -937,23 +946,17 @@ __device__ __forceinline__ int run_dct_class(const FrameDev& f, const WorkItem* 
               qq = tile_q4<S>(buf, b, k);  // converted in place: this lane alone touches (b, k..k+3)
               if constexpr (kPF) tt = tw[CH][j];
               else tt = *reinterpret_cast<const float4*>(table + CH * tsize + k);
-            } else if constexpr (kPF) {
-              qq = qv[CH][j];
-              tt = tw[CH][j];
             } else {
-              qq = gload_i4<JXLH_NT_COEF>(f.coeffs + bi.coef_off + CH * kGroupArea + k);
-              tt = *reinterpret_cast<const float4*>(table + CH * tsize + k);
-              if constexpr (kRecomputeY && CH != 1) {
-                const int4 qy = gload_i4<false>(f.coeffs + bi.coef_off + kGroupArea + k);
-                const float4 ty = *reinterpret_cast<const float4*>(table + tsize + k);
-                (void)dequant4t<1>(f, qy, ty, bi, adj, d4);
-              }
+              if constexpr (kQPF) qq = qv[CH][j];
+              else qq = gload_i4<JXLH_NT_COEF>(f.coeffs + bi.coef_off + CH * kGroupArea + k);
+              if constexpr (kPF) tt = tw[CH][j];
+              else tt = *reinterpret_cast<const float4*>(table + CH * tsize + k);
             }
             v = dequant4t<CH>(f, qq, tt, bi, adj, d4);
           }
           if constexpr (CH == 1 && kDyLds) {
             *reinterpret_cast<float4*>(s_dy + (j * 64 + lane) * 4) = make_float4(d4[0], d4[1], d4[2], d4[3]);
-          } else if constexpr (CH == 1 && !kRecomputeY) {
+          } else if constexpr (CH == 1) {
             dy[j * 4] = d4[0];
             dy[j * 4 + 1] = d4[1];
             dy[j * 4 + 2] = d4[2];
@@ -963,6 +966,52 @@ __device__ __forceinline__ int run_dct_class(const FrameDev& f, const WorkItem* 
         }
         wave_sync();
       };
+      if constexpr (kEarly && !GM) {
+        // 16 coefficients per lane and channel, all requested above: X and B are dequantised right behind Y, chunk by
+        // chunk (dequant4t in the reference's order Y, X, B; the Y a chunk's chroma-from-luma takes is four registers
+        // old), so what waits through the first two transforms is 32 finished values -- not 32 integers and 16 Y values
+        float4 vx[NCH];
+#pragma unroll
+        for (int j = 0; j < NCH; j++) {
+          const int fl = (j * 64 + lane) * 4;
+          const int b = fl / S::N, k = fl % S::N;
+          float4 vy = make_float4(0.f, 0.f, 0.f, 0.f);
+          float4 vb = vy;
+          vx[j] = vy;
+          if (b < nb) {
+            const BlockInfo bi = binfo[b];
+            float d4[4];
+            float4 ty, tx, tb;
+            if constexpr (kPF) {
+              ty = tw[1][j];
+              tx = tw[0][j];
+              tb = tw[2][j];
+            } else {
+              ty = *reinterpret_cast<const float4*>(table + tsize + k);
+              tx = *reinterpret_cast<const float4*>(table + k);
+              tb = *reinterpret_cast<const float4*>(table + 2 * tsize + k);
+            }
+            vy = dequant4t<1>(f, qv[1][j], ty, bi, adj, d4);
+            vx[j] = dequant4t<0>(f, qv[0][j], tx, bi, adj, d4);
+            vb = dequant4t<2>(f, qv[2][j], tb, bi, adj, d4);
+          }
+          stage4<S>(buf, b, k, vy);
+          *reinterpret_cast<float4*>(s_dy + (j * 64 + lane) * 4) = vb;  // (read back by this lane alone)
+        }
+        wave_sync();
+        transform_channel(TagY{});
+#pragma unroll
+        for (int j = 0; j < NCH; j++) stage4<S>(buf, ((j * 64 + lane) * 4) / S::N, ((j * 64 + lane) * 4) % S::N, vx[j]);
+        wave_sync();
+        transform_channel(TagX{});
+#pragma unroll
+        for (int j = 0; j < NCH; j++)
+          stage4<S>(buf, ((j * 64 + lane) * 4) / S::N, ((j * 64 + lane) * 4) % S::N,
+                    *reinterpret_cast<const float4*>(s_dy + (j * 64 + lane) * 4));
+        wave_sync();
+        transform_channel(TagB{});
+        return;
+      }
       // channel order of the reference: Y, X, B (group.rs:223)
       stage_channel(TagY{});
       transform_channel(TagY{});
@@ -1042,6 +1091,16 @@ using S8x32 = Shape<8, 32>;
 using S32x16 = Shape<32, 16>;
 using S16x32 = Shape<16, 32>;
 
+// Dense slabs: the classes with a 32-point side at HALF the varblocks per batch -- 16 coefficients per lane and channel,
+// like 16x16 and 32x8 -- so that their body is the one the small shapes run: the three channels' coefficients requested
+// together (48 registers), the dequantised Y kept in 16.  (At 32 per lane that form does not fit: the channels went to
+// memory one after the other and X / B loaded and dequantised their Y again.)
+using D32x32 = Shape<32, 32, 1>;
+using D32x16 = Shape<32, 16, 2>;
+using D16x32 = Shape<16, 32, 2>;
+using D8x32 = Shape<8, 32, 4>;
+constexpr int kTileD = cmax(cmax(cmax(cmax(S32x8::kTile, D8x32::kTile), cmax(D32x16::kTile, D16x32::kTile)), D32x32::kTile),
+                            cmax(cmax(S16x16::kTile, S16x8::kTile), cmax(S8x16::kTile, S8x8::kTile)));  // 1600 words
 constexpr int kTileA = S8x8::kTile;                                               // 832 words
 constexpr int kTileC = cmax(cmax(cmax(S32x8::kTile, S8x32::kTile), cmax(S32x16::kTile, S16x32::kTile)),
                             S32x32::kTile);                                       // 2624
@@ -1130,19 +1189,23 @@ __global__ __launch_bounds__(kThreads, SPARSE == 3 ? JXLH_K1_DIRECT_WPE : SPARSE
       if (__any(fb_pre[k] == (uint32_t)f.fb_epoch)) fb_live |= 1u << k;
     if (!fb_live) return;  // (every wave of the workgroup reads the same words: uniform)
   }
-  __shared__ __attribute__((aligned(16))) float s_buf[kWaves * kTileC];
+  constexpr bool kDense = SPARSE == 0;
+  constexpr int kTileK = kDense ? kTileD : kTileC;
+  __shared__ __attribute__((aligned(16))) float s_buf[kWaves * kTileK];
   __shared__ BlockInfo s_binfo[kWaves][8];
   using EX = std::conditional_t<SPARSE == 2, uint64_t, uint32_t>;  // mode 2 takes any entry count (excl_bits)
   __shared__ EX s_excl[SPARSE >= 2 ? kWaves : 1][kExclWords];
   __shared__ AdjTable s_adj;
   build_adj_table(f, &s_adj, threadIdx.x, kThreads);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* buf = s_buf + wave * kTileC;
+  float* buf = s_buf + wave * kTileK;
   EX* ex = s_excl[SPARSE >= 2 ? wave : 0];
   __shared__ float s_lfs[SPARSE >= 2 ? kWaves : 1][96];  // LF samples of a batch: NB * 3 * (R / 8) * (C / 8) <= 96
   float* lfs = s_lfs[SPARSE >= 2 ? wave : 0];
-  __shared__ __attribute__((aligned(16))) float s_dyb[SPARSE == 2 ? kWaves * kDyWords : 4];
-  float* sdy = SPARSE == 2 ? s_dyb + wave * kDyWords : nullptr;
+  // (dense slabs: the finished B values of a batch wait here through the Y and X transforms, 16 per lane)
+  constexpr int kParkWords = 16 * 64;
+  __shared__ __attribute__((aligned(16))) float s_dyb[SPARSE == 2 ? kWaves * kDyWords : kDense ? kWaves * kParkWords : 4];
+  float* sdy = SPARSE == 2 ? s_dyb + wave * kDyWords : kDense ? s_dyb + wave * kParkWords : nullptr;
   const int gw = blockIdx.x * kWaves + wave, nw = gridDim.x * kWaves;
   auto cnt = [&](int cls) { return wl.counts[cls * kCountPitch]; };
   // the long batches (32-point sides) first: the tail of the launch is then made of the short ones
@@ -1166,11 +1229,11 @@ __global__ __launch_bounds__(kThreads, SPARSE == 3 ? JXLH_K1_DIRECT_WPE : SPARSE
         wl.fallback[CLS], wl.counts + (kCntFallback0 + CLS) * kCountPitch, sdy, FB ? fb_pre[fb_k] : 0u, wl.fb_any, &fb_rank);
     used += FB ? (nbat + 15) / 16 : nbat;
   };
-  run(ShapeTag<S32x32>{}, std::false_type{}, std::integral_constant<int, kClsDct32x32>{}, 5, 0);
-  run(ShapeTag<S32x16>{}, std::false_type{}, std::integral_constant<int, kClsDct32x16>{}, 10, 1);
-  run(ShapeTag<S16x32>{}, std::false_type{}, std::integral_constant<int, kClsDct16x32>{}, 11, 2);
+  run(ShapeTag<std::conditional_t<kDense, D32x32, S32x32>>{}, std::false_type{}, std::integral_constant<int, kClsDct32x32>{}, 5, 0);
+  run(ShapeTag<std::conditional_t<kDense, D32x16, S32x16>>{}, std::false_type{}, std::integral_constant<int, kClsDct32x16>{}, 10, 1);
+  run(ShapeTag<std::conditional_t<kDense, D16x32, S16x32>>{}, std::false_type{}, std::integral_constant<int, kClsDct16x32>{}, 11, 2);
   run(ShapeTag<S32x8>{}, std::false_type{}, std::integral_constant<int, kClsDct32x8>{}, 8, 3);
-  run(ShapeTag<S8x32>{}, std::false_type{}, std::integral_constant<int, kClsDct8x32>{}, 9, 4);
+  run(ShapeTag<std::conditional_t<kDense, D8x32, S8x32>>{}, std::false_type{}, std::integral_constant<int, kClsDct8x32>{}, 9, 4);
   run(ShapeTag<S16x16>{}, std::true_type{}, std::integral_constant<int, kClsDct16x16>{}, 4, 5);
   run(ShapeTag<S16x8>{}, std::true_type{}, std::integral_constant<int, kClsDct16x8>{}, 6, 6);
   run(ShapeTag<S8x16>{}, std::true_type{}, std::integral_constant<int, kClsDct8x16>{}, 7, 7);

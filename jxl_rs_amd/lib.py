@@ -964,7 +964,9 @@ class Context:
         out = np.zeros(29, np.int32)
         self._chk(self.L.jxlh_frame_k1_counters(self._ctx, _addr(out), 29), "frame_k1_counters")
         names = ["dct8", "dct16x8", "dct8x16", "dct16x16", "dct32x8", "dct8x32", "dct32x16", "dct16x32", "dct32x32"]
-        nb = [8, 8, 8, 4, 4, 8, 4, 4, 2]   # varblocks per batch (Shape::NB)
+        # varblocks per batch (Shape::NB) of the entries form, which the fallback counters belong to; dense slabs run the
+        # classes with a 32-point side at half of it
+        nb = [8, 8, 8, 4, 4, 8, 4, 4, 2]
         return {"varblocks": {k: int(v) for k, v in zip(names + ["special", "large"], out[:11])},
                 "fallback_batches": {k: int(v) for k, v in zip(names, out[11:20])},
                 "batches": {k: int(-(-int(v) // b)) for k, v, b in zip(names, out[:9], nb)},
