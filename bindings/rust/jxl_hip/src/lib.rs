@@ -71,6 +71,29 @@ impl Context {
     pub fn raw(&self) -> *mut sys::jxlh_ctx {
         self.raw
     }
+    /// `jxlh_stage_save`: the save tail on caller planes in host memory -- `planes` are 3 colour + extra-channel planes of
+    /// `w x h` samples at `stride`; `frame_origin` is the position of plane pixel (0, 0) in its frame (the dither table
+    /// sees it); `out` holds the whole oriented image at `bytes_per_row`.  What a Modular frame calls.
+    #[allow(clippy::too_many_arguments)]
+    pub fn stage_save(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc, planes: &[&[f32]], w: u32,
+                      h: u32, stride: usize, frame_origin: (u32, u32), y0: u32, y1: u32, out: &mut [u8],
+                      bytes_per_row: usize) -> Result<()> {
+        if w == 0 || h == 0 || stride < w as usize || !save_fits(desc, w, h, bytes_per_row, out.len()) {
+            return Err(HipError::InvalidArgument);
+        }
+        let need = (h as usize - 1).checked_mul(stride).and_then(|n| n.checked_add(w as usize));
+        match need {
+            Some(n) if planes.iter().all(|p| p.len() >= n) => {}
+            _ => return Err(HipError::InvalidArgument),
+        }
+        let ptrs: Vec<*const f32> = planes.iter().map(|p| p.as_ptr()).collect();
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        // SAFETY: every plane holds h rows of w samples at `stride`, `out` the whole oriented image; the call waits
+        self.ok(unsafe {
+            sys::jxlh_stage_save(self.raw, colour, desc, ptrs.as_ptr(), ptrs.len() as u32, w, h, stride, frame_origin.0,
+                                 frame_origin.1, y0, y1, out.as_mut_ptr() as *mut c_void, bytes_per_row)
+        })
+    }
     fn ok(&self, st: sys::jxlh_status) -> Result<()> {
         check(self.raw, st)
     }
@@ -172,13 +195,46 @@ pub struct VarDctFrame<'a> {
     ctx: &'a Context,
     pub xsize: u32,
     pub ysize: u32,
+    /// size of the frame's own result (the upsampled size of an upsampled frame) and of what the read / save calls see
+    /// now: the same, or the image the frame was blended onto
+    frame_out: (u32, u32),
+    out_size: std::cell::Cell<(u32, u32)>,
+}
+
+/// Bytes of one pixel of a save: samples per pixel times the sample size of `format`.
+fn save_pixel_bytes(desc: &sys::jxlh_save_desc) -> usize {
+    let sample = match desc.format {
+        sys::JXLH_SAVE_U8 => 1,
+        sys::JXLH_SAVE_F32 => 4,
+        _ => 2,
+    };
+    (desc.n_channels as usize + usize::from(desc.fill_opaque_alpha != 0)) * sample
+}
+
+/// Whether `len` bytes hold the oriented image of a `w x h` source at `bytes_per_row`.
+fn save_fits(desc: &sys::jxlh_save_desc, w: u32, h: u32, bytes_per_row: usize, len: usize) -> bool {
+    let (ow, oh) = if desc.orientation >= 5 { (h as usize, w as usize) } else { (w as usize, h as usize) };
+    if ow == 0 || oh == 0 {
+        return false;
+    }
+    let row = match ow.checked_mul(save_pixel_bytes(desc)) {
+        Some(r) => r,
+        None => return false,
+    };
+    match (oh - 1).checked_mul(bytes_per_row).and_then(|b| b.checked_add(row)) {
+        Some(need) => bytes_per_row >= row && len >= need,
+        None => false,
+    }
 }
 
 impl<'a> VarDctFrame<'a> {
     /// `Frame::from_header_and_toc` + `prepare_render_pipeline` (frame/decode.rs:172-204, frame/render.rs:907)
     pub fn begin(ctx: &'a Context, p: &sys::jxlh_frame_params) -> Result<Self> {
         ctx.ok(unsafe { sys::jxlh_frame_begin(ctx.raw, p) })?;
-        Ok(Self { ctx, xsize: p.xsize, ysize: p.ysize })
+        let n = p.upsampling.max(1);
+        let out = (if p.xsize_upsampled != 0 { p.xsize_upsampled } else { p.xsize * n },
+                   if p.ysize_upsampled != 0 { p.ysize_upsampled } else { p.ysize * n });
+        Ok(Self { ctx, xsize: p.xsize, ysize: p.ysize, frame_out: out, out_size: std::cell::Cell::new(out) })
     }
     /// `decode_hf_global`: `DequantMatrices::matrix(table, c)` for the 17 tables (frame/quant_weights.rs:1081-1086)
     pub fn decode_hf_global(&self, tables: &[&[f32]; 17]) -> Result<()> {
@@ -256,6 +312,7 @@ impl<'a> VarDctFrame<'a> {
     /// `Frame::finalize_lf` + `SigmaSource::new` + the reconstruction of every submitted group + the Gaborish / EPF
     /// stages of frame/render.rs:569-622 (and chroma upsampling / upsampling / noise when the parameters ask for them)
     pub fn finalize_and_render(&self) -> Result<()> {
+        self.out_size.set(self.frame_out); // a render discards a composition
         self.ctx.ok(unsafe { sys::jxlh_frame_run(self.ctx.raw, 0, u32::MAX) })
     }
     /// The colour stage (`None`: the planes are in the output colour space already), `BlendingStage` and
@@ -264,10 +321,53 @@ impl<'a> VarDctFrame<'a> {
     /// `jxlh_frame_save_reference` see, until the next render.
     pub fn blend(&self, desc: &sys::jxlh_blend_desc, colour: Option<&sys::jxlh_output_desc>) -> Result<()> {
         let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
-        self.ctx.ok(unsafe { sys::jxlh_frame_blend(self.ctx.raw, desc, colour) })
+        self.ctx.ok(unsafe { sys::jxlh_frame_blend(self.ctx.raw, desc, colour) })?;
+        self.out_size.set((desc.image_w, desc.image_h));
+        Ok(())
+    }
+    /// (width, height) of what the read and save calls see: the frame, its upsampled image, or the image it was blended
+    /// onto
+    pub fn out_size(&self) -> (u32, u32) {
+        self.out_size.get()
+    }
+    /// The save tail of frame/render.rs:793-903 in one pass over the frame's result: spot colours, premultiplication,
+    /// the conversion to u8 / u16 / f16 / f32 and the save stage with its channel order, endianness, opaque-alpha fill and
+    /// orientation, behind the colour stage `colour` (`None` after `blend`).  Source rows `[y0, y1)` (`y1` is cut at the
+    /// result's height) go to their display positions in the whole oriented image at `out`.
+    ///
+    /// # Safety
+    /// `out` must be writable memory (host or device) holding the WHOLE oriented image at `bytes_per_row`: the result's
+    /// height in rows for orientations 1-4, its width in rows for 5-8 (the result is the frame, its upsampled image, or
+    /// the image it was blended onto -- a size only the caller's headers know).
+    pub unsafe fn save(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc, y0: u32, y1: u32,
+                       out: *mut c_void, bytes_per_row: usize) -> Result<()> {
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        self.ctx.ok(sys::jxlh_frame_save(self.ctx.raw, colour, desc, y0, y1, out, bytes_per_row))
+    }
+    /// `save` into host memory, checked: `out` must hold the whole oriented image of the current result (`out_size()`,
+    /// transposed for orientations 5-8) at `bytes_per_row`; the call returns after the copy has completed.
+    pub fn save_to_slice(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc, y0: u32, y1: u32,
+                         out: &mut [u8], bytes_per_row: usize) -> Result<()> {
+        let (w, h) = self.out_size.get();
+        if !save_fits(desc, w, h, bytes_per_row, out.len()) {
+            return Err(HipError::InvalidArgument);
+        }
+        // SAFETY: the slice holds every byte the oriented image can touch, and the call waits for the copy
+        unsafe { self.save(colour, desc, y0, y1, out.as_mut_ptr() as *mut c_void, bytes_per_row) }
+    }
+    /// `save` without the final wait (`jxlh_frame_save_async`): `out` holds the image after the next `Context::sync`.
+    ///
+    /// # Safety
+    /// As `save`; in addition `out` (pinned host memory, or device memory) must stay valid and untouched until the
+    /// context has been synchronised.
+    pub unsafe fn save_async(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc, y0: u32, y1: u32,
+                             out: *mut c_void, bytes_per_row: usize) -> Result<()> {
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        self.ctx.ok(sys::jxlh_frame_save_async(self.ctx.raw, colour, desc, y0, y1, out, bytes_per_row))
     }
     /// `mark_group_to_rerender` + re-render (render/mod.rs:143-146): after more passes arrived for `groups`
     pub fn rerender_groups(&self, groups: &[u32]) -> Result<()> {
+        self.out_size.set(self.frame_out); // a render discards a composition
         self.ctx.ok(unsafe { sys::jxlh_frame_rerender_groups(self.ctx.raw, groups.as_ptr(), groups.len() as u32) })
     }
     /// the save stage for planar f32 XYB output; `out[c]` = `RawImageBuffer` of channel c

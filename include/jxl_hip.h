@@ -650,8 +650,8 @@ jxlh_status jxlh_frame_read_output_async(jxlh_ctx* ctx, const jxlh_output_desc* 
  * jxlh_stage_blend: the same kernel on caller planes (host or device): frame[] are n_channels = 3 + num_ec planes of
  * w x h at row stride `stride` floats, already in the output colour space; out[] as many image_w x image_h planes at
  * row stride out_stride.  The Modular seam and tests.
- * Not done here: alpha taken from an extra channel into the interleaved 8 / 16-bit output, premultiplication, spot
- * colours, splines. */
+ * Alpha taken from an extra channel into the interleaved output, premultiplication and spot colours belong to the
+ * save tail behind this stage: jxlh_frame_save below.  Not done here: splines. */
 /* BlendingMode (headers/frame_header.rs:98-104) */
 enum {
   JXLH_BLEND_REPLACE = 0, JXLH_BLEND_ADD = 1, JXLH_BLEND_BLEND = 2, JXLH_BLEND_ALPHA_WEIGHTED_ADD = 3, JXLH_BLEND_MUL = 4
@@ -673,6 +673,80 @@ typedef struct jxlh_blend_desc {
 jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* desc, const jxlh_output_desc* colour);
 jxlh_status jxlh_stage_blend(jxlh_ctx* ctx, const jxlh_blend_desc* desc, const float* const frame[], uint32_t n_channels,
                              uint32_t w, uint32_t h, size_t stride, float* const out[], size_t out_stride);
+
+/* ---------------------------------------------------------------- the save tail (frame/render.rs:793-903)
+ * What the reference puts behind a frame's last f32 stage, fused into one pass over the frame's result (its planes, or
+ * the canvas after jxlh_frame_blend) and its extra channels; nothing is written back to them, so a frame can be saved
+ * any number of times, into several buffers, and jxlh_frame_read_planes keeps returning the planes in front of these
+ * stages.  Per output sample, in registers:
+ *   1. the colour stage `colour` names on channels 0..2 (as jxlh_frame_read_output; bits / channels are ignored; NULL =
+ *      JXLH_COLOR_NONE).  After jxlh_frame_blend it has run already: anything but JXLH_COLOR_NONE is JXLH_ERR_BAD_STATE;
+ *   2. SpotColorStage (render/stages/spot.rs:40-67) for spot[0 .. n_spot), in order: mix = rgba[3] * s,
+ *      c = mix * rgba[k] + (1 - mix) * c, two products and a sum rounded separately;
+ *   3. PremultiplyAlphaStage (premultiply_alpha.rs:47-92) when `premultiply`: the colour channels times the sample of
+ *      pipeline channel premultiply_alpha_channel;
+ *   4. conversion of each channel of `channels` (pipeline channels in output order: 0..2 colour, 3 + ec extra channel
+ *      ec; BGR(A) is {2, 1, 0(, a)}, gray {0}, a lone extra channel {3 + ec}):
+ *        JXLH_SAVE_U8   ConvertF32ToU8Stage, bit_depth 1..8: v * max + dither[(y + 13 ch) % 32][(x + 23 ch) % 32], clamped
+ *                       to [0, max] (NaN -> 0), round to nearest even; ch is the PIPELINE channel
+ *        JXLH_SAVE_U16  ConvertF32ToU16Stage, bit_depth 1..16: clamp to [0, 1] (NaN -> 0), * max, round to nearest even
+ *        JXLH_SAVE_F16  ConvertF32ToF16Stage: f32::clamp(f16_clamp_min, f16_clamp_max) when f16_clamp (a NaN stays, the
+ *                       reference uses (0, 1) for PQ and (-0.074, 1.1) for HLG), then f16::from_f32 of util/float16.rs as
+ *                       written: nearest even in the normal range, TRUNCATION into f16 denormals, NaN -> sign | 0x7E00.
+ *                       As written, that function shifts a denormal result one bit further than the 2^-24 unit asks for
+ *                       ((mant | 0x800000) >> -unbiased): |v| in [2^-24, 2^-23) gives a zero and every f16 denormal comes
+ *                       out at half its IEEE value.  The device gives the reference's bits, not IEEE's.
+ *        JXLH_SAVE_F32  the bits
+ *      16- and 32-bit samples little endian, or big endian when big_endian;
+ *   5. when fill_opaque_alpha, one more sample behind them: 2^bit_depth - 1, 0x3C00 or 1.0f (api/data_types.rs:114-149);
+ *   6. position: the samples of source pixel (x, y) go to pixel display_pixel((x, y), (w, h)) of the oriented image,
+ *      orientation 1..8 as headers/image_metadata.rs:85-96 (1 identity, 2 flip horizontal, 3 rotate 180, 4 flip
+ *      vertical, 5 transpose, 6 rotate 90 cw, 7 anti-transpose, 8 rotate 90 ccw); the image is h x w for 5..8.
+ * (x, y) are the result's coordinates -- image coordinates after jxlh_frame_blend, upsampled ones for an upsampled frame.
+ * jxlh_frame_save: `out` (host or device memory) is the origin of the WHOLE oriented image, bytes_per_row its row
+ * pitch; rows [y0, y1) of the SOURCE (y1 is cut at the result's height) are written, each pixel to its display
+ * position, so a caller can save in bands under every orientation.  Extra channels are the planes
+ * jxlh_frame_read_extra_channel returns (patched, upsampled, converted, or the canvas channel).  Host memory goes
+ * through the context's staging buffer; a chroma-subsampled frame materialises its chroma first.  _async: without the
+ * final wait, as jxlh_frame_read_output_async.
+ * jxlh_stage_save: the same kernel on caller planes (host or device): planes[] are n_planes >= 3 f32 planes (3 colour +
+ * extra channels) of w x h at row stride `stride` floats; (frame_x0, frame_y0) is the position of plane pixel (0, 0) in
+ * its frame, which only the dither table sees.  The Modular seam and tests.
+ * Checked before anything is launched or written.  JXLH_ERR_INVALID_ARGUMENT: a null pointer; n_channels 0 or > 4, or
+ * more than 4 samples with the fill; a channel >= 3 + JXLH_MAX_EXTRA_CHANNELS (jxlh_stage_save: >= n_planes); format,
+ * orientation or bit_depth out of range; y0 >= y1; bytes_per_row smaller than the oriented row or, like `out`, not a
+ * multiple of the sample size; f16_clamp with min > max or a NaN bound; a premultiply or spot channel that is not an
+ * extra channel; n_spot > JXLH_MAX_EXTRA_CHANNELS.  JXLH_ERR_BAD_STATE: no result; a colour stage on a blended frame; an
+ * extra channel that is not set or not rendered, or does not cover the result (an upsampled frame whose extra channels
+ * stayed smaller).  JXLH_ERR_UNSUPPORTED: sharded contexts; w * h >= 2^31. */
+enum { JXLH_SAVE_U8 = 0, JXLH_SAVE_U16 = 1, JXLH_SAVE_F16 = 2, JXLH_SAVE_F32 = 3 };
+typedef struct jxlh_spot_color {
+  uint32_t ec;    /* extra channel index */
+  float rgba[4];  /* ExtraChannelInfo::spot_color */
+} jxlh_spot_color;
+typedef struct jxlh_save_desc {
+  uint32_t n_channels;  /* 1..4 */
+  uint32_t channels[4]; /* pipeline channels in output order */
+  uint32_t fill_opaque_alpha;
+  uint32_t format;      /* JXLH_SAVE_* */
+  uint32_t bit_depth;   /* U8: 1..8, U16: 1..16; ignored for F16 / F32 */
+  uint32_t big_endian;
+  uint32_t orientation; /* 1..8 */
+  uint32_t f16_clamp;
+  float f16_clamp_min, f16_clamp_max;
+  uint32_t premultiply;
+  uint32_t premultiply_alpha_channel; /* pipeline channel, 3 + ec */
+  uint32_t n_spot;
+  jxlh_spot_color spot[8];
+} jxlh_save_desc;
+jxlh_status jxlh_frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save, uint32_t y0,
+                            uint32_t y1, void* out, size_t bytes_per_row);
+jxlh_status jxlh_frame_save_async(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save, uint32_t y0,
+                                  uint32_t y1, void* out, size_t bytes_per_row);
+jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save,
+                            const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
+                            uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
+                            size_t bytes_per_row);
 
 /* ---------------------------------------------------------------- stage-level hooks */
 /* Whole-image single stages with the pipeline's mirror edge semantics; the analogue of

@@ -166,6 +166,12 @@ class VarDctFrame {
                                       (size_t)out_width() * d.channels * (d.bits / 8)),
                "jxlh_frame_read_output");
   }
+  // the save tail (jxlh_frame_save): rows [y0, y1) of the result through spot colours, premultiplication, conversion and
+  // orientation into the oriented image at `out`; colour = the colour stage in front (nullptr after blend())
+  void save(const jxlh_output_desc* colour, const jxlh_save_desc& desc, void* out, size_t bytes_per_row, uint32_t y0 = 0,
+            uint32_t y1 = 0xFFFFFFFFu) {
+    ctx_.check(jxlh_frame_save(ctx_.raw(), colour, &desc, y0, y1, out, bytes_per_row), "jxlh_frame_save");
+  }
   uint32_t out_width() const {
     if (blend_w_) return blend_w_;
     const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;

@@ -62,6 +62,11 @@ jxlh_status jxlh_frame_k1_counters(jxlh_ctx* ctx, int32_t* out, int32_t n);
  * everything). */
 jxlh_status jxlh_worklist_layout(int32_t xblocks, int32_t yblocks, uint64_t* out, int32_t n);
 
+/* The tile of the transposing save kernel (orientations 5-8 of jxlh_frame_save, csrc/k_save.hip) for a pixel of
+ * `pixel_bytes` bytes (1..16), in source pixels: host code, no device.  Tests take the sizes that straddle a tile edge
+ * from here. */
+jxlh_status jxlh_save_tile_layout(uint32_t pixel_bytes, uint32_t* columns, uint32_t* rows);
+
 /* Device self-test of the EPF weight normalisation: the filters compute 1/(1 + sum of weights)
  * (epf0.rs:208, epf1.rs:140, epf2.rs:130 divide) with rcp + two FMA refinement steps.  Counts the
  * floats whose bit pattern lies in [lo_bits, hi_bits) for which that differs from the IEEE

@@ -187,8 +187,48 @@ struct ExtendToImageDimensionsStage {
   std::string display() const { return "extend-to-image-dims"; }
   bool uses_channel(int) const { return true; }
 };
-// A stage of the reference this path does not run on the device (patches by name, splines, spot colour,
-// premultiplied alpha, extra-channel conversions ...): adding one makes build() fail with JXLH_ERR_UNSUPPORTED.
+// SpotColorStage::new(spot_c_offset, spot_color) (spot.rs:24-29, added at frame/render.rs:793-806): in place on the
+// colour channels, reading extra channel `ec`
+struct SpotColorStage {
+  int ec;
+  std::array<float, 4> rgba;
+  std::string display() const { return "spot color stage for channel " + std::to_string(3 + ec); }
+  bool uses_channel(int c) const { return c < 3 || c == 3 + ec; }
+};
+// PremultiplyAlphaStage::new(first_color_channel, num_color_channels, alpha_channel) (premultiply_alpha.rs:33-45)
+struct PremultiplyAlphaStage {
+  int first_color_channel, num_color_channels, alpha_channel;
+  std::string display() const {
+    return "premultiply alpha stage for color channels " + std::to_string(first_color_channel) + "-" +
+           std::to_string(first_color_channel + num_color_channels - 1) + " with alpha channel " + std::to_string(alpha_channel);
+  }
+  bool uses_channel(int c) const {
+    return (c >= first_color_channel && c < first_color_channel + num_color_channels) || c == alpha_channel;
+  }
+};
+// ConvertF32ToF16Stage::new_with_clamp_range(channel, clamp_range) (convert.rs:796-811)
+struct ConvertF32ToF16Stage {
+  int channel;
+  bool clamp = false;
+  float clamp_min = 0.0f, clamp_max = 0.0f;
+  static constexpr Border BORDER{0, 0}, SHIFT{0, 0};
+  std::string display() const { return "convert F32 to F16 in channel " + std::to_string(channel); }
+  bool uses_channel(int c) const { return c == channel; }
+};
+// JxlColorType / JxlDataFormat / Endianness (api/data_types.rs) and Orientation (headers/image_metadata.rs:85-96, the
+// values 1..8 of the codestream) as the richer add_save_stage takes them
+enum class ColorType { kGrayscale, kGrayscaleAlpha, kRgb, kRgba, kBgr, kBgra };
+struct DataFormat {
+  uint32_t format;     // JXLH_SAVE_*
+  uint32_t bit_depth;  // U8 / U16
+  bool big_endian;
+  static DataFormat u8(uint32_t depth = 8) { return {JXLH_SAVE_U8, depth, false}; }
+  static DataFormat u16(uint32_t depth = 16, bool be = false) { return {JXLH_SAVE_U16, depth, be}; }
+  static DataFormat f16(bool be = false) { return {JXLH_SAVE_F16, 0, be}; }
+  static DataFormat f32(bool be = false) { return {JXLH_SAVE_F32, 0, be}; }
+};
+// A stage of the reference this path does not run on the device (patches by name, splines ...): adding one makes
+// build() fail with JXLH_ERR_UNSUPPORTED.
 struct CpuOnlyStage {
   std::string name;
   std::string display() const { return name; }
@@ -200,6 +240,12 @@ struct SaveStage {
   int output_buffer_index;
   uint32_t color_channels;  // 3 = RGB, 4 = RGBA (fill_opaque_alpha)
   uint32_t bits;            // 8, 16, or 32 = the f32 planes themselves (JxlDataFormat::F32)
+  // the six-argument form of builder.rs:87-105 (`full`): the stage lowers to a jxlh_save_desc; color_channels / bits unused
+  bool full = false;
+  uint32_t orientation = 1;
+  ColorType color_type = ColorType::kRgb;
+  DataFormat data_format{JXLH_SAVE_U8, 8, false};
+  bool fill_opaque_alpha = false;
   std::string display() const { return "save stage for buffer " + std::to_string(output_buffer_index); }
   bool uses_channel(int c) const {
     for (int ch : channels)
@@ -211,7 +257,8 @@ struct SaveStage {
 using Stage = std::variant<ConvertModularToF32Stage, ConvertModularXYBToF32Stage, HorizontalChromaUpsample, VerticalChromaUpsample, GaborishStage, Epf0Stage, Epf1Stage, Epf2Stage,
                            Upsample2x, Upsample4x, Upsample8x, ConvolveNoiseStage, AddNoiseStage, XybStage, YcbcrToRgbStage,
                            FromLinearStage, ConvertF32ToU8Stage, ConvertF32ToU16Stage, CpuOnlyStage, SaveStage, PatchesStage,
-                           BlendingStage, ExtendToImageDimensionsStage>;
+                           BlendingStage, ExtendToImageDimensionsStage, SpotColorStage, PremultiplyAlphaStage,
+                           ConvertF32ToF16Stage>;
 
 inline std::string stage_display(const Stage& s) {
   return std::visit([](const auto& st) { return st.display(); }, s);
@@ -246,6 +293,11 @@ struct LoweredPipeline {
   bool has_blend = false;
   jxlh_blend_desc blend{};
   jxlh_output_desc blend_colour{};
+  // The save tail (six-argument save stages): saves[i] is output buffer i, behind the colour stage `output` names
+  // (color / transfer / xyb / tf_param; JXLH_COLOR_NONE after a blend).  SpotColorStage and PremultiplyAlphaStage fold
+  // into the save that carries colour channels; extra-channel saves carry neither.  GpuRenderPipeline::save(i, ...) runs
+  // jxlh_frame_save with it.
+  std::vector<jxlh_save_desc> saves;
   uint32_t out_w = 0, out_h = 0;  // what the save stages see: the frame's (upsampled) size, or the image's when blending
   std::vector<std::string> stages;  // Display strings, in order (diagnostics; what `info!("adding stage")` logs)
 };
@@ -276,6 +328,18 @@ class RenderPipelineBuilder {
   RenderPipelineBuilder add_save_stage(std::vector<int> channels, int output_buffer_index, uint32_t color_channels,
                                        uint32_t bits) && {
     stages_.emplace_back(SaveStage{std::move(channels), output_buffer_index, color_channels, bits});
+    return std::move(*this);
+  }
+  // builder.rs:87-105 in full: channels, orientation, output buffer index, colour type, data format, fill_opaque_alpha
+  RenderPipelineBuilder add_save_stage(std::vector<int> channels, uint32_t orientation, int output_buffer_index,
+                                       ColorType color_type, DataFormat data_format, bool fill_opaque_alpha) && {
+    SaveStage st{std::move(channels), output_buffer_index, 0, 0};
+    st.full = true;
+    st.orientation = orientation;
+    st.color_type = color_type;
+    st.data_format = data_format;
+    st.fill_opaque_alpha = fill_opaque_alpha;
+    stages_.emplace_back(std::move(st));
     return std::move(*this);
   }
   RenderPipelineBuilder add_extend_stage() && {  // without the stage's arguments there is nothing to lower
@@ -336,6 +400,28 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   auto same_info = [](const jxlh_blending_info& a, const jxlh_blending_info& b) {
     return a.mode == b.mode && a.alpha_channel == b.alpha_channel && a.clamp == b.clamp && a.source == b.source;
   };
+  // the save tail: conversions since the last save stage (one per channel), spot colours, premultiplication
+  struct Conv {
+    int channel;
+    uint32_t format, depth;
+    bool clamp;
+    float clamp_min, clamp_max;
+    std::string name;
+  };
+  std::vector<Conv> convs;
+  std::vector<jxlh_spot_color> spots;
+  bool premul_seen = false, colour_saved = false, tail_seen = false;
+  // A list with a six-argument save stage is checked by the save tail's rules; a list without one goes through the
+  // checks it always went through, with the statuses it always got.
+  bool has_full_save = false;
+  for (const Stage& s : stages_)
+    if (const auto* sv = std::get_if<SaveStage>(&s)) has_full_save |= sv->full;
+  int premul_alpha = -1, premul_n = 0;
+  auto add_conv = [&](const Stage& s, int ch, uint32_t format, uint32_t depth, bool clamp, float lo, float hi) {
+    for (const Conv& c : convs)
+      if (c.channel == ch) fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': the channel is converted twice before a save stage");
+    convs.push_back(Conv{ch, format, depth, clamp, lo, hi, stage_display(s)});
+  };
   Border border{0, 0};
   auto add_border = [&](Border b) {
     if (pre_upsample) {
@@ -360,6 +446,9 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       // the reference's position: behind the colour stage, in front of the conversions (frame/render.rs:754-779)
       if (blend_seen) fail(JXLH_ERR_INVALID_ARGUMENT, "two blending stages");
       if (phase > kConvert || convert_seen) fail(JXLH_ERR_INVALID_ARGUMENT, "blending stage behind the conversion / save stages");
+      // frame/render.rs:765-806: spot colours, premultiplication and every conversion come behind blend / extend
+      if (!spots.empty() || premul_seen || !convs.empty() || tail_seen)
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "' behind a spot colour, premultiply or conversion stage: they follow the blending and extend stages");
       if (lp.modular != LoweredPipeline::Modular::kNone)
         fail(JXLH_ERR_UNSUPPORTED, "blending on a Modular frame (jxlh_stage_blend on the planes instead)");
       const size_t nec = bl->ec_blending_info.size();
@@ -382,6 +471,8 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       }
       phase = kConvert;
     } else if (const auto* ex = std::get_if<ExtendToImageDimensionsStage>(&s)) {
+      if (!spots.empty() || premul_seen || !convs.empty() || tail_seen)
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "' behind a spot colour, premultiply or conversion stage: they follow the blending and extend stages");
       if (!expect_extend) fail(JXLH_ERR_INVALID_ARGUMENT, extend_seen ? "two extend stages" : "extend stage without a blending stage in front of it");
       bool same = ex->x0 == lp.blend.x0 && ex->y0 == lp.blend.y0 && ex->image_w == lp.blend.image_w &&
                   ex->image_h == lp.blend.image_h && same_info(ex->blending_info, lp.blend.color) &&
@@ -537,11 +628,143 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       uint32_t bits, depth;
       if (const auto* c8 = std::get_if<ConvertF32ToU8Stage>(&s)) ch = c8->channel, bits = 8, depth = c8->bit_depth;
       else ch = std::get<ConvertF32ToU16Stage>(s).channel, bits = 16, depth = std::get<ConvertF32ToU16Stage>(s).bit_depth;
+      if (has_full_save) {  // the save tail: checked by the six-argument save stage that follows
+        if (ch < 0 || ch >= 3 + JXLH_MAX_EXTRA_CHANNELS || depth < 1 || depth > bits)
+          fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': channel or bit depth out of range");
+        add_conv(s, ch, bits == 8 ? JXLH_SAVE_U8 : JXLH_SAVE_U16, depth, false, 0.0f, 0.0f);
+        tail_seen = true;
+        continue;
+      }
       if (ch != convert_seen || ch > 2 || (convert_bits && convert_bits != bits)) fail(JXLH_ERR_INVALID_ARGUMENT, "integer conversion: channels 0, 1, 2 with one format");
       if (depth != bits) fail(JXLH_ERR_UNSUPPORTED, "integer output with a bit depth below the sample size");
       convert_bits = bits;
       convert_seen++;
+    } else if (const auto* f16 = std::get_if<ConvertF32ToF16Stage>(&s)) {
+      if (!has_full_save)
+        fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "' needs the save stage that carries colour type, data format and orientation");
+      if (phase < kConvert) enter(kConvert, s);
+      if (f16->channel < 0 || f16->channel >= 3 + JXLH_MAX_EXTRA_CHANNELS)
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': channel out of range");
+      if (f16->clamp && !(f16->clamp_min <= f16->clamp_max))
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': clamp range with min > max or a NaN bound");
+      add_conv(s, f16->channel, JXLH_SAVE_F16, 0, f16->clamp, f16->clamp_min, f16->clamp_max);
+      tail_seen = true;
+    } else if (const auto* sp = std::get_if<SpotColorStage>(&s)) {
+      if (!has_full_save)
+        fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "' needs the save stage that carries colour type, data format and orientation");
+      // frame/render.rs:793-806: behind blend / extend, in front of premultiplication and every conversion
+      if (phase > kConvert || have_save || premul_seen || !convs.empty())
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "' out of the order of Frame::build_render_pipeline");
+      if (sp->ec < 0 || sp->ec >= JXLH_MAX_EXTRA_CHANNELS || 3 + sp->ec >= (int)num_channels_ || !lp.extra[sp->ec].bits)
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': not an extra channel of the list");
+      if (spots.size() == JXLH_MAX_EXTRA_CHANNELS) fail(JXLH_ERR_INVALID_ARGUMENT, "more spot colour stages than extra channels");
+      jxlh_spot_color sc{};
+      sc.ec = (uint32_t)sp->ec;
+      for (int k = 0; k < 4; k++) sc.rgba[k] = sp->rgba[k];
+      spots.push_back(sc);
+      phase = kConvert;
+      tail_seen = true;
+    } else if (const auto* pm = std::get_if<PremultiplyAlphaStage>(&s)) {
+      if (!has_full_save)
+        fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "' needs the save stage that carries colour type, data format and orientation");
+      // frame/render.rs:858-866: directly in front of the colour conversions
+      if (phase > kConvert || have_save || premul_seen || !convs.empty())
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "' out of the order of Frame::build_render_pipeline");
+      if (pm->first_color_channel != 0 || (pm->num_color_channels != 1 && pm->num_color_channels != 3))
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': colour channels 0 or 0..2");
+      const int ec = pm->alpha_channel - 3;
+      if (ec < 0 || ec >= JXLH_MAX_EXTRA_CHANNELS || pm->alpha_channel >= (int)num_channels_ || !lp.extra[ec].bits)
+        fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "': the alpha is not an extra channel of the list");
+      premul_seen = true;
+      premul_alpha = pm->alpha_channel;
+      premul_n = pm->num_color_channels;
+      phase = kConvert;
+      tail_seen = true;
+    } else if (const auto* sv = std::get_if<SaveStage>(&s); sv && sv->full) {
+      // the save tail: lowers to a jxlh_save_desc.  Saves come in buffer order, the colour one first
+      // (frame/render.rs:858-902)
+      if (phase < kConvert) enter(kConvert, s);
+      const std::string name = "stage '" + stage_display(s) + "'";
+      if (lp.modular != LoweredPipeline::Modular::kNone)
+        fail(JXLH_ERR_UNSUPPORTED, name + " on a Modular frame (jxlh_stage_save on the planes instead)");
+      if (sv->output_buffer_index != (int)lp.saves.size())
+        fail(JXLH_ERR_INVALID_ARGUMENT, name + ": save stages come in output buffer order");
+      const DataFormat& df = sv->data_format;
+      if (df.format > JXLH_SAVE_F32 || sv->orientation < 1 || sv->orientation > 8)
+        fail(JXLH_ERR_INVALID_ARGUMENT, name + ": data format or orientation out of range");
+      // the channel list against the colour type (frame/render.rs:851-857, :888-899)
+      const bool gray = sv->color_type == ColorType::kGrayscale || sv->color_type == ColorType::kGrayscaleAlpha;
+      const bool alpha = sv->color_type == ColorType::kGrayscaleAlpha || sv->color_type == ColorType::kRgba ||
+                         sv->color_type == ColorType::kBgra;
+      const bool bgr = sv->color_type == ColorType::kBgr || sv->color_type == ColorType::kBgra;
+      const std::vector<int>& chs = sv->channels;
+      const size_t ncol = gray ? 1 : 3;
+      const bool ec_only = sv->color_type == ColorType::kGrayscale && chs.size() == 1 && chs[0] >= 3;
+      if (!ec_only) {
+        const size_t want = ncol + (alpha && !sv->fill_opaque_alpha ? 1 : 0);
+        bool ok = chs.size() == want && (!sv->fill_opaque_alpha || alpha);
+        for (size_t k = 0; ok && k < ncol; k++) ok = chs[k] == (int)k;
+        if (ok && chs.size() > ncol) ok = chs[ncol] >= 3;
+        if (!ok) fail(JXLH_ERR_INVALID_ARGUMENT, name + ": channels, colour type and fill_opaque_alpha disagree");
+      }
+      for (int ch : chs)
+        if (ch >= 3 && (ch >= (int)num_channels_ || ch - 3 >= JXLH_MAX_EXTRA_CHANNELS || !lp.extra[ch - 3].bits))
+          fail(JXLH_ERR_INVALID_ARGUMENT, name + ": an extra channel the list never converted to f32");
+      if (!ec_only && colour_saved) fail(JXLH_ERR_UNSUPPORTED, name + ": a second save of the colour channels");
+      if (ec_only && !colour_saved && (premul_seen || !spots.empty()))
+        fail(JXLH_ERR_INVALID_ARGUMENT, name + ": spot colour / premultiply stages without a colour save behind them");
+      // conversions: exactly the save's channels, in its format and depth; none for f32 (add_conversion_stages)
+      jxlh_save_desc d{};
+      d.format = df.format;
+      d.bit_depth = df.format <= JXLH_SAVE_U16 ? df.bit_depth : 0;
+      for (const Conv& c : convs) {
+        bool mine = false;
+        for (int ch : chs) mine |= ch == c.channel;
+        if (!mine) fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + c.name + "' converts a channel the following save stage does not save");
+      }
+      if (df.format == JXLH_SAVE_F32) {
+        if (!convs.empty()) fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + convs[0].name + "' in front of an f32 save stage");
+      } else {
+        if (df.format <= JXLH_SAVE_U16 && (df.bit_depth < 1 || df.bit_depth > (df.format == JXLH_SAVE_U8 ? 8u : 16u)))
+          fail(JXLH_ERR_INVALID_ARGUMENT, name + ": bit depth out of range");
+        for (size_t k = 0; k < chs.size(); k++) {
+          const Conv* c = nullptr;
+          for (const Conv& cv : convs)
+            if (cv.channel == chs[k]) c = &cv;
+          if (!c) fail(JXLH_ERR_INVALID_ARGUMENT, name + ": channel " + std::to_string(chs[k]) + " has no conversion to the save's format");
+          if (c->format != df.format || c->depth != d.bit_depth)
+            fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + c->name + "' and " + name + " disagree on format or bit depth");
+          if (k == 0) {
+            d.f16_clamp = c->clamp;
+            d.f16_clamp_min = c->clamp_min;
+            d.f16_clamp_max = c->clamp_max;
+          } else if ((bool)d.f16_clamp != c->clamp || (c->clamp && (d.f16_clamp_min != c->clamp_min || d.f16_clamp_max != c->clamp_max))) {
+            fail(JXLH_ERR_UNSUPPORTED, "stage '" + c->name + "': one f16 clamp range per save stage");
+          }
+        }
+      }
+      convs.clear();
+      d.n_channels = (uint32_t)chs.size();
+      for (size_t k = 0; k < chs.size(); k++) d.channels[k] = (uint32_t)chs[k];
+      if (bgr) std::swap(d.channels[0], d.channels[2]);  // render/save.rs:33-40
+      d.fill_opaque_alpha = sv->fill_opaque_alpha;
+      d.big_endian = df.big_endian && df.format != JXLH_SAVE_U8;
+      d.orientation = sv->orientation;
+      if (!ec_only) {
+        if (premul_seen && (premul_n != (int)ncol || chs.size() <= ncol || chs[ncol] != premul_alpha))
+          fail(JXLH_ERR_INVALID_ARGUMENT, name + ": the premultiply stage in front names other channels");
+        d.premultiply = premul_seen;
+        d.premultiply_alpha_channel = premul_seen ? (uint32_t)premul_alpha : 0;
+        d.n_spot = (uint32_t)spots.size();
+        for (size_t i = 0; i < spots.size(); i++) d.spot[i] = spots[i];
+        colour_saved = true;
+      }
+      lp.saves.push_back(d);
+      have_save = true;
+      tail_seen = true;
+      phase = kConvert;  // further conversions and saves (the extra channels' buffers) may follow
     } else if (const auto* sv = std::get_if<SaveStage>(&s)) {
+      if (has_full_save) fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "': the four-argument save stage in a list with a six-argument one");
       enter(kSave, s);
       if (have_save) fail(JXLH_ERR_UNSUPPORTED, "more than one save stage (extra-channel outputs stay on the CPU pipeline)");
       if (sv->channels != std::vector<int>{0, 1, 2} || sv->output_buffer_index != 0) fail(JXLH_ERR_UNSUPPORTED, "save stage other than the colour channels into buffer 0");
@@ -588,6 +811,12 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   if ((size_t)ups_factor != (ups_factor ? (size_t)1 << downsampling_shift_ : 0) && ups_factor != 0) fail(JXLH_ERR_INVALID_ARGUMENT, "upsampling factor and downsampling_shift disagree");
   if (!ups_factor && downsampling_shift_ != 0) fail(JXLH_ERR_INVALID_ARGUMENT, "downsampling_shift without upsampling stages");
   if (conv_seen != 0 && !p.noise) fail(JXLH_ERR_INVALID_ARGUMENT, "noise convolution without AddNoise");
+  if (!lp.saves.empty()) {
+    if (!convs.empty()) fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + convs[0].name + "' without a save stage behind it");
+    if ((premul_seen || !spots.empty()) && !colour_saved)
+      fail(JXLH_ERR_INVALID_ARGUMENT, "spot colour / premultiply stages without a save of the colour channels");
+    convert_seen = 0;  // the tail's conversions were checked by their save stages
+  }
   if (convert_seen != 0 && convert_seen != 3) fail(JXLH_ERR_INVALID_ARGUMENT, "integer conversion on some channels only");
   if (!have_save) fail(JXLH_ERR_INVALID_ARGUMENT, "no save stage");
   if (lp.has_output && lp.output.color == JXLH_COLOR_NONE && have_tf) fail(JXLH_ERR_INVALID_ARGUMENT, "transfer function without colour stage");
@@ -645,6 +874,15 @@ class GpuRenderPipeline {
     if (bytes_per_row < need || rows < lp_.out_h)
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::check_buffer_sizes", "output buffer too small");
   }
+  // ... of output buffer `buffer_index` of a list with six-argument save stages: the ORIENTED image
+  void check_buffer_sizes(size_t buffer_index, size_t bytes_per_row, size_t rows) const {
+    const jxlh_save_desc& d = save_desc(buffer_index);
+    const bool t = d.orientation >= 5;
+    const size_t bps = d.format == JXLH_SAVE_U8 ? 1 : d.format == JXLH_SAVE_F32 ? 4 : 2;
+    const size_t need = (size_t)(t ? lp_.out_h : lp_.out_w) * (d.n_channels + (d.fill_opaque_alpha ? 1 : 0)) * bps;
+    if (bytes_per_row < need || rows < (t ? lp_.out_w : lp_.out_h))
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::check_buffer_sizes", "output buffer too small");
+  }
   // what the reference does when the last group of a pass has been handed over (frame/decode.rs:547-558, :703-711)
   void do_render() {
     for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");
@@ -663,6 +901,11 @@ class GpuRenderPipeline {
     if (lp_.has_output) frame_.read_output(lp_.output, out);
     else throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::save", "planar f32 pipeline: use save_planes");
   }
+  // a six-argument save stage: output buffer `buffer_index` (host or device memory, the origin of the whole oriented
+  // image), source rows [y0, y1)
+  void save(size_t buffer_index, void* out, size_t bytes_per_row, uint32_t y0 = 0, uint32_t y1 = 0xFFFFFFFFu) {
+    frame_.save(&lp_.output, save_desc(buffer_index), out, bytes_per_row, y0, y1);
+  }
   void save_planes(float* c0, float* c1, float* c2) { frame_.read_planes(c0, c1, c2); }
   // An extra channel's integer samples as the Modular decoder leaves them (w x h at the channel's own resolution, host
   // or device memory).  The stage list decides what happens to them: ConvertModularToF32Stage with the channel's bit
@@ -680,6 +923,11 @@ class GpuRenderPipeline {
   }
 
  private:
+  const jxlh_save_desc& save_desc(size_t buffer_index) const {
+    if (buffer_index >= lp_.saves.size())
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::save", "the stage list has no save stage for this buffer");
+    return lp_.saves[buffer_index];
+  }
   Context& ctx_;
   LoweredPipeline lp_;
   VarDctFrame frame_;

@@ -223,6 +223,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   for (auto& b : ctx->hook_i) release(b);
   patches_release(ctx);
   blend_release(ctx);
+  save_release(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

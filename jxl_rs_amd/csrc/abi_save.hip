@@ -1,0 +1,290 @@
+// C ABI of the save tail (frame/render.rs:793-903): spot colours, premultiplication, the conversions to u8 / u16 / f16 /
+// f32 at any bit depth and the save stage with its channel order, endianness, opaque-alpha fill and orientation, behind
+// the frame's colour stage.  jxlh_frame_save runs it on the frame's result, jxlh_stage_save on caller planes; both launch
+// k_save.hip.
+#include <algorithm>
+#include <cmath>
+
+#include "../../include/jxl_hip_dev.h"
+#include "jxlh_ctx.h"
+
+namespace jxlh_host {
+
+namespace {
+
+int sample_bytes(uint32_t format) { return format == JXLH_SAVE_U8 ? 1 : format == JXLH_SAVE_F32 ? 4 : 2; }
+uint32_t samples_per_pixel(const jxlh_save_desc* d) { return d->n_channels + (d->fill_opaque_alpha ? 1 : 0); }
+bool is_extra(uint32_t ch, uint32_t n_planes) { return ch >= 3 && ch < n_planes; }
+
+// the descriptor's own checks; n_planes: pipeline channels that exist (3 + JXLH_MAX_EXTRA_CHANNELS for a frame)
+jxlh_status check_desc(const jxlh_save_desc* d, uint32_t n_planes) {
+  if (!d || d->n_channels == 0 || d->n_channels > 4 || samples_per_pixel(d) > 4) return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < d->n_channels; k++)
+    if (d->channels[k] >= n_planes) return JXLH_ERR_INVALID_ARGUMENT;
+  if (d->format > JXLH_SAVE_F32 || d->orientation < 1 || d->orientation > 8) return JXLH_ERR_INVALID_ARGUMENT;
+  if (d->format == JXLH_SAVE_U8 && (d->bit_depth < 1 || d->bit_depth > 8)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (d->format == JXLH_SAVE_U16 && (d->bit_depth < 1 || d->bit_depth > 16)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (d->f16_clamp && !(d->f16_clamp_min <= d->f16_clamp_max)) return JXLH_ERR_INVALID_ARGUMENT;  // NaN bounds included
+  if (d->premultiply && !is_extra(d->premultiply_alpha_channel, n_planes)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (d->n_spot > JXLH_MAX_EXTRA_CHANNELS) return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < d->n_spot; i++)
+    if (d->spot[i].ec >= JXLH_MAX_EXTRA_CHANNELS || !is_extra(3 + d->spot[i].ec, n_planes)) return JXLH_ERR_INVALID_ARGUMENT;
+  return JXLH_OK;
+}
+
+// `out` and its pitch against the oriented image of a w x h source
+jxlh_status check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row) {
+  const size_t bps = (size_t)sample_bytes(d->format);
+  const size_t row = (size_t)(d->orientation >= 5 ? h : w) * samples_per_pixel(d) * bps;
+  if (!out || bytes_per_row < row || bytes_per_row % bps != 0 || reinterpret_cast<uintptr_t>(out) % bps != 0)
+    return JXLH_ERR_INVALID_ARGUMENT;
+  return JXLH_OK;
+}
+
+jxlh_status colour_mode(const jxlh_output_desc* colour, SaveLaunch& a) {
+  a.mode = kModeNone;
+  if (!colour) return JXLH_OK;
+  switch (colour->color) {
+    case JXLH_COLOR_XYB:
+      if (colour->transfer > JXLH_TF_GAMMA) return JXLH_ERR_INVALID_ARGUMENT;
+      a.mode = (int)colour->transfer;  // JXLH_TF_* share the values of the internal modes
+      for (int i = 0; i < 9; i++) a.xyb.mat[i] = colour->xyb.opsin_inverse_matrix[i];
+      for (int i = 0; i < 3; i++) {
+        a.xyb.bias_cbrt[i] = colour->xyb.bias_cbrt[i];
+        a.xyb.scaled_bias[i] = colour->xyb.scaled_bias[i];
+      }
+      a.xyb.intensity_scale = colour->xyb.intensity_scale;
+      break;
+    case JXLH_COLOR_YCBCR: a.mode = kModeYcbcr; break;
+    case JXLH_COLOR_NONE: break;
+    default: return JXLH_ERR_INVALID_ARGUMENT;
+  }
+  a.tf.param = colour->tf_param;
+  for (int i = 0; i < 3; i++) a.tf.lum[i] = colour->hlg_luminance_rgb[i];
+  return JXLH_OK;
+}
+
+// everything of the launch the (checked) descriptor decides; plane(ch) / stride(ch) resolve a pipeline channel
+template <class PlaneOf, class StrideOf>
+void fill_desc(const jxlh_save_desc* d, PlaneOf plane, StrideOf stride, SaveLaunch& a) {
+  a.format = (int)d->format;  // JXLH_SAVE_* share the values of kSave*
+  a.spp = (int)samples_per_pixel(d);
+  a.colour = 0;
+  for (uint32_t k = 0; k < 4; k++) {
+    a.ch[k] = kSaveFill;
+    a.smp_plane[k] = nullptr;
+    a.smp_stride[k] = 0;
+    if (k >= d->n_channels) continue;
+    a.ch[k] = (int)d->channels[k];
+    if (d->channels[k] < 3) {
+      a.colour = 1;
+    } else {
+      a.smp_plane[k] = plane(d->channels[k]);
+      a.smp_stride[k] = stride(d->channels[k]);
+    }
+  }
+  for (int c = 0; c < 3; c++) {
+    a.plane[c] = plane(c);
+    a.stride[c] = stride(c);
+  }
+  // spot colours and premultiplication act on the colour channels only: an extra-channel save carries none of them
+  a.n_spot = a.colour ? (int)d->n_spot : 0;
+  for (int i = 0; i < a.n_spot; i++) {
+    a.spot_plane[i] = plane(3 + d->spot[i].ec);
+    a.spot_stride[i] = stride(3 + d->spot[i].ec);
+    for (int k = 0; k < 4; k++) a.spot[i][k] = d->spot[i].rgba[k];
+  }
+  const bool premul = a.colour && d->premultiply;
+  a.premul_plane = premul ? plane(d->premultiply_alpha_channel) : nullptr;
+  a.premul_stride = premul ? stride(d->premultiply_alpha_channel) : 0;
+  const uint32_t max_int = d->format <= JXLH_SAVE_U16 ? (1u << d->bit_depth) - 1 : 0;
+  a.maxv = (float)max_int;
+  a.big_endian = d->big_endian && d->format != JXLH_SAVE_U8;
+  a.fill_bits = d->format <= JXLH_SAVE_U16 ? max_int : d->format == JXLH_SAVE_F16 ? 0x3c00u : 0x3f800000u;
+  if (a.big_endian)
+    a.fill_bits = d->format == JXLH_SAVE_F32 ? __builtin_bswap32(a.fill_bits)
+                                             : (((a.fill_bits >> 8) | (a.fill_bits << 8)) & 0xffffu);
+  a.clamp = d->format == JXLH_SAVE_F16 && d->f16_clamp;
+  a.clamp_min = d->f16_clamp_min;
+  a.clamp_max = d->f16_clamp_max;
+  const uint32_t o = d->orientation;  // headers/image_metadata.rs:85-96
+  a.transpose = o >= 5;
+  a.flip_x = o == 2 || o == 3 || o == 6 || o == 7;
+  a.flip_y = o == 3 || o == 4 || o == 7 || o == 8;
+}
+
+// Launches `a` (everything but out / out_stride filled) for source rows [a.y0, a.y0 + a.rows) into the oriented image at
+// `out`.  Device memory is written in place; host memory goes through the staging buffer, which holds exactly the
+// rectangle of the oriented image the band covers (whole rows of it for orientations 1-4, a column range of every row
+// for 5-8), and a 2-D copy of that rectangle -- bytes outside it are never touched.
+jxlh_status launch_to(jxlh_ctx* ctx, SaveLaunch& a, void* out, size_t bytes_per_row, bool wait) {
+  const size_t pb = (size_t)a.spp * (size_t)sample_bytes((uint32_t)a.format);
+  if (is_device_ptr(out)) {
+    a.out = static_cast<uint8_t*>(out);
+    a.out_stride = bytes_per_row;
+    {
+      ScopedKernelTimer t(ctx, "k_save");
+      launch_save(ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return JXLH_OK;
+  }
+  // the band's rectangle in the oriented image: rect_w pixels from column ox0 of rows [oy0, oy0 + rect_h)
+  const int y1 = a.y0 + a.rows;
+  size_t ox0, oy0, rect_w, rect_h;
+  if (a.transpose) {
+    ox0 = (size_t)(a.flip_x ? a.h - y1 : a.y0);
+    oy0 = 0;
+    rect_w = (size_t)a.rows;
+    rect_h = (size_t)a.w;
+  } else {
+    ox0 = 0;
+    oy0 = (size_t)(a.flip_y ? a.h - y1 : a.y0);
+    rect_w = (size_t)a.w;
+    rect_h = (size_t)a.rows;
+  }
+  const size_t row_bytes = rect_w * pb, pitch = round_up(row_bytes, 4);
+  if (jxlh_status st = ensure(ctx, ctx->rgb8, pitch * rect_h)) return st;
+  // the image origin that puts the rectangle at the start of the staging buffer (never dereferenced outside it)
+  a.out = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->rgb8.p) - oy0 * pitch - ox0 * pb);
+  a.out_stride = pitch;
+  {
+    ScopedKernelTimer t(ctx, "k_save");
+    launch_save(ctx->stream, a);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (jxlh_status st = copy2d(ctx, static_cast<uint8_t*>(out) + oy0 * bytes_per_row + ox0 * pb, bytes_per_row, ctx->rgb8.p,
+                              pitch, row_bytes, rect_h, ctx->stream))
+    return st;
+  if (wait) JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d, uint32_t y0, uint32_t y1,
+                       void* out, size_t bytes_per_row, bool wait) {
+  if (!ctx || !d || !out) return JXLH_ERR_INVALID_ARGUMENT;
+  if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
+  if (jxlh_status st = check_desc(d, 3 + JXLH_MAX_EXTRA_CHANNELS)) return st;
+  SaveLaunch a{};
+  if (jxlh_status st = colour_mode(colour, a)) return st;
+  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
+  const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
+  if (y1 > h) y1 = h;
+  if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_out(d, w, h, out, bytes_per_row)) return st;
+  if ((uint64_t)w * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
+  // the extra channels the save reads, as jxlh_frame_read_extra_channel resolves them
+  const float* ec_plane[JXLH_MAX_EXTRA_CHANNELS] = {};
+  uint32_t ec_stride[JXLH_MAX_EXTRA_CHANNELS] = {};
+  auto resolve = [&](uint32_t ch) -> jxlh_status {
+    if (ch < 3) return JXLH_OK;
+    const uint32_t ec = ch - 3;
+    const jxlh_ctx::ExtraChannel& e = ctx->extra[ec];
+    if (!e.set || !e.done) return JXLH_ERR_BAD_STATE;
+    if (blended(ctx)) {  // the composed channel, image-sized
+      if (ec >= ctx->blend_nec) return JXLH_ERR_BAD_STATE;
+      ec_plane[ec] = ctx->blend_canvas.p + (size_t)(3 + ec) * ctx->res_stride * h;
+      ec_stride[ec] = (uint32_t)ctx->res_stride;
+      return JXLH_OK;
+    }
+    if (e.out_w != w || e.out_h != h) return JXLH_ERR_BAD_STATE;  // it does not cover the result
+    ec_plane[ec] = e.pat_ready ? e.pat.p : e.up > 1 ? e.out.p : e.f32.p;
+    ec_stride[ec] = (uint32_t)e.out_stride;
+    return JXLH_OK;
+  };
+  bool colour_named = false;
+  for (uint32_t k = 0; k < d->n_channels; k++) {
+    colour_named |= d->channels[k] < 3;
+    if (jxlh_status st = resolve(d->channels[k])) return st;
+  }
+  if (colour_named) {
+    if (d->premultiply)
+      if (jxlh_status st = resolve(d->premultiply_alpha_channel)) return st;
+    for (uint32_t i = 0; i < d->n_spot; i++)
+      if (jxlh_status st = resolve(3 + d->spot[i].ec)) return st;
+  }
+  // checked: from here on only the device can fail
+  materialise_chroma(ctx);
+  fill_desc(
+      d, [&](uint32_t ch) { return ch < 3 ? (const float*)ctx->result[ch] : ec_plane[ch - 3]; },
+      [&](uint32_t ch) { return ch < 3 ? (uint32_t)ctx->res_stride : ec_stride[ch - 3]; }, a);
+  a.w = (int)w;
+  a.h = (int)h;
+  a.y0 = (int)y0;
+  a.rows = (int)(y1 - y0);
+  a.dx = a.dy = 0;
+  return launch_to(ctx, a, out, bytes_per_row, wait);
+}
+
+}  // namespace
+
+void save_release(jxlh_ctx* ctx) { release(ctx->save_hook_in); }
+
+}  // namespace jxlh_host
+
+extern "C" {
+
+// jxl_hip_dev.h
+jxlh_status jxlh_save_tile_layout(uint32_t pixel_bytes, uint32_t* columns, uint32_t* rows) {
+  if (pixel_bytes < 1 || pixel_bytes > 16 || !columns || !rows) return JXLH_ERR_INVALID_ARGUMENT;
+  *columns = (uint32_t)kSaveTile;
+  *rows = (uint32_t)save_tile_rows((int)pixel_bytes);
+  return JXLH_OK;
+}
+
+jxlh_status jxlh_frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save, uint32_t y0,
+                            uint32_t y1, void* out, size_t bytes_per_row) {
+  JXLH_ON_DEVICE(ctx);
+  return frame_save(ctx, colour, save, y0, y1, out, bytes_per_row, /*wait=*/true);
+}
+
+jxlh_status jxlh_frame_save_async(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save, uint32_t y0,
+                                  uint32_t y1, void* out, size_t bytes_per_row) {
+  JXLH_ON_DEVICE(ctx);
+  return frame_save(ctx, colour, save, y0, y1, out, bytes_per_row, /*wait=*/false);
+}
+
+jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d,
+                            const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
+                            uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
+                            size_t bytes_per_row) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !d || !planes || !out || w == 0 || h == 0 || stride < w || stride > 0xffffffffu)
+    return JXLH_ERR_INVALID_ARGUMENT;
+  if (n_planes < 3 || n_planes > 3 + JXLH_MAX_EXTRA_CHANNELS) return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t c = 0; c < n_planes; c++)
+    if (!planes[c]) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_desc(d, n_planes)) return st;
+  SaveLaunch a{};
+  if (jxlh_status st = colour_mode(colour, a)) return st;
+  if (y1 > h) y1 = h;
+  if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_out(d, w, h, out, bytes_per_row)) return st;
+  if ((uint64_t)w * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
+  // host planes are staged whole, rows 16-byte aligned; device planes are read where they are
+  const size_t sstride = round_up(w, 4), splane = sstride * h;
+  bool all_device = true;
+  for (uint32_t c = 0; c < n_planes; c++) all_device &= is_device_ptr(planes[c]);
+  if (!all_device) {
+    if (jxlh_status st = ensure(ctx, ctx->save_hook_in, splane * n_planes)) return st;
+    for (uint32_t c = 0; c < n_planes; c++)
+      if (jxlh_status st = copy2d(ctx, ctx->save_hook_in.p + c * splane, sstride * sizeof(float), planes[c],
+                                  stride * sizeof(float), (size_t)w * sizeof(float), h, ctx->stream))
+        return st;
+  }
+  fill_desc(
+      d, [&](uint32_t ch) { return all_device ? planes[ch] : (const float*)(ctx->save_hook_in.p + ch * splane); },
+      [&](uint32_t) { return (uint32_t)(all_device ? stride : sstride); }, a);
+  a.w = (int)w;
+  a.h = (int)h;
+  a.y0 = (int)y0;
+  a.rows = (int)(y1 - y0);
+  a.dx = (int)(frame_x0 & 31);  // the table is 32 x 32
+  a.dy = (int)(frame_y0 & 31);
+  if (jxlh_status st = launch_to(ctx, a, out, bytes_per_row, /*wait=*/false)) return st;
+  JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+}  // extern "C"

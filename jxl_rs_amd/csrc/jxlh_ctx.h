@@ -191,6 +191,7 @@ struct jxlh_ctx {
   int blend_fw = 0, blend_fh = 0;
   size_t blend_fstride = 0;
   DevBuf<float> blend_hook_in, blend_hook_out;  // jxlh_stage_blend staging
+  DevBuf<float> save_hook_in;                   // jxlh_stage_save staging of host planes (abi_save.hip)
   // strip path (k_strip.hip): block descriptors / tile modes written by k1_scan, the strips' edge-column exchange
   // buffer, progress flags + ticket.  strip_all_closed: every rect of the transform map came from host memory and
   // every varblock in it is a small DCT inside its 64x64 tile (jxlh_frame_set_hf_meta); strip_ran: the last
@@ -341,6 +342,7 @@ void patches_release(jxlh_ctx* ctx);
 // abi_blend.hip.  blended(): the frame's result is the canvas jxlh_frame_blend composed (any render resets `result`).
 inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
 void blend_release(jxlh_ctx* ctx);
+void save_release(jxlh_ctx* ctx);  // abi_save.hip
 bool strip_eligible(const jxlh_ctx* ctx);
 jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan);
 // Where run_stages leaves the finished planes (1 = f.tmp, 0 = f.planes): a property of the frame's stage list, so a

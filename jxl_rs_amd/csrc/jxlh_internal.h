@@ -449,4 +449,44 @@ struct BlendLaunch {
 };
 void launch_blend(hipStream_t s, int num_ec, const BlendLaunch& a);
 
+// the save tail (k_save.hip): colour stage, spot colours, premultiply, conversion, opaque fill and orientation of source
+// rows [y0, y0 + rows) of w x h planes into the interleaved, oriented image at `out`.  Pipeline channel c = 0..2 is
+// colour, 3 + i extra channel i; the host resolves every channel the save reads to its plane, and the kernel indexes
+// the launch structure with constants only (it stays in the kernel-argument segment).
+enum { kSaveU8 = 0, kSaveU16 = 1, kSaveF16 = 2, kSaveF32 = 3 };
+constexpr int kSaveFill = 0xff;  // SaveLaunch::ch entry of the opaque-alpha sample
+// side of the transposing kernel's tile in source pixels: kSaveTile columns x save_tile_rows(pixel bytes) rows
+constexpr int kSaveTile = 64;
+constexpr int save_tile_rows(int pixel_bytes) { return pixel_bytes > 8 ? 32 : 64; }
+struct SaveLaunch {
+  const float* plane[3];            // the colour planes; read when `colour`
+  uint32_t stride[3];               // floats, here and below
+  int colour;                       // some named channel is < 3: channels 0..2 are loaded and pass stages 1..3
+  int mode;                         // colour stage on channels 0..2 (as BlendLaunch::mode)
+  XybParamsDev xyb;
+  TfParamsDev tf;
+  int n_spot;
+  const float* spot_plane[JXLH_MAX_EXTRA_CHANNELS];
+  uint32_t spot_stride[JXLH_MAX_EXTRA_CHANNELS];
+  float spot[JXLH_MAX_EXTRA_CHANNELS][4];
+  const float* premul_plane;        // the alpha the colour is multiplied by, or null
+  uint32_t premul_stride;
+  int format, spp;                  // kSave*, samples per pixel (1..4)
+  int ch[4];                        // pipeline channel of sample k (it picks the dither phase), or kSaveFill
+  const float* smp_plane[4];        // ... and its plane when the channel is an extra channel
+  uint32_t smp_stride[4];
+  int w, h;                         // the whole source image (orientation flips against these)
+  int y0, rows;
+  int dx, dy;                       // position of source pixel (0, 0) in the frame, for the dither table only
+  float maxv;                       // 2^depth - 1 (U8 / U16)
+  uint32_t fill_bits;               // the opaque sample in the sample's format and byte order
+  int big_endian;
+  int clamp;                        // F16: clamp to [clamp_min, clamp_max] first
+  float clamp_min, clamp_max;
+  int transpose, flip_x, flip_y;    // output (ox, oy) = transpose ? (y, x) : (x, y), then flipped per axis
+  uint8_t* out;                     // origin of the whole oriented image
+  size_t out_stride;                // bytes
+};
+void launch_save(hipStream_t s, const SaveLaunch& a);
+
 }  // namespace jxlh

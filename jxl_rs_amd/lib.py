@@ -61,12 +61,14 @@ ABI_SYMBOLS = [
     "jxlh_slot_writer_begin_varblock", "jxlh_slot_writer_add", "jxlh_slot_writer_add_many", "jxlh_slot_writer_end_group",
     "jxlh_ctx_set_reference", "jxlh_frame_save_reference", "jxlh_ctx_clear_reference", "jxlh_frame_set_patches",
     "jxlh_stage_patches", "jxlh_frame_blend", "jxlh_stage_blend",
+    "jxlh_frame_save", "jxlh_frame_save_async", "jxlh_stage_save",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
     "jxlh_timer_start", "jxlh_timer_stop", "jxlh_kernel_timing_enable", "jxlh_kernel_timing_get",
     "jxlh_kernel_timing_reset", "jxlh_selftest_recip", "jxlh_probe_copy_bandwidth", "jxlh_frame_path",
     "jxlh_flow_profile", "jxlh_frame_k1_counters", "jxlh_probe_placement", "jxlh_worklist_layout",
+    "jxlh_save_tile_layout",
 ]
 
 
@@ -155,6 +157,70 @@ def blend_desc(x0, y0, image_w, image_h, color, ec=(), ec_flags=(), num_ec=None)
         d.ec[i] = BlendingInfo(*[int(v) for v in b])
     for i, f in enumerate(list(ec_flags)[:8]):
         d.ec_flags[i] = int(f)
+    return d
+
+
+# the save tail (jxlh_frame_save): sample formats
+SAVE_U8, SAVE_U16, SAVE_F16, SAVE_F32 = range(4)
+SAVE_SAMPLE_BYTES = {SAVE_U8: 1, SAVE_U16: 2, SAVE_F16: 2, SAVE_F32: 4}
+
+
+def save_tile_layout(pixel_bytes):
+    """jxlh_save_tile_layout (jxl_hip_dev.h, host only): (columns, rows) in source pixels of the transposing save kernel's
+    tile for a pixel of that many bytes -- what sizes around a tile edge mean in tests"""
+    c, r = C.c_uint32(), C.c_uint32()
+    st = load().jxlh_save_tile_layout(C.c_uint32(pixel_bytes), C.byref(c), C.byref(r))
+    if st != OK:
+        raise JxlHipError(st, "jxlh_save_tile_layout")
+    return c.value, r.value
+
+
+class SpotColor(C.Structure):
+    """jxlh_spot_color."""
+    _fields_ = [("ec", C.c_uint32), ("rgba", C.c_float * 4)]
+
+
+class SaveDesc(C.Structure):
+    """jxlh_save_desc."""
+    _fields_ = [("n_channels", C.c_uint32), ("channels", C.c_uint32 * 4), ("fill_opaque_alpha", C.c_uint32),
+                ("format", C.c_uint32), ("bit_depth", C.c_uint32), ("big_endian", C.c_uint32), ("orientation", C.c_uint32),
+                ("f16_clamp", C.c_uint32), ("f16_clamp_min", C.c_float), ("f16_clamp_max", C.c_float),
+                ("premultiply", C.c_uint32), ("premultiply_alpha_channel", C.c_uint32), ("n_spot", C.c_uint32),
+                ("spot", SpotColor * 8)]
+
+    @property
+    def samples_per_pixel(self):
+        return self.n_channels + (1 if self.fill_opaque_alpha else 0)
+
+    @property
+    def pixel_bytes(self):
+        return self.samples_per_pixel * SAVE_SAMPLE_BYTES.get(self.format, 1)
+
+
+def save_desc(channels, format=SAVE_U8, bit_depth=None, fill_opaque_alpha=False, big_endian=False, orientation=1,
+              f16_clamp=None, premultiply=None, spot=(), n_channels=None, n_spot=None):
+    """jxlh_save_desc.  channels: pipeline channels in output order (0..2 colour, 3 + ec extra channel ec);
+    f16_clamp: (min, max) or None; premultiply: the alpha's pipeline channel or None; spot: [(ec, (r, g, b, a)), ...]"""
+    d = SaveDesc()
+    ch = list(channels)
+    d.n_channels = len(ch) if n_channels is None else int(n_channels)
+    for i, c in enumerate(ch[:4]):
+        d.channels[i] = int(c)
+    d.fill_opaque_alpha = 1 if fill_opaque_alpha else 0
+    d.format = int(format)
+    d.bit_depth = int({SAVE_U8: 8, SAVE_U16: 16}.get(format, 0) if bit_depth is None else bit_depth)
+    d.big_endian = 1 if big_endian else 0
+    d.orientation = int(orientation)
+    if f16_clamp is not None:
+        d.f16_clamp, d.f16_clamp_min, d.f16_clamp_max = 1, float(f16_clamp[0]), float(f16_clamp[1])
+    if premultiply is not None:
+        d.premultiply, d.premultiply_alpha_channel = 1, int(premultiply)
+    sp = list(spot)
+    d.n_spot = len(sp) if n_spot is None else int(n_spot)
+    for i, (ec, rgba) in enumerate(sp[:8]):
+        d.spot[i].ec = int(ec)
+        for k in range(4):
+            d.spot[i].rgba[k] = float(rgba[k])
     return d
 
 
@@ -287,6 +353,11 @@ def load():
     if hasattr(L, "jxlh_frame_blend"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
         L.jxlh_frame_blend.argtypes = [vp, C.POINTER(BlendDesc), C.POINTER(OutputDesc)]
         L.jxlh_stage_blend.argtypes = [vp, C.POINTER(BlendDesc), C.POINTER(vp), u32, u32, u32, sz, C.POINTER(vp), sz]
+    if hasattr(L, "jxlh_frame_save"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        L.jxlh_frame_save.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), u32, u32, vp, sz]
+        L.jxlh_frame_save_async.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), u32, u32, vp, sz]
+        L.jxlh_stage_save.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), C.POINTER(vp), u32, u32, u32, sz,
+                                      u32, u32, u32, u32, vp, sz]
     L.jxlh_comm_allgather_local.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), sz]
     L.jxlh_palette_strided.argtypes = [vp, vp, sz, vp, i32, sz, i32, i32, vp, sz]
     L.jxlh_modular_frame_filters.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32, sz]
@@ -942,6 +1013,65 @@ class Context:
         """jxlh_stage_blend: the 3 + num_ec f32 planes [h, w] blended onto the image; returns the image's planes"""
         st, out = self.try_stage_blend(desc, planes)
         self._chk(st, "stage_blend")
+        return out
+
+    # ---- the save tail ----
+    @staticmethod
+    def save_shape(desc, w, h):
+        """(rows, samples per row) of the oriented image a w x h source is saved as"""
+        ow, oh = (h, w) if desc.orientation >= 5 else (w, h)
+        return oh, ow * desc.samples_per_pixel
+
+    @staticmethod
+    def _save_dtype(desc):
+        return {SAVE_U8: np.uint8, SAVE_U16: np.uint16, SAVE_F16: np.uint16, SAVE_F32: np.uint32}[desc.format]
+
+    def try_frame_save(self, desc, colour=None, y0=0, y1=None, out=None, bytes_per_row=None, wait=True):
+        """jxlh_frame_save (_async when not `wait`), returning (status, out).  out: None (a zeroed array of the oriented
+        image's samples -- f16 as uint16 bits, f32 as uint32 bits -- is made), a numpy array, or a device pointer /
+        DeviceArray with bytes_per_row given"""
+        w, h = self.out_size
+        if out is None:
+            out = np.zeros(self.save_shape(desc, w, h), dtype=self._save_dtype(desc))
+        if bytes_per_row is None:
+            bytes_per_row = out.strides[0]
+        fn = self.L.jxlh_frame_save if wait else self.L.jxlh_frame_save_async
+        st = fn(self._ctx, None if colour is None else C.byref(colour), C.byref(desc), int(y0), int(h if y1 is None else y1),
+                _addr(out), int(bytes_per_row))
+        return st, out
+
+    def frame_save(self, desc, colour=None, y0=0, y1=None, out=None, bytes_per_row=None, wait=True):
+        """jxlh_frame_save: the frame's result through spot colours, premultiplication, conversion and orientation into
+        the interleaved image `desc` (save_desc(...)) names; colour: output_desc(...) of the colour stage in front"""
+        st, out = self.try_frame_save(desc, colour, y0, y1, out, bytes_per_row, wait)
+        self._chk(st, "frame_save")
+        return out
+
+    def try_stage_save(self, desc, planes, colour=None, origin=(0, 0), y0=0, y1=None, out=None, bytes_per_row=None,
+                       size=None, stride=None):
+        """jxlh_stage_save on 3 + num_ec planes: float32 arrays [h, w], or device pointers with size=(w, h) and stride"""
+        if size is None:
+            pl = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+            h, w = pl[0].shape
+            stride = w
+        else:
+            pl = list(planes)
+            w, h = size
+            stride = w if stride is None else stride
+        if out is None:
+            out = np.zeros(self.save_shape(desc, w, h), dtype=self._save_dtype(desc))
+        if bytes_per_row is None:
+            bytes_per_row = out.strides[0]
+        pp = (C.c_void_p * len(pl))(*[_addr(a).value for a in pl])
+        st = self.L.jxlh_stage_save(self._ctx, None if colour is None else C.byref(colour), C.byref(desc), pp, len(pl), w, h,
+                                    stride, int(origin[0]), int(origin[1]), int(y0), int(h if y1 is None else y1),
+                                    _addr(out), int(bytes_per_row))
+        return st, out
+
+    def stage_save(self, desc, planes, colour=None, origin=(0, 0), y0=0, y1=None, out=None, bytes_per_row=None,
+                   size=None, stride=None):
+        st, out = self.try_stage_save(desc, planes, colour, origin, y0, y1, out, bytes_per_row, size, stride)
+        self._chk(st, "stage_save")
         return out
 
     def tune_placement(self, trials=0):
