@@ -34,7 +34,8 @@ extern "C" {
 #define JXLH_ABI_VERSION 6  /* additions only since 6: round 6 added the jxlh_host_*, jxlh_slot_writer_* and
                                jxlh_ctx_wait_* / _record_event entry points; then the reference-frame slots and the
                                patch dictionary (jxlh_ctx_*_reference, jxlh_frame_save_reference,
-                               jxlh_frame_set_patches, jxlh_stage_patches) */
+                               jxlh_frame_set_patches, jxlh_stage_patches); frame blending and the save tail; splines
+                               (jxlh_frame_set_splines, jxlh_stage_splines, jxlh_splines_build_segments) */
 #define JXLH_NUM_TRANSFORMS 27   /* HfTransformType::CARDINALITY, transform_map.rs:59-61 */
 #define JXLH_NUM_QUANT_TABLES 17 /* NUM_QUANT_TABLES, quantizer.rs:11 */
 #define JXLH_GROUP_DIM 256       /* GROUP_DIM, jxl/src/lib.rs:24-26 */
@@ -548,6 +549,48 @@ jxlh_status jxlh_frame_set_patches(jxlh_ctx* ctx, const jxlh_patch* patches, uin
 jxlh_status jxlh_stage_patches(jxlh_ctx* ctx, float* const planes[], uint32_t n_channels, uint32_t w, uint32_t h,
                                size_t stride);
 
+/* ---------------------------------------------------------------- splines (features/spline.rs)
+ * THE SEGMENTS of the current frame: the draw cache Splines::initialize_draw_cache leaves (SplineSegment, :338-346), in
+ * its order.  They are taken as they are -- the reference filters at add_segment, not at the draw.  Segment s touches
+ * pixel (x, y) of a w x h plane iff  max(0, round(cy - md)) <= y < min(h, round(cy + md) + 1)  and
+ * round(cx - md) <= x < min(w, round(cx + md) + 1)  with Rust's conversions (round half away from zero; NaN -> 0; a
+ * negative column -> 0, so a segment wholly left of the frame still adds to column 0 and one whose maximum_distance is
+ * NaN adds to pixel (0, 0) only), and adds color[c] * sigma_over_4_times_intensity * (erf(a1) - erf(a2))^2 to channel
+ * c there (draw_segment_inner, :540-584, its FMA form bit for bit).  Per pixel the segments are added in ascending
+ * index.  Needs a begun frame (JXLH_ERR_BAD_STATE otherwise); n = 0 clears the segments, jxlh_frame_begin clears them
+ * too; a null pointer with n > 0 is JXLH_ERR_INVALID_ARGUMENT with nothing launched.
+ * Position in the frame: SplinesStage (frame/render.rs:652-653) -- after patches, BEFORE the colour upsampling and
+ * noise, at the coded size; jxlh_frame_save_reference, jxlh_frame_blend, the read-outs and jxlh_frame_save see the
+ * drawn result.  Splines are added in place like patches: what is said there about band runs holds here, a partial
+ * re-render of a frame without a filter stage renders the frame again, and a sharded run is JXLH_ERR_UNSUPPORTED. */
+typedef struct jxlh_spline_segment { /* SplineSegment, 32 bytes */
+  float center_x, center_y, maximum_distance, inv_sigma, sigma_over_4_times_intensity;
+  float color[3];
+} jxlh_spline_segment;
+jxlh_status jxlh_frame_set_splines(jxlh_ctx* ctx, const jxlh_spline_segment* segments, uint32_t n);
+/* The context's current segments drawn onto three caller planes in place (w x h, row stride `stride` floats, host or
+ * device; what lies beyond w in a row is not touched), with the frame path's kernel: the Modular seam and tests.
+ * stride * h >= 2^31, or w or h >= 2147483520: JXLH_ERR_UNSUPPORTED.  Both set and stage calls wait for the context's
+ * stream (their uploads come from host memory that is reused). */
+jxlh_status jxlh_stage_splines(jxlh_ctx* ctx, float* const planes[3], uint32_t w, uint32_t h, size_t stride);
+/* From the bitstream's form to segments, on the host (no context, no device): Splines::initialize_draw_cache
+ * (features/spline.rs:733-797) -- dequantize with its range, distance and area checks, the adjacent-point check,
+ * centripetal Catmull-Rom, equal spacing at distance 1, the continuous IDCT with fast_cos, add_segment's filter.
+ * control_points: n_points (dx, dy) pairs, double-delta coded as read; color_dct: X, Y, B, 32 each.  out == NULL
+ * counts only; *count is the number of segments either way, JXLH_ERR_INVALID_ARGUMENT if it exceeds `capacity` (nothing
+ * partial is written) and for everything the reference answers with an error. */
+typedef struct jxlh_quantized_spline {
+  const int64_t* control_points;
+  uint32_t n_points;
+  int32_t color_dct[96];
+  int32_t sigma_dct[32];
+  float start_x, start_y; /* starting point */
+} jxlh_quantized_spline;
+jxlh_status jxlh_splines_build_segments(const jxlh_quantized_spline* splines, uint32_t n,
+                                        int32_t quantization_adjustment, float y_to_x_lf, float y_to_b_lf,
+                                        uint64_t image_xsize, uint64_t image_ysize, uint32_t high_precision,
+                                        jxlh_spline_segment* out, size_t capacity, size_t* count);
+
 /* smoothed LF image as used by K1 (tests) */
 jxlh_status jxlh_frame_read_lf(jxlh_ctx* ctx, float* x, float* y, float* b, size_t stride);
 
@@ -651,7 +694,7 @@ jxlh_status jxlh_frame_read_output_async(jxlh_ctx* ctx, const jxlh_output_desc* 
  * w x h at row stride `stride` floats, already in the output colour space; out[] as many image_w x image_h planes at
  * row stride out_stride.  The Modular seam and tests.
  * Alpha taken from an extra channel into the interleaved output, premultiplication and spot colours belong to the
- * save tail behind this stage: jxlh_frame_save below.  Not done here: splines. */
+ * save tail behind this stage: jxlh_frame_save below.  (Splines are drawn before this stage: jxlh_frame_set_splines.) */
 /* BlendingMode (headers/frame_header.rs:98-104) */
 enum {
   JXLH_BLEND_REPLACE = 0, JXLH_BLEND_ADD = 1, JXLH_BLEND_BLEND = 2, JXLH_BLEND_ALPHA_WEIGHTED_ADD = 3, JXLH_BLEND_MUL = 4

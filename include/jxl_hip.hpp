@@ -61,6 +61,10 @@ class Context {
   void stage_patches(const std::vector<float*>& planes, uint32_t w, uint32_t h, size_t stride) {
     check(jxlh_stage_patches(c_, planes.data(), (uint32_t)planes.size(), w, h, stride), "jxlh_stage_patches");
   }
+  // the current frame's spline segments drawn onto three caller planes, in place
+  void stage_splines(float* const planes[3], uint32_t w, uint32_t h, size_t stride) {
+    check(jxlh_stage_splines(c_, planes, w, h, stride), "jxlh_stage_splines");
+  }
 
  private:
   jxlh_ctx* c_ = nullptr;
@@ -123,6 +127,30 @@ class VarDctFrame {
     ctx_.check(jxlh_frame_set_patches(ctx_.raw(), patches.data(), (uint32_t)patches.size(), blendings.data(),
                                       (uint32_t)ec_flags.size(), ec_flags.data()),
                "jxlh_frame_set_patches");
+  }
+  // Splines::initialize_draw_cache's result (frame/render.rs:652-653 hands it to SplinesStage): the draw cache's
+  // segments, in its order
+  void set_spline_segments(const std::vector<jxlh_spline_segment>& segments) {
+    ctx_.check(jxlh_frame_set_splines(ctx_.raw(), segments.data(), (uint32_t)segments.size()), "jxlh_frame_set_splines");
+  }
+  // ... or the splines as Splines::read leaves them (decode_lf_global): built into segments on the host
+  // (jxlh_splines_build_segments) with the frame's size and its LF colour correlation, then set.  Returns the segments.
+  std::vector<jxlh_spline_segment> decode_splines(const std::vector<jxlh_quantized_spline>& splines,
+                                                  int32_t quantization_adjustment, bool high_precision = false) {
+    // the size is header.size(), the coded size also of an upsampled frame (frame/decode.rs:372-377): p_.xsize / ysize
+    // ColorCorrelationParams::y_to_x_lf / y_to_b_lf (frame/color_correlation_map.rs:81-93)
+    const float y_to_x_lf = p_.base_correlation_x + (float)p_.ytox_lf / (float)p_.color_factor;
+    const float y_to_b_lf = p_.base_correlation_b + (float)p_.ytob_lf / (float)p_.color_factor;
+    size_t n = 0;
+    ctx_.check(jxlh_splines_build_segments(splines.data(), (uint32_t)splines.size(), quantization_adjustment, y_to_x_lf,
+                                           y_to_b_lf, p_.xsize, p_.ysize, high_precision ? 1u : 0u, nullptr, 0, &n),
+               "jxlh_splines_build_segments");
+    std::vector<jxlh_spline_segment> seg(n);
+    ctx_.check(jxlh_splines_build_segments(splines.data(), (uint32_t)splines.size(), quantization_adjustment, y_to_x_lf,
+                                           y_to_b_lf, p_.xsize, p_.ysize, high_precision ? 1u : 0u, seg.data(), n, &n),
+               "jxlh_splines_build_segments");
+    set_spline_segments(seg);
+    return seg;
   }
   // the save_before_ct save stage: the rendered frame becomes reference frame `slot`
   void save_reference(uint32_t slot) { ctx_.check(jxlh_frame_save_reference(ctx_.raw(), slot), "jxlh_frame_save_reference"); }

@@ -67,6 +67,15 @@ jxlh_status jxlh_worklist_layout(int32_t xblocks, int32_t yblocks, uint64_t* out
  * from here. */
 jxlh_status jxlh_save_tile_layout(uint32_t pixel_bytes, uint32_t* columns, uint32_t* rows);
 
+/* The splines stage draws its segments in batches of consecutive segments, each batch's bin list (one entry per segment
+ * and 64 x 4 px bin it touches) held to `entries` entries; a segment that alone has more is a batch of its own.  0
+ * restores the default (2^24).  Takes effect with the next draw; the result does not depend on it.  Tests force many
+ * batches with a small budget. */
+jxlh_status jxlh_splines_set_batch_budget(jxlh_ctx* ctx, uint64_t entries);
+/* The bin of the splines draw (csrc/k_splines.hip) in pixels: host code, no device.  Tests take the sizes that straddle
+ * a bin edge from here. */
+jxlh_status jxlh_splines_bin_layout(uint32_t* columns, uint32_t* rows);
+
 /* Device self-test of the EPF weight normalisation: the filters compute 1/(1 + sum of weights)
  * (epf0.rs:208, epf1.rs:140, epf2.rs:130 divide) with rcp + two FMA refinement steps.  Counts the
  * floats whose bit pattern lies in [lo_bits, hi_bits) for which that differs from the IEEE

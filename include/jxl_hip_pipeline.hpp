@@ -164,6 +164,15 @@ struct PatchesStage {
   std::string display() const { return "patches"; }
   bool uses_channel(int) const { return true; }
 };
+// SplinesStage (render/stages/splines.rs, added at frame/render.rs:652-653 when the frame has splines): the draw cache's
+// segments (Splines::initialize_draw_cache; VarDctFrame::decode_splines builds them from the bitstream's form).  In
+// place on the three colour channels.
+struct SplinesStage {
+  std::vector<jxlh_spline_segment> segments;
+  static constexpr Border BORDER{0, 0}, SHIFT{0, 0};
+  std::string display() const { return "splines"; }
+  bool uses_channel(int c) const { return c < 3; }
+};
 // BlendingStage (render/stages/blending.rs:17-27, added at frame/render.rs:765-771 when needs_blending()): the fields
 // BlendingStage::new takes from the frame and file headers that matter on the device -- the reference frames it reads
 // are the context's slots.  In place on the colour and extra channels.
@@ -227,7 +236,7 @@ struct DataFormat {
   static DataFormat f16(bool be = false) { return {JXLH_SAVE_F16, 0, be}; }
   static DataFormat f32(bool be = false) { return {JXLH_SAVE_F32, 0, be}; }
 };
-// A stage of the reference this path does not run on the device (patches by name, splines ...): adding one makes
+// A stage of the reference this path does not run on the device (patches or splines by name ...): adding one makes
 // build() fail with JXLH_ERR_UNSUPPORTED.
 struct CpuOnlyStage {
   std::string name;
@@ -258,7 +267,7 @@ using Stage = std::variant<ConvertModularToF32Stage, ConvertModularXYBToF32Stage
                            Upsample2x, Upsample4x, Upsample8x, ConvolveNoiseStage, AddNoiseStage, XybStage, YcbcrToRgbStage,
                            FromLinearStage, ConvertF32ToU8Stage, ConvertF32ToU16Stage, CpuOnlyStage, SaveStage, PatchesStage,
                            BlendingStage, ExtendToImageDimensionsStage, SpotColorStage, PremultiplyAlphaStage,
-                           ConvertF32ToF16Stage>;
+                           ConvertF32ToF16Stage, SplinesStage>;
 
 inline std::string stage_display(const Stage& s) {
   return std::visit([](const auto& st) { return st.display(); }, s);
@@ -288,6 +297,9 @@ struct LoweredPipeline {
   // PatchesStage: the dictionary build() hands to jxlh_frame_set_patches
   bool has_patches = false;
   PatchesStage patches;
+  // SplinesStage: the segments build() hands to jxlh_frame_set_splines
+  bool has_splines = false;
+  SplinesStage splines;
   // BlendingStage + ExtendToImageDimensionsStage: do_render() ends in jxlh_frame_blend(blend, blend_colour).  The colour
   // stage of the list runs inside that call (blend_colour), so `output.color` is JXLH_COLOR_NONE
   bool has_blend = false;
@@ -394,7 +406,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   const float*(&ec_weights)[3] = lp.weights_by_factor;  // index n >> 2: factor 2, 4, 8
   uint32_t convert_bits = 0;
   bool have_colour = false, have_tf = false, have_save = false, pre_upsample = true, epf1_seen = false, epf2_seen = false;
-  bool patches_seen = false;
+  bool patches_seen = false, splines_seen = false;
   // BlendingStage must be followed at once by the extend stage (frame/render.rs:765-771)
   bool blend_seen = false, extend_seen = false, expect_extend = false;
   auto same_info = [](const jxlh_blending_info& a, const jxlh_blending_info& b) {
@@ -560,6 +572,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
         // an extra channel's own upsampling comes before the patches (frame/render.rs:624-650); only the late form,
         // together with the colour channels, may follow them
         if (patches_seen && ups_seen == 0) fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "' after the patches stage");
+        if (splines_seen && ups_seen == 0) fail(JXLH_ERR_UNSUPPORTED, "stage '" + stage_display(s) + "' after the splines stage");
         if (ups_seen != 0 && (ups_seen != 3 || n != ups_factor)) fail(JXLH_ERR_INVALID_ARGUMENT, "extra channels upsampled with the colour channels use the frame's factor, after channel 2");
         if (ec_weights[n >> 2] && ec_weights[n >> 2] != w) fail(JXLH_ERR_INVALID_ARGUMENT, "one weight table per upsampling factor (CustomTransformData)");
         ec_weights[n >> 2] = w;
@@ -578,7 +591,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
     } else if (const auto* ps = std::get_if<PatchesStage>(&s)) {
       // the reference's position: after the filters and the extra channels' own upsampling, before the colour
       // upsampling, noise and the colour stage (frame/render.rs:624-683)
-      if (phase > kUpsample || ups_seen != 0 || patches_seen)
+      if (phase > kUpsample || ups_seen != 0 || patches_seen || splines_seen)
         fail(JXLH_ERR_UNSUPPORTED, "stage 'patches' out of the order of Frame::build_render_pipeline");
       if (lp.modular != LoweredPipeline::Modular::kNone)
         fail(JXLH_ERR_UNSUPPORTED, "patches on a Modular frame (jxlh_stage_patches on the planes instead)");
@@ -588,6 +601,17 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       patches_seen = true;
       lp.has_patches = true;
       lp.patches = *ps;
+    } else if (const auto* sp = std::get_if<SplinesStage>(&s)) {
+      // the reference's position: behind the patches stage (if any), before the colour upsampling, noise and the colour
+      // stage (frame/render.rs:644-683)
+      if (phase > kUpsample || ups_seen != 0 || splines_seen)
+        fail(JXLH_ERR_UNSUPPORTED, "stage 'splines' out of the order of Frame::build_render_pipeline");
+      if (lp.modular != LoweredPipeline::Modular::kNone)
+        fail(JXLH_ERR_UNSUPPORTED, "splines on a Modular frame (jxlh_stage_splines on the planes instead)");
+      phase = kUpsample;
+      splines_seen = true;
+      lp.has_splines = true;
+      lp.splines = *sp;
     } else if (const auto* cn = std::get_if<ConvolveNoiseStage>(&s)) {
       enter(kNoiseConvolve, s);
       if (cn->channel != (int)num_channels_ - 3 + conv_seen) fail(JXLH_ERR_INVALID_ARGUMENT, "noise convolution: the three temporaries behind the image channels");
@@ -852,6 +876,7 @@ class GpuRenderPipeline {
     if (w[0] || w[1] || w[2])  // CustomTransformData::weights{2,4,8} of the factors in use; the others keep their state
       ctx_.check(jxlh_set_upsampling_weights(ctx_.raw(), w[0], w[1], w[2]), "jxlh_set_upsampling_weights");
     if (lp_.has_patches) frame_.decode_patches(lp_.patches.patches, lp_.patches.blendings, lp_.patches.ec_flags);
+    if (lp_.has_splines) frame_.set_spline_segments(lp_.splines.segments);
   }
   VarDctFrame& frame() { return frame_; }  // decode_hf_global / decode_lf_group / decode_hf_metadata go here
   const LoweredPipeline& lowered() const { return lp_; }

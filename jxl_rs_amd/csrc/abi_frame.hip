@@ -222,6 +222,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   for (auto& b : ctx->hook_f) release(b);
   for (auto& b : ctx->hook_i) release(b);
   patches_release(ctx);
+  splines_release(ctx);
   blend_release(ctx);
   save_release(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
@@ -468,6 +469,8 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   ctx->patch_slots_used = 0;
   ctx->patch_ec_stale = true;
   ctx->patch_desc_host.clear();
+  ctx->spline_n = 0;  // ... and so are the splines
+  ctx->spline_desc_host.clear();
   for (auto& s : ctx->slots) s.used = false;
   for (int c = 0; c < 3; c++) ctx->result[c] = nullptr;
   ctx->chroma_lazy = false;
@@ -909,7 +912,7 @@ jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan, int gr0, int gr1) {
     // ... and brought to full resolution into planes[c] before any filter (frame/render.rs:569-576) -- or, when no
     // stage follows at all, only when the planes are asked for (materialise_chroma)
     const bool stages_follow = f.gab || f.epf_iters > 0 || p.upsampling > 1 || (p.noise && !noise_lut_is_zero(p.noise_lut)) ||
-                               ctx->patch_n > 0;
+                               draws_in_place(ctx);
     ctx->lazy_gr0 = gr0;
     ctx->lazy_gr1 = gr1;
     // A sharded frame gathers planes[c] band by band (jxlh_frame_allgather): the full-resolution chroma must exist
@@ -1073,7 +1076,7 @@ jxlh_status run_stages_rows(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_
   return run_post_stages(ctx, cur, y_lo, y_hi, whole_frame);
 }
 
-// what follows the filters: patches, upsampling and noise on the finished planes `cur` (rows [y_lo, y_hi))
+// what follows the filters: patches, splines, upsampling and noise on the finished planes `cur` (rows [y_lo, y_hi))
 jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
@@ -1093,6 +1096,9 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
     }
     if (jxlh_status st = run_patches(ctx, cur, f.plane_stride, y_lo, y_hi)) return st;
   }
+  // SplinesStage (frame/render.rs:652-653): behind patches, at the coded size
+  if (ctx->spline_n > 0)
+    if (jxlh_status st = run_splines(ctx, cur, f.plane_stride, f.xsize, f.ysize, y_lo, y_hi)) return st;
   if (p.upsampling > 1) {
     // Upsample2x/4x/8x on the three colour channels (frame/render.rs:655-671).  The 5x5 window crosses band
     // edges, so an upsampled frame is run whole.
@@ -1198,10 +1204,10 @@ jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_ro
   bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
   plan.want_strip = whole && strip_eligible(ctx);
   if (jxlh_status st = run_prologue(ctx, &plan)) return st;
-  // Patches are drawn in place on the result.  When the result lives in the planes K1 writes and K1 rewrites a group
+  // Patches and splines are drawn in place on the result.  When the result lives in the planes K1 writes and K1 rewrites a group
   // row beyond the band (the filters' or the chroma upsampling's halo), a band run would overwrite the neighbouring
-  // band's patched pixels with unpatched ones: such a frame is rendered whole.
-  if (!whole && ctx->patch_n > 0 && (plan.halo_px > 0 || f.subsampled) && result_in_tmp(ctx) == 0) {
+  // band's drawn pixels with bare ones: such a frame is rendered whole.
+  if (!whole && draws_in_place(ctx) && (plan.halo_px > 0 || f.subsampled) && result_in_tmp(ctx) == 0) {
     group_row0 = 0;
     group_row1 = (uint32_t)f.ygroups;
     whole = true;
@@ -1245,8 +1251,8 @@ jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids,
   const bool unfiltered_kept = !ctx->strip_ran && (ns == 0 || (per_stage ? ns == 1 : result_in_tmp(ctx) != 0));
   // Noise is added IN PLACE to the result planes.  Without a filter stage the result lives in `planes`, the planes K1
   // writes: the groups that are not re-transformed would receive their noise a second time.
-  // The same holds for patches: they are drawn in place (an Add would reach the other groups twice).
-  const bool noise_in_place = ns == 0 && ((p.noise && !noise_lut_is_zero(p.noise_lut)) || ctx->patch_n > 0);
+  // The same holds for patches and splines: they are drawn in place (an Add would reach the other groups twice).
+  const bool noise_in_place = ns == 0 && ((p.noise && !noise_lut_is_zero(p.noise_lut)) || draws_in_place(ctx));
   if (!ctx->rendered || !unfiltered_kept || f.subsampled || noise_in_place) return jxlh_frame_run(ctx, 0, UINT32_MAX);
   RunPlan plan;
   if (jxlh_status st = run_prologue(ctx, &plan)) return st;

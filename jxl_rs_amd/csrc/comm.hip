@@ -221,7 +221,8 @@ static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan, int* r0, int* r1) {
   if (ctx->params.upsampling > 1) return JXLH_ERR_UNSUPPORTED;  // the 5x5 upsampling window crosses bands: run whole
   const Comm* c = ctx->comm;
   // patches on a sharded frame: a patch crosses band edges and its reference slot is per context (not supported)
-  if (ctx->patch_n > 0 && c->nranks > 1) return JXLH_ERR_UNSUPPORTED;
+  // (splines likewise: a segment crosses band edges)
+  if (draws_in_place(ctx) && c->nranks > 1) return JXLH_ERR_UNSUPPORTED;
   if (jxlh_status st = patches_check_run(ctx)) return st;
   band_of(ctx->fd.ygroups, c->nranks, c->rank, r0, r1);
   if (jxlh_status st = run_prologue(ctx, plan)) return st;

@@ -183,6 +183,19 @@ struct jxlh_ctx {
   PatchBins patch_bins, patch_hook_bins;
   bool patch_ec_stale = true;  // the patched extra channels must be rebuilt from their base planes on all rows
   DevBuf<float> patch_hook;    // jxlh_stage_patches staging
+  // the frame's spline segments (jxlh_frame_set_splines, abi_splines.hip): as the kernel reads them, host and device;
+  // spline_first = the batches of consecutive segments planned for spline_plan_w x _h under spline_budget entries;
+  // spline_bins = the bin list of batch spline_resident for that size, also on the device (-1: none)
+  uint32_t spline_n = 0;
+  std::vector<SplineDev> spline_desc_host;
+  DevBuf<SplineDev> spline_desc;
+  std::vector<uint32_t> spline_first;
+  int spline_plan_w = 0, spline_plan_h = 0;
+  SplineBins spline_bins;
+  DevBuf<uint32_t> spline_bins_dev;
+  int spline_resident = -1;
+  uint64_t spline_budget = kSplineDefaultBudget;
+  DevBuf<float> spline_hook;  // jxlh_stage_splines staging
   // frame blending (abi_blend.hip): the image-sized canvas of 3 + blend_nec planes, channel c at c * res_stride * res_h.
   // While the frame's result points at it (blended()), blend_frame / blend_f* keep the frame's own planes and geometry.
   DevBuf<float> blend_canvas;
@@ -339,6 +352,11 @@ jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsampl
 jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y_lo, int y_hi);
 jxlh_status patches_check_run(const jxlh_ctx* ctx);
 void patches_release(jxlh_ctx* ctx);
+// abi_splines.hip: the splines stage on the colour planes `cur` (rows [y_lo, y_hi)); release of the context's buffers
+jxlh_status run_splines(jxlh_ctx* ctx, float* const cur[3], size_t stride, int w, int h, int y_lo, int y_hi);
+void splines_release(jxlh_ctx* ctx);
+// patches and splines are drawn IN PLACE on the finished planes: whatever must not reach a pixel twice asks this
+inline bool draws_in_place(const jxlh_ctx* ctx) { return ctx->patch_n > 0 || ctx->spline_n > 0; }
 // abi_blend.hip.  blended(): the frame's result is the canvas jxlh_frame_blend composed (any render resets `result`).
 inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
 void blend_release(jxlh_ctx* ctx);

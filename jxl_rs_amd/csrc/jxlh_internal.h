@@ -6,6 +6,7 @@
 
 #include "../../include/jxl_hip.h"
 #include "coeff_epoch.h"
+#include "splines_host.h"
 
 namespace jxlh {
 // 16-byte global accesses with a selectable cache policy (NT = streamed once: `nt` loads / stores)
@@ -428,6 +429,18 @@ struct PatchLaunch {
 // tiles[t] = tile id (ty * ntx + tx), start[t] .. start[t + 1] = its entries of `list` (patch indices, ascending)
 void launch_patches(hipStream_t s, int num_ec, const PatchLaunch& a, uint32_t ntiles, const uint32_t* tiles,
                     const uint32_t* start, const uint32_t* list, const PatchDev* desc);
+
+// splines stage (k_splines.hip; SplineDev and the bin geometry: splines_host.h)
+struct SplineLaunch {
+  float* col[3];  // colour planes, added to in place
+  size_t stride;
+  int w, h, ntx;   // clip size, bins per row (64 x 4 px bins)
+  int y0, y1;      // rows that are drawn
+  uint32_t bin0;   // first entry of the compact bin list this launch covers
+};
+// bins[t] = bin id (ty * ntx + tx), start[t] .. start[t + 1] = its entries of `list` (segment indices, ascending)
+void launch_splines(hipStream_t s, const SplineLaunch& a, uint32_t nbins, const uint32_t* bins, const uint32_t* start,
+                    const uint32_t* list, const SplineDev* seg);
 
 // frame blending + extension to the image size (k_blend.hip).  Channel c = 0..2 colour, 3 + i extra channel i; the host
 // resolves each channel's source slot, so the kernel sees one plane per channel on every side.

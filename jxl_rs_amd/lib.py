@@ -62,13 +62,14 @@ ABI_SYMBOLS = [
     "jxlh_ctx_set_reference", "jxlh_frame_save_reference", "jxlh_ctx_clear_reference", "jxlh_frame_set_patches",
     "jxlh_stage_patches", "jxlh_frame_blend", "jxlh_stage_blend",
     "jxlh_frame_save", "jxlh_frame_save_async", "jxlh_stage_save",
+    "jxlh_frame_set_splines", "jxlh_stage_splines", "jxlh_splines_build_segments",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
     "jxlh_timer_start", "jxlh_timer_stop", "jxlh_kernel_timing_enable", "jxlh_kernel_timing_get",
     "jxlh_kernel_timing_reset", "jxlh_selftest_recip", "jxlh_probe_copy_bandwidth", "jxlh_frame_path",
     "jxlh_flow_profile", "jxlh_frame_k1_counters", "jxlh_probe_placement", "jxlh_worklist_layout",
-    "jxlh_save_tile_layout",
+    "jxlh_save_tile_layout", "jxlh_splines_set_batch_budget", "jxlh_splines_bin_layout",
 ]
 
 
@@ -130,6 +131,18 @@ class Patch(C.Structure):
 
 class PatchBlending(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mode", "alpha_channel", "clamp")]
+
+
+class SplineSegment(C.Structure):
+    """jxlh_spline_segment."""
+    _fields_ = [("center_x", C.c_float), ("center_y", C.c_float), ("maximum_distance", C.c_float),
+                ("inv_sigma", C.c_float), ("sigma_over_4_times_intensity", C.c_float), ("color", C.c_float * 3)]
+
+
+class QuantizedSpline(C.Structure):
+    """jxlh_quantized_spline."""
+    _fields_ = [("control_points", C.c_void_p), ("n_points", C.c_uint32), ("color_dct", C.c_int32 * 96),
+                ("sigma_dct", C.c_int32 * 32), ("start_x", C.c_float), ("start_y", C.c_float)]
 
 
 # frame blending (jxlh_frame_blend): BlendingMode values
@@ -358,6 +371,13 @@ def load():
         L.jxlh_frame_save_async.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), u32, u32, vp, sz]
         L.jxlh_stage_save.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), C.POINTER(vp), u32, u32, u32, sz,
                                       u32, u32, u32, u32, vp, sz]
+    if hasattr(L, "jxlh_frame_set_splines"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        L.jxlh_frame_set_splines.argtypes = [vp, vp, u32]
+        L.jxlh_stage_splines.argtypes = [vp, C.POINTER(vp), u32, u32, sz]
+        L.jxlh_splines_build_segments.argtypes = [vp, u32, i32, C.c_float, C.c_float, C.c_uint64, C.c_uint64, u32, vp,
+                                                  sz, C.POINTER(sz)]
+        L.jxlh_splines_set_batch_budget.argtypes = [vp, C.c_uint64]
+        L.jxlh_splines_bin_layout.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.jxlh_comm_allgather_local.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), sz]
     L.jxlh_palette_strided.argtypes = [vp, vp, sz, vp, i32, sz, i32, i32, vp, sz]
     L.jxlh_modular_frame_filters.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32, sz]
@@ -386,6 +406,43 @@ def load():
         getattr(L, name).argtypes = [i32]
         getattr(L, name).restype = i32
     return L
+
+
+def splines_bin_layout():
+    """jxlh_splines_bin_layout (jxl_hip_dev.h, host only): (columns, rows) of the splines draw's bin"""
+    cols, rows = C.c_uint32(0), C.c_uint32(0)
+    st = _lib().jxlh_splines_bin_layout(C.byref(cols), C.byref(rows))
+    if st != OK:
+        raise JxlHipError(st, "splines_bin_layout")
+    return cols.value, rows.value
+
+
+def try_build_spline_segments(splines, quantization_adjustment, y_to_x_lf, y_to_b_lf, image_xsize, image_ysize,
+                              high_precision=False, count_only=False):
+    """jxlh_splines_build_segments (host only).  splines: (control point deltas [(dx, dy)], color_dct 3 x 32,
+    sigma_dct 32, (start_x, start_y)) each.  Returns (status, segments as a float32 [n, 8] array in the field order of
+    jxlh_spline_segment, or the count alone with count_only)."""
+    L = _lib()
+    n = len(splines)
+    qs = (QuantizedSpline * max(n, 1))()
+    keep = []
+    for i, (deltas, color, sigma, start) in enumerate(splines):
+        d = np.ascontiguousarray(np.asarray(deltas, dtype=np.int64).reshape(-1, 2))
+        keep.append(d)
+        qs[i].control_points = d.ctypes.data if d.size else None
+        qs[i].n_points = d.shape[0]
+        qs[i].color_dct[:] = [int(v) for v in np.asarray(color).reshape(96)]
+        qs[i].sigma_dct[:] = [int(v) for v in np.asarray(sigma).reshape(32)]
+        qs[i].start_x, qs[i].start_y = float(start[0]), float(start[1])
+    count = C.c_size_t(0)
+    args = (C.byref(qs), n, int(quantization_adjustment), C.c_float(y_to_x_lf), C.c_float(y_to_b_lf),
+            int(image_xsize), int(image_ysize), 1 if high_precision else 0)
+    st = L.jxlh_splines_build_segments(*args, None, 0, C.byref(count))
+    if st != OK or count_only:
+        return st, (count.value if st == OK else None)
+    out = np.zeros((count.value, 8), np.float32)
+    st = L.jxlh_splines_build_segments(*args, out.ctypes.data if out.size else None, count.value, C.byref(count))
+    return st, out
 
 
 WORKLIST_REGIONS = 42  # jxlh_worklist_layout: counters, 11 class lists, 9 + 9 + 9 DCT-class regions, fb_any, units, LLF
@@ -986,6 +1043,30 @@ class Context:
         pp = (C.c_void_p * len(pl))(*[a.ctypes.data for a in pl])
         self._chk(self.L.jxlh_stage_patches(self._ctx, pp, len(pl), w, h, w), "stage_patches")
         return pl
+
+    # ---- splines ----
+    def try_set_splines(self, segments):
+        """jxlh_frame_set_splines, returning the status.  segments: float32 [n, 8] in the field order of
+        jxlh_spline_segment (center_x, center_y, maximum_distance, inv_sigma, sigma_over_4_times_intensity, color[3])"""
+        seg = np.ascontiguousarray(np.asarray(segments, dtype=np.float32).reshape(-1, 8))
+        return self.L.jxlh_frame_set_splines(self._ctx, seg.ctypes.data if seg.size else None, seg.shape[0])
+
+    def set_splines(self, segments):
+        self._chk(self.try_set_splines(segments), "frame_set_splines")
+
+    def stage_splines(self, planes, w=None):
+        """jxlh_stage_splines: the current segments drawn onto copies of the three f32 planes [h, row]; the image is
+        their first w columns (all of them by default), the row stride is `row`"""
+        pl = [np.ascontiguousarray(a, dtype=np.float32).copy() for a in planes]
+        h, row = pl[0].shape
+        w = row if w is None else w
+        pp = (C.c_void_p * 3)(*[a.ctypes.data for a in pl])
+        self._chk(self.L.jxlh_stage_splines(self._ctx, pp, w, h, row), "stage_splines")
+        return pl
+
+    def set_spline_batch_budget(self, entries):
+        """jxlh_splines_set_batch_budget (jxl_hip_dev.h): bin entries per batch of the splines draw, 0 = default"""
+        self._chk(self.L.jxlh_splines_set_batch_budget(self._ctx, int(entries)), "splines_set_batch_budget")
 
     # ---- frame blending ----
     def try_blend(self, desc, colour=None):
