@@ -152,6 +152,9 @@ enum {
   JXLH_FRAME_DENSE_DEQUANT = 1u << 3,   /* a frame resident in the slot-bucketed form (jxlh_submit_groups_slots): the
                                            transforms always dequantise every coefficient position instead of only the
                                            positions that have an entry (debug/parity: both give the same bits) */
+  JXLH_FRAME_MODULAR = 1u << 4,         /* a Modular frame (lossless, lossy Modular): xsize x ysize coded samples handed
+                                           over with jxlh_frame_set_modular_channels instead of LF, HF metadata and
+                                           coefficients; see "Modular frames" below */
 };
 
 /* Header defaults of the reference (RestorationFilter / ColorCorrelationParams /
@@ -190,6 +193,46 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p);
  * Per decoder like the reference's file header: persists across frames; callable outside a frame. */
 jxlh_status jxlh_set_upsampling_weights(jxlh_ctx* ctx, const float* weights2, const float* weights4,
                                         const float* weights8);
+
+/* ---------------------------------------------------------------- Modular frames
+ * jxlh_frame_begin with JXLH_FRAME_MODULAR starts a Modular frame: the reference's render list for such a frame
+ * (frame/render.rs:553-903) opens with ConvertModularToF32Stage x3 or ConvertModularXYBToF32Stage (:554-563), reads a
+ * CONSTANT EPF sigma (features/epf.rs:81-84: INV_SIGMA_NUM / epf_sigma_for_modular) and is otherwise the VarDCT list.
+ * upsampling, hshift / vshift, noise*, the restoration-filter fields and lf_quant_factors mean what they mean for a VarDCT
+ * frame; JXLH_FRAME_STRIP, _EXPAND_SPARSE and _DENSE_DEQUANT are ignored.  The frame allocates no coefficient buffer, LF
+ * planes, HF-meta maps or work list (its i32 sample planes take the coefficient buffer's place, 12 B/px); the limit of
+ * 2^31 coefficients does not apply, the limit of 2^30 samples per plane does.  No dequant tables are needed.
+ * JXLH_ERR_INVALID_ARGUMENT: epf_iters > 0 with epf_sigma_for_modular <= 0; JXLH_ERR_UNSUPPORTED: a sharded context.
+ *
+ * jxlh_frame_set_modular_channels hands over the three colour channels of a rect as the inverse transforms left them
+ * (the Modular counterpart of jxlh_frame_set_lf): host or device memory, row stride `stride` >= w samples; per rect, in
+ * any order, and again after a run to replace a rect.  The context keeps the samples (rows never set read as zero
+ * samples), not the caller's pointers: the call returns when the copies have landed.
+ *   sample_format  bits | exponent_bits << 8 as for the extra channels: integer samples give v * (1 / (2^bits - 1)),
+ *                  float samples are widened exactly (convert.rs:416-533).  | JXLH_MODULAR_XYB selects
+ *                  ConvertModularXYBToF32Stage (convert.rs:316-342): c0, c1, c2 are the coded order Y, X, B and
+ *                  X = x * s[0], Y = y * s[1], B = ((float)b + (float)y) * s[2] with s = lf_quant_factors (the bit depth
+ *                  is not read then; the frame must not be chroma-subsampled).  The same on every rect of a frame.
+ *   grey frames    pass one pointer three times (the reference fans channel 0 out to pipeline channels 0..2,
+ *                  modular/transforms/meta_apply.rs:697-701).
+ *   sub-sampling   x0, y0, w, h are full-resolution coordinates, x0 and y0 multiples of the coarsest shift; channel c
+ *                  supplies the ceil(w / 2^hshift[c]) x ceil(h / 2^vshift[c]) samples at (x0 >> hshift[c], y0 >> vshift[c]).
+ * JXLH_ERR_INVALID_ARGUMENT: a null pointer, stride < w, a rect that leaves the coded size, a bad or changed format, a
+ * misaligned sub-sampled origin; JXLH_ERR_BAD_STATE: outside a frame or on a VarDCT frame.  A refused call changes nothing.
+ *
+ * jxlh_frame_run on a Modular frame: group rows are 256-row bands whatever the codestream's group size.  The run takes in
+ * the band's rows plus the filters' halo (k_modular_intake), upsamples sub-sampled channels, runs Gaborish / EPF and the
+ * post stages exactly as for a VarDCT frame.  A band run whose halo would overwrite a neighbouring band's finished rows
+ * (a stage list that ends in the planes the intake writes; any filtered chroma-subsampled frame, whose sub-sampled
+ * channels are taken into the other set of planes) renders the whole frame instead.  jxlh_frame_rerender_groups
+ * returns JXLH_ERR_UNSUPPORTED: a progressive Modular decode sets the changed rects and runs again.  The VarDCT-only calls
+ * (jxlh_frame_set_lf*, jxlh_frame_set_hf_meta, jxlh_submit_group*, jxlh_frame_coeff_buffer, jxlh_frame_read_lf) return
+ * JXLH_ERR_BAD_STATE with nothing launched.  Patches, splines, extra channels, read-outs, jxlh_frame_blend, jxlh_frame_save
+ * and jxlh_frame_save_reference serve the frame as they serve a VarDCT one.  Not covered: LF frames (lf_level != 0). */
+#define JXLH_MODULAR_XYB (1u << 16)
+jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                            const int32_t* c0, const int32_t* c1, const int32_t* c2, size_t stride,
+                                            uint32_t sample_format);
 
 /* HfGlobalState::dequant_matrices (frame/quant_weights.rs:347-351): 17 tables, table t holds
  * 3 * n[t] inverse weights, channel-major (matrix(type, c), :1081-1086). */
@@ -506,9 +549,9 @@ jxlh_status jxlh_frame_read_extra_channel(jxlh_ctx* ctx, uint32_t ec, const jxlh
  * alpha and num_ec > 1 (the reference reads it only then and leaves 0 otherwise: it is ignored); the patch rectangle
  * lies within the frame's PADDED size in its VarDCT form (FrameHeader::size_padded, headers/frame_header.rs:572-581:
  * whole 8x8 blocks of the coded size, as frame/decode.rs:317-323 passes it for a VarDCT frame), drawing is clipped at
- * the frame's edge.  A Modular frame's bound is its coded size (frame_header.rs:574-575), which is never larger: its
- * dictionary, as PatchesDictionary::read accepted it, always passes here, but a patch reaching into the VarDCT padding
- * is NOT rejected -- a caller using the Modular seam (jxlh_stage_patches) checks that bound itself.  The dictionary
+ * the frame's edge.  A Modular frame's bound is its coded size (frame_header.rs:574-575): on a frame begun with
+ * JXLH_FRAME_MODULAR the patch rectangle is checked against xsize x ysize, and a patch reaching into the 8x8 padding is
+ * rejected; only a caller using the Modular seam (jxlh_stage_patches) still checks that bound itself.  The dictionary
  * needs a begun frame (jxlh_frame_begin with the frame's size).  n = 0 clears the dictionary; jxlh_frame_begin clears
  * it too.
  * Position in the frame: PatchesStage (frame/render.rs:644-650) -- after the filters and the extra channels' own

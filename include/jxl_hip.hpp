@@ -118,6 +118,13 @@ class VarDctFrame {
                "jxlh_submit_group_sparse");
   }
   void slot_wait(int slot = 0) { ctx_.check(jxlh_slot_wait(ctx_.raw(), slot), "jxlh_slot_wait"); }
+  // a frame begun with JXLH_FRAME_MODULAR takes samples instead of LF, HF metadata and coefficients: one rect of the
+  // three colour channels as the inverse transforms left them (jxlh_frame_set_modular_channels)
+  void set_modular_channels(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const int32_t* const planes[3], size_t stride,
+                            uint32_t sample_format) {
+    ctx_.check(jxlh_frame_set_modular_channels(ctx_.raw(), x0, y0, w, h, planes[0], planes[1], planes[2], stride, sample_format),
+               "jxlh_frame_set_modular_channels");
+  }
   // PatchesDictionary::read's result (decode_lf_global, frame/decode.rs:315-324), flattened: blendings holds
   // patches.size() * (1 + ec_flags.size()) entries, ec_flags the JXLH_EC_* of each extra channel
   void decode_patches(const std::vector<jxlh_patch>& patches, const std::vector<jxlh_patch_blending>& blendings,

@@ -286,6 +286,9 @@ struct LoweredPipeline {
   uint32_t modular_bits = 0;                       // kToF32: bits per integer sample
   std::array<float, 3> modular_quant_factors{};    // kXybToF32
   int32_t i32_to_u8_multiplier = 0, i32_to_u8_max = 0;  // kI32ToU8: ConvertI32ToU8Stage::new(c, mult, max), builder.rs:152-170
+  // lower_modular_frame(): what jxlh_frame_set_modular_channels takes as sample_format (frame.flags then carries
+  // JXLH_FRAME_MODULAR, and frame.lf_quant_factors the XYB conversion's factors)
+  uint32_t modular_sample_format = 0;
   Border input_border{0, 0};   // accumulated BORDER of the in-out stages before any upsampling, in input pixels
   // Extra channels (pipeline channels 3..): ConvertModularToF32Stage::new(3 + ec, ec_bit_depth) (frame/render.rs:564-567)
   // and the channel's own Upsample{2,4,8}x::new(transform_data, 3 + ec) (frame/render.rs:624-637, or with the colour
@@ -315,6 +318,7 @@ struct LoweredPipeline {
 };
 
 class GpuRenderPipeline;
+class GpuModularFramePipeline;
 
 // RenderPipelineBuilder (builder.rs:19-120).  `base` carries what is not a stage: frame size, quantiser and colour
 // correlation fields, the EPF sharpness LUT / quant_mul of the sigma map, flags.
@@ -366,14 +370,24 @@ class RenderPipelineBuilder {
 
   // The host-side half of build(): validation + lowering, no device needed.  Throws Error(JXLH_ERR_UNSUPPORTED)
   // for a stage list outside this path and Error(JXLH_ERR_INVALID_ARGUMENT) for an inconsistent one.
-  LoweredPipeline lower() const;
+  LoweredPipeline lower() const { return lower_list(false); }
+  // The same for a Modular frame that lives on the context (JXLH_FRAME_MODULAR): the reference's full Modular list --
+  // conversions, chroma upsampling, Gaborish / EPF, extra channels, patches, splines, frame upsampling, noise, colour
+  // stages, blending + extend, spot / premultiply / convert / save -- under the order and consistency checks lower()
+  // applies to a VarDCT list, onto the same LoweredPipeline fields plus modular_sample_format.
+  LoweredPipeline lower_modular_frame() const { return lower_list(true); }
   // builder.rs:120: returns the pipeline (here: begins the frame on the context with the lowered parameters)
   std::unique_ptr<GpuRenderPipeline> build(Context& ctx) &&;
   // the same for a Modular frame's list (it opens with ConvertModularToF32Stage x3 or ConvertModularXYBToF32Stage)
   std::unique_ptr<class GpuModularPipeline> build_modular(Context& ctx) &&;
+  // ... as a frame of the context: begins it with JXLH_FRAME_MODULAR and the lowered parameters
+  std::unique_ptr<GpuModularFramePipeline> build_modular_frame(Context& ctx) &&;
 
  private:
   [[noreturn]] static void fail(jxlh_status st, const std::string& what) { throw Error(st, "RenderPipelineBuilder::build", what); }
+  // modular_frame: the list is a Modular frame's and the frame runs through jxlh_frame_run (lower_modular_frame);
+  // otherwise a Modular list is the caller-held-planes form of build_modular, with its narrower stage set
+  LoweredPipeline lower_list(bool modular_frame) const;
   size_t num_channels_;
   std::pair<size_t, size_t> size_;
   size_t downsampling_shift_, log_group_size_;
@@ -381,7 +395,7 @@ class RenderPipelineBuilder {
   std::vector<Stage> stages_;
 };
 
-inline LoweredPipeline RenderPipelineBuilder::lower() const {
+inline LoweredPipeline RenderPipelineBuilder::lower_list(bool modular_frame) const {
   LoweredPipeline lp;
   lp.frame = base_;
   jxlh_frame_params& p = lp.frame;
@@ -461,7 +475,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       // frame/render.rs:765-806: spot colours, premultiplication and every conversion come behind blend / extend
       if (!spots.empty() || premul_seen || !convs.empty() || tail_seen)
         fail(JXLH_ERR_INVALID_ARGUMENT, "stage '" + stage_display(s) + "' behind a spot colour, premultiply or conversion stage: they follow the blending and extend stages");
-      if (lp.modular != LoweredPipeline::Modular::kNone)
+      if (!modular_frame && lp.modular != LoweredPipeline::Modular::kNone)
         fail(JXLH_ERR_UNSUPPORTED, "blending on a Modular frame (jxlh_stage_blend on the planes instead)");
       const size_t nec = bl->ec_blending_info.size();
       size_t named = 0;
@@ -593,7 +607,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       // upsampling, noise and the colour stage (frame/render.rs:624-683)
       if (phase > kUpsample || ups_seen != 0 || patches_seen || splines_seen)
         fail(JXLH_ERR_UNSUPPORTED, "stage 'patches' out of the order of Frame::build_render_pipeline");
-      if (lp.modular != LoweredPipeline::Modular::kNone)
+      if (!modular_frame && lp.modular != LoweredPipeline::Modular::kNone)
         fail(JXLH_ERR_UNSUPPORTED, "patches on a Modular frame (jxlh_stage_patches on the planes instead)");
       if (ps->blendings.size() != ps->patches.size() * (1 + ps->ec_flags.size()))
         fail(JXLH_ERR_INVALID_ARGUMENT, "patches: blendings != patches * (1 + num_ec)");
@@ -606,7 +620,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       // stage (frame/render.rs:644-683)
       if (phase > kUpsample || ups_seen != 0 || splines_seen)
         fail(JXLH_ERR_UNSUPPORTED, "stage 'splines' out of the order of Frame::build_render_pipeline");
-      if (lp.modular != LoweredPipeline::Modular::kNone)
+      if (!modular_frame && lp.modular != LoweredPipeline::Modular::kNone)
         fail(JXLH_ERR_UNSUPPORTED, "splines on a Modular frame (jxlh_stage_splines on the planes instead)");
       phase = kUpsample;
       splines_seen = true;
@@ -709,7 +723,7 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
       // (frame/render.rs:858-902)
       if (phase < kConvert) enter(kConvert, s);
       const std::string name = "stage '" + stage_display(s) + "'";
-      if (lp.modular != LoweredPipeline::Modular::kNone)
+      if (!modular_frame && lp.modular != LoweredPipeline::Modular::kNone)
         fail(JXLH_ERR_UNSUPPORTED, name + " on a Modular frame (jxlh_stage_save on the planes instead)");
       if (sv->output_buffer_index != (int)lp.saves.size())
         fail(JXLH_ERR_INVALID_ARGUMENT, name + ": save stages come in output buffer order");
@@ -808,7 +822,20 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   }
   // consistency of the whole list
   if (lp.modular == LoweredPipeline::Modular::kToF32 && modular_seen != 3) fail(JXLH_ERR_INVALID_ARGUMENT, "Modular -> f32 conversion on some channels only");
-  if (lp.modular != LoweredPipeline::Modular::kNone) {
+  if (modular_frame) {
+    // the frame runs through jxlh_frame_run: every stage the VarDCT list may hold is served; the I32 -> U8 special case
+    // stays with build_modular
+    if (lp.modular == LoweredPipeline::Modular::kNone) fail(JXLH_ERR_INVALID_ARGUMENT, "the stage list holds no Modular conversion");
+    p.flags |= JXLH_FRAME_MODULAR;
+    if (lp.modular == LoweredPipeline::Modular::kXybToF32) {
+      if (p.hshift[0] | p.hshift[1] | p.hshift[2] | p.vshift[0] | p.vshift[1] | p.vshift[2])
+        fail(JXLH_ERR_INVALID_ARGUMENT, "chroma subsampling on an XYB Modular frame");
+      lp.modular_sample_format = JXLH_MODULAR_XYB;
+      for (int c = 0; c < 3; c++) p.lf_quant_factors[c] = lp.modular_quant_factors[c];
+    } else {
+      lp.modular_sample_format = lp.modular_bits;
+    }
+  } else if (lp.modular != LoweredPipeline::Modular::kNone) {
     // what this path runs for a Modular frame: the conversion, Gaborish / EPF with the constant sigma of
     // features/epf.rs:81-84 (jxlh_modular_frame_filters), then either the planes themselves or -- the builder's special
     // case -- straight to bytes
@@ -867,11 +894,11 @@ inline LoweredPipeline RenderPipelineBuilder::lower() const {
   return lp;
 }
 
-// RenderPipeline (render/mod.rs:116-157) for this path: inputs are a group's coefficient slabs instead of its pixel
-// buffers (the transforms run on the device too), everything else keeps the trait's meaning.
-class GpuRenderPipeline {
+// What GpuRenderPipeline and GpuModularFramePipeline share: the frame begun on the context with the lowered parameters,
+// its dictionary and splines, the extra channels, and the output side -- blend, save, read.
+class GpuFramePipeline {
  public:
-  GpuRenderPipeline(Context& ctx, LoweredPipeline lp) : ctx_(ctx), lp_(std::move(lp)), frame_(ctx, lp_.frame) {
+  GpuFramePipeline(Context& ctx, LoweredPipeline lp) : ctx_(ctx), lp_(std::move(lp)), frame_(ctx, lp_.frame) {
     const float* const* w = lp_.weights_by_factor;
     if (w[0] || w[1] || w[2])  // CustomTransformData::weights{2,4,8} of the factors in use; the others keep their state
       ctx_.check(jxlh_set_upsampling_weights(ctx_.raw(), w[0], w[1], w[2]), "jxlh_set_upsampling_weights");
@@ -880,16 +907,6 @@ class GpuRenderPipeline {
   }
   VarDctFrame& frame() { return frame_; }  // decode_hf_global / decode_lf_group / decode_hf_metadata go here
   const LoweredPipeline& lowered() const { return lp_; }
-  // render/mod.rs:128-136.  complete = false: a progressive pass that leaves the group open
-  void set_buffer_for_group(uint32_t group_id, bool complete, const int32_t* coeffs, int slot = 0) {
-    ctx_.check(jxlh_submit_group(ctx_.raw(), slot, group_id, coeffs, complete ? JXLH_GROUP_COMPLETE : 0u), "jxlh_submit_group");
-    // the reference renders every group it is handed (render/mod.rs:128-136): once the frame has been rendered, a group
-    // that receives new coefficients is re-rendered whether or not the caller also marks it (duplicates are merged by
-    // jxlh_frame_rerender_groups)
-    if (!dirty_first_) rerender_.push_back(group_id);
-  }
-  // render/mod.rs:146
-  void mark_group_to_rerender(uint32_t g) { rerender_.push_back(g); }
   // render/mod.rs:141-144: nothing of the frame lies outside what the groups cover on this path
   void render_outside_frame() {}
   // render/mod.rs:138: the caller's buffer must hold out_height rows of out_width * channels samples
@@ -907,19 +924,6 @@ class GpuRenderPipeline {
     const size_t need = (size_t)(t ? lp_.out_h : lp_.out_w) * (d.n_channels + (d.fill_opaque_alpha ? 1 : 0)) * bps;
     if (bytes_per_row < need || rows < (t ? lp_.out_w : lp_.out_h))
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::check_buffer_sizes", "output buffer too small");
-  }
-  // what the reference does when the last group of a pass has been handed over (frame/decode.rs:547-558, :703-711)
-  void do_render() {
-    for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");
-    if (!rerender_.empty() && !dirty_first_) {
-      ctx_.check(jxlh_frame_rerender_groups(ctx_.raw(), rerender_.data(), (uint32_t)rerender_.size()), "jxlh_frame_rerender_groups");
-    } else {
-      frame_.finalize_and_render();
-    }
-    // BlendingStage + extend (with the list's colour stage in front): the image becomes what the save stages read
-    if (lp_.has_blend) frame_.blend(lp_.blend, &lp_.blend_colour);
-    dirty_first_ = false;
-    rerender_.clear();
   }
   // the save stage: interleaved integers through the colour tail, or the three f32 planes
   void save(void* out) {
@@ -947,7 +951,11 @@ class GpuRenderPipeline {
     ctx_.check(jxlh_frame_read_extra_channel(ctx_.raw(), ec, &pl), "jxlh_frame_read_extra_channel");
   }
 
- private:
+ protected:
+  // BlendingStage + extend (with the list's colour stage in front): the image becomes what the save stages read
+  void blend_if_listed() {
+    if (lp_.has_blend) frame_.blend(lp_.blend, &lp_.blend_colour);
+  }
   const jxlh_save_desc& save_desc(size_t buffer_index) const {
     if (buffer_index >= lp_.saves.size())
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::save", "the stage list has no save stage for this buffer");
@@ -956,8 +964,65 @@ class GpuRenderPipeline {
   Context& ctx_;
   LoweredPipeline lp_;
   VarDctFrame frame_;
+};
+
+// RenderPipeline (render/mod.rs:116-157) for this path: inputs are a group's coefficient slabs instead of its pixel
+// buffers (the transforms run on the device too), everything else keeps the trait's meaning.
+class GpuRenderPipeline : public GpuFramePipeline {
+ public:
+  using GpuFramePipeline::GpuFramePipeline;
+  // render/mod.rs:128-136.  complete = false: a progressive pass that leaves the group open
+  void set_buffer_for_group(uint32_t group_id, bool complete, const int32_t* coeffs, int slot = 0) {
+    ctx_.check(jxlh_submit_group(ctx_.raw(), slot, group_id, coeffs, complete ? JXLH_GROUP_COMPLETE : 0u), "jxlh_submit_group");
+    // the reference renders every group it is handed (render/mod.rs:128-136): once the frame has been rendered, a group
+    // that receives new coefficients is re-rendered whether or not the caller also marks it (duplicates are merged by
+    // jxlh_frame_rerender_groups)
+    if (!dirty_first_) rerender_.push_back(group_id);
+  }
+  // render/mod.rs:146
+  void mark_group_to_rerender(uint32_t g) { rerender_.push_back(g); }
+  // what the reference does when the last group of a pass has been handed over (frame/decode.rs:547-558, :703-711)
+  void do_render() {
+    for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");
+    if (!rerender_.empty() && !dirty_first_) {
+      ctx_.check(jxlh_frame_rerender_groups(ctx_.raw(), rerender_.data(), (uint32_t)rerender_.size()), "jxlh_frame_rerender_groups");
+    } else {
+      frame_.finalize_and_render();
+    }
+    blend_if_listed();
+    dirty_first_ = false;
+    rerender_.clear();
+  }
+
+ private:
   std::vector<uint32_t> rerender_;
   bool dirty_first_ = true;
+};
+
+// A Modular frame as a frame of the context (lower_modular_frame): the samples come out of the Modular inverse
+// transforms (jxlh_rct, jxlh_palette*, jxlh_unsqueeze_chain) as three i32 planes, host or device memory, and go in rect
+// by rect; render() is the whole stage list behind jxlh_frame_run, and the output side is GpuRenderPipeline's.
+class GpuModularFramePipeline : public GpuFramePipeline {
+ public:
+  GpuModularFramePipeline(Context& ctx, LoweredPipeline lp) : GpuFramePipeline(ctx, std::move(lp)) {
+    if (!(lp_.frame.flags & JXLH_FRAME_MODULAR))
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuModularFramePipeline", "the list was not lowered by lower_modular_frame");
+  }
+  // one rect of the three colour channels (coded order Y, X, B for an XYB list; one pointer three times for a grey
+  // frame), full-resolution coordinates, row stride in samples
+  void set_channels(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const int32_t* const planes[3], size_t stride) {
+    frame_.set_modular_channels(x0, y0, w, h, planes, stride, lp_.modular_sample_format);
+  }
+  // the whole frame, then the list's blending
+  void render() {
+    frame_.finalize_and_render();
+    blend_if_listed();
+  }
+  // 256-row bands [band0, band1) (a list with blending or frame upsampling renders whole)
+  void render_band(uint32_t band0, uint32_t band1) {
+    if (lp_.has_blend) throw Error(JXLH_ERR_UNSUPPORTED, "GpuModularFramePipeline::render_band", "a blended frame is rendered whole");
+    frame_.finalize_and_render(band0, band1);
+  }
 };
 
 // A Modular frame's stage list on the device: the samples come out of the Modular inverse transforms (jxlh_rct,
@@ -1011,6 +1076,10 @@ inline std::unique_ptr<GpuRenderPipeline> RenderPipelineBuilder::build(Context& 
 
 inline std::unique_ptr<GpuModularPipeline> RenderPipelineBuilder::build_modular(Context& ctx) && {
   return std::make_unique<GpuModularPipeline>(ctx, lower());
+}
+
+inline std::unique_ptr<GpuModularFramePipeline> RenderPipelineBuilder::build_modular_frame(Context& ctx) && {
+  return std::make_unique<GpuModularFramePipeline>(ctx, lower_modular_frame());
 }
 
 }  // namespace jxlh

@@ -34,7 +34,7 @@ extern "C" {
 jxlh_status jxlh_submit_group(jxlh_ctx* ctx, int32_t slot, uint32_t group_id, const int32_t* coeffs, uint32_t flags) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !coeffs || slot < 0 || (size_t)slot >= ctx->slots.size()) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
   if (group_id >= ctx->ngroups) return JXLH_ERR_INVALID_ARGUMENT;
   // JXLH_GROUP_COMPLETE is the caller's bookkeeping (set_buffer_for_group's `complete`): a slab always REPLACES the
   // group's coefficients, so a progressive decoder submits what it has accumulated so far (the reference keeps that
@@ -64,7 +64,7 @@ jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const ui
                            size_t* offset_out, size_t* total_out) {
   if (!ctx || slot < 0 || (size_t)slot >= ctx->slots.size() || !group_ids || !n || (n_wide && !wide))
     return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;  // (a Modular frame has no coefficients)
   size_t total = 0;
   for (uint32_t i = 0; i < count; i++) {
     if (group_ids[i] >= ctx->ngroups) return JXLH_ERR_INVALID_ARGUMENT;
@@ -113,6 +113,7 @@ jxlh_status jxlh_submit_groups_sparse(jxlh_ctx* ctx, int32_t slot, uint32_t coun
                                       const jxlh_coeff16* pairs, const uint32_t* n, const jxlh_coeff32* wide,
                                       uint32_t n_wide, uint32_t flags) {
   JXLH_ON_DEVICE(ctx);
+  if (ctx && ctx->in_frame && ctx->modular) return JXLH_ERR_BAD_STATE;  // a Modular frame has no coefficients
   if (count == 0 && ctx && ctx->in_frame) return JXLH_OK;
   size_t offset = 0, total = 0;
   if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, Sub::kPairs, pairs != nullptr,
@@ -130,6 +131,7 @@ jxlh_status jxlh_submit_groups_sparse8(jxlh_ctx* ctx, int32_t slot, uint32_t cou
                                        const uint16_t* pos, const int8_t* val, const uint32_t* n,
                                        const jxlh_coeff32* wide, uint32_t n_wide, uint32_t flags) {
   JXLH_ON_DEVICE(ctx);
+  if (ctx && ctx->in_frame && ctx->modular) return JXLH_ERR_BAD_STATE;  // a Modular frame has no coefficients
   if (count == 0 && ctx && ctx->in_frame) return JXLH_OK;
   size_t offset = 0, total = 0;
   if (jxlh_status st = sparse_reserve(ctx, slot, count, group_ids, n, wide, n_wide, flags, Sub::kPairs, pos && val,
@@ -157,6 +159,7 @@ jxlh_status jxlh_submit_groups_sparse4(jxlh_ctx* ctx, int32_t slot, uint32_t cou
                                        const int8_t* val8, const uint32_t* n8, const jxlh_coeff32* wide,
                                        uint32_t n_wide, uint32_t flags) {
   JXLH_ON_DEVICE(ctx);
+  if (ctx && ctx->in_frame && ctx->modular) return JXLH_ERR_BAD_STATE;  // a Modular frame has no coefficients
   if (count == 0 && ctx && ctx->in_frame) return JXLH_OK;
   if (!ctx || !seg_counts) return JXLH_ERR_INVALID_ARGUMENT;
   // per (group, channel): entries of the 2-byte form, overflow updates; their sum is what the pair buffer receives
@@ -216,6 +219,7 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
                                      const uint16_t* entries, const uint8_t* slot_counts, const uint32_t* n,
                                      const jxlh_coeff32* wide, uint32_t n_wide, uint32_t flags) {
   JXLH_ON_DEVICE(ctx);
+  if (ctx && ctx->in_frame && ctx->modular) return JXLH_ERR_BAD_STATE;  // a Modular frame has no coefficients
   if (count == 0 && ctx && ctx->in_frame) return JXLH_OK;
   // every argument is checked BEFORE anything is reserved: a failed call leaves the epoch as it was
   if (!ctx || !slot_counts || !n || !group_ids || slot < 0 || (size_t)slot >= ctx->slots.size()) return JXLH_ERR_INVALID_ARGUMENT;
@@ -324,7 +328,7 @@ jxlh_status jxlh_slot_after(jxlh_ctx* ctx, int32_t slot, jxlh_ctx* after_ctx, in
 jxlh_status jxlh_frame_coeff_buffer(jxlh_ctx* ctx, int32_t** device_ptr, size_t* n_int32) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !device_ptr) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
   *device_ptr = ctx->coeffs.p;
   if (n_int32) *n_int32 = ctx->ngroups * 3 * kGroupArea;
   return JXLH_OK;

@@ -171,6 +171,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
     release(ctx->lf_sm[c]);
   }
   release(ctx->sigma);
+  for (auto& b : ctx->mod_src) release(b);
   release(ctx->tables);
   release(ctx->coeffs);
   release(ctx->sp_pairs);
@@ -343,6 +344,11 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
     maxhs |= p->hshift[c];
     maxvs |= p->vshift[c];
   }
+  const bool modular = (p->flags & JXLH_FRAME_MODULAR) != 0;
+  if (modular) {  // SigmaSource::Constant divides by it (features/epf.rs:81-84); a rank would hold only its band
+    if (p->epf_iters > 0 && !(p->epf_sigma_for_modular > 0.0f)) return JXLH_ERR_INVALID_ARGUMENT;
+    if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;
+  }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->params = *p;
   FrameDev& f = ctx->fd;
@@ -366,13 +372,16 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   const size_t gather_elems = (size_t)comm_nranks(ctx) * comm_rows_per_rank(ctx, f.ygroups) * kGroupDim * f.plane_stride;
   // K1 uses 32-bit pixel and coefficient offsets
   // planes are addressed with 32-bit BYTE offsets in the filter kernels, coefficients with 32-bit indices
-  if (plane_elems >= (1ull << 30) || (size_t)f.xgroups * f.ygroups * 3 * kGroupArea >= (1ull << 31))
+  // (a Modular frame has no coefficients)
+  if (plane_elems >= (1ull << 30) || (!modular && (size_t)f.xgroups * f.ygroups * 3 * kGroupArea >= (1ull << 31)))
     return JXLH_ERR_UNSUPPORTED;
   ctx->ngroups = (size_t)f.xgroups * f.ygroups;
   {
     std::lock_guard<std::mutex> lock(ctx->sp_mutex);
     ctx->epoch.reset(ctx->ngroups);
   }
+  ctx->modular = modular;
+  if (modular) return modular_frame_begin(ctx);  // no coefficient buffer, LF planes, HF-meta maps or work list
   const size_t nblocks = (size_t)f.xblocks * f.yblocks;
   const size_t ncmap = (size_t)f.cmap_stride * ((f.yblocks + 7) / 8);
   jxlh_status st;
@@ -458,6 +467,15 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
     ctx->params_direct_ok = f.se_direct_ok != 0;
     f.se_direct_ok = ctx->params_direct_ok && ctx->tables_set && ctx->tables_ok_host != 0;
   }
+  reset_frame_state(ctx);
+  return JXLH_OK;
+}
+
+}  // extern "C"
+
+namespace jxlh_host {
+// the per-frame state every jxlh_frame_begin starts from
+void reset_frame_state(jxlh_ctx* ctx) {
   ctx->lf_smoothed = false;
   ctx->rendered = false;
   ctx->has_special = ctx->has_large = false;
@@ -474,8 +492,10 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   for (auto& s : ctx->slots) s.used = false;
   for (int c = 0; c < 3; c++) ctx->result[c] = nullptr;
   ctx->chroma_lazy = false;
-  return JXLH_OK;
 }
+}  // namespace jxlh_host
+
+extern "C" {
 
 jxlh_status jxlh_set_upsampling_weights(jxlh_ctx* ctx, const float* weights2, const float* weights4,
                                         const float* weights8) {
@@ -533,7 +553,7 @@ jxlh_status jxlh_frame_set_lf_quantized(jxlh_ctx* ctx, uint32_t x0, uint32_t y0,
                                         uint32_t extra_precision) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !qy || !qx || !qb || stride < w || extra_precision > 3) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
   if (!rect_ok(ctx, x0, y0, w, h)) return JXLH_ERR_INVALID_ARGUMENT;
   if (w == 0 || h == 0) return JXLH_OK;
   const size_t n = (size_t)w * h;
@@ -578,7 +598,7 @@ jxlh_status jxlh_frame_set_lf(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t 
                               const float* y, const float* b, size_t stride) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !x || !y || !b || stride < w) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
   if (!rect_ok(ctx, x0, y0, w, h)) return JXLH_ERR_INVALID_ARGUMENT;
   const float* src[3] = {x, y, b};
   const size_t off = (size_t)y0 * ctx->fd.xblocks + x0;
@@ -598,7 +618,7 @@ jxlh_status jxlh_frame_set_hf_meta(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !transform_map || !raw_quant || !epf_map || !ytox || !ytob || map_stride < w)
     return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
   if (!rect_ok(ctx, x0, y0, w, h) || (x0 % 8) || (y0 % 8)) return JXLH_ERR_INVALID_ARGUMENT;
   const size_t cw = (w + 7) / 8, ch = (h + 7) / 8;
   if (cmap_stride < cw) return JXLH_ERR_INVALID_ARGUMENT;
@@ -697,7 +717,10 @@ bool noise_lut_is_zero(const float lut[8]) {
 
 // chroma upsampling of the sub-sampled channels, tmp[c] -> planes[c], over the rows K1 produced for group rows
 // [gr0, gr1) (the outermost rows of a halo group row read beyond the region, and nobody reads them)
-void run_chroma_upsample(jxlh_ctx* ctx, int gr0, int gr1) {
+void run_chroma_upsample(jxlh_ctx* ctx, int gr0, int gr1) { run_chroma_upsample_rows(ctx, gr0 * kGroupDim, gr1 * kGroupDim); }
+
+// ... over the rows of the sub-sampled channels that cover pixel rows [y0, y1) (y0 even)
+void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1) {
   const FrameDev& f = ctx->fd;
   ScopedKernelTimer t(ctx, "k_chroma_upsample");
   const PixLayout lay = pix_layout(f);
@@ -705,7 +728,7 @@ void run_chroma_upsample(jxlh_ctx* ctx, int gr0, int gr1) {
     const int hs = f.hshift[c], vs = f.vshift[c];
     if (!(hs | vs)) continue;
     const int cw = (f.xsize + (1 << hs) - 1) >> hs, ch = (f.ysize + (1 << vs) - 1) >> vs;
-    const int sy0 = (gr0 * kGroupDim) >> vs, sy1 = min(ch, (gr1 * kGroupDim) >> vs);
+    const int sy0 = y0 >> vs, sy1 = min(ch, (y1 + (1 << vs) - 1) >> vs);
     launch_chroma_upsample(ctx->stream, f.tmp[c], f.planes[c], lay, lay, hs, vs, cw, ch, sy0, sy1, f.xblocks * 8,
                            f.yblocks * 8);
   }
@@ -1195,10 +1218,11 @@ extern "C" {
 jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_row1) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->tables_set) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || (!ctx->modular && !ctx->tables_set)) return JXLH_ERR_BAD_STATE;
   FrameDev& f = ctx->fd;
   if (group_row1 > (uint32_t)f.ygroups) group_row1 = (uint32_t)f.ygroups;
   if (group_row0 >= group_row1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (ctx->modular) return modular_frame_run(ctx, group_row0, group_row1);
   if (jxlh_status st = patches_check_run(ctx)) return st;
   RunPlan plan;
   bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
@@ -1232,7 +1256,9 @@ jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_ro
 jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids, uint32_t count) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || (count && !group_ids)) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->tables_set) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (ctx->modular) return JXLH_ERR_UNSUPPORTED;  // a progressive Modular decode sets the changed rects and runs again
+  if (!ctx->tables_set) return JXLH_ERR_BAD_STATE;
   FrameDev& f = ctx->fd;
   for (uint32_t i = 0; i < count; i++)
     if (group_ids[i] >= ctx->ngroups) return JXLH_ERR_INVALID_ARGUMENT;

@@ -280,7 +280,7 @@ jxlh_status jxlh_frame_device_planes(jxlh_ctx* ctx, float* planes[3], size_t* st
 jxlh_status jxlh_frame_read_lf(jxlh_ctx* ctx, float* x, float* y, float* b, size_t stride) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !x || !y || !b) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
   const FrameDev& f = ctx->fd;
   if (stride < (size_t)f.xblocks) return JXLH_ERR_INVALID_ARGUMENT;
   float* dst[3] = {x, y, b};

@@ -299,8 +299,10 @@ jxlh_status jxlh_frame_set_patches(jxlh_ctx* ctx, const jxlh_patch* patches, uin
       }
     if (handed > 0 && (handed != top || handed != num_ec)) return JXLH_ERR_INVALID_ARGUMENT;
     if (num_ec > 0 && ctx->params.upsampling > 1) return JXLH_ERR_UNSUPPORTED;
-    // FrameHeader::size_padded (frame_header.rs:572-581) of a VarDCT frame, as frame/decode.rs:317-323 passes it
-    const uint64_t pw = (uint64_t)ctx->fd.xblocks * 8, ph = (uint64_t)ctx->fd.yblocks * 8;
+    // FrameHeader::size_padded (frame_header.rs:572-581) as frame/decode.rs:317-323 passes it: whole 8x8 blocks for a
+    // VarDCT frame, the coded size for a Modular one (:574-575)
+    const uint64_t pw = ctx->modular ? (uint64_t)ctx->fd.xsize : (uint64_t)ctx->fd.xblocks * 8,
+                   ph = ctx->modular ? (uint64_t)ctx->fd.ysize : (uint64_t)ctx->fd.yblocks * 8;
     const uint32_t stride = 1 + num_ec;
     for (uint32_t i = 0; i < n; i++) {
       const jxlh_patch& p = patches[i];

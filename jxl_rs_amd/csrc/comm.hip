@@ -217,7 +217,7 @@ static bool exchange_applies(const jxlh_ctx* ctx, const RunPlan& plan) {
 
 // transforms of the own band (plus recomputed halo group rows when the exchange does not apply)
 static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan, int* r0, int* r1) {
-  if (!ctx->in_frame || !ctx->tables_set) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular || !ctx->tables_set) return JXLH_ERR_BAD_STATE;
   if (ctx->params.upsampling > 1) return JXLH_ERR_UNSUPPORTED;  // the 5x5 upsampling window crosses bands: run whole
   const Comm* c = ctx->comm;
   // patches on a sharded frame: a patch crosses band edges and its reference slot is per context (not supported)

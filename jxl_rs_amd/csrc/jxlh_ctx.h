@@ -67,6 +67,12 @@ struct jxlh_ctx {
   std::string last_error;
   // frame state
   bool in_frame = false;
+  // a Modular frame (JXLH_FRAME_MODULAR, abi_modular_frame.hip): the i32 samples of the three colour channels as
+  // jxlh_frame_set_modular_channels handed them over, at the planes' row stride (rows 256-byte aligned), and their format
+  // (0 = no rect set yet)
+  bool modular = false;
+  DevBuf<int32_t> mod_src[3];
+  uint32_t mod_format = 0;
   bool tables_set = false, lf_smoothed = false;
   jxlh_frame_params params;
   FrameDev fd;
@@ -373,6 +379,11 @@ inline int result_in_tmp(const jxlh_ctx* ctx) {
   return ns & 1;
 }
 void set_filter_params(FrameDev& f, const jxlh_frame_params& p);
+// abi_modular_frame.hip: jxlh_frame_begin / jxlh_frame_run of a Modular frame (behind the shared argument checks)
+void reset_frame_state(jxlh_ctx* ctx);  // abi_frame.hip: the per-frame state every jxlh_frame_begin starts from
+jxlh_status modular_frame_begin(jxlh_ctx* ctx);
+jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_row1);
+void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1);  // abi_frame.hip: ... of the rows that cover [y0, y1)
 // abi_frame.hip: pieces of the frame pipeline the read-out and stage-hook entry points share
 bool noise_lut_is_zero(const float lut[8]);
 void materialise_chroma(jxlh_ctx* ctx);          // deferred chroma upsampling of a sub-sampled frame, if still pending

@@ -363,6 +363,21 @@ inline bool bit_depth_ok(uint32_t packed, uint32_t max_int_bits) {
   if (eb == 0) return packed == bits && bits >= 1 && bits <= max_int_bits;
   return (packed >> 16) == 0 && bits <= 32 && eb >= 2 && eb <= 8 && bits >= eb + 2 && bits - eb - 1 <= 23;
 }
+// k_modular_frame.hip: the conversion stages that open a Modular frame's render list (ConvertModularToF32Stage x3 or
+// ConvertModularXYBToF32Stage, frame/render.rs:554-563), all three channels of a row range in one launch, from the
+// context's i32 planes into the frame layout.  Channel c: w[c] samples per row, rows [y0[c], y1[c]).
+enum { kIntakeInt = 0, kIntakeFloat = 1, kIntakeXyb = 2 };
+struct IntakeLaunch {
+  const int32_t* src[3];  // rows 16-byte aligned
+  float* dst[3];          // rows 16-byte aligned
+  uint32_t src_stride, dst_stride;  // samples
+  int w[3], y0[3], y1[3];
+  int form;               // kIntake*; kIntakeXyb: src = Y, X, B, dst = X, Y, B, one geometry (channel 0's)
+  float scale[3];         // kIntakeInt: 1 / (2^bits - 1) per channel; kIntakeXyb: lf_quant_factors
+  uint32_t bits, exp_bits;  // kIntakeFloat
+};
+void launch_modular_intake(hipStream_t s, const IntakeLaunch& a);
+void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
 void launch_modular_xyb_to_f32(hipStream_t s, const int32_t* y, const int32_t* x, const int32_t* b, size_t n,
                                const float scale[3], float* ox, float* oy, float* ob);
 // n_planes (<= 3) planes of identical geometry in one launch (the channels of one squeeze step)

@@ -11,6 +11,7 @@
 // coalesced (lanes = adjacent columns); horizontal steps walk rows (lanes = adjacent rows)
 // and lean on L1/L2 for the 128-byte lines they share across iterations.
 #include "jxlh_internal.h"
+#include "modular_convert_device.h"
 
 namespace jxlh {
 namespace {
@@ -966,35 +967,7 @@ __global__ void k_float_samples_to_f32(const int32_t* __restrict__ in, size_t n,
                                        float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const int exp_bias = (1 << (exp_bits - 1)) - 1;
-  const uint32_t sign_shift = bits - 1, mant_bits = bits - exp_bits - 1, mant_shift = 23 - mant_bits;
-  uint32_t f = (uint32_t)in[i];
-  const bool signbit = (f >> sign_shift) != 0;
-  f &= (sign_shift >= 32 ? 0xffffffffu : (1u << sign_shift) - 1u);
-  uint32_t r;
-  if (f == 0) {
-    r = signbit ? 0x80000000u : 0u;
-  } else {
-    int exp = (int)(f >> mant_bits);
-    uint32_t mantissa = f & ((1u << mant_bits) - 1u);
-    if (exp == (1 << exp_bits) - 1) {  // NaN or infinity
-      r = (signbit ? 0x80000000u : 0u) | 0xffu << 23 | mantissa << mant_shift;
-    } else {
-      mantissa <<= mant_shift;
-      if (exp == 0 && exp_bits < 8) {  // subnormal: normalise
-        while ((mantissa & 0x800000u) == 0) {
-          mantissa <<= 1;
-          exp -= 1;
-        }
-        exp += 1;
-        mantissa &= 0x7fffffu;  // the leading 1 is implicit now
-      }
-      exp -= exp_bias;
-      exp += 127;
-      r = (signbit ? 0x80000000u : 0u) | (uint32_t)exp << 23 | mantissa;
-    }
-  }
-  out[i] = __uint_as_float(r);
+  out[i] = float_sample_to_f32((uint32_t)in[i], bits, exp_bits);
 }
 // ConvertModularXYBToF32Stage (convert.rs:306-343)
 __global__ void k_modular_xyb_to_f32(const int32_t* __restrict__ y, const int32_t* __restrict__ x,

@@ -150,7 +150,7 @@ jxlh_status probe_placement(jxlh_ctx* ctx, const int32_t* coeffs, size_t ngroups
 extern "C" jxlh_status jxlh_probe_placement(jxlh_ctx* ctx, float* k1_like_ms, float* filter_like_ms) {
   if (!ctx || !k1_like_ms || !filter_like_ms) return JXLH_ERR_INVALID_ARGUMENT;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!ctx->in_frame || !ctx->coeffs.p || !ctx->planes[0].p) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular || !ctx->coeffs.p || !ctx->planes[0].p) return JXLH_ERR_BAD_STATE;
   float* p[3] = {ctx->planes[0].p, ctx->planes[1].p, ctx->planes[2].p};
   float* t[3] = {ctx->tmp[0].p, ctx->tmp[1].p, ctx->tmp[2].p};
   const size_t plane_elems = std::min(std::min(ctx->planes[0].n, ctx->planes[1].n), ctx->planes[2].n) & ~(size_t)511;

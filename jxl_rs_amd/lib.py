@@ -30,6 +30,8 @@ FRAME_UNFUSED_FILTERS = 1
 FRAME_EXPAND_SPARSE = 2
 FRAME_STRIP = 4
 FRAME_DENSE_DEQUANT = 8
+FRAME_MODULAR = 16
+MODULAR_XYB = 1 << 16  # jxlh_frame_set_modular_channels: sample_format | MODULAR_XYB
 GROUP_COMPLETE = 1
 GROUP_ACCUMULATE = 2
 GROUP_ENTRIES12 = 4
@@ -63,6 +65,7 @@ ABI_SYMBOLS = [
     "jxlh_stage_patches", "jxlh_frame_blend", "jxlh_stage_blend",
     "jxlh_frame_save", "jxlh_frame_save_async", "jxlh_stage_save",
     "jxlh_frame_set_splines", "jxlh_stage_splines", "jxlh_splines_build_segments",
+    "jxlh_frame_set_modular_channels",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
@@ -297,6 +300,8 @@ def load():
     L.jxlh_frame_set_lf_quantized.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, u32]
     L.jxlh_frame_set_lf.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz]
     L.jxlh_frame_set_hf_meta.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, vp, vp, sz]
+    if hasattr(L, "jxlh_frame_set_modular_channels"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        L.jxlh_frame_set_modular_channels.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, u32]
     L.jxlh_submit_group.argtypes = [vp, i32, u32, vp, u32]
     L.jxlh_slot_wait.argtypes = [vp, i32]
     L.jxlh_submit_group_sparse.argtypes = [vp, i32, u32, vp, vp, vp, u32, u32]
@@ -793,6 +798,24 @@ class Context:
         self.xblocks = -(-params.xsize // (8 << mh)) << mh
         self.yblocks = -(-params.ysize // (8 << mv)) << mv
         self._chk(self.L.jxlh_frame_begin(self._ctx, C.byref(params)), "frame_begin")
+
+    def modular_frame_begin(self, params):
+        """jxlh_frame_begin of a Modular frame: params.xsize x params.ysize coded samples, handed over with
+        set_modular_channels; run, blend, save and the read-outs as for a VarDCT frame"""
+        p = FrameParams.from_buffer_copy(params)  # the caller's params stay what they were
+        p.flags |= FRAME_MODULAR
+        self.frame_begin(p)
+
+    def set_modular_channels(self, c0, c1, c2, sample_format, x0=0, y0=0, w=None, h=None, stride=None):
+        """One rect of the three colour channels as the inverse transforms left them (sample_format: bits | exponent bits
+        << 8, | MODULAR_XYB for coded Y, X, B).  Host arrays as in set_lf_quantized (a grey frame passes one array three
+        times); DeviceArrays / raw device pointers: give w, h and stride (samples).  With chroma subsampling pass
+        pointers or call the ABI directly: the three planes of a rect then differ in size."""
+        if not hasattr(self.L, "jxlh_frame_set_modular_channels"):
+            raise JxlHipError(ERR_UNSUPPORTED, "set_modular_channels", f"{LIB_PATH} predates Modular frames (no jxlh_frame_set_modular_channels)")
+        (c0, c1, c2), w, h, stride = _rect_planes((c0, c1, c2), np.int32, w, h, stride)
+        self._chk(self.L.jxlh_frame_set_modular_channels(self._ctx, x0, y0, w, h, _addr(c0), _addr(c1), _addr(c2), stride,
+                                                         sample_format), "set_modular_channels")
 
     def set_dequant_tables(self, tables):
         tabs = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]

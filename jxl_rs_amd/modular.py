@@ -94,6 +94,12 @@ class ModularChain:
         self.ctx.sync()
         return [d.download(np.int32, self.w * self.h).reshape(self.h, self.w) for d in self.d_out]
 
+    def feed_frame(self, sample_format=8):
+        """the chain's finished planes (run_chain, same context: the setter's copies are ordered behind it on the
+        context's stream) as the three colour channels of the context's Modular frame (ctx.modular_frame_begin with the
+        chain's w x h), device to device -- the path a decoder takes from the inverse transforms to the render list"""
+        self.ctx.set_modular_channels(*[d.ptr for d in self.d_out], sample_format, w=self.w, h=self.h, stride=self.w)
+
     def free(self):
         for d in self.d_base + self.d_out + [d for lvl in self.d_res for d in lvl if d is not None]:
             d.free()
