@@ -227,8 +227,8 @@ jxlh_status jxlh_set_upsampling_weights(jxlh_ctx* ctx, const float* weights2, co
  * channels are taken into the other set of planes) renders the whole frame instead.  jxlh_frame_rerender_groups
  * returns JXLH_ERR_UNSUPPORTED: a progressive Modular decode sets the changed rects and runs again.  The VarDCT-only calls
  * (jxlh_frame_set_lf*, jxlh_frame_set_hf_meta, jxlh_submit_group*, jxlh_frame_coeff_buffer, jxlh_frame_read_lf) return
- * JXLH_ERR_BAD_STATE with nothing launched.  Patches, splines, extra channels, read-outs, jxlh_frame_blend, jxlh_frame_save
- * and jxlh_frame_save_reference serve the frame as they serve a VarDCT one.  Not covered: LF frames (lf_level != 0). */
+ * JXLH_ERR_BAD_STATE with nothing launched.  Patches, splines, extra channels, read-outs, jxlh_frame_blend, jxlh_frame_save,
+ * jxlh_frame_save_reference and jxlh_frame_save_lf serve the frame as they serve a VarDCT one. */
 #define JXLH_MODULAR_XYB (1u << 16)
 jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                             const int32_t* c0, const int32_t* c1, const int32_t* c2, size_t stride,
@@ -833,6 +833,74 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
                             const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
                             uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
                             size_t bytes_per_row);
+
+/* ---------------------------------------------------------------- LF frames
+ * A frame with lf_level = L >= 1 (the layers of a progressive_dc file) is an ordinary frame of ceil(size / 8^L) pixels,
+ * usually Modular XYB, sometimes VarDCT (FrameHeader::size_upsampled, headers/frame_header.rs:584-589): begin, fill and
+ * run it like any other.  What sets it apart is where its result goes: the three colour planes ahead of the colour
+ * transform are kept in DecoderState::lf_frames[L - 1] (frame/mod.rs:120,136,399-401; the Grayscale f32 save stages of
+ * frame/render.rs:699-710), and a later VarDCT frame with USE_LF_FRAME takes lf_frames[its lf_level] as its LF image
+ * (frame/decode.rs:172-178,737-743) -- it decodes no LF of its own and skips adaptive LF smoothing
+ * (should_do_adaptive_lf_smoothing, frame_header.rs:496-500).  The context holds those JXLH_NUM_LF_FRAMES slots next to
+ * the reference slots: three f32 planes (X, Y, B) of w x h each, rows 256-byte aligned, surviving jxlh_frame_begin, freed
+ * by jxlh_ctx_clear_lf_frame and jxlh_ctx_destroy.  Slot mapping: an LF frame saves into slot lf_level - 1; the frame it
+ * feeds (whose own lf_level is one lower) reads slot = ITS lf_level -- the same number.
+ *   jxlh_ctx_set_lf_frame        slot <- caller planes (host or device, order X, Y, B as jxlh_frame_set_lf, row stride
+ *                                `stride` >= w floats): an LF frame decoded elsewhere.  Returns when the copy has landed.
+ *   jxlh_frame_save_lf           slot <- the current frame's finished colour result (what jxlh_frame_save_reference
+ *                                saves: after filters, patches, splines, upsampling and noise, before the colour
+ *                                transform), device to device on the context's stream.  VarDCT and Modular frames alike.
+ *                                Needs a whole-frame render: JXLH_ERR_BAD_STATE before one and after jxlh_frame_blend.
+ *   jxlh_ctx_clear_lf_frame      frees the slot (waits for the stream first).
+ *   jxlh_frame_set_lf_from_slot  the WHOLE LF image of the current VarDCT frame becomes a copy of the slot's planes
+ *                                (device to device, on the stream): overwriting or clearing the slot afterwards does
+ *                                not change the frame.  The frame then never runs adaptive LF smoothing, whatever
+ *                                params.do_lf_smoothing says, and jxlh_frame_read_lf returns the slot's samples.  A
+ *                                later jxlh_frame_set_lf / _set_lf_quantized on such a frame is JXLH_ERR_BAD_STATE, and
+ *                                so is this call after one of them in the same frame.  Everything downstream is
+ *                                unchanged: HF metadata, coefficient submissions, bands, jxlh_frame_rerender_groups,
+ *                                filters, post stages, save.
+ * Checked before anything is launched; a refused call changes nothing.  JXLH_ERR_INVALID_ARGUMENT: slot >=
+ * JXLH_NUM_LF_FRAMES; a null plane; stride < w; w or h zero or above 2^20; (set_lf_from_slot) an unset slot or one whose
+ * size differs from the frame's size in blocks.  JXLH_ERR_BAD_STATE: outside a frame; (set_lf_from_slot) a Modular frame.
+ * JXLH_ERR_UNSUPPORTED: a sharded context; (set_lf_from_slot) a chroma-subsampled frame, whose size in blocks rounds past
+ * the LF frame's size (the reference has no defined answer there).
+ *
+ * jxlh_lf_preview: while such a file is still arriving, the reference shows lf_frames[0] as a full-size preview
+ * (Frame::render_lf_frame_rect / maybe_preview_lf_frame, frame/lf_preview.rs:24-387): Upsample8x -> XybStage ->
+ * FromLinearStage -> integer / f16 conversion -> oriented interleaved save, rect by rect.  This call is that chain for one
+ * rect (x0, y0, w, h in LF pixels) of `slot`, one kernel, nothing in between written to memory; callable inside or outside
+ * a frame, ordered on the context's stream.  image_w x image_h is the image the preview stands for: the slot must be
+ * ceil(image_w / 8) x ceil(image_h / 8).  `out` is the origin of the WHOLE oriented image as for jxlh_frame_save (host or
+ * device memory; host memory goes through the staging buffer); _async omits the final wait.  Per output pixel:
+ *   1. Upsample8x of the slot's three planes with the weights of jxlh_set_upsampling_weights, bit for bit the stage of
+ *      jxlh_stage_upsample; the 5x5 window is mirrored against the whole SLOT, not the rect (lf_preview.rs:127-140).  LF
+ *      pixel (x, y) yields image pixels [8x, 8x + 8) x [8y, 8y + 8), clipped to the image (:364);
+ *   2. the colour stage `colour` names: JXLH_COLOR_XYB with a non-linear transfer function, as jxlh_frame_save step 1;
+ *   3. conversion as jxlh_frame_save step 4, with the pipeline position the reference's preview has: every converter is
+ *      built for channel 0 and every row handed over at (0, 0) (:60,67,72,208-214).  JXLH_SAVE_U8 therefore dithers all
+ *      three channels and all rows with dither[0][(X - 8 * x0) % 32], X the image column -- no channel term, no row term,
+ *      and a phase that depends on the rect's left edge.  JXLH_SAVE_F16 is never clamped (f16_clamp* are ignored: a caller
+ *      may pass the frame's own descriptor).  U16, F32 and the byte order as there;
+ *   4. save->channels is {0, 1, 2} or {2, 1, 0} with n_channels == 3; fill_opaque_alpha appends the opaque sample (:56-83);
+ *   5. position: display_pixel of save->orientation against image_w x image_h, as jxlh_frame_save step 6.
+ * Checked before anything is launched or written.  JXLH_ERR_INVALID_ARGUMENT: a null ctx, save or out; slot >=
+ * JXLH_NUM_LF_FRAMES or unset; a slot whose size is not ceil(image / 8); a rect that leaves the slot; any other channel
+ * list; premultiply or n_spot non-zero; format, orientation, bit depth, bytes_per_row and alignment as jxlh_frame_save.
+ * JXLH_ERR_UNSUPPORTED: colour NULL, not XYB or JXLH_TF_LINEAR (where the reference shows no preview); a sharded context;
+ * image_w * image_h >= 2^31.  A zero-sized rect is JXLH_OK and writes nothing. */
+#define JXLH_NUM_LF_FRAMES 4
+jxlh_status jxlh_ctx_set_lf_frame(jxlh_ctx* ctx, uint32_t slot, uint32_t w, uint32_t h, const float* x, const float* y,
+                                  const float* b, size_t stride);
+jxlh_status jxlh_frame_save_lf(jxlh_ctx* ctx, uint32_t slot);
+jxlh_status jxlh_ctx_clear_lf_frame(jxlh_ctx* ctx, uint32_t slot);
+jxlh_status jxlh_frame_set_lf_from_slot(jxlh_ctx* ctx, uint32_t slot);
+jxlh_status jxlh_lf_preview(jxlh_ctx* ctx, uint32_t slot, uint32_t image_w, uint32_t image_h, uint32_t x0, uint32_t y0,
+                            uint32_t w, uint32_t h, const jxlh_output_desc* colour, const jxlh_save_desc* save, void* out,
+                            size_t bytes_per_row);
+jxlh_status jxlh_lf_preview_async(jxlh_ctx* ctx, uint32_t slot, uint32_t image_w, uint32_t image_h, uint32_t x0,
+                                  uint32_t y0, uint32_t w, uint32_t h, const jxlh_output_desc* colour,
+                                  const jxlh_save_desc* save, void* out, size_t bytes_per_row);
 
 /* ---------------------------------------------------------------- stage-level hooks */
 /* Whole-image single stages with the pipeline's mirror edge semantics; the analogue of

@@ -57,6 +57,18 @@ class Context {
     check(jxlh_ctx_set_reference(c_, slot, (uint32_t)planes.size(), w, h, planes.data(), stride), "jxlh_ctx_set_reference");
   }
   void clear_reference(uint32_t slot) { check(jxlh_ctx_clear_reference(c_, slot), "jxlh_ctx_clear_reference"); }
+  // LF slots (DecoderState::lf_frames): an LF frame's X, Y, B planes from the caller / from the rendered frame; a VarDCT
+  // frame's LF image from a slot (slot = that frame's lf_level); the full-size preview of one rect of a slot
+  void set_lf_frame(uint32_t slot, uint32_t w, uint32_t h, const float* x, const float* y, const float* b, size_t stride) {
+    check(jxlh_ctx_set_lf_frame(c_, slot, w, h, x, y, b, stride), "jxlh_ctx_set_lf_frame");
+  }
+  void save_lf(uint32_t slot) { check(jxlh_frame_save_lf(c_, slot), "jxlh_frame_save_lf"); }
+  void clear_lf_frame(uint32_t slot) { check(jxlh_ctx_clear_lf_frame(c_, slot), "jxlh_ctx_clear_lf_frame"); }
+  void set_lf_from_slot(uint32_t slot) { check(jxlh_frame_set_lf_from_slot(c_, slot), "jxlh_frame_set_lf_from_slot"); }
+  void lf_preview(uint32_t slot, uint32_t image_w, uint32_t image_h, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                  const jxlh_output_desc& colour, const jxlh_save_desc& save, void* out, size_t bytes_per_row) {
+    check(jxlh_lf_preview(c_, slot, image_w, image_h, x0, y0, w, h, &colour, &save, out, bytes_per_row), "jxlh_lf_preview");
+  }
   // the current frame's patch dictionary on caller planes (3 + num_ec), in place
   void stage_patches(const std::vector<float*>& planes, uint32_t w, uint32_t h, size_t stride) {
     check(jxlh_stage_patches(c_, planes.data(), (uint32_t)planes.size(), w, h, stride), "jxlh_stage_patches");
@@ -161,6 +173,8 @@ class VarDctFrame {
   }
   // the save_before_ct save stage: the rendered frame becomes reference frame `slot`
   void save_reference(uint32_t slot) { ctx_.check(jxlh_frame_save_reference(ctx_.raw(), slot), "jxlh_frame_save_reference"); }
+  // an LF frame's result into LF slot lf_level - 1 (frame/mod.rs:399-401)
+  void save_lf(uint32_t slot) { ctx_.check(jxlh_frame_save_lf(ctx_.raw(), slot), "jxlh_frame_save_lf"); }
   // the colour stage (null: none), BlendingStage and ExtendToImageDimensionsStage (frame/render.rs:754-771): the rendered
   // frame composed onto the image from the reference slots; the image becomes what the read calls and save_reference see
   void blend(const jxlh_blend_desc& desc, const jxlh_output_desc* colour = nullptr) {

@@ -936,6 +936,9 @@ class GpuFramePipeline {
     frame_.save(&lp_.output, save_desc(buffer_index), out, bytes_per_row, y0, y1);
   }
   void save_planes(float* c0, float* c1, float* c2) { frame_.read_planes(c0, c1, c2); }
+  // an LF frame's result (lf_level = L) into LF slot L - 1, where the reference's list has its three Grayscale f32 save
+  // stages (frame/render.rs:699-710); those stages are not lowered
+  void save_lf(uint32_t slot) { frame_.save_lf(slot); }
   // An extra channel's integer samples as the Modular decoder leaves them (w x h at the channel's own resolution, host
   // or device memory).  The stage list decides what happens to them: ConvertModularToF32Stage with the channel's bit
   // depth, then its Upsample stage if it has one; both run inside do_render() behind the colour channels' stages.

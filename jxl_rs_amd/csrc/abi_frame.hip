@@ -226,6 +226,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   splines_release(ctx);
   blend_release(ctx);
   save_release(ctx);
+  lf_frames_release(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -477,6 +478,7 @@ namespace jxlh_host {
 // the per-frame state every jxlh_frame_begin starts from
 void reset_frame_state(jxlh_ctx* ctx) {
   ctx->lf_smoothed = false;
+  ctx->lf_from_slot = ctx->lf_from_caller = false;
   ctx->rendered = false;
   ctx->has_special = ctx->has_large = false;
   ctx->strip_all_closed = true;
@@ -553,9 +555,10 @@ jxlh_status jxlh_frame_set_lf_quantized(jxlh_ctx* ctx, uint32_t x0, uint32_t y0,
                                         uint32_t extra_precision) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !qy || !qx || !qb || stride < w || extra_precision > 3) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular || ctx->lf_from_slot) return JXLH_ERR_BAD_STATE;
   if (!rect_ok(ctx, x0, y0, w, h)) return JXLH_ERR_INVALID_ARGUMENT;
   if (w == 0 || h == 0) return JXLH_OK;
+  ctx->lf_from_caller = true;
   const size_t n = (size_t)w * h;
   jxlh_status st = ensure(ctx, ctx->lfq, 3 * n);
   if (st != JXLH_OK) return st;
@@ -598,8 +601,10 @@ jxlh_status jxlh_frame_set_lf(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t 
                               const float* y, const float* b, size_t stride) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !x || !y || !b || stride < w) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || ctx->modular) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular || ctx->lf_from_slot) return JXLH_ERR_BAD_STATE;
   if (!rect_ok(ctx, x0, y0, w, h)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (w == 0 || h == 0) return JXLH_OK;  // nothing written: the frame may still take a slot
+  ctx->lf_from_caller = true;
   const float* src[3] = {x, y, b};
   const size_t off = (size_t)y0 * ctx->fd.xblocks + x0;
   for (int c = 0; c < 3; c++) {
@@ -850,7 +855,8 @@ jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan) {
   }
   if (jxlh_status st = apply_coeff_epoch(ctx, plan->want_strip, &plan->sparse_k1)) return st;
   // ---- K0b: Frame::finalize_lf (frame/mod.rs:360-378)
-  const bool smooth = p.do_lf_smoothing && f.xblocks > 2 && f.yblocks > 2;  // adaptive_lf_smoothing.rs:51-53
+  // (adaptive_lf_smoothing.rs:51-53; an LF image taken from an LF frame is used as it is, frame_header.rs:496-500)
+  const bool smooth = p.do_lf_smoothing && !ctx->lf_from_slot && f.xblocks > 2 && f.yblocks > 2;
   if (smooth) {
     {  // out of place (raw -> smoothed), so re-running a frame repeats the full work
       const float inv_quant_lf = f.inv_global_scale / (float)p.quant_lf;  // quantizer.rs:82-84

@@ -16,8 +16,10 @@ int sample_bytes(uint32_t format) { return format == JXLH_SAVE_U8 ? 1 : format =
 uint32_t samples_per_pixel(const jxlh_save_desc* d) { return d->n_channels + (d->fill_opaque_alpha ? 1 : 0); }
 bool is_extra(uint32_t ch, uint32_t n_planes) { return ch >= 3 && ch < n_planes; }
 
+}  // namespace
+
 // the descriptor's own checks; n_planes: pipeline channels that exist (3 + JXLH_MAX_EXTRA_CHANNELS for a frame)
-jxlh_status check_desc(const jxlh_save_desc* d, uint32_t n_planes) {
+jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes) {
   if (!d || d->n_channels == 0 || d->n_channels > 4 || samples_per_pixel(d) > 4) return JXLH_ERR_INVALID_ARGUMENT;
   for (uint32_t k = 0; k < d->n_channels; k++)
     if (d->channels[k] >= n_planes) return JXLH_ERR_INVALID_ARGUMENT;
@@ -33,7 +35,7 @@ jxlh_status check_desc(const jxlh_save_desc* d, uint32_t n_planes) {
 }
 
 // `out` and its pitch against the oriented image of a w x h source
-jxlh_status check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row) {
+jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row) {
   const size_t bps = (size_t)sample_bytes(d->format);
   const size_t row = (size_t)(d->orientation >= 5 ? h : w) * samples_per_pixel(d) * bps;
   if (!out || bytes_per_row < row || bytes_per_row % bps != 0 || reinterpret_cast<uintptr_t>(out) % bps != 0)
@@ -41,7 +43,7 @@ jxlh_status check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const voi
   return JXLH_OK;
 }
 
-jxlh_status colour_mode(const jxlh_output_desc* colour, SaveLaunch& a) {
+jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a) {
   a.mode = kModeNone;
   if (!colour) return JXLH_OK;
   switch (colour->color) {
@@ -63,6 +65,8 @@ jxlh_status colour_mode(const jxlh_output_desc* colour, SaveLaunch& a) {
   for (int i = 0; i < 3; i++) a.tf.lum[i] = colour->hlg_luminance_rgb[i];
   return JXLH_OK;
 }
+
+namespace {
 
 // everything of the launch the (checked) descriptor decides; plane(ch) / stride(ch) resolve a pipeline channel
 template <class PlaneOf, class StrideOf>
@@ -164,15 +168,15 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
                        void* out, size_t bytes_per_row, bool wait) {
   if (!ctx || !d || !out) return JXLH_ERR_INVALID_ARGUMENT;
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
-  if (jxlh_status st = check_desc(d, 3 + JXLH_MAX_EXTRA_CHANNELS)) return st;
+  if (jxlh_status st = save_check_desc(d, 3 + JXLH_MAX_EXTRA_CHANNELS)) return st;
   SaveLaunch a{};
-  if (jxlh_status st = colour_mode(colour, a)) return st;
+  if (jxlh_status st = save_colour_mode(colour, a)) return st;
   if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
   if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
   if (y1 > h) y1 = h;
   if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
-  if (jxlh_status st = check_out(d, w, h, out, bytes_per_row)) return st;
+  if (jxlh_status st = save_check_out(d, w, h, out, bytes_per_row)) return st;
   if ((uint64_t)w * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
   // the extra channels the save reads, as jxlh_frame_read_extra_channel resolves them
   const float* ec_plane[JXLH_MAX_EXTRA_CHANNELS] = {};
@@ -255,12 +259,12 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
   if (n_planes < 3 || n_planes > 3 + JXLH_MAX_EXTRA_CHANNELS) return JXLH_ERR_INVALID_ARGUMENT;
   for (uint32_t c = 0; c < n_planes; c++)
     if (!planes[c]) return JXLH_ERR_INVALID_ARGUMENT;
-  if (jxlh_status st = check_desc(d, n_planes)) return st;
+  if (jxlh_status st = save_check_desc(d, n_planes)) return st;
   SaveLaunch a{};
-  if (jxlh_status st = colour_mode(colour, a)) return st;
+  if (jxlh_status st = save_colour_mode(colour, a)) return st;
   if (y1 > h) y1 = h;
   if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
-  if (jxlh_status st = check_out(d, w, h, out, bytes_per_row)) return st;
+  if (jxlh_status st = save_check_out(d, w, h, out, bytes_per_row)) return st;
   if ((uint64_t)w * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
   // host planes are staged whole, rows 16-byte aligned; device planes are read where they are
   const size_t sstride = round_up(w, 4), splane = sstride * h;

@@ -172,6 +172,17 @@ struct jxlh_ctx {
     DevBuf<float> buf;
   };
   RefSlot refs[JXLH_MAX_REFERENCE_FRAMES];
+  // LF frames (DecoderState::lf_frames, abi_lf_frame.hip): the X, Y, B planes of w x h at `stride` (rows 256-byte
+  // aligned), channel c at c * stride * h.  lf_from_slot: this frame's LF image is a copy of a slot (no K0b, no
+  // jxlh_frame_set_lf*); lf_from_caller: a jxlh_frame_set_lf* call has written into it
+  struct LfSlot {
+    bool set = false;
+    uint32_t w = 0, h = 0;
+    size_t stride = 0;
+    DevBuf<float> buf;
+  };
+  LfSlot lf_slots[JXLH_NUM_LF_FRAMES];
+  bool lf_from_slot = false, lf_from_caller = false;
   // the frame's patch dictionary (jxlh_frame_set_patches), binned into 64 x 4 tiles: words = tile ids | starts | patch
   // indices; row_first[r] = first listed tile of tile row r
   struct PatchBins {
@@ -367,6 +378,12 @@ inline bool draws_in_place(const jxlh_ctx* ctx) { return ctx->patch_n > 0 || ctx
 inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
 void blend_release(jxlh_ctx* ctx);
 void save_release(jxlh_ctx* ctx);  // abi_save.hip
+// ... and its argument checks, shared with jxlh_lf_preview: the descriptor's own (n_planes: pipeline channels that
+// exist), `out` and its pitch against the oriented image of a w x h source, the colour stage named by `colour`
+jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes);
+jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row);
+jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a);
+void lf_frames_release(jxlh_ctx* ctx);  // abi_lf_frame.hip
 bool strip_eligible(const jxlh_ctx* ctx);
 jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan);
 // Where run_stages leaves the finished planes (1 = f.tmp, 0 = f.planes): a property of the frame's stage list, so a

@@ -509,6 +509,7 @@ struct SaveLaunch {
   float maxv;                       // 2^depth - 1 (U8 / U16)
   uint32_t fill_bits;               // the opaque sample in the sample's format and byte order
   int big_endian;
+  static constexpr bool kF16Clamp = true;  // convert_sample reads the three fields below
   int clamp;                        // F16: clamp to [clamp_min, clamp_max] first
   float clamp_min, clamp_max;
   int transpose, flip_x, flip_y;    // output (ox, oy) = transpose ? (y, x) : (x, y), then flipped per axis
@@ -516,5 +517,30 @@ struct SaveLaunch {
   size_t out_stride;                // bytes
 };
 void launch_save(hipStream_t s, const SaveLaunch& a);
+
+// the LF-frame preview (k_lf_preview.hip): Upsample8x of a rect of an LF slot, the colour stage, the conversion at
+// pipeline position (channel 0, row 0) and the oriented interleaved store, one pass.  The kernel indexes the structure
+// with constants only, like SaveLaunch.
+struct LfPreviewLaunch {
+  const float* plane[3];          // the slot's X, Y, B planes, sw x sh at `stride` floats
+  uint32_t stride;
+  int sw, sh;
+  int x0, y0, w, h;               // the rect, in LF pixels (inside the slot)
+  int iw, ih;                     // the image: LF pixel (x, y) yields image pixels [8x, 8x + 8) x [8y, 8y + 8), clipped
+  const float* kernels;           // 8 * 8 * 25 expanded taps (launch_upsample)
+  int mode;                       // kTfSrgb .. kTfGamma behind XybStage
+  XybParamsDev xyb;
+  TfParamsDev tf;
+  int format, spp;                // kSave*, 3 or 4 samples per pixel (the 4th is the opaque fill)
+  int bgr;                        // samples 0..2 are channels 2, 1, 0
+  float maxv;
+  uint32_t fill_bits;
+  int big_endian;
+  static constexpr bool kF16Clamp = false;  // ConvertF32ToF16Stage::new(0): convert_sample compiles no clamp
+  int transpose, flip_x, flip_y;  // as SaveLaunch, against iw x ih
+  uint8_t* out;                   // origin of the whole oriented image
+  size_t out_stride;              // bytes
+};
+void launch_lf_preview(hipStream_t s, const LfPreviewLaunch& a);
 
 }  // namespace jxlh

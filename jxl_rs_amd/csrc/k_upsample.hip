@@ -11,14 +11,10 @@
 // per input pixel (25 per output pixel) put it near the f32 vector roof instead -- still no MFMA shape:
 // the 25-tap kernels differ per output phase and the data is a sliding window.
 #include "jxlh_internal.h"
+#include "upsample_device.h"
 
 namespace jxlh {
 namespace {
-
-__device__ __forceinline__ int mirror_idx(int v, int s) {
-  while (v < 0 || v >= s) v = v < 0 ? -v - 1 : 2 * s - v - 1;
-  return v;
-}
 
 // R consecutive input rows per thread: the 5x5 window slides down, so a row costs 5 loads instead of 25
 template <int N, int R>
@@ -31,49 +27,19 @@ __global__ __launch_bounds__(256) void k_upsample(const float* __restrict__ in, 
   if (x >= w || y0 >= h) return;
   float win[25];
   int xs[5];
-#pragma unroll
-  for (int k = 0; k < 5; k++) xs[k] = mirror_idx(x - 2 + k, w);
-#pragma unroll
-  for (int ky = 0; ky < 4; ky++) {  // rows y0-2 .. y0+1 sit in window rows 1..4; the loop shifts before loading
-    const float* __restrict__ row = in + (size_t)mirror_idx(y0 - 2 + ky, h) * in_stride;
-#pragma unroll
-    for (int kx = 0; kx < 5; kx++) win[(ky + 1) * 5 + kx] = row[xs[kx]];
-  }
+  ups_columns(x, w, xs);
+  ups_window_prime(in, in_stride, h, y0, xs, win);
 #pragma unroll 1
   for (int r = 0; r < R; r++) {
     const int y = y0 + r;
     if (y >= h) break;
-#pragma unroll
-    for (int t = 0; t < 20; t++) win[t] = win[t + 5];
-    {
-      const float* __restrict__ row = in + (size_t)mirror_idx(y + 2, h) * in_stride;
-#pragma unroll
-      for (int kx = 0; kx < 5; kx++) win[20 + kx] = row[xs[kx]];
-    }
-    float mn = win[0], mx = win[0];
-#pragma unroll
-    for (int t = 1; t < 25; t++) {
-      mn = win[t] < mn ? win[t] : mn;
-      mx = win[t] > mx ? win[t] : mx;
-    }
+    ups_window_advance(in, in_stride, h, y, xs, win);
+    float mn, mx;
+    ups_minmax(win, mn, mx);
 #pragma unroll
     for (int oy = 0; oy < N; oy++) {
       float v[N];
-#pragma unroll
-      for (int ox = 0; ox < N; ox++) {
-        const float* __restrict__ k = kernels + (oy * N + ox) * 25;
-        float a0 = win[0] * k[0], a1 = win[1] * k[1], a2 = win[2] * k[2];
-#pragma unroll
-        for (int t = 3; t < 25; t += 3) {
-          a0 = __builtin_fmaf(win[t], k[t], a0);
-          if (t + 1 < 25) a1 = __builtin_fmaf(win[t + 1], k[t + 1], a1);
-          if (t + 2 < 25) a2 = __builtin_fmaf(win[t + 2], k[t + 2], a2);
-        }
-        float q = (a0 + a1) + a2;
-        q = q > mn ? q : mn;
-        q = q < mx ? q : mx;
-        v[ox] = q;
-      }
+      ups_patch_row<N>(win, mn, mx, kernels, oy, v);
       const int oyy = y * N + oy;
       if (oyy >= out_h) continue;
       float* __restrict__ dst = out + (size_t)oyy * out_stride + (size_t)x * N;

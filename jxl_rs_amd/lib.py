@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("JXLH_LIBRARY") or os.path.join(_HERE, "libjxl_hip.so"
 NUM_TRANSFORMS = 27
 NUM_QUANT_TABLES = 17
 GROUP_DIM = 256
+NUM_LF_FRAMES = 4
 
 OK = 0
 ERR_INVALID_ARGUMENT = -1
@@ -66,6 +67,8 @@ ABI_SYMBOLS = [
     "jxlh_frame_save", "jxlh_frame_save_async", "jxlh_stage_save",
     "jxlh_frame_set_splines", "jxlh_stage_splines", "jxlh_splines_build_segments",
     "jxlh_frame_set_modular_channels",
+    "jxlh_ctx_set_lf_frame", "jxlh_frame_save_lf", "jxlh_ctx_clear_lf_frame", "jxlh_frame_set_lf_from_slot",
+    "jxlh_lf_preview", "jxlh_lf_preview_async",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
@@ -376,6 +379,13 @@ def load():
         L.jxlh_frame_save_async.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), u32, u32, vp, sz]
         L.jxlh_stage_save.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), C.POINTER(vp), u32, u32, u32, sz,
                                       u32, u32, u32, u32, vp, sz]
+    if hasattr(L, "jxlh_lf_preview"):
+        L.jxlh_ctx_set_lf_frame.argtypes = [vp, u32, u32, u32, vp, vp, vp, sz]
+        L.jxlh_frame_save_lf.argtypes = [vp, u32]
+        L.jxlh_ctx_clear_lf_frame.argtypes = [vp, u32]
+        L.jxlh_frame_set_lf_from_slot.argtypes = [vp, u32]
+        for fn in (L.jxlh_lf_preview, L.jxlh_lf_preview_async):
+            fn.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, C.POINTER(OutputDesc), C.POINTER(SaveDesc), vp, sz]
     if hasattr(L, "jxlh_frame_set_splines"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
         L.jxlh_frame_set_splines.argtypes = [vp, vp, u32]
         L.jxlh_stage_splines.argtypes = [vp, C.POINTER(vp), u32, u32, sz]
@@ -1176,6 +1186,58 @@ class Context:
                    size=None, stride=None):
         st, out = self.try_stage_save(desc, planes, colour, origin, y0, y1, out, bytes_per_row, size, stride)
         self._chk(st, "stage_save")
+        return out
+
+    # ---- LF frames ----
+    def try_set_lf_frame(self, slot, x, y, b, w=None, h=None, stride=None):
+        """jxlh_ctx_set_lf_frame, returning the status.  x, y, b: host arrays (2-D, rows contiguous, any row pitch), or
+        DeviceArrays / raw device pointers with w, h and stride (floats)"""
+        (x, y, b), w, h, stride = _rect_planes((x, y, b), np.float32, w, h, stride)
+        return self.L.jxlh_ctx_set_lf_frame(self._ctx, int(slot), w, h, _addr(x), _addr(y), _addr(b), stride)
+
+    def set_lf_frame(self, slot, x, y, b, w=None, h=None, stride=None):
+        """LF slot `slot` <- the X, Y, B planes of an LF frame decoded elsewhere"""
+        self._chk(self.try_set_lf_frame(slot, x, y, b, w, h, stride), "ctx_set_lf_frame")
+
+    def try_save_lf(self, slot):
+        return self.L.jxlh_frame_save_lf(self._ctx, int(slot))
+
+    def save_lf(self, slot):
+        """jxlh_frame_save_lf: LF slot `slot` (= the frame's lf_level - 1) <- the rendered frame's colour planes"""
+        self._chk(self.try_save_lf(slot), "frame_save_lf")
+
+    def clear_lf_frame(self, slot):
+        self._chk(self.L.jxlh_ctx_clear_lf_frame(self._ctx, int(slot)), "ctx_clear_lf_frame")
+
+    def try_set_lf_from_slot(self, slot):
+        return self.L.jxlh_frame_set_lf_from_slot(self._ctx, int(slot))
+
+    def set_lf_from_slot(self, slot):
+        """jxlh_frame_set_lf_from_slot: the current VarDCT frame's LF image <- a copy of LF slot `slot` (= the frame's
+        lf_level); the frame then runs no adaptive LF smoothing"""
+        self._chk(self.try_set_lf_from_slot(slot), "frame_set_lf_from_slot")
+
+    def try_lf_preview(self, slot, image_w, image_h, desc, colour, rect=None, out=None, bytes_per_row=None, wait=True):
+        """jxlh_lf_preview (_async when not `wait`), returning (status, out).  rect: (x0, y0, w, h) in LF pixels, the
+        whole slot by default; out: None (a zeroed array of the oriented image's samples is made), a numpy array, or a
+        device pointer / DeviceArray with bytes_per_row given"""
+        if rect is None:
+            rect = (0, 0, (image_w + 7) // 8, (image_h + 7) // 8)
+        if out is None:
+            out = np.zeros(self.save_shape(desc, image_w, image_h), dtype=self._save_dtype(desc))
+        if bytes_per_row is None:
+            bytes_per_row = out.strides[0]
+        fn = self.L.jxlh_lf_preview if wait else self.L.jxlh_lf_preview_async
+        st = fn(self._ctx, int(slot), int(image_w), int(image_h), *[int(v) for v in rect],
+                None if colour is None else C.byref(colour), None if desc is None else C.byref(desc), _addr(out),
+                int(bytes_per_row))
+        return st, out
+
+    def lf_preview(self, slot, image_w, image_h, desc, colour, rect=None, out=None, bytes_per_row=None, wait=True):
+        """the full-size preview of LF slot `slot`: Upsample8x, colour stage, conversion and oriented interleaved save
+        of one rect in one pass"""
+        st, out = self.try_lf_preview(slot, image_w, image_h, desc, colour, rect, out, bytes_per_row, wait)
+        self._chk(st, "lf_preview")
         return out
 
     def tune_placement(self, trials=0):
