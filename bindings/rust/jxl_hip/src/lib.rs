@@ -370,6 +370,11 @@ impl<'a> VarDctFrame<'a> {
         self.out_size.set(self.frame_out); // a render discards a composition
         self.ctx.ok(unsafe { sys::jxlh_frame_rerender_groups(self.ctx.raw, groups.as_ptr(), groups.len() as u32) })
     }
+    /// `upsample_lf_group` (frame/decode.rs:51-158, taken at :744-752): `group` has no HF yet -- the next render fills it
+    /// from the LF image upsampled 8x instead of transforming it; a later submission of the group clears the mark
+    pub fn upsample_lf_group(&self, group: u32) -> Result<()> {
+        self.ctx.ok(unsafe { sys::jxlh_frame_set_groups_lf_only(self.ctx.raw, &group, 1) })
+    }
     /// the save stage for planar f32 XYB output; `out[c]` = `RawImageBuffer` of channel c
     ///
     /// # Safety

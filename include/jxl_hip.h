@@ -443,6 +443,46 @@ jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_ro
  * lists that overwrite the transforms' output (epf_iters == 3, per-stage kernels with an even stage count) and
  * chroma-subsampled frames re-render the whole frame instead; upsampled frames return JXLH_ERR_UNSUPPORTED. */
 jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids, uint32_t count);
+/* GROUPS WITHOUT HF.  The groups listed have no HF yet (DataStatus::Zero, frame/decode.rs:744-752): the next jxlh_frame_run /
+ * jxlh_frame_rerender_groups fills their pixels from the frame's LF image, upsampled 8x with weights8, instead of
+ * transforming them; every later stage treats them like any other group.  This is upsample_lf_group of the reference
+ * (frame/decode.rs:51-158), the first paint of a file that is still arriving: mark every group, run, paint; then, as
+ * groups arrive, submit them and call jxlh_frame_rerender_groups on them.
+ *
+ * Pixels: ahead of the filters a marked group's pixels equal, bit for bit, the group's rect of Upsample8x (three
+ * accumulators, the reference's tap order, clamped to the 5x5 window's range) applied to the WHOLE LF image -- the
+ * smoothed one, the raw one, or the LF slot's, whichever the frame uses -- with the window mirrored at the image's edges
+ * only.  The kernels are the ones jxlh_set_upsampling_weights installed (its weights8), else the defaults; the frame's
+ * own upsampling factor and the extra channels' keep their kernels.
+ *   That is what the reference computes for every group except in two geometries, in which it reads its scratch row
+ * beyond what it filled for that row (stale values of the previous row or channel, or zeros); the device does not
+ * reproduce them, it mirrors properly:
+ *   (a) a frame one group wide (xsize <= 256): the right padding is read from
+ *       storage[save_start + mirror(save_end, save_end)], an index that is off by save_start = 2 (decode.rs:114-118);
+ *   (b) xblocks % 32 == 1 (264 or 520 pixels wide, say): in the group column left of the one-block-wide last column,
+ *       end_x = lf_x1 + 1 is neither lf_x1 nor two columns further, and the second padding column is never written.
+ *
+ * State: the marks are state of the frame.  jxlh_frame_begin clears them; they persist across runs.  Any later
+ * submission of a group, in any form, with or without JXLH_GROUP_COMPLETE or JXLH_GROUP_ACCUMULATE, clears that group's
+ * mark (the moment channel_status leaves Zero).  Marking a group after it was submitted in the same epoch marks it: the
+ * last call wins; its coefficients stay where they are and are not read.
+ *
+ * Runs: a marked group's coefficient store is never read (on a long-lived context it holds an earlier frame's data).
+ * K1 runs on the unmarked groups of the band only, the fill writes the marked ones into the planes K1 writes, whole
+ * blocks up to xblocks * 8 x yblocks * 8, in the layout of that run.  A run over a group-row range fills the marked
+ * groups of the band and of its halo group rows, like K1.  jxlh_frame_rerender_groups fills a listed group that is
+ * marked and transforms one that is not; the filter bands are unchanged.  A frame with at least one marked group does
+ * not take the strip kernel (JXLH_FRAME_STRIP): it falls to the two-kernel path with the same pixels, and
+ * jxlh_frame_path says so.  A frame with no marked group enqueues exactly what it did without this call.
+ *
+ * Status, checked in this order, the marks unchanged by a refused call:
+ *   JXLH_ERR_BAD_STATE         no frame begun, or a Modular frame (like the other VarDCT-only calls)
+ *   JXLH_ERR_UNSUPPORTED       a chroma-subsampled frame (the reference's own code sizes the LF rect of such a frame
+ *                              with hshift where it means vshift, decode.rs:88-89: there is nothing sound to match);
+ *                              a context with comm_nranks > 1 (a rank holds only its band)
+ *   JXLH_ERR_INVALID_ARGUMENT  an id >= the frame's number of groups (none of the call's ids is marked then)
+ *   JXLH_OK                    count == 0 (nothing changes) */
+jxlh_status jxlh_frame_set_groups_lf_only(jxlh_ctx* ctx, const uint32_t* group_ids, uint32_t count);
 /* blocks until the main stream is idle */
 jxlh_status jxlh_ctx_sync(jxlh_ctx* ctx);
 /* PLACEMENT OF A CONTEXT'S BUFFERS (round 6; profiles/r06_q_context_placement.txt).  Where the driver places a context's

@@ -130,6 +130,11 @@ class VarDctFrame {
                "jxlh_submit_group_sparse");
   }
   void slot_wait(int slot = 0) { ctx_.check(jxlh_slot_wait(ctx_.raw(), slot), "jxlh_slot_wait"); }
+  // upsample_lf_group (frame/decode.rs:51-158) for the groups listed: they have no HF yet, and the next render fills them
+  // from the LF image upsampled 8x instead of transforming them; a group's later decode_vardct_group* clears its mark
+  void upsample_lf_groups(const uint32_t* groups, uint32_t n) {
+    ctx_.check(jxlh_frame_set_groups_lf_only(ctx_.raw(), groups, n), "jxlh_frame_set_groups_lf_only");
+  }
   // a frame begun with JXLH_FRAME_MODULAR takes samples instead of LF, HF metadata and coefficients: one rect of the
   // three colour channels as the inverse transforms left them (jxlh_frame_set_modular_channels)
   void set_modular_channels(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const int32_t* const planes[3], size_t stride,

@@ -984,6 +984,13 @@ class GpuRenderPipeline : public GpuFramePipeline {
   }
   // render/mod.rs:146
   void mark_group_to_rerender(uint32_t g) { rerender_.push_back(g); }
+  // A group that must be rendered while its HF has not arrived (force_render with DataStatus::Zero, frame/decode.rs:
+  // 744-752): the reference hands the pipeline the LF image upsampled 8x as the group's buffers; here the group is marked
+  // and the next do_render() fills it on the device.  set_buffer_for_group on the group later clears the mark.
+  void set_lf_only_group(uint32_t group_id) {
+    frame_.upsample_lf_groups(&group_id, 1);
+    if (!dirty_first_) rerender_.push_back(group_id);
+  }
   // what the reference does when the last group of a pass has been handed over (frame/decode.rs:547-558, :703-711)
   void do_render() {
     for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");

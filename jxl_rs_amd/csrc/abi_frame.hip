@@ -380,7 +380,9 @@ jxlh_status jxlh_frame_begin(jxlh_ctx* ctx, const jxlh_frame_params* p) {
   {
     std::lock_guard<std::mutex> lock(ctx->sp_mutex);
     ctx->epoch.reset(ctx->ngroups);
+    ctx->epoch.clear_lf_only();  // jxlh_frame_set_groups_lf_only: per-frame state
   }
+  ctx->lf_only_run.clear();
   ctx->modular = modular;
   if (modular) return modular_frame_begin(ctx);  // no coefficient buffer, LF planes, HF-meta maps or work list
   const size_t nblocks = (size_t)f.xblocks * f.yblocks;
@@ -921,20 +923,35 @@ jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan, int gr0, int gr1) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
   const bool sparse_k1 = plan.sparse_k1;
+  // Groups without HF (jxlh_frame_set_groups_lf_only; never a sub-sampled frame): K1 runs on the band's other groups
+  // through its group list, the fill writes the marked ones into the same planes.  Their coefficient store is not read.
+  const bool lf_only = !ctx->lf_only_run.empty();
+  int n_k1 = 0, n_fill = 0;
+  if (lf_only) {
+    std::vector<int> band;
+    for (int g = gr0 * f.xgroups; g < gr1 * f.xgroups; g++) band.push_back(g);
+    if (jxlh_status st = lf_split_groups(ctx, band, &n_k1, &n_fill)) return st;
+  }
   {
     ScopedKernelTimer t(ctx, "k1_vardct");
     set_sparse_view(ctx, f, sparse_k1);
     // (a whole-frame run rewrites every group's flag in k1_scan: no clearing launch then)
-    if (sparse_k1 && !(gr0 == 0 && gr1 == f.ygroups))
+    if (sparse_k1 && (lf_only || !(gr0 == 0 && gr1 == f.ygroups)))
       HIPCHK(ctx, hipMemsetAsync(ctx->group_dense.p, 0, ctx->ngroups, ctx->stream));
     // a sub-sampled channel is reconstructed at its own resolution into tmp[c] ...
     FrameDev fk = f;
     for (int c = 0; c < 3; c++)
       if (f.hshift[c] | f.vshift[c]) fk.planes[c] = f.tmp[c];
-    launch_vardct_groups(ctx->stream, fk, gr0, gr1, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
-                         sparse_k1 ? ctx->coeffs.p : nullptr, nullptr, 0, ctx->has_special, ctx->has_large,
-                         dense_route_groups(ctx, sparse_k1));
+    if (lf_only)
+      launch_vardct_groups(ctx->stream, fk, 0, 0, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
+                           sparse_k1 ? ctx->coeffs.p : nullptr, ctx->rerender_list.p, n_k1, ctx->has_special,
+                           ctx->has_large, dense_route_groups(ctx, sparse_k1));
+    else
+      launch_vardct_groups(ctx->stream, fk, gr0, gr1, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
+                           sparse_k1 ? ctx->coeffs.p : nullptr, nullptr, 0, ctx->has_special, ctx->has_large,
+                           dense_route_groups(ctx, sparse_k1));
   }
+  if (jxlh_status st = run_lf_fill(ctx, f, ctx->rerender_list.p + n_k1, n_fill)) return st;
   if (jxlh_status st = mark_coefficients_read(ctx, sparse_k1)) return st;
   ctx->chroma_lazy = false;
   if (f.subsampled) {
@@ -1232,7 +1249,9 @@ jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_ro
   if (jxlh_status st = patches_check_run(ctx)) return st;
   RunPlan plan;
   bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
-  plan.want_strip = whole && strip_eligible(ctx);
+  // (a frame with a group whose HF has not arrived takes the two-kernel path: the strip kernel transforms every tile)
+  const bool lf_only = lf_only_snapshot(ctx);
+  plan.want_strip = whole && !lf_only && strip_eligible(ctx);
   if (jxlh_status st = run_prologue(ctx, &plan)) return st;
   // Patches and splines are drawn in place on the result.  When the result lives in the planes K1 writes and K1 rewrites a group
   // row beyond the band (the filters' or the chroma upsampling's halo), a band run would overwrite the neighbouring
@@ -1294,17 +1313,25 @@ jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids,
   ctx->rerender_upload.erase(std::unique(ctx->rerender_upload.begin(), ctx->rerender_upload.end()),
                              ctx->rerender_upload.end());
   const int n = (int)ctx->rerender_upload.size();
-  if (jxlh_status st = ensure(ctx, ctx->rerender_list, (size_t)n)) return st;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rerender_list.p, ctx->rerender_upload.data(), n * sizeof(int), hipMemcpyHostToDevice,
-                             ctx->stream));
+  // a listed group whose HF has not arrived (jxlh_frame_set_groups_lf_only) is filled from the LF image again, the
+  // others are transformed: the list goes up with the transforms' groups first
+  int n_k1 = n, n_fill = 0;
+  if (lf_only_snapshot(ctx)) {
+    if (jxlh_status st = lf_split_groups(ctx, ctx->rerender_upload, &n_k1, &n_fill)) return st;
+  } else {
+    if (jxlh_status st = ensure(ctx, ctx->rerender_list, (size_t)n)) return st;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rerender_list.p, ctx->rerender_upload.data(), n * sizeof(int), hipMemcpyHostToDevice,
+                               ctx->stream));
+  }
   {
     ScopedKernelTimer t(ctx, "k1_vardct");
     set_sparse_view(ctx, f, plan.sparse_k1);
     if (plan.sparse_k1) HIPCHK(ctx, hipMemsetAsync(ctx->group_dense.p, 0, ctx->ngroups, ctx->stream));
     launch_vardct_groups(ctx->stream, f, 0, 0, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
-                         plan.sparse_k1 ? ctx->coeffs.p : nullptr, ctx->rerender_list.p, n, ctx->has_special,
+                         plan.sparse_k1 ? ctx->coeffs.p : nullptr, ctx->rerender_list.p, n_k1, ctx->has_special,
                          ctx->has_large, dense_route_groups(ctx, plan.sparse_k1));
   }
+  if (jxlh_status st = run_lf_fill(ctx, f, ctx->rerender_list.p + n_k1, n_fill)) return st;
   if (jxlh_status st = mark_coefficients_read(ctx, plan.sparse_k1)) return st;
   // ---- the filters on every pixel row the listed groups influence: their own rows widened by the stage list's
   // reach (mark_group_to_rerender's 3x3 neighbourhood, restricted to what can actually change), merged into bands

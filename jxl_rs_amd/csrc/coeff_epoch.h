@@ -135,7 +135,21 @@ struct CoeffEpoch {
   bool dirty = false;                        // something was submitted in this epoch
   Residence live;                            // the form the frame is resident in
   EpochPlan plan;  // the last run's plan: its route / rebuild / widen arrays are what that run's copies read
+  // Groups whose HF has not arrived (jxlh_frame_set_groups_lf_only; the reference's channel_status == DataStatus::Zero):
+  // state of the FRAME, not of the epoch -- reset() leaves it alone, a new frame calls clear_lf_only(), and any
+  // submission of a group takes its mark away (record()).  Empty until a group is marked in the frame.
+  std::vector<uint8_t> lf_only;
+  size_t n_lf_only = 0;
 
+  void clear_lf_only() {
+    lf_only.clear();
+    n_lf_only = 0;
+  }
+  void mark_lf_only(uint32_t g) {
+    if (lf_only.size() != groups.size()) lf_only.assign(groups.size(), 0);
+    n_lf_only += !lf_only[g];
+    lf_only[g] = 1;
+  }
   // a new frame (nothing resident) / after a run has consumed the epoch (the caller then installs the plan's outcome)
   void reset(size_t ngroups) {
     groups.assign(ngroups, EpochGroup{});
@@ -158,6 +172,10 @@ struct CoeffEpoch {
     groups[g].sub = kind;
     groups[g].accumulate = accumulate;
     dirty = true;
+    if (n_lf_only && lf_only[g]) {  // the moment channel_status leaves Zero
+      lf_only[g] = 0;
+      n_lf_only--;
+    }
   }
   // what the planner needs of the epoch whose descriptors / wide values have been moved to upload / wide_upload
   EpochInputs inputs(bool expand_sparse, bool want_strip) const {

@@ -91,6 +91,11 @@ struct jxlh_ctx {
   DevBuf<uint8_t> worklist;
   DevBuf<int> rerender_list;          // group ids of jxlh_frame_rerender_groups on the device
   std::vector<int> rerender_upload;   // ... and their host copy (alive until the copy has run)
+  // jxlh_frame_set_groups_lf_only (abi_lf_fill.hip): the marks (CoeffEpoch::lf_only) as the run in progress took them
+  // (empty = no group is marked: the run enqueues what it always did), and the split of the run's groups -- the ones
+  // K1 transforms, then the ones the fill writes -- as it is copied to rerender_list
+  std::vector<uint8_t> lf_only_run;
+  std::vector<int> lf_split_upload;
   bool rendered = false;              // a full jxlh_frame_run has happened in this frame
   bool has_special = false, has_large = false;  // transform families seen in the frame's maps (jxlh_frame_set_hf_meta)
   float* result[3] = {nullptr, nullptr, nullptr};
@@ -384,6 +389,13 @@ jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes);
 jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row);
 jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a);
 void lf_frames_release(jxlh_ctx* ctx);  // abi_lf_frame.hip
+// abi_lf_fill.hip.  lf_only_snapshot: ctx->lf_only_run <- the frame's marks (true = at least one group is marked).
+// lf_split_groups: the sorted `groups` of a run with marks, the unmarked ones first, on the device (rerender_list);
+// *n_k1 of them are K1's, the *n_fill behind them the fill's.  run_lf_fill: Upsample8x of the LF image into the planes
+// K1 writes, for the n groups listed at `groups_dev`.
+bool lf_only_snapshot(jxlh_ctx* ctx);
+jxlh_status lf_split_groups(jxlh_ctx* ctx, const std::vector<int>& groups, int* n_k1, int* n_fill);
+jxlh_status run_lf_fill(jxlh_ctx* ctx, const FrameDev& f, const int* groups_dev, int n);
 bool strip_eligible(const jxlh_ctx* ctx);
 jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan);
 // Where run_stages leaves the finished planes (1 = f.tmp, 0 = f.planes): a property of the frame's stage list, so a

@@ -216,6 +216,10 @@ void launch_chroma_upsample(hipStream_t s, const float* src, float* dst, const P
 // upsample.rs: n = 2, 4, 8; kernels = n*n*25 expanded taps on the device; writes are clipped to out_w x out_h
 void launch_upsample(hipStream_t s, int n, const float* in, size_t in_stride, int w, int h, const float* kernels,
                      float* out, size_t out_stride, int out_w, int out_h);
+// k_lf_fill.hip: the 8 x 8 patches of Upsample8x over f.lf[c] (the whole image, mirrored at its edges) for every block of
+// the n groups listed at `groups` (device), into f.planes[c] in the layout of pix_layout(f); kernels = the expanded
+// taps of factor 8
+void launch_lf_fill(hipStream_t s, const FrameDev& f, const float* kernels, const int* groups, int n);
 // noise synthesis (k_noise.hip)
 void xorshift_jump_table(uint64_t out[16][128][2]);
 void launch_noise_generate(hipStream_t s, float* const out[3], size_t stride, int w, int h, int tile_y0, int tile_y1,

@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "jxlh_frame_set_modular_channels",
     "jxlh_ctx_set_lf_frame", "jxlh_frame_save_lf", "jxlh_ctx_clear_lf_frame", "jxlh_frame_set_lf_from_slot",
     "jxlh_lf_preview", "jxlh_lf_preview_async",
+    "jxlh_frame_set_groups_lf_only",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
@@ -386,6 +387,8 @@ def load():
         L.jxlh_frame_set_lf_from_slot.argtypes = [vp, u32]
         for fn in (L.jxlh_lf_preview, L.jxlh_lf_preview_async):
             fn.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, C.POINTER(OutputDesc), C.POINTER(SaveDesc), vp, sz]
+    if hasattr(L, "jxlh_frame_set_groups_lf_only"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        L.jxlh_frame_set_groups_lf_only.argtypes = [vp, vp, u32]
     if hasattr(L, "jxlh_frame_set_splines"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
         L.jxlh_frame_set_splines.argtypes = [vp, vp, u32]
         L.jxlh_stage_splines.argtypes = [vp, C.POINTER(vp), u32, u32, sz]
@@ -983,6 +986,16 @@ class Context:
         if len(ids):
             self._blend_size = None
         self._chk(self.L.jxlh_frame_rerender_groups(self._ctx, _addr(ids), len(ids)), "frame_rerender_groups")
+
+    def try_set_groups_lf_only(self, group_ids):
+        ids = np.ascontiguousarray(group_ids, dtype=np.uint32)
+        return self.L.jxlh_frame_set_groups_lf_only(self._ctx, _addr(ids), len(ids))
+
+    def set_groups_lf_only(self, group_ids):
+        """jxlh_frame_set_groups_lf_only: the listed groups have no HF yet -- the next frame_run / rerender_groups fills
+        them from the LF image upsampled 8x instead of transforming them (upsample_lf_group of the reference); a later
+        submission of a group clears its mark, frame_begin clears them all"""
+        self._chk(self.try_set_groups_lf_only(group_ids), "frame_set_groups_lf_only")
 
     def sync(self):
         self._chk(self.L.jxlh_ctx_sync(self._ctx), "ctx_sync")
