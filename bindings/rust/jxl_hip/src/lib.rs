@@ -94,6 +94,31 @@ impl Context {
                                  frame_origin.1, y0, y1, out.as_mut_ptr() as *mut c_void, bytes_per_row)
         })
     }
+    /// `jxlh_frame_set_modular_groups`: the group-local transforms of a Modular frame on the device.  `arena` holds
+    /// every group's coded channels and palettes (host memory), `groups` each group's rect, transform list in bitstream
+    /// order and offsets into the arena (what `decode_modular_section` leaves instead of running `local_apply`).  All
+    /// groups run in one launch; the call returns when `arena` may be reused.  A group the device does not take
+    /// (`HipError::Unsupported`: delta palettes, local squeeze) stays on the host and goes in with
+    /// `jxlh_frame_set_modular_channels`.
+    pub fn set_modular_groups(&self, arena: &[i32], groups: &[sys::jxlh_local_group], sample_format: u32) -> Result<()> {
+        let mut first_bad = usize::MAX;
+        // SAFETY: the library checks every offset + extent against arena.len() before it reads; the call waits
+        self.ok(unsafe {
+            sys::jxlh_frame_set_modular_groups(self.raw, arena.as_ptr(), arena.len() as u64, groups.as_ptr(), groups.len(),
+                                               sample_format, &mut first_bad)
+        })
+    }
+    /// `jxlh_modular_local_lower`: the host-side lowering and checks alone; `Err` carries the first refused group
+    pub fn lower_modular_groups(groups: &[sys::jxlh_local_group], bit_depth: u32, arena_samples: u64)
+                                -> std::result::Result<Vec<sys::jxlh_local_program>, (sys::jxlh_status, usize)> {
+        // SAFETY: plain-old-data structs, fully written by a successful call
+        let mut progs: Vec<sys::jxlh_local_program> = vec![unsafe { std::mem::zeroed() }; groups.len()];
+        let mut first_bad = usize::MAX;
+        let st = unsafe {
+            sys::jxlh_modular_local_lower(groups.as_ptr(), groups.len(), bit_depth, arena_samples, progs.as_mut_ptr(), &mut first_bad)
+        };
+        if st == sys::JXLH_OK { Ok(progs) } else { Err((st, first_bad)) }
+    }
     fn ok(&self, st: sys::jxlh_status) -> Result<()> {
         check(self.raw, st)
     }

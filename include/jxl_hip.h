@@ -234,6 +234,103 @@ jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t
                                             const int32_t* c0, const int32_t* c1, const int32_t* c2, size_t stride,
                                             uint32_t sample_format);
 
+/* ---- group-local Modular transforms (frame/modular/transforms/apply_local.rs) ---------------------------------------
+ * A lossless encoder picks an RCT per group and very often a per-group palette.  These calls take the channels of many
+ * groups AS DECODED (before meta_apply_local_transforms' steps have run) plus each group's transform list, run every
+ * group's inverse steps on the device and write the finished channels at the group's rect -- the whole batch in ONE
+ * kernel launch (k_modular_local).
+ *
+ *   arena    one block of i32 samples, host or device memory, that holds every group's coded channels and palettes;
+ *            descriptors address it by sample offsets.
+ *   group    the rect it covers, the image channels its steps see (n_channels), its steps in BITSTREAM order (the
+ *            headers::modular::Transform entries of its GroupHeader) and where its coded channels sit.  The device
+ *            applies the inverses last-to-first (TransformStep::local_apply).
+ *   RCT      do_rct_step on channels begin_c .. begin_c + 2: wrapping i32, op = rct_type % 7, permutation = rct_type / 7.
+ *   palette  the num_deltas == 0, predictor == Zero branch of do_palette_step_general (palette.rs:182-199): explicit
+ *            entries, the implicit 4x4x4 and 5x5x5 cubes behind them, negative indices from the delta table scaled by
+ *            the bit depth (taken as min(bit_depth, 24), palette.rs:177), channels >= 3 of implicit entries zero.
+ *   begin_c  indexes the channel list AS IT STANDS when meta_apply_single_transform reaches the step: every palette in
+ *            front of it has put its meta channel at position 0 and folded its num_c channels into one index channel.
+ *   n_coded  the image-sized channels the list holds after all steps (palette meta channels not counted: their
+ *            samples are at palette_offset), coded_offset[i] the i-th of them in list order, rows of w samples at
+ *            coded_stride.
+ * Rects of one call that overlap are not diagnosed; the order in which they land is unspecified.
+ *
+ * Every refusal is decided before anything is enqueued; a refused call changes nothing, *first_bad (may be null) and
+ * jxlh_last_error name the group.
+ *   JXLH_ERR_INVALID_ARGUMENT  a null pointer; n_channels, n_coded outside 1..4, n_steps above 4; an n_coded that is
+ *                              not what the steps leave; rct_type >= 42; a channel range that leaves the list (the
+ *                              reference's InvalidChannelRange); num_c == 0; coded_stride < w; an offset + extent beyond
+ *                              arena_samples; num_colors + num_deltas == 0; a palette with a bit_depth outside 1..31;
+ *                              a rect outside the frame / the out planes; a bad or changed sample_format.
+ *   JXLH_ERR_UNSUPPORTED       (keep that group on the host and hand it over with jxlh_frame_set_modular_channels) a
+ *                              palette with num_deltas > 0 or predictor != 0; a step whose range touches a palette meta
+ *                              channel; any other transform kind (local squeeze); a chroma-subsampled frame; a sharded
+ *                              context.
+ *   JXLH_ERR_BAD_STATE         jxlh_frame_set_modular_groups* outside a frame or on a VarDCT frame. */
+#define JXLH_LOCAL_MAX_STEPS 4
+#define JXLH_LOCAL_MAX_CHANNELS 4
+enum { JXLH_LOCAL_RCT = 0, JXLH_LOCAL_PALETTE = 1 };
+typedef struct jxlh_local_step {
+  uint32_t kind;        /* JXLH_LOCAL_* */
+  uint32_t begin_c;     /* Transform::begin_channel */
+  uint32_t rct_type;    /* RCT: 0..41 */
+  uint32_t num_c, num_colors, num_deltas, predictor; /* palette */
+  uint64_t palette_offset; /* palette: samples into the arena; num_c rows of num_colors + num_deltas values (the meta
+                              channel's layout, size (num_colors + num_deltas, num_c)) */
+} jxlh_local_step;
+typedef struct jxlh_local_group {
+  uint32_t x0, y0, w, h;      /* the rect of the frame (or of the out planes) this group covers; w or h 0: skipped */
+  uint32_t n_channels;        /* image channels the steps see, 1..JXLH_LOCAL_MAX_CHANNELS */
+  uint32_t n_steps;           /* 0..JXLH_LOCAL_MAX_STEPS; 0 = plain copy */
+  jxlh_local_step steps[4];   /* [JXLH_LOCAL_MAX_STEPS] */
+  uint32_t n_coded;
+  uint64_t coded_offset[4];   /* [JXLH_LOCAL_MAX_CHANNELS] samples into the arena */
+  uint32_t coded_stride;      /* >= w */
+} jxlh_local_group;
+/* What a group's list lowers to: the kernel keeps channel s of the finished group in SLOT s (a register per sample);
+ * coded channel i is loaded into coded_slot[i], then ops[0 .. n_ops) run -- the inverse steps, last step first. */
+typedef struct jxlh_local_op {
+  uint32_t kind;         /* JXLH_LOCAL_* */
+  uint32_t rct_op;       /* RCT: 0..6 */
+  uint32_t n_slots;      /* RCT: 3; palette: num_c */
+  uint32_t in_slot[3];   /* RCT: the slots read as v0, v1, v2; palette: in_slot[0] holds the index */
+  uint32_t out_slot[4];  /* RCT: the slots w0, w1, w2 go to (permutation applied); palette: the slot of channel c */
+  uint32_t num_colors;
+  uint64_t palette_offset;
+} jxlh_local_op;
+typedef struct jxlh_local_program {
+  uint32_t n_coded;
+  uint32_t coded_slot[4];
+  uint32_t n_ops;
+  jxlh_local_op ops[4];
+} jxlh_local_program;
+/* Pure host code (no context, no device): mirrors meta_apply_single_transform on each group's channel list and checks
+ * everything listed above that does not need a frame.  bit_depth: the channels' (0 allowed without palettes).
+ * programs: n entries, or null for the checks alone.  The launches below lower through the same function. */
+jxlh_status jxlh_modular_local_lower(const jxlh_local_group* groups, size_t n, uint32_t bit_depth, uint64_t arena_samples,
+                                     jxlh_local_program* programs, size_t* first_bad);
+/* The stage-level form: group g's n_channels finished channels go to out[0 .. n_channels) at (x0, y0); out: n_out
+ * (1..4, >= every n_channels) DEVICE planes of out_w x out_h samples, rows out_stride apart.  What a frame with a global
+ * transform behind the local ones feeds into jxlh_rct / jxlh_unsqueeze_chain, and how a fourth channel reaches
+ * jxlh_frame_set_extra_channel without leaving the device.  Returns when the result is in `out`. */
+jxlh_status jxlh_modular_local_transforms(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                          const jxlh_local_group* groups, size_t n, uint32_t bit_depth, int32_t* const out[],
+                                          uint32_t n_out, uint32_t out_w, uint32_t out_h, size_t out_stride,
+                                          size_t* first_bad);
+/* The same launch into the frame's sample planes; the rules of jxlh_frame_set_modular_channels apply (rects inside the
+ * coded size, one sample_format per frame, replaceable after a run, freely mixed with jxlh_frame_set_modular_channels on
+ * other rects).  The palettes' bit depth is sample_format's.  n_channels is 3, or 1 for a grey frame, whose channel is
+ * fanned out to all three planes (meta_apply.rs:697-701).  A host arena goes up in one asynchronous copy into context
+ * scratch.  jxlh_frame_set_modular_groups returns when the caller's arena may be reused; the _async form returns after
+ * enqueueing, and the arena stays valid until the next jxlh_ctx_sync / waited mark (as for jxlh_frame_save_async). */
+jxlh_status jxlh_frame_set_modular_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                          const jxlh_local_group* groups, size_t n, uint32_t sample_format,
+                                          size_t* first_bad);
+jxlh_status jxlh_frame_set_modular_groups_async(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                const jxlh_local_group* groups, size_t n, uint32_t sample_format,
+                                                size_t* first_bad);
+
 /* HfGlobalState::dequant_matrices (frame/quant_weights.rs:347-351): 17 tables, table t holds
  * 3 * n[t] inverse weights, channel-major (matrix(type, c), :1081-1086). */
 jxlh_status jxlh_frame_set_dequant_tables(jxlh_ctx* ctx, const float* const tables[JXLH_NUM_QUANT_TABLES],

@@ -142,6 +142,16 @@ class VarDctFrame {
     ctx_.check(jxlh_frame_set_modular_channels(ctx_.raw(), x0, y0, w, h, planes[0], planes[1], planes[2], stride, sample_format),
                "jxlh_frame_set_modular_channels");
   }
+  // ... or the channels of many groups AS DECODED plus each group's local transform list (decode_modular_section's
+  // output instead of TransformStep::local_apply): RCTs and palettes run on the device, one launch for the batch.  The
+  // arena (host or device memory) may be reused when the call returns; with async = true, after the next sync / mark.
+  void set_modular_groups(const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups, size_t n,
+                          uint32_t sample_format, bool async = false) {
+    size_t bad = 0;
+    ctx_.check(async ? jxlh_frame_set_modular_groups_async(ctx_.raw(), arena, arena_samples, groups, n, sample_format, &bad)
+                     : jxlh_frame_set_modular_groups(ctx_.raw(), arena, arena_samples, groups, n, sample_format, &bad),
+               "jxlh_frame_set_modular_groups");
+  }
   // PatchesDictionary::read's result (decode_lf_global, frame/decode.rs:315-324), flattened: blendings holds
   // patches.size() * (1 + ec_flags.size()) entries, ec_flags the JXLH_EC_* of each extra channel
   void decode_patches(const std::vector<jxlh_patch>& patches, const std::vector<jxlh_patch_blending>& blendings,

@@ -1023,6 +1023,12 @@ class GpuModularFramePipeline : public GpuFramePipeline {
   void set_channels(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const int32_t* const planes[3], size_t stride) {
     frame_.set_modular_channels(x0, y0, w, h, planes, stride, lp_.modular_sample_format);
   }
+  // the batched intake: many groups as decoded, each with its local transform list (jxlh_frame_set_modular_groups);
+  // what a group's list holds that the device does not take comes back as JXLH_ERR_UNSUPPORTED before anything ran, and
+  // that group goes through set_channels after the host's local_apply
+  void set_groups(const int32_t* arena, uint64_t arena_samples, const std::vector<jxlh_local_group>& groups, bool async = false) {
+    frame_.set_modular_groups(arena, arena_samples, groups.data(), groups.size(), lp_.modular_sample_format, async);
+  }
   // the whole frame, then the list's blending
   void render() {
     frame_.finalize_and_render();
@@ -1044,6 +1050,15 @@ class GpuModularPipeline {
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuModularPipeline", "the stage list holds no Modular conversion");
   }
   const LoweredPipeline& lowered() const { return lp_; }
+  // the batched intake of the caller-held-planes form (jxlh_modular_local_transforms): every group's local transforms,
+  // finished channels into `planes` (n_planes DEVICE planes of the frame's size) at the group's rect, one launch
+  void local_transforms(const int32_t* arena, uint64_t arena_samples, const std::vector<jxlh_local_group>& groups,
+                        uint32_t bit_depth, int32_t* const planes[], uint32_t n_planes, size_t stride) {
+    size_t bad = 0;
+    ctx_.check(jxlh_modular_local_transforms(ctx_.raw(), arena, arena_samples, groups.data(), groups.size(), bit_depth, planes,
+                                             n_planes, lp_.frame.xsize, lp_.frame.ysize, stride, &bad),
+               "jxlh_modular_local_transforms");
+  }
   // ConvertI32ToU8Stage: interleaved bytes (3 or 4 per pixel) in one pass
   void render_u8(const int32_t* const planes[3], size_t stride, void* out, size_t bytes_per_row) {
     if (lp_.modular != LoweredPipeline::Modular::kI32ToU8)

@@ -227,6 +227,7 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   blend_release(ctx);
   save_release(ctx);
   lf_frames_release(ctx);
+  modular_local_release(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -1,0 +1,230 @@
+// C ABI, group-local Modular transforms (jxlh_modular_local_lower, jxlh_modular_local_transforms,
+// jxlh_frame_set_modular_groups*): every group's transform list is lowered on the host (modular_local_host.h), the
+// lowered programs and a flat (group, row chunk) work list go up in one copy from a pinned block, a host arena in one
+// more, and the whole batch is one launch of k_modular_local.  Everything that can refuse a call is checked before the
+// first copy is enqueued.
+#include <algorithm>
+
+#include "jxlh_ctx.h"
+#include "modular_local_host.h"
+
+namespace jxlh_host {
+namespace {
+
+constexpr uint32_t kLocalItemSamples = 8192;  // samples of one channel a work item covers (32 rows of a 256-wide group)
+
+jxlh_status refuse_group(jxlh_ctx* ctx, jxlh_status st, size_t g, const char* why, size_t* first_bad) {
+  if (first_bad) *first_bad = g;
+  if (ctx) ctx->last_error = "group " + std::to_string(g) + ": " + why;
+  return st;
+}
+
+struct LocalDest {
+  int32_t* out[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint32_t n_out = 0, w = 0, h = 0;
+  size_t stride = 0;
+  bool frame = false;  // the frame's sample planes: 3 or 1 (fanned out) channels per group
+};
+
+// checks, lowering, upload, launch; nothing is enqueued unless every group passed
+jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
+                          size_t n, uint32_t bit_depth, const LocalDest& d, size_t* first_bad) {
+  if (n > 0x7fffffffu || d.w > 0x7fffffffu || d.h > 0x7fffffffu) return JXLH_ERR_INVALID_ARGUMENT;
+  std::vector<LocalGroupDev> dev(n);
+  std::vector<LocalItem> items;
+  bool dst_aligned = (d.stride & 3) == 0 && (reinterpret_cast<uintptr_t>(arena) & 15) == 0;
+  for (uint32_t c = 0; c < d.n_out; c++) dst_aligned = dst_aligned && (reinterpret_cast<uintptr_t>(d.out[c]) & 15) == 0;
+  for (size_t gi = 0; gi < n; gi++) {
+    const jxlh_local_group& g = groups[gi];
+    jxlh_local_program prog;
+    const char* why = "";
+    if (jxlh_status st = local_lower_group(g, bit_depth, arena_samples, &prog, &why)) return refuse_group(ctx, st, gi, why, first_bad);
+    if (d.frame ? (g.n_channels != 3 && g.n_channels != 1) : g.n_channels > d.n_out)
+      return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, d.frame ? "a frame's groups hold 3 channels, or 1 (grey)" : "more channels than out planes", first_bad);
+    if ((uint64_t)g.x0 + g.w > d.w || (uint64_t)g.y0 + g.h > d.h)
+      return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the rect leaves the planes", first_bad);
+    LocalGroupDev& o = dev[gi];
+    o = LocalGroupDev{};
+    o.x0 = g.x0, o.y0 = g.y0, o.w = g.w, o.h = g.h;
+    o.n_channels = g.n_channels;
+    o.n_ops = prog.n_ops;
+    o.coded_stride = g.coded_stride;
+    bool vec = dst_aligned && (g.coded_stride & 3) == 0 && (g.x0 & 3) == 0;
+    for (uint32_t k = 0; k < prog.n_coded; k++) {
+      o.slot_mask |= 1u << prog.coded_slot[k];
+      o.slot_off[prog.coded_slot[k]] = g.coded_offset[k];
+      vec = vec && (g.coded_offset[k] & 3) == 0;
+    }
+    o.vec = vec;
+    // palettes share the workgroup's LDS block while they fit, in the order they run
+    for (uint32_t k = 0; k < prog.n_ops; k++) {
+      const jxlh_local_op& p = prog.ops[k];
+      LocalOpDev& q = o.ops[k];
+      q.kind = p.kind, q.rct_op = p.rct_op, q.n_slots = p.n_slots, q.num_colors = p.num_colors, q.pal_off = p.palette_offset;
+      for (int i = 0; i < 3; i++) q.in_slot[i] = p.in_slot[i];
+      for (int i = 0; i < 4; i++) q.out_slot[i] = p.out_slot[i];
+      q.lds_off = kLocalNoLds;
+      if (p.kind == JXLH_LOCAL_PALETTE) {
+        const uint64_t entries = (uint64_t)p.n_slots * p.num_colors;
+        if (entries <= kLocalLdsEntries - o.lds_entries) {
+          q.lds_off = o.lds_entries;
+          o.lds_entries += (uint32_t)entries;
+        }
+      }
+    }
+    if (g.w == 0 || g.h == 0) continue;
+    // threads along x: the smallest power of two that covers the row's 4-sample vectors, at most the workgroup
+    const uint32_t nvx = (g.w + 3) / 4;
+    uint32_t lx = 0;
+    while (lx < 8 && (1u << lx) < nvx) lx++;
+    o.lanes_x_log2 = lx;
+    o.rows_per_item = std::max(256u >> lx, kLocalItemSamples / (4 * nvx));
+    for (uint64_t r = 0; r < g.h; r += o.rows_per_item) items.push_back(LocalItem{(uint32_t)gi, (uint32_t)r});
+    if (items.size() > 0x7fffffffu) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the batch holds more than 2^31 - 1 work items", first_bad);
+  }
+  if (items.empty()) return JXLH_OK;
+  // ---- from here on the call cannot be refused for its arguments
+  const size_t desc_bytes = round_up(n * sizeof(LocalGroupDev), 16), bytes = desc_bytes + items.size() * sizeof(LocalItem);
+  if (ctx->local_copied_valid) {  // the pinned block's previous content is on its way
+    HIPCHK(ctx, hipEventSynchronize(ctx->local_copied));
+    ctx->local_copied_valid = false;
+  }
+  if (ctx->local_desc_host_cap < bytes) {
+    if (ctx->local_desc_host) HIPCHK(ctx, hipHostFree(ctx->local_desc_host));
+    ctx->local_desc_host = nullptr;
+    ctx->local_desc_host_cap = 0;
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->local_desc_host), bytes + bytes / 2, hipHostMallocDefault));
+    ctx->local_desc_host_cap = bytes + bytes / 2;
+  }
+  if (!ctx->local_copied) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->local_copied, hipEventDisableTiming));
+  if (jxlh_status st = ensure(ctx, ctx->local_desc, bytes)) return st;
+  std::memcpy(ctx->local_desc_host, dev.data(), n * sizeof(LocalGroupDev));
+  std::memcpy(ctx->local_desc_host + desc_bytes, items.data(), items.size() * sizeof(LocalItem));
+  const int32_t* arena_dev = arena;
+  if (!is_device_ptr(arena)) {
+    // one copy; 16-byte alignment of the samples is kept (hipMalloc's and the caller's bases are both taken as they
+    // are: the vector path was decided on the caller's base, so an unaligned host arena already runs the scalar path)
+    if (jxlh_status st = stage_in(ctx, ctx->local_arena, arena, (size_t)arena_samples)) return st;
+    arena_dev = ctx->local_arena.p;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->local_desc.p, ctx->local_desc_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipEventRecord(ctx->local_copied, ctx->stream));
+  ctx->local_copied_valid = true;
+  LocalLaunch a{};
+  a.arena = arena_dev;
+  a.groups = reinterpret_cast<const LocalGroupDev*>(ctx->local_desc.p);
+  a.items = reinterpret_cast<const LocalItem*>(ctx->local_desc.p + desc_bytes);
+  a.n_items = (uint32_t)items.size();
+  for (int c = 0; c < 4; c++) a.out[c] = d.out[c];
+  a.n_out = d.n_out;
+  a.fan_grey = d.frame ? 1 : 0;
+  a.out_stride = d.stride;
+  a.bit_depth = (int)std::min(bit_depth, 24u);  // do_palette_step_general: bits_per_sample().min(24), palette.rs:177
+  {
+    ScopedKernelTimer t(ctx, "k_modular_local");
+    launch_modular_local(ctx->stream, a);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return JXLH_OK;
+}
+
+jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
+                             size_t n, uint32_t sample_format, size_t* first_bad, bool wait) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !arena || (!groups && n > 0)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (!ctx->in_frame || !ctx->modular) return JXLH_ERR_BAD_STATE;
+  const FrameDev& f = ctx->fd;
+  if (f.subsampled) {
+    ctx->last_error = "group-local transforms on a chroma-subsampled frame";
+    return JXLH_ERR_UNSUPPORTED;
+  }
+  if (ctx->comm) {
+    ctx->last_error = "group-local transforms on a sharded context";
+    return JXLH_ERR_UNSUPPORTED;
+  }
+  const bool xyb = (sample_format & JXLH_MODULAR_XYB) != 0;
+  const uint32_t depth = sample_format & ~(uint32_t)JXLH_MODULAR_XYB;
+  if (!(xyb && depth == 0) && !bit_depth_ok(depth, 31)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (ctx->mod_format && ctx->mod_format != sample_format) return JXLH_ERR_INVALID_ARGUMENT;
+  LocalDest d;
+  for (int c = 0; c < 3; c++) d.out[c] = ctx->mod_src[c].p;
+  d.n_out = 3;
+  d.w = (uint32_t)f.xsize, d.h = (uint32_t)f.ysize;
+  d.stride = f.plane_stride;
+  d.frame = true;
+  // the palettes' bit depth is the samples' (a palette on 32-bit float samples is refused: no bit depth of 1..31)
+  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, depth & 0xffu, d, first_bad)) return st;
+  ctx->mod_format = sample_format;
+  if (wait) JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+}  // namespace
+
+void modular_local_release(jxlh_ctx* ctx) {
+  release(ctx->local_arena);
+  release(ctx->local_desc);
+  if (ctx->local_desc_host) (void)hipHostFree(ctx->local_desc_host);
+  ctx->local_desc_host = nullptr;
+  ctx->local_desc_host_cap = 0;
+  if (ctx->local_copied) (void)hipEventDestroy(ctx->local_copied);
+  ctx->local_copied = nullptr;
+  ctx->local_copied_valid = false;
+}
+
+}  // namespace jxlh_host
+
+extern "C" {
+
+jxlh_status jxlh_modular_local_lower(const jxlh_local_group* groups, size_t n, uint32_t bit_depth, uint64_t arena_samples,
+                                     jxlh_local_program* programs, size_t* first_bad) {
+  if (!groups && n > 0) return JXLH_ERR_INVALID_ARGUMENT;
+  // two passes, so that a refused call leaves `programs` as it was
+  for (int pass = 0; pass < (programs ? 2 : 1); pass++) {
+    for (size_t g = 0; g < n; g++) {
+      if (jxlh_status st = local_lower_group(groups[g], bit_depth, arena_samples, pass ? &programs[g] : nullptr, nullptr)) {
+        if (first_bad) *first_bad = g;
+        return st;
+      }
+    }
+  }
+  return JXLH_OK;
+}
+
+jxlh_status jxlh_modular_local_transforms(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                          const jxlh_local_group* groups, size_t n, uint32_t bit_depth, int32_t* const out[],
+                                          uint32_t n_out, uint32_t out_w, uint32_t out_h, size_t out_stride,
+                                          size_t* first_bad) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !arena || (!groups && n > 0) || !out || n_out < 1 || n_out > JXLH_LOCAL_MAX_CHANNELS || out_stride < out_w)
+    return JXLH_ERR_INVALID_ARGUMENT;
+  LocalDest d;
+  for (uint32_t c = 0; c < n_out; c++) {
+    if (!out[c] || !is_device_ptr(out[c])) return JXLH_ERR_INVALID_ARGUMENT;
+    d.out[c] = out[c];
+  }
+  if (ctx->comm) {
+    ctx->last_error = "group-local transforms on a sharded context";
+    return JXLH_ERR_UNSUPPORTED;
+  }
+  d.n_out = n_out;
+  d.w = out_w, d.h = out_h;
+  d.stride = out_stride;
+  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, bit_depth, d, first_bad)) return st;
+  JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+jxlh_status jxlh_frame_set_modular_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                          const jxlh_local_group* groups, size_t n, uint32_t sample_format,
+                                          size_t* first_bad) {
+  return frame_set_groups(ctx, arena, arena_samples, groups, n, sample_format, first_bad, true);
+}
+
+jxlh_status jxlh_frame_set_modular_groups_async(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                const jxlh_local_group* groups, size_t n, uint32_t sample_format,
+                                                size_t* first_bad) {
+  return frame_set_groups(ctx, arena, arena_samples, groups, n, sample_format, first_bad, false);
+}
+
+}  // extern "C"

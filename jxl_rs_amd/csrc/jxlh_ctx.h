@@ -73,6 +73,14 @@ struct jxlh_ctx {
   bool modular = false;
   DevBuf<int32_t> mod_src[3];
   uint32_t mod_format = 0;
+  // group-local transforms (abi_modular_local.hip): device scratch of a host arena and of a batch's descriptors + work
+  // list; the descriptors go up from a pinned block, reused once local_copied (recorded behind its copy) has passed
+  DevBuf<int32_t> local_arena;
+  DevBuf<uint8_t> local_desc;
+  uint8_t* local_desc_host = nullptr;
+  size_t local_desc_host_cap = 0;
+  hipEvent_t local_copied = nullptr;
+  bool local_copied_valid = false;
   bool tables_set = false, lf_smoothed = false;
   jxlh_frame_params params;
   FrameDev fd;
@@ -389,6 +397,7 @@ jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes);
 jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row);
 jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a);
 void lf_frames_release(jxlh_ctx* ctx);  // abi_lf_frame.hip
+void modular_local_release(jxlh_ctx* ctx);  // abi_modular_local.hip
 // abi_lf_fill.hip.  lf_only_snapshot: ctx->lf_only_run <- the frame's marks (true = at least one group is marked).
 // lf_split_groups: the sorted `groups` of a run with marks, the unmarked ones first, on the device (rerender_list);
 // *n_k1 of them are K1's, the *n_fill behind them the fill's.  run_lf_fill: Upsample8x of the LF image into the planes

@@ -381,6 +381,43 @@ struct IntakeLaunch {
   uint32_t bits, exp_bits;  // kIntakeFloat
 };
 void launch_modular_intake(hipStream_t s, const IntakeLaunch& a);
+// k_modular_local.hip: the group-local transforms of a batch of groups in one launch.  A group's lowered program
+// (modular_local_host.h) as the kernel reads it -- workgroup-uniform, fetched through scalar loads --, and the flat work
+// list of (group, first row) items; an item covers rows_per_item rows of its group.
+constexpr uint32_t kLocalLdsEntries = 4096;    // palette entries staged in LDS per workgroup (16 KiB)
+constexpr uint32_t kLocalNoLds = 0xffffffffu;  // LocalOpDev::lds_off of a palette read from global memory
+struct LocalOpDev {
+  uint32_t kind, rct_op, n_slots;
+  uint32_t in_slot[3], out_slot[4];
+  uint32_t num_colors, lds_off;
+  uint64_t pal_off;  // samples into the arena
+};
+struct LocalGroupDev {
+  uint32_t x0, y0, w, h;
+  uint32_t n_channels, n_ops, coded_stride;
+  uint32_t vec;            // 1: every row of the group starts 16-byte aligned on both sides (16-byte accesses)
+  uint32_t rows_per_item;  // rows per work item
+  uint32_t lanes_x_log2;   // threads of the workgroup along x: 1 << lanes_x_log2 (four samples each), the rest along y
+  uint32_t slot_mask;      // bit s: slot s is loaded from slot_off[s]
+  uint32_t lds_entries;    // palette entries this group stages
+  uint64_t slot_off[4];    // samples into the arena
+  LocalOpDev ops[4];
+};
+struct LocalItem {
+  uint32_t group, row0;
+};
+struct LocalLaunch {
+  const int32_t* arena;
+  const LocalGroupDev* groups;
+  const LocalItem* items;
+  uint32_t n_items;
+  int32_t* out[4];
+  uint32_t n_out;     // planes of `out`
+  uint32_t fan_grey;  // 1: a group of one channel writes it to planes 0..2
+  size_t out_stride;  // samples
+  int bit_depth;
+};
+void launch_modular_local(hipStream_t s, const LocalLaunch& a);
 void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
 void launch_modular_xyb_to_f32(hipStream_t s, const int32_t* y, const int32_t* x, const int32_t* b, size_t n,
                                const float scale[3], float* ox, float* oy, float* ob);

@@ -12,55 +12,17 @@
 // and lean on L1/L2 for the 128-byte lines they share across iterations.
 #include "jxlh_internal.h"
 #include "modular_convert_device.h"
+#include "modular_ops_device.h"  // wadd / wsub, rct_op, rct_permute, kDeltaPalette, palette_value
 
 namespace jxlh {
 namespace {
-
-__device__ __forceinline__ int32_t wadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
-__device__ __forceinline__ int32_t wsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
-
-template <int OP>
-__device__ __forceinline__ void rct_op(int32_t v0, int32_t v1, int32_t v2, int32_t& w0, int32_t& w1, int32_t& w2) {
-  w0 = v0;
-  w1 = v1;
-  w2 = v2;
-  if constexpr (OP == 1) {
-    w2 = wadd(v2, v0);
-  } else if constexpr (OP == 2) {
-    w1 = wadd(v1, v0);
-  } else if constexpr (OP == 3) {
-    w1 = wadd(v1, v0);
-    w2 = wadd(v2, v0);
-  } else if constexpr (OP == 4) {
-    w1 = wadd(v1, wadd(v0, v2) >> 1);
-  } else if constexpr (OP == 5) {
-    const int32_t t2 = wadd(v0, v2);
-    w1 = wadd(v1, wadd(v0, t2) >> 1);
-    w2 = t2;
-  } else if constexpr (OP == 6) {
-    int32_t y = wsub(v0, v2 >> 1);
-    const int32_t g = wadd(v2, y);
-    y = wsub(y, v1 >> 1);
-    w0 = wadd(y, v1);
-    w1 = g;
-    w2 = y;
-  }
-}
 
 // perm: which output plane receives w0/w1/w2 (rct.rs:132-156)
 template <int OP>
 __global__ void k4_rct(int32_t* __restrict__ p0, int32_t* __restrict__ p1, int32_t* __restrict__ p2, size_t n,
                        int perm, size_t nvec) {
   int32_t* o[3];
-  switch (perm) {
-    default:
-    case 0: o[0] = p0; o[1] = p1; o[2] = p2; break;
-    case 1: o[0] = p1; o[1] = p2; o[2] = p0; break;  // Gbr: out[1,2,0] = in[0,1,2]
-    case 2: o[0] = p2; o[1] = p0; o[2] = p1; break;  // Brg
-    case 3: o[0] = p0; o[1] = p2; o[2] = p1; break;  // Rbg
-    case 4: o[0] = p1; o[1] = p0; o[2] = p2; break;  // Grb
-    case 5: o[0] = p2; o[1] = p1; o[2] = p0; break;  // Bgr
-  }
+  rct_permute<int32_t*>(perm, p0, p1, p2, o);
   // nvec = n / 4 when the three planes are 16-byte aligned (launch_rct), else 0: everything takes the scalar loop
   const size_t stride = (size_t)gridDim.x * blockDim.x;
 #ifndef JXLH_RCT_NT
@@ -95,15 +57,7 @@ template <int OP>
 __global__ void k4_rct_rows(int32_t* __restrict__ p0, int32_t* __restrict__ p1, int32_t* __restrict__ p2, uint32_t w,
                             uint32_t h, size_t stride, int perm) {
   int32_t* o[3];
-  switch (perm) {
-    default:
-    case 0: o[0] = p0; o[1] = p1; o[2] = p2; break;
-    case 1: o[0] = p1; o[1] = p2; o[2] = p0; break;
-    case 2: o[0] = p2; o[1] = p0; o[2] = p1; break;
-    case 3: o[0] = p0; o[1] = p2; o[2] = p1; break;
-    case 4: o[0] = p1; o[1] = p0; o[2] = p2; break;
-    case 5: o[0] = p2; o[1] = p1; o[2] = p0; break;
-  }
+  rct_permute<int32_t*>(perm, p0, p1, p2, o);
   for (uint32_t y = blockIdx.y; y < h; y += gridDim.y) {
     const size_t row = (size_t)y * stride;
     for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < w; x += gridDim.x * blockDim.x) {
@@ -114,40 +68,6 @@ __global__ void k4_rct_rows(int32_t* __restrict__ p0, int32_t* __restrict__ p1, 
       o[2][row + x] = c;
     }
   }
-}
-
-__constant__ int16_t kDeltaPalette[72][3] = {
-#include "delta_palette.inc"
-};
-
-// get_palette_value (palette.rs:39-163)
-__device__ __forceinline__ int32_t palette_value(const int32_t* __restrict__ palette, size_t pstride, int32_t index,
-                                                 int c, int palette_size, int bit_depth) {
-  if (index < 0) {
-    if (c >= 3) return 0;
-    uint32_t i = (uint32_t)(-(index + 1));
-    i %= 1 + 2 * (72 - 1);
-    int32_t r = kDeltaPalette[(i + 1) >> 1][c];
-    if ((i & 1) == 0) r = -r;
-    if (bit_depth > 8) r *= 1 << (bit_depth - 8);
-    return r;
-  }
-  uint32_t i = (uint32_t)index;
-  const uint32_t ps = (uint32_t)palette_size;
-  if (i >= ps && i < ps + 64) {
-    if (c >= 3) return 0;
-    i -= ps;
-    i >>= c * 2;
-    const int sh = bit_depth > 3 ? bit_depth - 3 : 0;
-    return (int32_t)(((uint64_t)(i % 4) * (uint64_t)((1u << bit_depth) - 1)) >> 2) + (1 << sh);
-  } else if (i >= ps + 64) {
-    if (c >= 3) return 0;
-    i -= ps + 64;
-    if (c == 1) i /= 5;
-    if (c == 2) i /= 25;
-    return (int32_t)(((uint64_t)(i % 5) * (uint64_t)((1u << bit_depth) - 1)) >> 2);
-  }
-  return palette[(size_t)c * pstride + i];
 }
 
 // ---- palette step with delta entries and / or a neighbour predictor (do_palette_step_general, palette.rs:228-251)

@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "jxlh_ctx_set_lf_frame", "jxlh_frame_save_lf", "jxlh_ctx_clear_lf_frame", "jxlh_frame_set_lf_from_slot",
     "jxlh_lf_preview", "jxlh_lf_preview_async",
     "jxlh_frame_set_groups_lf_only",
+    "jxlh_modular_local_lower", "jxlh_modular_local_transforms", "jxlh_frame_set_modular_groups",
+    "jxlh_frame_set_modular_groups_async",
 ]
 # developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
 DEV_SYMBOLS = [
@@ -244,6 +246,95 @@ def save_desc(channels, format=SAVE_U8, bit_depth=None, fill_opaque_alpha=False,
     return d
 
 
+# group-local Modular transforms (jxlh_local_*)
+LOCAL_MAX_STEPS = 4
+LOCAL_MAX_CHANNELS = 4
+LOCAL_RCT, LOCAL_PALETTE = 0, 1
+
+
+class LocalStep(C.Structure):  # jxlh_local_step
+    _fields_ = [("kind", C.c_uint32), ("begin_c", C.c_uint32), ("rct_type", C.c_uint32), ("num_c", C.c_uint32),
+                ("num_colors", C.c_uint32), ("num_deltas", C.c_uint32), ("predictor", C.c_uint32),
+                ("palette_offset", C.c_uint64)]
+
+
+class LocalGroup(C.Structure):  # jxlh_local_group
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("n_channels", C.c_uint32),
+                ("n_steps", C.c_uint32), ("steps", LocalStep * LOCAL_MAX_STEPS), ("n_coded", C.c_uint32),
+                ("coded_offset", C.c_uint64 * LOCAL_MAX_CHANNELS), ("coded_stride", C.c_uint32)]
+
+
+class LocalOp(C.Structure):  # jxlh_local_op
+    _fields_ = [("kind", C.c_uint32), ("rct_op", C.c_uint32), ("n_slots", C.c_uint32), ("in_slot", C.c_uint32 * 3),
+                ("out_slot", C.c_uint32 * 4), ("num_colors", C.c_uint32), ("palette_offset", C.c_uint64)]
+
+
+class LocalProgram(C.Structure):  # jxlh_local_program
+    _fields_ = [("n_coded", C.c_uint32), ("coded_slot", C.c_uint32 * 4), ("n_ops", C.c_uint32), ("ops", LocalOp * 4)]
+
+
+def local_rct(begin_c, rct_type):
+    """one RCT of a group's transform list, for pack_local_groups"""
+    return {"kind": LOCAL_RCT, "begin_c": int(begin_c), "rct_type": int(rct_type)}
+
+
+def local_palette(begin_c, num_c, table, num_deltas=0, predictor=0):
+    """one palette of a group's transform list; table: the meta channel, i32 [num_c, num_colors + num_deltas]"""
+    t = np.ascontiguousarray(table, dtype=np.int32).reshape(int(num_c), -1)
+    return {"kind": LOCAL_PALETTE, "begin_c": int(begin_c), "num_c": int(num_c), "table": t,
+            "num_colors": t.shape[1] - int(num_deltas), "num_deltas": int(num_deltas), "predictor": int(predictor)}
+
+
+def pack_local_groups(specs, align=4, skew=0, stride_pad=0, fill=0):
+    """Packs the coded channels and palettes of many groups into one arena.  specs: dicts with x0, y0, n_channels,
+    steps (local_rct / local_palette, bitstream order) and coded (the 2-D i32 channels as decoded, one shape).  Every
+    block starts on a multiple of `align` samples plus `skew`, rows are stride_pad samples longer than a multiple of
+    `align`; the gaps hold `fill`.  Returns (arena, groups): an i32 array and a (LocalGroup * n) array."""
+    groups = (LocalGroup * max(len(specs), 1))()
+    blocks, pos = [], 0
+
+    def place(a):
+        nonlocal pos
+        pos = -(-pos // align) * align + skew
+        at = pos
+        blocks.append((at, a))
+        pos += a.size
+        return at
+
+    for g, sp in zip(groups, specs):
+        coded = [np.asarray(c, dtype=np.int32) for c in sp["coded"]]
+        h, w = coded[0].shape
+        g.x0, g.y0, g.w, g.h = int(sp["x0"]), int(sp["y0"]), w, h
+        g.n_channels, g.n_steps, g.n_coded = int(sp["n_channels"]), len(sp["steps"]), len(coded)
+        if g.n_steps > LOCAL_MAX_STEPS or g.n_coded > LOCAL_MAX_CHANNELS:
+            raise ValueError("a group holds at most 4 steps and 4 coded channels")
+        for st, d in zip(g.steps, sp["steps"]):
+            st.kind, st.begin_c, st.rct_type = d["kind"], d["begin_c"], d.get("rct_type", 0)
+            if d["kind"] == LOCAL_PALETTE:
+                st.num_c, st.num_colors, st.num_deltas, st.predictor = d["num_c"], d["num_colors"], d["num_deltas"], d["predictor"]
+                st.palette_offset = place(d["table"].reshape(-1))
+        stride = -(-w // align) * align + stride_pad
+        g.coded_stride = stride
+        for i, c in enumerate(coded):
+            rows = np.full((h, stride), fill, dtype=np.int32)
+            rows[:, :w] = c
+            g.coded_offset[i] = place(rows.reshape(-1))
+    arena = np.full(max(pos, 1), fill, dtype=np.int32)
+    for at, a in blocks:
+        arena[at:at + a.size] = a
+    return arena, groups
+
+
+def modular_local_lower(groups, bit_depth, arena_samples, n=None):
+    """jxlh_modular_local_lower: (status, programs, first_bad); first_bad is None when no group was refused"""
+    L = _lib()
+    n = len(groups) if n is None else n
+    progs = (LocalProgram * max(n, 1))()
+    bad = C.c_size_t(2 ** 64 - 1)
+    st = L.jxlh_modular_local_lower(groups, n, bit_depth, arena_samples, progs, C.byref(bad))
+    return st, progs, (None if bad.value == 2 ** 64 - 1 else bad.value)
+
+
 class JxlHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -306,6 +397,12 @@ def load():
     L.jxlh_frame_set_hf_meta.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, vp, vp, sz]
     if hasattr(L, "jxlh_frame_set_modular_channels"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
         L.jxlh_frame_set_modular_channels.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, u32]
+    if hasattr(L, "jxlh_modular_local_lower"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        gp, u64, szp = C.POINTER(LocalGroup), C.c_uint64, C.POINTER(C.c_size_t)
+        L.jxlh_modular_local_lower.argtypes = [gp, sz, u32, u64, C.POINTER(LocalProgram), szp]
+        L.jxlh_modular_local_transforms.argtypes = [vp, vp, u64, gp, sz, u32, C.POINTER(vp), u32, u32, u32, sz, szp]
+        L.jxlh_frame_set_modular_groups.argtypes = [vp, vp, u64, gp, sz, u32, szp]
+        L.jxlh_frame_set_modular_groups_async.argtypes = [vp, vp, u64, gp, sz, u32, szp]
     L.jxlh_submit_group.argtypes = [vp, i32, u32, vp, u32]
     L.jxlh_slot_wait.argtypes = [vp, i32]
     L.jxlh_submit_group_sparse.argtypes = [vp, i32, u32, vp, vp, vp, u32, u32]
@@ -829,6 +926,29 @@ class Context:
         (c0, c1, c2), w, h, stride = _rect_planes((c0, c1, c2), np.int32, w, h, stride)
         self._chk(self.L.jxlh_frame_set_modular_channels(self._ctx, x0, y0, w, h, _addr(c0), _addr(c1), _addr(c2), stride,
                                                          sample_format), "set_modular_channels")
+
+    def set_modular_groups(self, arena, groups, sample_format, n=None, arena_samples=None, wait=True):
+        """jxlh_frame_set_modular_groups (wait=False: the _async form, the arena stays valid until the next sync): every
+        group's coded channels and transform list (pack_local_groups) -> the frame's sample planes in one launch.  arena:
+        an i32 array, or a DeviceArray / raw device pointer with arena_samples."""
+        n = len(groups) if n is None else n
+        if not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+            if not wait:
+                self._keep["local_arena"] = arena
+        fn = self.L.jxlh_frame_set_modular_groups if wait else self.L.jxlh_frame_set_modular_groups_async
+        self._chk(fn(self._ctx, _addr(arena), arena_samples, groups, n, sample_format, None), "set_modular_groups")
+
+    def modular_local_transforms(self, arena, groups, bit_depth, out, out_w, out_h, out_stride, n=None, arena_samples=None):
+        """jxlh_modular_local_transforms: the same launch into caller DEVICE planes (out: DeviceArrays / pointers)"""
+        n = len(groups) if n is None else n
+        if not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+        ptrs = (C.c_void_p * len(out))(*[_addr(o) for o in out])
+        self._chk(self.L.jxlh_modular_local_transforms(self._ctx, _addr(arena), arena_samples, groups, n, bit_depth, ptrs,
+                                                       len(out), out_w, out_h, out_stride, None), "modular_local_transforms")
 
     def set_dequant_tables(self, tables):
         tabs = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]

@@ -1,0 +1,129 @@
+"""Cost of the group-local Modular transforms on the device (k_modular_local.hip, abi_modular_local.hip) on an 8192 x 8192
+8-bit RGB frame in 1024 rects of 256 x 256 (a measurement tool, not a test).
+
+Cases of the new call (jxlh_frame_set_modular_groups*, device-resident arena, the descriptors lowered and uploaded inside
+the timed call): rct = every rect an RCT, types cycling; palette = every rect a 256-colour three-channel palette; mixed =
+half and half.  One JSON line per case:
+  kernel_ms       k_modular_local alone, from the library's event timers: median over `reps` of the mean of `steps`
+  bytes / TBps    the kernel's own traffic (12 B/px read for an RCT rect, 4 B/px for a palette rect, 12 B/px written)
+  call_ms         the _async call by the host clock, `steps` calls and one synchronise: lowering, upload, launch
+  blocking_ms     the blocking call, one at a time
+  host_arena_ms   (rct only) the blocking call with the arena in host memory: the one-copy upload included
+What the interface offered before, on the same data, same session:
+  whole_plane     one whole-plane jxlh_rct (k4_rct, in place) + one whole-frame jxlh_frame_set_modular_channels from device
+                  memory: only possible when all groups share an op
+  per_group       1024 x (jxlh_rct on the group's contiguous buffer + one rect call)
+Two contexts alternate between repetitions.
+
+  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only]
+--kernel-only: a few launches of the rct case and nothing else, for a profiler run of its own."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kernel-only", action="store_true")
+    a = ap.parse_args()
+    import numpy as np
+    import jxl_rs_amd
+    from jxl_rs_amd import lib
+    n, g = a.size, 256
+    rng = np.random.default_rng(1)
+    chan = [rng.integers(0, 64, size=(g, g)).astype(np.int32) for _ in range(3)]
+    index = rng.integers(0, 256, size=(g, g)).astype(np.int32)
+    table = rng.integers(0, 256, size=(3, 256)).astype(np.int32)
+
+    def specs(kind):
+        out = []
+        for k, (gy, gx) in enumerate((y, x) for y in range(0, n, g) for x in range(0, n, g)):
+            pal = kind == "palette" or (kind == "mixed" and k % 2)
+            steps = [lib.local_palette(0, 3, table)] if pal else [lib.local_rct(0, k % 42)]
+            out.append({"x0": gx, "y0": gy, "n_channels": 3, "steps": steps, "coded": [index] if pal else chan})
+        return out
+
+    ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(2)]
+    p = ctxs[0].default_params(n, n)
+    p.gab, p.epf_iters = 0, 0
+    for c in ctxs:
+        c.modular_frame_begin(p)
+
+    def timed(c, call, steps, kernel):
+        c.kernel_timing_reset()
+        c.kernel_timing(True)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            call(c)
+        c.sync()
+        host = (time.perf_counter() - t0) * 1e3 / steps
+        kt = c.kernel_times()
+        c.kernel_timing(False)
+        return host, sum(ms for k, (ms, _) in kt.items() if k == kernel) / steps
+
+    def measure(call, steps, kernel):
+        """median over reps of (host ms per call, kernel ms per call), the two contexts alternating"""
+        for c in ctxs:
+            call(c)
+            c.sync()
+        h, k = zip(*[timed(ctxs[r % 2], call, steps, kernel) for r in range(a.reps)])
+        return statistics.median(h), [min(h), max(h)], statistics.median(k), [min(k), max(k)]
+
+    for kind in ("rct", "palette", "mixed"):
+        sp = specs(kind)
+        arena, groups = lib.pack_local_groups(sp)
+        dev = lib.DeviceArray(arena)
+        launch = lambda c, wait=False: c.set_modular_groups(dev, groups, 8, n=len(sp), arena_samples=arena.size, wait=wait)
+        if a.kernel_only:
+            for _ in range(5):
+                launch(ctxs[0])
+            ctxs[0].sync()
+            dev.free()
+            break
+        n_pal = sum(1 for s in sp if len(s["coded"]) == 1)
+        nbytes = g * g * 4 * (3 * len(sp) + n_pal * 1 + (len(sp) - n_pal) * 3)
+        call_ms, call_mm, k_ms, k_mm = measure(launch, a.steps, "k_modular_local")
+        block_ms = measure(lambda c: launch(c, True), a.steps, "k_modular_local")[0]
+        row = {"case": kind, "frame": f"{n}x{n}", "rects": len(sp), "bytes": nbytes, "kernel_ms": k_ms, "kernel_ms_min_max": k_mm,
+               "TBps": nbytes / k_ms * 1e-9, "call_ms": call_ms, "call_ms_min_max": call_mm, "blocking_ms": block_ms}
+        if kind == "rct":
+            row["host_arena_ms"] = measure(lambda c: c.set_modular_groups(arena, groups, 8, n=len(sp)), 2, "k_modular_local")[0]
+        print(json.dumps(row), flush=True)
+        dev.free()
+    if not a.kernel_only:
+        # the old interface on the same amount of data: three device planes, transformed in place
+        planes = [lib.DeviceArray(rng.integers(0, 64, size=(n, n)).astype(np.int32)) for _ in range(3)]
+
+        def whole(c):
+            c._chk(c.L.jxlh_rct(c._ctx, planes[0].ptr, planes[1].ptr, planes[2].ptr, n * n, 6, 0), "rct")
+            c.set_modular_channels(*[d.ptr for d in planes], 8, w=n, h=n, stride=n)
+
+        h_ms, h_mm, k_ms, k_mm = measure(whole, a.steps, "k4_rct")
+        print(json.dumps({"case": "whole_plane", "call_ms": h_ms, "call_ms_min_max": h_mm, "k4_rct_ms": k_ms, "k4_rct_ms_min_max": k_mm,
+                          "k4_rct_TBps": 24 * n * n / k_ms * 1e-9}), flush=True)
+        bufs = [lib.DeviceArray(c) for c in chan]
+
+        def per_group(c):
+            for k, (gy, gx) in enumerate((y, x) for y in range(0, n, g) for x in range(0, n, g)):
+                c._chk(c.L.jxlh_rct(c._ctx, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, g * g, k % 7, k // 7 % 6), "rct")
+                c.set_modular_channels(*[d.ptr for d in bufs], 8, x0=gx, y0=gy, w=g, h=g, stride=g)
+
+        h_ms, h_mm, _, _ = measure(per_group, 2, "k4_rct")
+        print(json.dumps({"case": "per_group", "call_ms": h_ms, "call_ms_min_max": h_mm}), flush=True)
+        for d in planes + bufs:
+            d.free()
+    for c in ctxs:
+        c.close()
+
+
+if __name__ == "__main__":
+    main()
