@@ -723,11 +723,9 @@ bool noise_lut_is_zero(const float lut[8]) {
   return true;
 }
 
-// chroma upsampling of the sub-sampled channels, tmp[c] -> planes[c], over the rows K1 produced for group rows
-// [gr0, gr1) (the outermost rows of a halo group row read beyond the region, and nobody reads them)
-void run_chroma_upsample(jxlh_ctx* ctx, int gr0, int gr1) { run_chroma_upsample_rows(ctx, gr0 * kGroupDim, gr1 * kGroupDim); }
-
-// ... over the rows of the sub-sampled channels that cover pixel rows [y0, y1) (y0 even)
+// chroma upsampling of the sub-sampled channels, tmp[c] -> planes[c], over the rows of the sub-sampled channels that
+// cover pixel rows [y0, y1) (y0 even).  Over the rows K1 produced for group rows: the outermost rows of a halo group row
+// read beyond the region, and nobody reads them.
 void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1) {
   const FrameDev& f = ctx->fd;
   ScopedKernelTimer t(ctx, "k_chroma_upsample");
@@ -744,7 +742,7 @@ void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1) {
 
 void materialise_chroma(jxlh_ctx* ctx) {
   if (!ctx->chroma_lazy) return;
-  run_chroma_upsample(ctx, ctx->lazy_gr0, ctx->lazy_gr1);
+  run_chroma_upsample_rows(ctx, ctx->lazy_gr0 * kGroupDim, ctx->lazy_gr1 * kGroupDim);
   ctx->chroma_lazy = false;
 }
 
@@ -848,15 +846,32 @@ static jxlh_status apply_coeff_epoch(jxlh_ctx* ctx, bool want_strip, bool* spars
   return JXLH_OK;
 }
 
+// the frame's stage list, and what a run's routing reads from the context (run_plan.h; takes the snapshot of the
+// LF-only marks)
+StageList stage_list(const jxlh_ctx* ctx) {
+  return StageList{ctx->fd.gab != 0, ctx->fd.epf_iters, (ctx->params.flags & JXLH_FRAME_UNFUSED_FILTERS) != 0};
+}
+RunInputs run_inputs(jxlh_ctx* ctx) {
+  const FrameDev& f = ctx->fd;
+  const jxlh_frame_params& p = ctx->params;
+  static const bool strip_forced = [] {  // JXLH_STRIP=1: every eligible frame, whatever its flags say (A/B runs of whole suites)
+    const char* e = getenv("JXLH_STRIP");
+    return e && *e && *e != '0';
+  }();
+  return RunInputs{stage_list(ctx), f.xgroups, f.ygroups, f.ysize, (int)p.upsampling, comm_nranks(ctx), f.subsampled != 0,
+                   ctx->modular, p.noise && !noise_lut_is_zero(p.noise_lut), draws_in_place(ctx),
+                   strip_forced || (p.flags & JXLH_FRAME_STRIP), lf_only_snapshot(ctx), ctx->rendered, ctx->strip_ran};
+}
+
 // everything before K1: upload fences, the coefficient transport, K0b, K3 sigma
-jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan) {
+jxlh_status run_prologue(jxlh_ctx* ctx, bool strip_candidate, bool tiled, bool* sparse_k1) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
   // coefficient uploads issued on slot streams must land before K1
   for (auto& s : ctx->slots) {
     if (s.used) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s.done, 0));
   }
-  if (jxlh_status st = apply_coeff_epoch(ctx, plan->want_strip, &plan->sparse_k1)) return st;
+  if (jxlh_status st = apply_coeff_epoch(ctx, strip_candidate, sparse_k1)) return st;
   // ---- K0b: Frame::finalize_lf (frame/mod.rs:360-378)
   // (adaptive_lf_smoothing.rs:51-53; an LF image taken from an LF frame is used as it is, frame_header.rs:496-500)
   const bool smooth = p.do_lf_smoothing && !ctx->lf_from_slot && f.xblocks > 2 && f.yblocks > 2;
@@ -880,11 +895,7 @@ jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan) {
     ScopedKernelTimer t(ctx, "k3_sigma_map");
     launch_sigma_map(ctx->stream, f, p.epf_quant_mul, p.epf_sharp_lut);
   }
-  plan->halo_px = (f.gab ? 1 : 0) + (f.epf_iters >= 3 ? 3 : 0) + (f.epf_iters >= 1 ? 2 : 0) + (f.epf_iters >= 2 ? 1 : 0);
-  // K1 writes the 8x8-tiled layout whenever the fused filter kernel is its only consumer
-  plan->will_fuse = !(p.flags & JXLH_FRAME_UNFUSED_FILTERS) && (f.gab || f.epf_iters > 0);
-  f.tiled = plan->will_fuse ? 1 : 0;
-  plan->want_strip = plan->want_strip && !plan->sparse_k1;
+  f.tiled = tiled ? 1 : 0;
   return JXLH_OK;
 }
 
@@ -903,7 +914,6 @@ static void set_sparse_view(jxlh_ctx* ctx, FrameDev& f, bool sparse_k1) {
   f.se_dense_hint = ent ? e.live.se_dense_hint : 0;
   f.k1_stats = ctx->timing ? 1 : 0;
 }
-static int dense_route_groups(const jxlh_ctx* ctx, bool sparse_k1) { return sparse_k1 ? ctx->epoch.live.n_route : 0; }
 // behind the transforms: the coefficient slabs are free again (dense resubmissions of the next frame wait for this,
 // jxlh_submit_group), and so is the live set of the slot-bucketed form once it has become the pending one
 static jxlh_status mark_coefficients_read(jxlh_ctx* ctx, bool sparse_k1) {
@@ -919,13 +929,34 @@ static jxlh_status mark_coefficients_read(jxlh_ctx* ctx, bool sparse_k1) {
   return JXLH_OK;
 }
 
-// K1 for group rows [gr0, gr1) (+ the chroma upsampling of a sub-sampled frame)
-jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan, int gr0, int gr1) {
+// The transforms of group rows [gr0, gr1) or, `listed`, of the first n_k1 groups of rerender_list; the LF fill of the
+// n_fill groups listed behind them (jxlh_frame_set_groups_lf_only; never a sub-sampled frame): it writes them into the
+// same planes, their coefficient store is not read.
+static jxlh_status run_transforms(jxlh_ctx* ctx, bool sparse_k1, int gr0, int gr1, bool listed, int n_k1, int n_fill) {
   FrameDev& f = ctx->fd;
-  const jxlh_frame_params& p = ctx->params;
-  const bool sparse_k1 = plan.sparse_k1;
-  // Groups without HF (jxlh_frame_set_groups_lf_only; never a sub-sampled frame): K1 runs on the band's other groups
-  // through its group list, the fill writes the marked ones into the same planes.  Their coefficient store is not read.
+  {
+    ScopedKernelTimer t(ctx, "k1_vardct");
+    set_sparse_view(ctx, f, sparse_k1);
+    // (a whole-frame run rewrites every group's flag in k1_scan: no clearing launch then)
+    if (sparse_k1 && (listed || !(gr0 == 0 && gr1 == f.ygroups)))
+      HIPCHK(ctx, hipMemsetAsync(ctx->group_dense.p, 0, ctx->ngroups, ctx->stream));
+    // a sub-sampled channel is reconstructed at its own resolution into tmp[c] ...
+    FrameDev fk = f;
+    for (int c = 0; c < 3; c++)
+      if (f.hshift[c] | f.vshift[c]) fk.planes[c] = f.tmp[c];
+    launch_vardct_groups(ctx->stream, fk, listed ? 0 : gr0, listed ? 0 : gr1, ctx->worklist.p, &ctx->k1_launches,
+                         ctx->error_flag.p, sparse_k1 ? ctx->coeffs.p : nullptr, listed ? ctx->rerender_list.p : nullptr,
+                         listed ? n_k1 : 0, ctx->has_special, ctx->has_large, sparse_k1 ? ctx->epoch.live.n_route : 0);
+  }
+  if (jxlh_status st = run_lf_fill(ctx, f, ctx->rerender_list.p + n_k1, n_fill)) return st;
+  return mark_coefficients_read(ctx, sparse_k1);
+}
+
+// K1 for the plan's group rows (+ the chroma upsampling of a sub-sampled frame)
+jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan) {
+  const FrameDev& f = ctx->fd;
+  const int gr0 = plan.k1_row0, gr1 = plan.k1_row1;
+  // a run with marked groups: K1 runs on the band's other groups through its group list
   const bool lf_only = !ctx->lf_only_run.empty();
   int n_k1 = 0, n_fill = 0;
   if (lf_only) {
@@ -933,61 +964,21 @@ jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan, int gr0, int gr1) {
     for (int g = gr0 * f.xgroups; g < gr1 * f.xgroups; g++) band.push_back(g);
     if (jxlh_status st = lf_split_groups(ctx, band, &n_k1, &n_fill)) return st;
   }
-  {
-    ScopedKernelTimer t(ctx, "k1_vardct");
-    set_sparse_view(ctx, f, sparse_k1);
-    // (a whole-frame run rewrites every group's flag in k1_scan: no clearing launch then)
-    if (sparse_k1 && (lf_only || !(gr0 == 0 && gr1 == f.ygroups)))
-      HIPCHK(ctx, hipMemsetAsync(ctx->group_dense.p, 0, ctx->ngroups, ctx->stream));
-    // a sub-sampled channel is reconstructed at its own resolution into tmp[c] ...
-    FrameDev fk = f;
-    for (int c = 0; c < 3; c++)
-      if (f.hshift[c] | f.vshift[c]) fk.planes[c] = f.tmp[c];
-    if (lf_only)
-      launch_vardct_groups(ctx->stream, fk, 0, 0, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
-                           sparse_k1 ? ctx->coeffs.p : nullptr, ctx->rerender_list.p, n_k1, ctx->has_special,
-                           ctx->has_large, dense_route_groups(ctx, sparse_k1));
-    else
-      launch_vardct_groups(ctx->stream, fk, gr0, gr1, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
-                           sparse_k1 ? ctx->coeffs.p : nullptr, nullptr, 0, ctx->has_special, ctx->has_large,
-                           dense_route_groups(ctx, sparse_k1));
-  }
-  if (jxlh_status st = run_lf_fill(ctx, f, ctx->rerender_list.p + n_k1, n_fill)) return st;
-  if (jxlh_status st = mark_coefficients_read(ctx, sparse_k1)) return st;
-  ctx->chroma_lazy = false;
+  if (jxlh_status st = run_transforms(ctx, plan.sparse_k1, gr0, gr1, lf_only, n_k1, n_fill)) return st;
+  ctx->chroma_lazy = plan.chroma_lazy;
   if (f.subsampled) {
-    // ... and brought to full resolution into planes[c] before any filter (frame/render.rs:569-576) -- or, when no
-    // stage follows at all, only when the planes are asked for (materialise_chroma)
-    const bool stages_follow = f.gab || f.epf_iters > 0 || p.upsampling > 1 || (p.noise && !noise_lut_is_zero(p.noise_lut)) ||
-                               draws_in_place(ctx);
+    // ... and brought to full resolution into planes[c] before any filter, or lazily (run_plan.h: band_plan)
     ctx->lazy_gr0 = gr0;
     ctx->lazy_gr1 = gr1;
-    // A sharded frame gathers planes[c] band by band (jxlh_frame_allgather): the full-resolution chroma must exist
-    // on every rank before the gather, and a deferred upsampling would cover only this rank's band afterwards.
-    if (stages_follow || jxlh_host::comm_nranks(ctx) > 1) run_chroma_upsample(ctx, gr0, gr1);
-    else ctx->chroma_lazy = true;
+    if (!plan.chroma_lazy) run_chroma_upsample_rows(ctx, gr0 * kGroupDim, gr1 * kGroupDim);
   }
   return JXLH_OK;
 }
 
-// Whole-frame runs of a 4:4:4 frame with Gaborish and / or EPF1 (+ EPF2) may go through the strip kernel (k_strip.hip):
-// opt-in (JXLH_FRAME_STRIP), see the flag's comment in jxl_hip.h
-bool strip_eligible(const jxlh_ctx* ctx) {
-  const FrameDev& f = ctx->fd;
-  const jxlh_frame_params& p = ctx->params;
-  static const bool forced = [] {  // JXLH_STRIP=1: every eligible frame, whatever its flags say (A/B runs of whole suites)
-    const char* e = getenv("JXLH_STRIP");
-    return e && *e && *e != '0';
-  }();
-  return (forced || (p.flags & JXLH_FRAME_STRIP)) && !(p.flags & JXLH_FRAME_UNFUSED_FILTERS) && !f.subsampled &&
-         f.epf_iters <= 2 && (f.gab || f.epf_iters >= 1) && comm_nranks(ctx) <= 1;
-}
-
 // transforms + stage list of the whole frame in the strip kernel; tiles it cannot take (k1_scan decides) go through
 // K1's class kernels first
-jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan) {
+jxlh_status run_strip(jxlh_ctx* ctx) {
   FrameDev& f = ctx->fd;
-  (void)plan;
   if (!ctx->cu_count) {
     hipDeviceProp_t prop;
     HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
@@ -1041,7 +1032,7 @@ jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan) {
                       ctx->error_flag.p, deadline_s)) {
       f.strip_desc = nullptr;
       f.strip_mode = nullptr;
-      return JXLH_ERR_UNSUPPORTED;  // stage list not covered (strip_eligible should have said so)
+      return JXLH_ERR_UNSUPPORTED;  // stage list not covered (run_plan.h: strip_eligible should have said so)
     }
   }
   f.strip_desc = nullptr;  // band runs / re-renders of this frame take the two-kernel path
@@ -1054,44 +1045,25 @@ jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan) {
   return run_post_stages(ctx, f.tmp, 0, f.ysize, true);
 }
 
-// the stage list on group rows [group_row0, group_row1), then upsampling and noise
-jxlh_status run_stages(jxlh_ctx* ctx, const RunPlan& plan, uint32_t group_row0, uint32_t group_row1) {
-  const bool whole = group_row0 == 0 && group_row1 == (uint32_t)ctx->fd.ygroups;
-  return run_stages_rows(ctx, plan, (int)group_row0 * kGroupDim, min((int)group_row1 * kGroupDim, ctx->fd.ysize), whole);
-}
-
-// ... on pixel rows [y_lo, y_hi)
-jxlh_status run_stages_rows(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_hi, bool whole_frame) {
+// the stage list on pixel rows [y_lo, y_hi), then upsampling and noise
+jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& sl, int y_lo, int y_hi, bool whole_frame) {
   FrameDev& f = ctx->fd;
-  const jxlh_frame_params& p = ctx->params;
-  (void)plan;
   // ---- stage list of frame/render.rs:569-622
-  int stages[4], borders[4], ns = 0;
-  if (f.gab) { stages[ns] = -1; borders[ns++] = 1; }
-  if (f.epf_iters >= 3) { stages[ns] = 0; borders[ns++] = 3; }
-  if (f.epf_iters >= 1) { stages[ns] = 1; borders[ns++] = 2; }
-  if (f.epf_iters >= 2) { stages[ns] = 2; borders[ns++] = 1; }
+  StageList::Stage stages[4];
+  int ns = sl.sequence(stages);
   float* cur[3] = {f.planes[0], f.planes[1], f.planes[2]};
   float* oth[3] = {f.tmp[0], f.tmp[1], f.tmp[2]};
-  if (!(p.flags & JXLH_FRAME_UNFUSED_FILTERS) && ns > 0) {
+  if (sl.fused()) {
     // production path: the whole stage list in one pass over HBM (two for epf_iters == 3)
     ScopedKernelTimer t(ctx, "k23_fused_filters");
-    const int where = launch_fused_filters(ctx->stream, f, y_lo, y_hi);
-    if (where == 1) {
-      for (int c = 0; c < 3; c++) {
-        cur[c] = f.tmp[c];
-        oth[c] = f.planes[c];
-      }
-      ns = 0;
-    } else if (where == 2) {
-      ns = 0;  // result back in f.planes
-    }
+    (void)launch_fused_filters(ctx->stream, f, y_lo, y_hi);
+    if (sl.result_in_tmp()) std::swap(cur, oth);
+    ns = 0;
   }
   for (int s = 0; s < ns; s++) {
-    int later = 0;
-    for (int k = s + 1; k < ns; k++) later += borders[k];
+    const int later = sl.reach_after(s), kind = stages[s].kind;
     const int y0 = max(0, y_lo - later), y1 = min(f.ysize, y_hi + later);
-    if (stages[s] < 0) {
+    if (kind == StageList::kGaborish) {
       ScopedKernelTimer t(ctx, "k2_gaborish");
       for (int c = 0; c < 3; c++)
         launch_gaborish(ctx->stream, cur[c], oth[c], f.xsize, f.ysize, f.plane_stride, f.gab_k[c][0], f.gab_k[c][1],
@@ -1108,17 +1080,13 @@ jxlh_status run_stages_rows(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_
       a.sigma_stride = (size_t)f.xblocks;
       a.w = f.xsize;
       a.h = f.ysize;
-      a.sm = f.epf_sm[stages[s]];
-      a.bsm = f.epf_bsm[stages[s]];
+      a.sm = f.epf_sm[kind];
+      a.bsm = f.epf_bsm[kind];
       static const char* names[3] = {"k3a_epf0", "k3b_epf1", "k3c_epf2"};
-      ScopedKernelTimer t(ctx, names[stages[s]]);
-      launch_epf(ctx->stream, stages[s], a, y0, y1);
+      ScopedKernelTimer t(ctx, names[kind]);
+      launch_epf(ctx->stream, kind, a, y0, y1);
     }
-    for (int c = 0; c < 3; c++) {
-      float* t = cur[c];
-      cur[c] = oth[c];
-      oth[c] = t;
-    }
+    std::swap(cur, oth);
   }
   return run_post_stages(ctx, cur, y_lo, y_hi, whole_frame);
 }
@@ -1243,40 +1211,24 @@ jxlh_status jxlh_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_ro
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame || (!ctx->modular && !ctx->tables_set)) return JXLH_ERR_BAD_STATE;
-  FrameDev& f = ctx->fd;
-  if (group_row1 > (uint32_t)f.ygroups) group_row1 = (uint32_t)f.ygroups;
+  group_row1 = std::min(group_row1, (uint32_t)ctx->fd.ygroups);
   if (group_row0 >= group_row1) return JXLH_ERR_INVALID_ARGUMENT;
   if (ctx->modular) return modular_frame_run(ctx, group_row0, group_row1);
   if (jxlh_status st = patches_check_run(ctx)) return st;
-  RunPlan plan;
-  bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
-  // (a frame with a group whose HF has not arrived takes the two-kernel path: the strip kernel transforms every tile)
-  const bool lf_only = lf_only_snapshot(ctx);
-  plan.want_strip = whole && !lf_only && strip_eligible(ctx);
-  if (jxlh_status st = run_prologue(ctx, &plan)) return st;
-  // Patches and splines are drawn in place on the result.  When the result lives in the planes K1 writes and K1 rewrites a group
-  // row beyond the band (the filters' or the chroma upsampling's halo), a band run would overwrite the neighbouring
-  // band's drawn pixels with bare ones: such a frame is rendered whole.
-  if (!whole && draws_in_place(ctx) && (plan.halo_px > 0 || f.subsampled) && result_in_tmp(ctx) == 0) {
-    group_row0 = 0;
-    group_row1 = (uint32_t)f.ygroups;
-    whole = true;
-  }
+  RunPlan plan = plan_run(run_inputs(ctx), (int)group_row0, (int)group_row1);
+  bool sparse_k1 = false;
+  if (jxlh_status st = run_prologue(ctx, plan.strip_candidate, plan.tiled, &sparse_k1)) return st;
+  plan = resolve_strip(plan, sparse_k1);
   ctx->strip_ran = false;
-  if (plan.want_strip) {
-    const jxlh_status st = run_strip(ctx, plan);
+  if (plan.strip) {
+    const jxlh_status st = run_strip(ctx);
     if (st != JXLH_ERR_UNSUPPORTED) return st;
     ctx->fd.strip_desc = nullptr;  // (nothing was launched) the two-kernel path takes the frame
     ctx->fd.strip_mode = nullptr;
   }
-  // ---- K1 on the band plus one halo group row on each side (filters read across it)
-  // (vertical chroma upsampling reads one sub-sampled row beyond the band as well)
-  const bool need_halo = plan.halo_px > 0 || f.subsampled;
-  const int gr0 = need_halo && group_row0 > 0 ? (int)group_row0 - 1 : (int)group_row0;
-  const int gr1 = need_halo && group_row1 < (uint32_t)f.ygroups ? (int)group_row1 + 1 : (int)group_row1;
-  if (jxlh_status st = run_k1(ctx, plan, gr0, gr1)) return st;
-  if (group_row0 == 0 && group_row1 == (uint32_t)f.ygroups) ctx->rendered = true;
-  return run_stages(ctx, plan, group_row0, group_row1);
+  if (jxlh_status st = run_k1(ctx, plan)) return st;
+  if (plan.whole) ctx->rendered = true;
+  return run_stages_rows(ctx, plan.stages, plan.y_lo, plan.y_hi, plan.whole);
 }
 
 jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids, uint32_t count) {
@@ -1285,74 +1237,29 @@ jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids,
   if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
   if (ctx->modular) return JXLH_ERR_UNSUPPORTED;  // a progressive Modular decode sets the changed rects and runs again
   if (!ctx->tables_set) return JXLH_ERR_BAD_STATE;
-  FrameDev& f = ctx->fd;
   for (uint32_t i = 0; i < count; i++)
     if (group_ids[i] >= ctx->ngroups) return JXLH_ERR_INVALID_ARGUMENT;
   if (count == 0) return JXLH_OK;
   if (jxlh_status st = patches_check_run(ctx)) return st;
-  const jxlh_frame_params& p = ctx->params;
-  if (p.upsampling > 1) return JXLH_ERR_UNSUPPORTED;  // like a band run: the 5x5 upsampling window crosses groups
-  // a rank of a sharded frame holds only its band: progressive re-renders run on unsharded contexts
-  if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;
-  const int ns = (f.gab ? 1 : 0) + (f.epf_iters >= 3 ? 1 : 0) + (f.epf_iters >= 1 ? 1 : 0) + (f.epf_iters >= 2 ? 1 : 0);
-  // Re-rendering a group needs its neighbours' UNFILTERED pixels (the filters read across the group edge).  They
-  // are still in `planes` when the stage list leaves its result in `tmp` (the fused path with up to two EPF passes,
-  // or no filter at all); a stage list that ends in `planes` has overwritten them, a sub-sampled frame keeps them
-  // in another form, and a frame that was never rendered has none: those render the frame again.
-  const bool per_stage = (p.flags & JXLH_FRAME_UNFUSED_FILTERS) != 0;  // ping-pongs planes <-> tmp: kept only for one stage
-  const bool unfiltered_kept = !ctx->strip_ran && (ns == 0 || (per_stage ? ns == 1 : result_in_tmp(ctx) != 0));
-  // Noise is added IN PLACE to the result planes.  Without a filter stage the result lives in `planes`, the planes K1
-  // writes: the groups that are not re-transformed would receive their noise a second time.
-  // The same holds for patches and splines: they are drawn in place (an Add would reach the other groups twice).
-  const bool noise_in_place = ns == 0 && ((p.noise && !noise_lut_is_zero(p.noise_lut)) || draws_in_place(ctx));
-  if (!ctx->rendered || !unfiltered_kept || f.subsampled || noise_in_place) return jxlh_frame_run(ctx, 0, UINT32_MAX);
-  RunPlan plan;
-  if (jxlh_status st = run_prologue(ctx, &plan)) return st;
-  // ---- transforms of exactly the listed groups
   ctx->rerender_upload.assign(group_ids, group_ids + count);
   std::sort(ctx->rerender_upload.begin(), ctx->rerender_upload.end());
   ctx->rerender_upload.erase(std::unique(ctx->rerender_upload.begin(), ctx->rerender_upload.end()),
                              ctx->rerender_upload.end());
-  const int n = (int)ctx->rerender_upload.size();
+  const RunInputs in = run_inputs(ctx);
+  const RerenderPlan plan = plan_rerender(in, ctx->rerender_upload);
+  if (plan.route == RerenderPlan::kUnsupported) return JXLH_ERR_UNSUPPORTED;
+  if (plan.route == RerenderPlan::kFullRun) return jxlh_frame_run(ctx, 0, UINT32_MAX);
+  bool sparse_k1 = false;
+  if (jxlh_status st = run_prologue(ctx, false, in.stages.fused(), &sparse_k1)) return st;
+  // ---- transforms of exactly the listed groups
   // a listed group whose HF has not arrived (jxlh_frame_set_groups_lf_only) is filled from the LF image again, the
   // others are transformed: the list goes up with the transforms' groups first
-  int n_k1 = n, n_fill = 0;
-  if (lf_only_snapshot(ctx)) {
-    if (jxlh_status st = lf_split_groups(ctx, ctx->rerender_upload, &n_k1, &n_fill)) return st;
-  } else {
-    if (jxlh_status st = ensure(ctx, ctx->rerender_list, (size_t)n)) return st;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rerender_list.p, ctx->rerender_upload.data(), n * sizeof(int), hipMemcpyHostToDevice,
-                               ctx->stream));
-  }
-  {
-    ScopedKernelTimer t(ctx, "k1_vardct");
-    set_sparse_view(ctx, f, plan.sparse_k1);
-    if (plan.sparse_k1) HIPCHK(ctx, hipMemsetAsync(ctx->group_dense.p, 0, ctx->ngroups, ctx->stream));
-    launch_vardct_groups(ctx->stream, f, 0, 0, ctx->worklist.p, &ctx->k1_launches, ctx->error_flag.p,
-                         plan.sparse_k1 ? ctx->coeffs.p : nullptr, ctx->rerender_list.p, n_k1, ctx->has_special,
-                         ctx->has_large, dense_route_groups(ctx, plan.sparse_k1));
-  }
-  if (jxlh_status st = run_lf_fill(ctx, f, ctx->rerender_list.p + n_k1, n_fill)) return st;
-  if (jxlh_status st = mark_coefficients_read(ctx, plan.sparse_k1)) return st;
-  // ---- the filters on every pixel row the listed groups influence: their own rows widened by the stage list's
-  // reach (mark_group_to_rerender's 3x3 neighbourhood, restricted to what can actually change), merged into bands
-  int prev_lo = -1, prev_hi = -1;
-  for (int i = 0; i <= n; i++) {
-    int lo = -1, hi = -1;
-    if (i < n) {
-      const int gy = ctx->rerender_upload[i] / f.xgroups;
-      lo = max(0, gy * kGroupDim - plan.halo_px);
-      hi = min(f.ysize, (gy + 1) * kGroupDim + plan.halo_px);
-    }
-    if (i < n && prev_hi >= lo) {
-      prev_hi = max(prev_hi, hi);
-      continue;
-    }
-    if (prev_lo >= 0)
-      if (jxlh_status st = run_stages_rows(ctx, plan, prev_lo, prev_hi, prev_lo == 0 && prev_hi == f.ysize)) return st;
-    prev_lo = lo;
-    prev_hi = hi;
-  }
+  int n_k1 = 0, n_fill = 0;
+  if (jxlh_status st = lf_split_groups(ctx, ctx->rerender_upload, &n_k1, &n_fill)) return st;
+  if (jxlh_status st = run_transforms(ctx, sparse_k1, 0, 0, true, n_k1, n_fill)) return st;
+  // ---- the filters on every pixel row the listed groups influence
+  for (const RowBand& b : plan.bands)
+    if (jxlh_status st = run_stages_rows(ctx, in.stages, b.y_lo, b.y_hi, b.whole_frame)) return st;
   return JXLH_OK;
 }
 

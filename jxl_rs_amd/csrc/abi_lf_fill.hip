@@ -21,12 +21,13 @@ bool lf_only_snapshot(jxlh_ctx* ctx) {
 
 jxlh_status lf_split_groups(jxlh_ctx* ctx, const std::vector<int>& groups, int* n_k1, int* n_fill) {
   std::vector<int>& up = ctx->lf_split_upload;
+  const std::vector<uint8_t>& marks = ctx->lf_only_run;  // (empty: no group is marked)
   up.clear();
   for (int g : groups)
-    if (!ctx->lf_only_run[(size_t)g]) up.push_back(g);
+    if (marks.empty() || !marks[(size_t)g]) up.push_back(g);
   *n_k1 = (int)up.size();
   for (int g : groups)
-    if (ctx->lf_only_run[(size_t)g]) up.push_back(g);
+    if (!marks.empty() && marks[(size_t)g]) up.push_back(g);
   *n_fill = (int)up.size() - *n_k1;
   if (up.empty()) return JXLH_OK;
   if (jxlh_status st = ensure(ctx, ctx->rerender_list, up.size())) return st;

@@ -51,31 +51,12 @@ jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
   if (jxlh_status st = patches_check_run(ctx)) return st;
-  RunPlan plan;
-  const int ns = (f.gab ? 1 : 0) + (f.epf_iters >= 3 ? 1 : 0) + (f.epf_iters >= 1 ? 1 : 0) + (f.epf_iters >= 2 ? 1 : 0);
-  plan.halo_px = (f.gab ? 1 : 0) + (f.epf_iters >= 3 ? 3 : 0) + (f.epf_iters >= 1 ? 2 : 0) + (f.epf_iters >= 2 ? 1 : 0);
-  const bool per_stage = (p.flags & JXLH_FRAME_UNFUSED_FILTERS) != 0;
-  plan.will_fuse = !per_stage && ns > 0;
-  f.tiled = 0;  // the intake writes raster planes
-  bool whole = group_row0 == 0 && group_row1 == (uint32_t)f.ygroups;
-  // A band's halo rows are taken in again with every run.  When the stage list ends in the planes the intake writes
-  // (no stage would be fine, but it has no halo; the two-pass list of epf_iters == 3; an even number of single stages)
-  // that undoes the neighbouring band's finished rows -- drawn patches and splines included --, and the single stages
-  // of JXLH_FRAME_UNFUSED_FILTERS write their intermediate halo rows over the neighbour's result in either set of
-  // planes.  A sub-sampled channel is taken into tmp[c], the other set: with a halo its rows land on the neighbour's
-  // result when the list ends THERE.  So a sub-sampled frame with a filter has no safe set at all.  Such frames are
-  // rendered whole.
-  if (!whole && plan.halo_px > 0 && (result_in_tmp(ctx) == 0 || (per_stage && ns > 1) || f.subsampled)) {
-    group_row0 = 0;
-    group_row1 = (uint32_t)f.ygroups;
-    whole = true;
-  }
+  // (a band whose halo rows would undo the neighbouring band's finished rows is rendered whole: run_plan.h)
+  const RunPlan plan = plan_run(run_inputs(ctx), (int)group_row0, (int)group_row1);
+  f.tiled = plan.tiled ? 1 : 0;  // the intake writes raster planes
   ctx->strip_ran = false;
-  ctx->chroma_lazy = false;
-  const int y_lo = (int)group_row0 * kGroupDim, y_hi = std::min((int)group_row1 * kGroupDim, f.ysize);
-  // the filters read up to 7 rows beyond the band, and the first pass of epf_iters == 3 starts on a multiple of 4: 8
-  const int halo = plan.halo_px > 0 ? 8 : 0;
-  const int ya = std::max(0, y_lo - halo), yb = std::min(f.ysize, y_hi + halo);
+  ctx->chroma_lazy = plan.chroma_lazy;
+  const int ya = plan.intake_y0, yb = plan.intake_y1;
   {
     IntakeLaunch a{};
     const uint32_t fmt = ctx->mod_format ? ctx->mod_format : 8u;  // (no rect was set: zero samples in any format)
@@ -89,7 +70,7 @@ jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group
       a.src[c] = ctx->mod_src[c].p;
       a.w[c] = (f.xsize + (1 << hs) - 1) >> hs;
       const int ch = (f.ysize + (1 << vs) - 1) >> vs;
-      // a sub-sampled channel goes where K1 puts it: tmp[c], for run_chroma_upsample; the vertical upsampling reads one
+      // a sub-sampled channel goes where K1 puts it: tmp[c], for run_chroma_upsample_rows; the vertical upsampling reads one
       // row of the channel beyond the rows it produces
       a.dst[c] = (hs | vs) ? f.tmp[c] : f.planes[c];
       a.y0[c] = vs ? std::max(0, (ya >> vs) - 1) : ya;
@@ -100,8 +81,8 @@ jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group
     launch_modular_intake(ctx->stream, a);
   }
   if (f.subsampled) run_chroma_upsample_rows(ctx, ya, yb);  // frame/render.rs:569-576, in front of the filters
-  if (whole) ctx->rendered = true;
-  return run_stages_rows(ctx, plan, y_lo, y_hi, whole);
+  if (plan.whole) ctx->rendered = true;
+  return run_stages_rows(ctx, plan.stages, plan.y_lo, plan.y_hi, plan.whole);
 }
 
 }  // namespace jxlh_host

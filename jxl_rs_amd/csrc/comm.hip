@@ -209,14 +209,8 @@ static void block_row_span(const FrameDev& f, int by, size_t* off, size_t* count
   }
 }
 
-static bool exchange_applies(const jxlh_ctx* ctx, const RunPlan& plan) {
-  // chroma-subsampled frames keep the recomputed halo group row (their vertical upsampling reads across the band
-  // edge in the sub-sampled domain); frames without filters need no halo at all
-  return plan.halo_px > 0 && !ctx->fd.subsampled;
-}
-
-// transforms of the own band (plus recomputed halo group rows when the exchange does not apply)
-static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan, int* r0, int* r1) {
+// transforms of the own band (plus recomputed halo group rows when the exchange does not apply: plan_shard)
+static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan) {
   if (!ctx->in_frame || ctx->modular || !ctx->tables_set) return JXLH_ERR_BAD_STATE;
   if (ctx->params.upsampling > 1) return JXLH_ERR_UNSUPPORTED;  // the 5x5 upsampling window crosses bands: run whole
   const Comm* c = ctx->comm;
@@ -224,15 +218,14 @@ static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan, int* r0, int* r1) {
   // (splines likewise: a segment crosses band edges)
   if (draws_in_place(ctx) && c->nranks > 1) return JXLH_ERR_UNSUPPORTED;
   if (jxlh_status st = patches_check_run(ctx)) return st;
-  band_of(ctx->fd.ygroups, c->nranks, c->rank, r0, r1);
-  if (jxlh_status st = run_prologue(ctx, plan)) return st;
-  if (*r0 >= *r1) return JXLH_OK;
-  int g0 = *r0, g1 = *r1;
-  if (!exchange_applies(ctx, *plan) && (plan->halo_px > 0 || ctx->fd.subsampled)) {
-    g0 = std::max(0, g0 - 1);
-    g1 = std::min(ctx->fd.ygroups, g1 + 1);
-  }
-  return run_k1(ctx, *plan, g0, g1);
+  int r0, r1;
+  band_of(ctx->fd.ygroups, c->nranks, c->rank, &r0, &r1);
+  *plan = plan_shard(run_inputs(ctx), r0, r1);
+  bool sparse_k1 = false;
+  if (jxlh_status st = run_prologue(ctx, false, plan->tiled, &sparse_k1)) return st;
+  *plan = resolve_strip(*plan, sparse_k1);
+  if (r0 >= r1) return JXLH_OK;
+  return run_k1(ctx, *plan);
 }
 
 }  // namespace jxlh_host
@@ -347,10 +340,10 @@ jxlh_status jxlh_frame_run_sharded(jxlh_ctx* ctx) {
   Comm* c = ctx->comm;
   RcclApi* api = rccl_api(nullptr);
   RunPlan plan;
-  int r0, r1;
-  if (jxlh_status st = shard_k1(ctx, &plan, &r0, &r1)) return st;
+  if (jxlh_status st = shard_k1(ctx, &plan)) return st;
+  const int r0 = plan.group_row0, r1 = plan.group_row1;
   const FrameDev& f = ctx->fd;
-  if (exchange_applies(ctx, plan) && c->nranks > 1) {
+  if (plan.exchange && c->nranks > 1) {
     // neighbours = the adjacent NON-EMPTY bands (empty bands only trail)
     int up0, up1, dn0, dn1;
     const bool mine = r0 < r1;
@@ -386,7 +379,17 @@ jxlh_status jxlh_frame_run_sharded(jxlh_ctx* ctx) {
     }
   }
   if (r0 >= r1) return JXLH_OK;
-  return run_stages(ctx, plan, (uint32_t)r0, (uint32_t)r1);
+  return run_stages_rows(ctx, plan.stages, plan.y_lo, plan.y_hi, plan.whole);
+}
+
+// where a band run left the finished planes (a rank whose band is empty ran no stage: the frame's stage list says
+// where the result lives) + the geometry the read-out stages use
+static void set_band_result(jxlh_ctx* ctx) {
+  const FrameDev& f = ctx->fd;
+  for (int ch = 0; ch < 3; ch++) ctx->result[ch] = stage_list(ctx).result_in_tmp() ? f.tmp[ch] : f.planes[ch];
+  ctx->res_w = f.xsize;
+  ctx->res_h = f.ysize;
+  ctx->res_stride = f.plane_stride;
 }
 
 jxlh_status jxlh_frame_allgather(jxlh_ctx* ctx) {
@@ -397,28 +400,14 @@ jxlh_status jxlh_frame_allgather(jxlh_ctx* ctx) {
   Comm* c = ctx->comm;
   RcclApi* api = rccl_api(nullptr);
   const FrameDev& f = ctx->fd;
-  // a rank whose band is empty ran no stage: the frame's stage list says where the result lives
-  float* res[3];
-  for (int ch = 0; ch < 3; ch++) res[ch] = ctx->result[ch] = result_in_tmp(ctx) ? f.tmp[ch] : f.planes[ch];
-  ctx->res_w = f.xsize;
-  ctx->res_h = f.ysize;
-  ctx->res_stride = f.plane_stride;
+  set_band_result(ctx);
   const size_t count = (size_t)comm_rows_per_rank(ctx, f.ygroups) * kGroupDim * f.plane_stride;
   c->last_op = "ncclAllGather of the finished planes (" + std::to_string(count * 4) + " bytes per rank and plane)";
   NCCLCHK(ctx, api, api->GroupStart());
   for (int ch = 0; ch < 3; ch++)
-    NCCLCHK_IN_GROUP(ctx, api, api->AllGather(res[ch] + (size_t)c->rank * count, res[ch], count, ncclFloat32, c->nccl, ctx->stream));
+    NCCLCHK_IN_GROUP(ctx, api, api->AllGather(ctx->result[ch] + (size_t)c->rank * count, ctx->result[ch], count, ncclFloat32, c->nccl, ctx->stream));
   NCCLCHK(ctx, api, api->GroupEnd());
   return JXLH_OK;
-}
-
-// where a band run left the finished planes + the geometry the read-out stages use
-static void set_band_result(jxlh_ctx* ctx) {
-  const FrameDev& f = ctx->fd;
-  for (int ch = 0; ch < 3; ch++) ctx->result[ch] = result_in_tmp(ctx) ? f.tmp[ch] : f.planes[ch];
-  ctx->res_w = f.xsize;
-  ctx->res_h = f.ysize;
-  ctx->res_stride = f.plane_stride;
 }
 
 jxlh_status jxlh_frame_allgather_output(jxlh_ctx* ctx, const jxlh_output_desc* d, void* out, size_t bytes_per_row) {
@@ -528,14 +517,13 @@ jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
     if (!peers[i] || !peers[i]->comm || peers[i]->comm->nccl || peers[i]->comm->nranks != n || peers[i]->comm->rank != i)
       return JXLH_ERR_BAD_STATE;
   std::vector<RunPlan> plan(n);
-  std::vector<int> r0(n), r1(n);
   // phase 1: every rank's transforms
   for (int i = 0; i < n; i++) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (int k = 0; k < n; k++)  // the previous frame's gather may still be reading this rank's band
       if (k != i && peers[k]->comm->gathered_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, peers[k]->comm->gathered_ev, 0));
-    if (jxlh_status st = shard_k1(ctx, &plan[i], &r0[i], &r1[i])) return st;
+    if (jxlh_status st = shard_k1(ctx, &plan[i])) return st;
     HIPCHK(ctx, hipEventRecord(ctx->comm->k1_ev, ctx->stream));
   }
   // phase 2: every rank pulls the edge block rows it reads across its band edges from the neighbours ...
@@ -543,15 +531,15 @@ jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const FrameDev& f = ctx->fd;
-    if (r0[i] < r1[i] && exchange_applies(ctx, plan[i])) {
+    if (plan[i].group_row0 < plan[i].group_row1 && plan[i].exchange) {
       for (int side = 0; side < 2; side++) {
         const int nb = side == 0 ? i - 1 : i + 1;
-        if (nb < 0 || nb >= n || r0[nb] >= r1[nb]) continue;
+        if (nb < 0 || nb >= n || plan[nb].group_row0 >= plan[nb].group_row1) continue;
         jxlh_ctx* src = peers[nb];
         if (src->fd.tiled != f.tiled || src->fd.xblocks != f.xblocks || src->fd.plane_stride != f.plane_stride)
           return JXLH_ERR_BAD_STATE;  // the peers decode the same frame
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->comm->k1_ev, 0));
-        const int by = side == 0 ? r0[i] * kGroupBlocks - 1 : r1[i] * kGroupBlocks;
+        const int by = side == 0 ? plan[i].group_row0 * kGroupBlocks - 1 : plan[i].group_row1 * kGroupBlocks;
         size_t off, cnt;
         block_row_span(f, by, &off, &cnt);
         for (int ch = 0; ch < 3; ch++)
@@ -566,10 +554,10 @@ jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
   for (int i = 0; i < n; i++) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (r0[i] >= r1[i]) continue;
+    if (plan[i].group_row0 >= plan[i].group_row1) continue;
     if (i > 0) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, peers[i - 1]->comm->pulled_ev, 0));
     if (i + 1 < n) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, peers[i + 1]->comm->pulled_ev, 0));
-    if (jxlh_status st = run_stages(ctx, plan[i], (uint32_t)r0[i], (uint32_t)r1[i])) return st;
+    if (jxlh_status st = run_stages_rows(ctx, plan[i].stages, plan[i].y_lo, plan[i].y_hi, plan[i].whole)) return st;
   }
   for (int i = 0; i < n; i++) {
     jxlh_ctx* ctx = peers[i];
@@ -584,15 +572,12 @@ jxlh_status jxlh_frames_allgather_local(jxlh_ctx* const peers[], int32_t n) {
   for (int i = 0; i < n; i++)
     if (!peers[i] || !peers[i]->comm || peers[i]->comm->nccl || peers[i]->comm->nranks != n || !peers[i]->in_frame)
       return JXLH_ERR_BAD_STATE;
-  const int which = result_in_tmp(peers[0]);  // a property of the stage list, identical on every peer
+  const int which = stage_list(peers[0]).result_in_tmp();  // a property of the stage list, identical on every peer
   for (int i = 0; i < n; i++) {
     jxlh_ctx* dst = peers[i];
     HIPCHK(dst, hipSetDevice(dst->device));
     const FrameDev& f = dst->fd;
-    for (int c = 0; c < 3; c++) dst->result[c] = which ? f.tmp[c] : f.planes[c];
-    dst->res_w = f.xsize;
-    dst->res_h = f.ysize;
-    dst->res_stride = f.plane_stride;
+    set_band_result(dst);
     for (int k = 0; k < n; k++) {
       if (k == i) continue;
       jxlh_ctx* src = peers[k];

@@ -1,4 +1,4 @@
-// Host-side state behind the C ABI: the context structure and the small helpers abi.hip and comm.hip share.
+// Host-side state behind the C ABI: the context structure and the small helpers the abi_*.hip files and comm.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "jxlh_internal.h"
+#include "run_plan.h"
 
 using namespace jxlh;
 
@@ -363,18 +364,17 @@ inline jxlh_status copy2d(jxlh_ctx* ctx, void* dst, size_t dpitch, const void* s
   return JXLH_OK;
 }
 
-// jxlh_frame_run in three pieces (abi.hip), so that a sharded run (comm.hip) can put the halo exchange between the
-// transforms and the filters
-struct RunPlan {
-  bool sparse_k1 = false;
-  int halo_px = 0;       // rows the filters read beyond a band
-  bool will_fuse = false;
-  bool want_strip = false;  // in: the caller would run the strip kernel (dense slabs needed); out: it will
-};
-jxlh_status run_prologue(jxlh_ctx* ctx, RunPlan* plan);
-jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan, int gr0, int gr1);
-jxlh_status run_stages(jxlh_ctx* ctx, const RunPlan& plan, uint32_t group_row0, uint32_t group_row1);
-jxlh_status run_stages_rows(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_hi, bool whole_frame);
+// A run is "fill the inputs, plan, issue" (run_plan.h): run_inputs reads what the decisions depend on out of the context
+// (and takes the snapshot of the LF-only marks), plan_run / plan_rerender / plan_shard decide, and the pieces below issue
+// what the plan says -- three of them, so that a sharded run (comm.hip) can put the halo exchange between the
+// transforms and the filters.  run_prologue: everything before K1; *sparse_k1 is the coefficient epoch's answer, which
+// resolve_strip puts into the plan.  run_k1: the transforms on the plan's k1 rows.  run_stages_rows: the stage list on
+// pixel rows (the plan's, or a re-render's bands), then the post stages.
+StageList stage_list(const jxlh_ctx* ctx);
+RunInputs run_inputs(jxlh_ctx* ctx);
+jxlh_status run_prologue(jxlh_ctx* ctx, bool strip_candidate, bool tiled, bool* sparse_k1);
+jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan);
+jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& stages, int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsample of the channels handed over
 // abi_patches.hip: the patches stage on the colour planes `cur` (rows [y_lo, y_hi)) and, when stale, on every row of
@@ -399,23 +399,13 @@ jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a);
 void lf_frames_release(jxlh_ctx* ctx);  // abi_lf_frame.hip
 void modular_local_release(jxlh_ctx* ctx);  // abi_modular_local.hip
 // abi_lf_fill.hip.  lf_only_snapshot: ctx->lf_only_run <- the frame's marks (true = at least one group is marked).
-// lf_split_groups: the sorted `groups` of a run with marks, the unmarked ones first, on the device (rerender_list);
+// lf_split_groups: the sorted `groups` of a run, the unmarked ones (all, without marks) first, on the device (rerender_list);
 // *n_k1 of them are K1's, the *n_fill behind them the fill's.  run_lf_fill: Upsample8x of the LF image into the planes
 // K1 writes, for the n groups listed at `groups_dev`.
 bool lf_only_snapshot(jxlh_ctx* ctx);
 jxlh_status lf_split_groups(jxlh_ctx* ctx, const std::vector<int>& groups, int* n_k1, int* n_fill);
 jxlh_status run_lf_fill(jxlh_ctx* ctx, const FrameDev& f, const int* groups_dev, int n);
-bool strip_eligible(const jxlh_ctx* ctx);
-jxlh_status run_strip(jxlh_ctx* ctx, const RunPlan& plan);
-// Where run_stages leaves the finished planes (1 = f.tmp, 0 = f.planes): a property of the frame's stage list, so a
-// rank that filtered nothing (empty band) still knows where the gathered frame lives.
-inline int result_in_tmp(const jxlh_ctx* ctx) {
-  const FrameDev& f = ctx->fd;
-  const int ns = (f.gab ? 1 : 0) + (f.epf_iters >= 3 ? 1 : 0) + (f.epf_iters >= 1 ? 1 : 0) + (f.epf_iters >= 2 ? 1 : 0);
-  if (ns == 0) return 0;
-  if (!(ctx->params.flags & JXLH_FRAME_UNFUSED_FILTERS)) return f.epf_iters >= 3 ? 0 : 1;
-  return ns & 1;
-}
+jxlh_status run_strip(jxlh_ctx* ctx);
 void set_filter_params(FrameDev& f, const jxlh_frame_params& p);
 // abi_modular_frame.hip: jxlh_frame_begin / jxlh_frame_run of a Modular frame (behind the shared argument checks)
 void reset_frame_state(jxlh_ctx* ctx);  // abi_frame.hip: the per-frame state every jxlh_frame_begin starts from

@@ -34,6 +34,7 @@
 // epf_iters == 3 runs as two launches: Gaborish + EPF0 (EPF0 always closes its kernel: its 7x10
 // register window leaves no room to hold outputs across an in-place barrier), then EPF1 + EPF2.
 #include "jxlh_internal.h"
+#include "run_plan.h"
 
 // Tile heights and workgroup sizes of the two geometries (one 4x2 item per thread in the EPF stages:
 // (TH + 6) / 2 * 16 <= THREADS); which stage list uses which: see the namespaces below.
@@ -161,13 +162,13 @@ void launch_selftest_recip(hipStream_t s, uint32_t lo_bits, uint32_t hi_bits, un
   hipLaunchKernelGGL(k_selftest_recip, dim3(2048), dim3(256), 0, s, lo_bits, hi_bits, mismatches);
 }
 
-// Runs the frame's stage list fused.  Returns 0 if there is nothing to do, 1 if the result is in
-// f.tmp (one pass: gab?, epf1?, epf2?), 2 if it is in f.planes (epf_iters == 3: Gaborish + EPF0 go
+// Runs the frame's stage list fused.  Returns StageList::fused_where() (run_plan.h): 0 if there is nothing to do, 1 if
+// the result is in f.tmp (one pass: gab?, epf1?, epf2?), 2 if it is in f.planes (epf_iters == 3: Gaborish + EPF0 go
 // planes -> tmp, EPF1 + EPF2 come back tmp -> planes, both raster).
 int launch_fused_filters(hipStream_t s, const FrameDev& f, int y0, int y1) {
   const bool gab = f.gab != 0, e0 = f.epf_iters >= 3, e1 = f.epf_iters >= 1, e2 = f.epf_iters >= 2;
-  if (!gab && !e1 && !e2) return 0;
-  if (y1 <= y0) return e0 ? 2 : 1;
+  const int where = StageList{gab, f.epf_iters, false}.fused_where();
+  if (where == 0 || y1 <= y0) return where;
   FusedArgs a;
   for (int c = 0; c < 3; c++) {
     a.in[c] = f.planes[c];
@@ -207,14 +208,14 @@ int launch_fused_filters(hipStream_t s, const FrameDev& f, int y0, int y1) {
     a.y0 = y0;
     a.y1 = y1;
     tall::launch_variant<false, false, true, true>(s, a);
-    return 2;
+    return where;
   }
   if (gab && e1 && e2) low::launch_variant<true, false, true, true>(s, a);
   else if (gab && e1) low::launch_variant<true, false, true, false>(s, a);
   else if (gab) tall::launch_variant<true, false, false, false>(s, a);
   else if (e1 && e2) low::launch_variant<false, false, true, true>(s, a);
   else low::launch_variant<false, false, true, false>(s, a);
-  return 1;
+  return where;
 }
 
 }  // namespace jxlh
