@@ -89,6 +89,11 @@ jxlh_status jxlh_selftest_recip(jxlh_ctx* ctx, uint32_t lo_bits, uint32_t hi_bit
  * ticks (100 MHz); rows[11 i + 5..10] are zero unless the library was built with the mover-phase experiment.  The profile costs two small memsets and five atomics per workgroup; off by default. */
 jxlh_status jxlh_flow_profile(jxlh_ctx* ctx, int32_t enable, int32_t* n_levels, uint64_t* rows, int32_t max_levels);
 
+/* What the library holds from the HIP runtime right now, over all contexts of the process (host only: no context, no
+ * device): out[0] = device buffers, out[1] = pinned host blocks, out[2] = events, out[3] = streams.  Everything a
+ * context holds is counted, so the counts return to where they were once it is destroyed. */
+jxlh_status jxlh_live_resources(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

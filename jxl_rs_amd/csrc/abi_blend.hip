@@ -63,12 +63,6 @@ bool sides_ok(const jxlh_blend_desc* d, uint32_t w, uint32_t h) {
 
 }  // namespace
 
-void blend_release(jxlh_ctx* ctx) {
-  release(ctx->blend_canvas);
-  release(ctx->blend_hook_in);
-  release(ctx->blend_hook_out);
-}
-
 }  // namespace jxlh_host
 
 extern "C" {

@@ -8,21 +8,15 @@
 namespace {
 // the slot's device staging, grown to `bytes` (5/4 + 4 KiB of headroom)
 jxlh_status grow_stage(jxlh_ctx* ctx, Slot& s, size_t bytes) {
-  if (s.stage8_cap >= bytes) return JXLH_OK;
+  if (s.stage8.n >= bytes) return JXLH_OK;
   HIPCHK(ctx, hipStreamSynchronize(s.stream));  // the old staging may still be read by a queued kernel
-  if (s.stage8) (void)hipFree(s.stage8);
-  s.stage8 = nullptr;
-  s.stage8_cap = 0;
-  const size_t cap = bytes * 5 / 4 + 4096;
-  if (hipMalloc(reinterpret_cast<void**>(&s.stage8), cap) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
-  s.stage8_cap = cap;
-  return JXLH_OK;
+  return s.stage8.alloc(bytes * 5 / 4 + 4096) == hipSuccess ? JXLH_OK : JXLH_ERR_OUT_OF_MEMORY;
 }
 
 // the end of every submission: `done` behind its work on the slot's stream; `copied` (already recorded) when device
-// work follows the copies
+// work follows the copies, cleared otherwise
 jxlh_status submitted(jxlh_ctx* ctx, Slot& s, bool copied = false) {
-  s.copied_valid = copied;
+  if (!copied) s.copied.clear();
   HIPCHK(ctx, hipEventRecord(s.done, s.stream));
   s.used = true;
   return JXLH_OK;
@@ -48,7 +42,7 @@ jxlh_status jxlh_submit_group(jxlh_ctx* ctx, int32_t slot, uint32_t group_id, co
   int32_t* dst = ctx->coeffs.p + (size_t)group_id * 3 * kGroupArea;
   // the previous jxlh_frame_run's transforms may still be reading the slab (callers that use the *_async reads
   // do not wait between frames)
-  if (ctx->k1_done_valid) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->k1_done, 0));
+  HIPCHK(ctx, ctx->k1_done.wait(s.stream));
   if (dst != coeffs) {
     HIPCHK(ctx, hipMemcpyAsync(dst, coeffs, (size_t)3 * kGroupArea * sizeof(int32_t), hipMemcpyDefault, s.stream));
   }
@@ -77,7 +71,7 @@ jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const ui
   std::lock_guard<std::mutex> lock(ctx->sp_mutex);
   const size_t capacity = ctx->ngroups * 3 * (size_t)kGroupArea;  // one pair per coefficient
   if (jxlh_status st = ensure(ctx, ctx->sp_pairs, capacity)) return st;
-  if (!ctx->sp_expanded) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sp_expanded, hipEventDisableTiming));
+  HIPCHK(ctx, ctx->sp_expanded.ev.create());
   CoeffEpoch& e = ctx->epoch;
   if (e.pairs_used + total > capacity) return JXLH_ERR_INVALID_ARGUMENT;  // more pairs than coefficients
   for (uint32_t i = 0; i < count; i++) {  // one sparse submission per group between two runs (its list may
@@ -102,7 +96,7 @@ jxlh_status sparse_reserve(jxlh_ctx* ctx, int32_t slot, uint32_t count, const ui
   }
   for (uint32_t i = 0; i < n_wide; i++) e.wide.push_back(WideValue{wide[i].pos, (uint32_t)wide[i].val});
   // the pair buffer is recycled per frame: the previous frame's expansion must have read it
-  if (ctx->sp_expanded_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->slots[slot].stream, ctx->sp_expanded, 0));
+  HIPCHK(ctx, ctx->sp_expanded.wait(ctx->slots[slot].stream));
   *offset_out = offset;
   *total_out = total;
   return JXLH_OK;
@@ -142,10 +136,10 @@ jxlh_status jxlh_submit_groups_sparse8(jxlh_ctx* ctx, int32_t slot, uint32_t cou
     // staging: [positions | values], reused by the slot (stream-ordered)
     const size_t pos_bytes = (total * sizeof(uint16_t) + 15) & ~(size_t)15;
     if (jxlh_status st = grow_stage(ctx, s, pos_bytes + total)) return st;
-    HIPCHK(ctx, hipMemcpyAsync(s.stage8, pos, total * sizeof(uint16_t), hipMemcpyDefault, s.stream));
-    HIPCHK(ctx, hipMemcpyAsync(s.stage8 + pos_bytes, val, total, hipMemcpyDefault, s.stream));
-    launch_pack_pairs8(s.stream, reinterpret_cast<const uint16_t*>(s.stage8),
-                       reinterpret_cast<const int8_t*>(s.stage8 + pos_bytes), total, ctx->sp_pairs.p + offset);
+    HIPCHK(ctx, hipMemcpyAsync(s.stage8.p, pos, total * sizeof(uint16_t), hipMemcpyDefault, s.stream));
+    HIPCHK(ctx, hipMemcpyAsync(s.stage8.p + pos_bytes, val, total, hipMemcpyDefault, s.stream));
+    launch_pack_pairs8(s.stream, reinterpret_cast<const uint16_t*>(s.stage8.p),
+                       reinterpret_cast<const int8_t*>(s.stage8.p + pos_bytes), total, ctx->sp_pairs.p + offset);
     HIPCHK(ctx, hipGetLastError());
   }
   return submitted(ctx, s);
@@ -196,7 +190,7 @@ jxlh_status jxlh_submit_groups_sparse4(jxlh_ctx* ctx, int32_t slot, uint32_t cou
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t b_ent = up(tot4 * 2), b_cnt = up(runs * 16 * 2), b_pos = up(tot8 * 2), b_val = up(tot8), b_desc = up(runs * 16);
     if (jxlh_status st = grow_stage(ctx, s, b_ent + b_cnt + b_pos + b_val + b_desc)) return st;
-    uint8_t* d_ent = s.stage8, *d_cnt = d_ent + b_ent, *d_pos = d_cnt + b_cnt, *d_val = d_pos + b_pos, *d_desc = d_val + b_val;
+    uint8_t* d_ent = s.stage8.p, *d_cnt = d_ent + b_ent, *d_pos = d_cnt + b_cnt, *d_val = d_pos + b_pos, *d_desc = d_val + b_val;
     if (tot4) HIPCHK(ctx, hipMemcpyAsync(d_ent, entries, tot4 * 2, hipMemcpyDefault, s.stream));
     HIPCHK(ctx, hipMemcpyAsync(d_cnt, seg_counts, runs * 16 * 2, hipMemcpyDefault, s.stream));
     if (tot8) {
@@ -245,7 +239,7 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
   Slot& s = ctx->slots[slot];
   // the pending set was last read two frames ago (by the transforms of the frame that made it live, or by the previous
   // epoch's widening into the pair buffer): nothing here waits for the frame that is running now
-  if (ctx->se_read_valid[pend]) HIPCHK(ctx, hipStreamWaitEvent(s.stream, ctx->se_read[pend], 0));
+  HIPCHK(ctx, ctx->se_read[pend].wait(s.stream));
   uint16_t* d_ent = ctx->se_entries[pend].p + offset;
   if (total) {
     if (!e12) {
@@ -253,7 +247,7 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
     } else {
       const size_t bytes = total / 2 * 3;
       if (jxlh_status st = grow_stage(ctx, s, bytes)) return st;
-      HIPCHK(ctx, hipMemcpyAsync(s.stage8, entries, bytes, hipMemcpyDefault, s.stream));
+      HIPCHK(ctx, hipMemcpyAsync(s.stage8.p, entries, bytes, hipMemcpyDefault, s.stream));
       // (the unpack kernel goes behind the other copies, below: what jxlh_slot_wait / jxlh_slot_after wait for is the
       // copies -- a kernel queued behind another context's transforms would hold the next upload, and the bus, back)
     }
@@ -279,8 +273,8 @@ jxlh_status jxlh_submit_groups_slots(jxlh_ctx* ctx, int32_t slot, uint32_t count
     i0 = i1;
   }
   if (total && e12) {
-    HIPCHK(ctx, hipEventRecord(s.copied, s.stream));
-    launch_unpack_entries12(s.stream, s.stage8, total / 2, d_ent);
+    HIPCHK(ctx, s.copied.record(s.stream));
+    launch_unpack_entries12(s.stream, s.stage8.p, total / 2, d_ent);
     HIPCHK(ctx, hipGetLastError());
   }
   return submitted(ctx, s, total && e12);
@@ -309,7 +303,7 @@ jxlh_status jxlh_slot_wait(jxlh_ctx* ctx, int32_t slot) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || slot < 0 || (size_t)slot >= ctx->slots.size()) return JXLH_ERR_INVALID_ARGUMENT;
   Slot& s = ctx->slots[slot];
-  if (s.copied_valid) HIPCHK(ctx, hipEventSynchronize(s.copied));  // device work behind the copies is the frame's business
+  if (s.copied.recorded) HIPCHK(ctx, s.copied.sync());  // device work behind the copies is the frame's business
   else HIPCHK(ctx, hipStreamSynchronize(s.stream));
   return JXLH_OK;
 }
@@ -321,7 +315,7 @@ jxlh_status jxlh_slot_after(jxlh_ctx* ctx, int32_t slot, jxlh_ctx* after_ctx, in
     return JXLH_ERR_INVALID_ARGUMENT;
   const Slot& a = after_ctx->slots[after_slot];
   // (`done` is re-recorded by every submission on that slot: this waits for the latest one recorded so far)
-  if (a.used) HIPCHK(ctx, hipStreamWaitEvent(ctx->slots[slot].stream, a.copied_valid ? a.copied : a.done, 0));
+  if (a.used) HIPCHK(ctx, hipStreamWaitEvent(ctx->slots[slot].stream, a.copied.recorded ? a.copied.ev : a.done, 0));
   return JXLH_OK;
 }
 

@@ -52,6 +52,12 @@ jxlh_status jxlh_kernel_timing_reset(jxlh_ctx* ctx) {
   return JXLH_OK;
 }
 
+jxlh_status jxlh_live_resources(uint64_t out[4]) {
+  if (!out) return JXLH_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 4; i++) out[i] = live_resources[i].load(std::memory_order_relaxed);
+  return JXLH_OK;
+}
+
 jxlh_status jxlh_worklist_layout(int32_t xblocks, int32_t yblocks, uint64_t* out, int32_t n) {
   if (xblocks <= 0 || yblocks <= 0 || !out || n < 0) return JXLH_ERR_INVALID_ARGUMENT;
   const WorklistLayout L = vardct_worklist_layout((size_t)xblocks * (size_t)yblocks);

@@ -133,17 +133,14 @@ jxlh_status jxlh_ctx_create(int32_t device_ordinal, int32_t n_slots, jxlh_ctx** 
     }
   }
   if (hipSetDevice(device_ordinal) != hipSuccess ||
-      (cu_mask.empty() ? hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio.main_p)
-                       : hipExtStreamCreateWithCUMask(&ctx->stream, (uint32_t)cu_mask.size(), cu_mask.data())) != hipSuccess ||
-      hipEventCreate(&ctx->t0) != hipSuccess || hipEventCreate(&ctx->t1) != hipSuccess) {
-    delete ctx;
+      ctx->stream.create(prio.main_p, cu_mask.data(), (uint32_t)cu_mask.size()) != hipSuccess ||
+      ctx->t0.create(true) != hipSuccess || ctx->t1.create(true) != hipSuccess) {
+    jxlh_ctx_destroy(ctx);
     return JXLH_ERR_DEVICE;
   }
   ctx->slots.resize(n_slots);
   for (auto& s : ctx->slots) {
-    if (hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, prio.slot_p) != hipSuccess ||
-        hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) != hipSuccess) {
+    if (s.stream.create(prio.slot_p) != hipSuccess || s.done.create() != hipSuccess || s.copied.ev.create() != hipSuccess) {
       jxlh_ctx_destroy(ctx);
       return JXLH_ERR_DEVICE;
     }
@@ -157,81 +154,8 @@ void jxlh_ctx_destroy(jxlh_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
   drain_timers(ctx);
-  if (ctx->handover) (void)hipEventDestroy(ctx->handover);
-  for (auto& s : ctx->slots) {
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.copied) (void)hipEventDestroy(s.copied);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.stage8) (void)hipFree(s.stage8);
-  }
-  for (int c = 0; c < 3; c++) {
-    release(ctx->planes[c]);
-    release(ctx->tmp[c]);
-    release(ctx->lf_raw[c]);
-    release(ctx->lf_sm[c]);
-  }
-  release(ctx->sigma);
-  for (auto& b : ctx->mod_src) release(b);
-  release(ctx->tables);
-  release(ctx->coeffs);
-  release(ctx->sp_pairs);
-  release(ctx->sp_groups_dev);
-  release(ctx->sp_wide_dev);
-  release(ctx->sp_sorted);
-  release(ctx->sp_slot_start);
-  release(ctx->bucketed_dev);
-  release(ctx->route_dev);
-  for (int i = 0; i < 2; i++) {
-    release(ctx->se_entries[i]);
-    release(ctx->se_counts[i]);
-    release(ctx->se_runs[i]);
-    if (ctx->se_read[i]) (void)hipEventDestroy(ctx->se_read[i]);
-  }
-  release(ctx->group_dense);
-  for (auto& e : ctx->marks)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->sp_expanded) (void)hipEventDestroy(ctx->sp_expanded);
-  if (ctx->k1_done) (void)hipEventDestroy(ctx->k1_done);
-  comm_release(ctx);
-  release(ctx->raw_quant);
-  release(ctx->lfq);
-  release(ctx->transform_map);
-  release(ctx->epf_map);
-  release(ctx->ytox);
-  release(ctx->ytob);
-  release(ctx->error_flag);
-  release(ctx->tables_ok);
-  release(ctx->rgb8);
-  for (auto& b : ctx->ups) release(b);
-  for (auto& b : ctx->noise) release(b);
-  release(ctx->xs_jump);
-  for (auto& b : ctx->ups_kernels_n) release(b);
-  if (ctx->host_flag) (void)hipHostFree(ctx->host_flag);
-  if (ctx->host_flow_flag) (void)hipHostFree(ctx->host_flow_flag);
-  release(ctx->flow_words);
-  release(ctx->flow_prof);
-  release(ctx->worklist);
-  for (auto& e : ctx->extra) {
-    release(e.raw);
-    release(e.f32);
-    release(e.out);
-  }
-  release(ctx->strip_desc);
-  release(ctx->strip_mode);
-  release(ctx->strip_xchg);
-  release(ctx->strip_flags);
-  for (auto& b : ctx->hook_f) release(b);
-  for (auto& b : ctx->hook_i) release(b);
-  patches_release(ctx);
-  splines_release(ctx);
-  blend_release(ctx);
-  save_release(ctx);
-  lf_frames_release(ctx);
-  modular_local_release(ctx);
-  if (ctx->t0) (void)hipEventDestroy(ctx->t0);
-  if (ctx->t1) (void)hipEventDestroy(ctx->t1);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  comm_release(ctx);  // (talks to the peers: the one explicit step)
+  delete ctx;  // every device resource goes with the member that owns it (device_owned.h)
 }
 
 jxlh_status jxlh_alloc_pinned(jxlh_ctx* ctx, size_t bytes, void** out) {
@@ -257,18 +181,9 @@ jxlh_status jxlh_free_pinned(jxlh_ctx* ctx, void* p) {
 // transient device memory at 8192^2 and a few ms per candidate; a candidate that cannot be allocated ends the trials.
 static jxlh_status choose_placement(jxlh_ctx* ctx, size_t plane_n, size_t tmp_n, size_t coeff_n, size_t probe_elems) {
   struct Cand {
-    float* planes[3] = {nullptr, nullptr, nullptr};
-    float* tmp[3] = {nullptr, nullptr, nullptr};
-    int32_t* coeffs = nullptr;
+    DevBuf<float> planes[3], tmp[3];
+    DevBuf<int32_t> coeffs;
     float k1 = 0.f, filt = 0.f;
-  };
-  auto drop = [](Cand& c) {
-    for (int i = 0; i < 3; i++) {
-      if (c.planes[i]) (void)hipFree(c.planes[i]);
-      if (c.tmp[i]) (void)hipFree(c.tmp[i]);
-    }
-    if (c.coeffs) (void)hipFree(c.coeffs);
-    c = Cand();
   };
   std::vector<Cand> cands;
   ctx->placement_report.clear();
@@ -284,24 +199,20 @@ static jxlh_status choose_placement(jxlh_ctx* ctx, size_t plane_n, size_t tmp_n,
     Cand c;
     bool ok = true;
     for (int i = 0; i < 3 && ok; i++) {  // (the order of the plain path below)
-      ok = hipMalloc(reinterpret_cast<void**>(&c.planes[i]), plane_n * sizeof(float)) == hipSuccess &&
-           hipMalloc(reinterpret_cast<void**>(&c.tmp[i]), tmp_n * sizeof(float)) == hipSuccess;
+      ok = c.planes[i].alloc(plane_n) == hipSuccess && c.tmp[i].alloc(tmp_n) == hipSuccess;
     }
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c.coeffs), coeff_n * sizeof(int32_t)) == hipSuccess;
+    ok = ok && c.coeffs.alloc(coeff_n) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();  // out of memory: the candidates so far are the choice
-      drop(c);
       break;
     }
-    const jxlh_status st = probe_placement(ctx, c.coeffs, ctx->ngroups, c.planes, c.tmp, probe_elems & ~(size_t)511, &c.k1, &c.filt);
-    if (st != JXLH_OK) {
-      drop(c);
-      for (Cand& o : cands) drop(o);
+    float* const planes[3] = {c.planes[0].p, c.planes[1].p, c.planes[2].p};
+    float* const tmp[3] = {c.tmp[0].p, c.tmp[1].p, c.tmp[2].p};
+    if (jxlh_status st = probe_placement(ctx, c.coeffs.p, ctx->ngroups, planes, tmp, probe_elems & ~(size_t)511, &c.k1, &c.filt))
       return st;
-    }
     ctx->placement_report.push_back(c.k1);
     ctx->placement_report.push_back(c.filt);
-    cands.push_back(c);
+    cands.push_back(std::move(c));
   }
   if (cands.empty()) return JXLH_OK;  // (the plain path reports the allocation failure)
   // the real K1 follows its mover closely (0.283 -> 0.351 ms, 0.303-0.311 -> 0.380-0.387), the filters theirs loosely
@@ -311,16 +222,11 @@ static jxlh_status choose_placement(jxlh_ctx* ctx, size_t plane_n, size_t tmp_n,
   for (size_t i = 1; i < cands.size(); i++)
     if (score(cands[i]) < score(cands[best])) best = i;
   ctx->placement_pick = (int)best;
-  for (size_t i = 0; i < cands.size(); i++)
-    if (i != best) drop(cands[i]);
-  for (int i = 0; i < 3; i++) {
-    ctx->planes[i].p = cands[best].planes[i];
-    ctx->planes[i].n = plane_n;
-    ctx->tmp[i].p = cands[best].tmp[i];
-    ctx->tmp[i].n = tmp_n;
+  for (int i = 0; i < 3; i++) {  // (the other candidates go with `cands`)
+    ctx->planes[i] = std::move(cands[best].planes[i]);
+    ctx->tmp[i] = std::move(cands[best].tmp[i]);
   }
-  ctx->coeffs.p = cands[best].coeffs;
-  ctx->coeffs.n = coeff_n;
+  ctx->coeffs = std::move(cands[best].coeffs);
   return JXLH_OK;
 }
 
@@ -830,17 +736,12 @@ static jxlh_status apply_coeff_epoch(jxlh_ctx* ctx, bool want_strip, bool* spars
                            ctx->sp_wide_dev.p, (uint32_t)nw, nullptr);
     }
     if (pl.pending_read) {
-      if (!ctx->se_read[pend]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->se_read[pend], hipEventDisableTiming));
-      HIPCHK(ctx, hipEventRecord(ctx->se_read[pend], ctx->stream));
-      ctx->se_read_valid[pend] = true;
+      HIPCHK(ctx, ctx->se_read[pend].record(ctx->stream));
     }
     if (pl.trade_sets()) ctx->se_live = pend;  // the next epoch's uploads go to the set read two frames ago
     e.reset(n);
     e.live = pl.after;
-    if (ctx->sp_expanded) {  // the pair buffer has been consumed (bucketed or expanded)
-      HIPCHK(ctx, hipEventRecord(ctx->sp_expanded, ctx->stream));
-      ctx->sp_expanded_valid = true;
-    }
+    if (ctx->sp_expanded.ev) HIPCHK(ctx, ctx->sp_expanded.record(ctx->stream));  // the pair buffer has been consumed
   }
   *sparse_k1 = e.live.form != Resident::kDense;
   return JXLH_OK;
@@ -917,15 +818,8 @@ static void set_sparse_view(jxlh_ctx* ctx, FrameDev& f, bool sparse_k1) {
 // behind the transforms: the coefficient slabs are free again (dense resubmissions of the next frame wait for this,
 // jxlh_submit_group), and so is the live set of the slot-bucketed form once it has become the pending one
 static jxlh_status mark_coefficients_read(jxlh_ctx* ctx, bool sparse_k1) {
-  if (!ctx->k1_done) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->k1_done, hipEventDisableTiming));
-  HIPCHK(ctx, hipEventRecord(ctx->k1_done, ctx->stream));
-  ctx->k1_done_valid = true;
-  if (sparse_k1 && ctx->epoch.live.form == Resident::kEntries) {
-    const int l = ctx->se_live;
-    if (!ctx->se_read[l]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->se_read[l], hipEventDisableTiming));
-    HIPCHK(ctx, hipEventRecord(ctx->se_read[l], ctx->stream));
-    ctx->se_read_valid[l] = true;
-  }
+  HIPCHK(ctx, ctx->k1_done.record(ctx->stream));
+  if (sparse_k1 && ctx->epoch.live.form == Resident::kEntries) HIPCHK(ctx, ctx->se_read[ctx->se_live].record(ctx->stream));
   return JXLH_OK;
 }
 
@@ -1342,7 +1236,7 @@ jxlh_status jxlh_ctx_wait_event(jxlh_ctx* ctx, void* hip_event) {
 jxlh_status jxlh_ctx_wait_stream(jxlh_ctx* ctx, void* hip_stream) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->handover) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->handover, hipEventDisableTiming));
+  HIPCHK(ctx, ctx->handover.create());
   // (an event may be re-recorded while earlier waits on it are still pending: a wait captures the record it follows)
   HIPCHK(ctx, hipEventRecord(ctx->handover, static_cast<hipStream_t>(hip_stream)));
   return all_streams_wait(ctx, ctx->handover);
@@ -1358,10 +1252,10 @@ jxlh_status jxlh_ctx_record_event(jxlh_ctx* ctx, void* hip_event) {
 // the dataflow squeeze launch's error word (pinned host memory the kernel writes): non-zero = a wait between two levels
 // outlasted its deadline; reported once
 static jxlh_status flow_error_status(jxlh_ctx* ctx) {
-  if (!ctx->host_flow_flag) return JXLH_OK;
-  const int v = *reinterpret_cast<volatile int*>(ctx->host_flow_flag);
+  if (!ctx->host_flow_flag.p) return JXLH_OK;
+  const int v = *reinterpret_cast<volatile int*>(ctx->host_flow_flag.p);
   if (v == 0) return JXLH_OK;
-  *ctx->host_flow_flag = 0;
+  *ctx->host_flow_flag.p = 0;
   ctx->last_error = "jxlh_unsqueeze_chain: a wait between two levels of the dataflow launch outlasted its deadline";
   return (jxlh_status)v;
 }
@@ -1370,8 +1264,8 @@ jxlh_status jxlh_ctx_mark(jxlh_ctx* ctx, uint32_t* mark) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !mark) return JXLH_ERR_INVALID_ARGUMENT;
   const uint32_t seq = ++ctx->mark_seq;
-  hipEvent_t& e = ctx->marks[seq % JXLH_MAX_MARKS];
-  if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  Event& e = ctx->marks[seq % JXLH_MAX_MARKS];
+  HIPCHK(ctx, e.create());
   HIPCHK(ctx, hipEventRecord(e, ctx->stream));
   *mark = seq;
   return JXLH_OK;
@@ -1390,7 +1284,7 @@ jxlh_status jxlh_ctx_wait_mark(jxlh_ctx* ctx, uint32_t mark) {
 jxlh_status jxlh_ctx_sync(jxlh_ctx* ctx) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
-  if (ctx->flow_used && ctx->host_flow_flag) {
+  if (ctx->flow_used && ctx->host_flow_flag.p) {
     // a dataflow squeeze launch ran since the last synchronisation: did one of its waits give up?
     ctx->flow_used = false;
     if (jxlh_status st = comm_wait_stream(ctx)) return st;
@@ -1399,10 +1293,10 @@ jxlh_status jxlh_ctx_sync(jxlh_ctx* ctx) {
   if (ctx->in_frame && ctx->error_flag.p) {
     // read the flag on the context's own stream into pinned memory: a synchronous hipMemcpy would
     // go through the null stream and serialise against other contexts' work
-    if (!ctx->host_flag) HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->host_flag), sizeof(int), hipHostMallocDefault));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->host_flag, ctx->error_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (!ctx->host_flag.p) HIPCHK(ctx, ctx->host_flag.alloc(1));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->host_flag.p, ctx->error_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (jxlh_status st = comm_wait_stream(ctx)) return st;
-    if (*ctx->host_flag != 0) return (jxlh_status)*ctx->host_flag;
+    if (*ctx->host_flag.p != 0) return (jxlh_status)*ctx->host_flag.p;
     return JXLH_OK;
   }
   return comm_wait_stream(ctx);

@@ -118,13 +118,6 @@ jxlh_status lf_preview(jxlh_ctx* ctx, uint32_t slot, uint32_t image_w, uint32_t 
 
 }  // namespace
 
-void lf_frames_release(jxlh_ctx* ctx) {
-  for (auto& s : ctx->lf_slots) {
-    release(s.buf);
-    s = jxlh_ctx::LfSlot{};
-  }
-}
-
 }  // namespace jxlh_host
 
 extern "C" {
@@ -172,7 +165,7 @@ jxlh_status jxlh_ctx_clear_lf_frame(jxlh_ctx* ctx, uint32_t slot) {
   if (!ctx || slot >= JXLH_NUM_LF_FRAMES) return JXLH_ERR_INVALID_ARGUMENT;
   jxlh_ctx::LfSlot& s = ctx->lf_slots[slot];
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a queued copy or preview may still read the slot)
-  release(s.buf);
+  (void)s.buf.reset();
   s = jxlh_ctx::LfSlot{};
   return JXLH_OK;
 }

@@ -435,14 +435,14 @@ jxlh_status jxlh_unsqueeze_chain(jxlh_ctx* ctx, int32_t n_planes, int32_t n_leve
       }
       if (n >= 2) {
         if ((st = ensure(ctx, ctx->flow_words, unsqueeze_flow_words(n_planes, n, steps)))) return st;
-        if (!ctx->host_flow_flag) {
+        if (!ctx->host_flow_flag.p) {
           // the error word lives in pinned host memory (device-visible under the same address): jxlh_ctx_sync AND
           // jxlh_ctx_wait_mark read it without queueing a copy behind later work
-          HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->host_flow_flag), sizeof(int), hipHostMallocDefault));
-          *ctx->host_flow_flag = 0;
+          HIPCHK(ctx, ctx->host_flow_flag.alloc(1));
+          *ctx->host_flow_flag.p = 0;
         }
         if (ctx->flow_prof_on && (st = ensure(ctx, ctx->flow_prof, 11 * (size_t)unsqueeze_flow_max_steps()))) return st;
-        launch_unsqueeze_flow(ctx->stream, n_planes, n, steps, ctx->flow_words.p, ctx->host_flow_flag, 4.0f,
+        launch_unsqueeze_flow(ctx->stream, n_planes, n, steps, ctx->flow_words.p, ctx->host_flow_flag.p, 4.0f,
                               ctx->flow_prof_on ? ctx->flow_prof.p : nullptr);
         ctx->flow_prof_levels = n;
         ctx->flow_used = true;

@@ -85,21 +85,15 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
   if (items.empty()) return JXLH_OK;
   // ---- from here on the call cannot be refused for its arguments
   const size_t desc_bytes = round_up(n * sizeof(LocalGroupDev), 16), bytes = desc_bytes + items.size() * sizeof(LocalItem);
-  if (ctx->local_copied_valid) {  // the pinned block's previous content is on its way
-    HIPCHK(ctx, hipEventSynchronize(ctx->local_copied));
-    ctx->local_copied_valid = false;
+  HIPCHK(ctx, ctx->local_copied.sync());  // the pinned block's previous content is on its way
+  ctx->local_copied.clear();
+  if (ctx->local_desc_host.n < bytes) {
+    HIPCHK(ctx, ctx->local_desc_host.reset());
+    HIPCHK(ctx, ctx->local_desc_host.alloc(bytes + bytes / 2));
   }
-  if (ctx->local_desc_host_cap < bytes) {
-    if (ctx->local_desc_host) HIPCHK(ctx, hipHostFree(ctx->local_desc_host));
-    ctx->local_desc_host = nullptr;
-    ctx->local_desc_host_cap = 0;
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->local_desc_host), bytes + bytes / 2, hipHostMallocDefault));
-    ctx->local_desc_host_cap = bytes + bytes / 2;
-  }
-  if (!ctx->local_copied) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->local_copied, hipEventDisableTiming));
   if (jxlh_status st = ensure(ctx, ctx->local_desc, bytes)) return st;
-  std::memcpy(ctx->local_desc_host, dev.data(), n * sizeof(LocalGroupDev));
-  std::memcpy(ctx->local_desc_host + desc_bytes, items.data(), items.size() * sizeof(LocalItem));
+  std::memcpy(ctx->local_desc_host.p, dev.data(), n * sizeof(LocalGroupDev));
+  std::memcpy(ctx->local_desc_host.p + desc_bytes, items.data(), items.size() * sizeof(LocalItem));
   const int32_t* arena_dev = arena;
   if (!is_device_ptr(arena)) {
     // one copy; 16-byte alignment of the samples is kept (hipMalloc's and the caller's bases are both taken as they
@@ -107,9 +101,8 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     if (jxlh_status st = stage_in(ctx, ctx->local_arena, arena, (size_t)arena_samples)) return st;
     arena_dev = ctx->local_arena.p;
   }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->local_desc.p, ctx->local_desc_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(ctx->local_copied, ctx->stream));
-  ctx->local_copied_valid = true;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->local_desc.p, ctx->local_desc_host.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, ctx->local_copied.record(ctx->stream));
   LocalLaunch a{};
   a.arena = arena_dev;
   a.groups = reinterpret_cast<const LocalGroupDev*>(ctx->local_desc.p);
@@ -160,17 +153,6 @@ jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
 }
 
 }  // namespace
-
-void modular_local_release(jxlh_ctx* ctx) {
-  release(ctx->local_arena);
-  release(ctx->local_desc);
-  if (ctx->local_desc_host) (void)hipHostFree(ctx->local_desc_host);
-  ctx->local_desc_host = nullptr;
-  ctx->local_desc_host_cap = 0;
-  if (ctx->local_copied) (void)hipEventDestroy(ctx->local_copied);
-  ctx->local_copied = nullptr;
-  ctx->local_copied_valid = false;
-}
 
 }  // namespace jxlh_host
 

@@ -176,18 +176,6 @@ jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y
   return JXLH_OK;
 }
 
-void patches_release(jxlh_ctx* ctx) {
-  for (auto& r : ctx->refs) {
-    release(r.buf);
-    r.set = false;
-  }
-  release(ctx->patch_desc);
-  release(ctx->patch_bins.dev);
-  release(ctx->patch_hook_bins.dev);
-  release(ctx->patch_hook);
-  for (auto& e : ctx->extra) release(e.pat);
-}
-
 }  // namespace jxlh_host
 
 extern "C" {
@@ -277,7 +265,7 @@ jxlh_status jxlh_ctx_clear_reference(jxlh_ctx* ctx, uint32_t slot) {
   if (!ctx || slot >= JXLH_MAX_REFERENCE_FRAMES) return JXLH_ERR_INVALID_ARGUMENT;
   jxlh_ctx::RefSlot& r = ctx->refs[slot];
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a queued patches launch may still read the slot)
-  release(r.buf);
+  (void)r.buf.reset();
   r = jxlh_ctx::RefSlot{};
   return JXLH_OK;
 }

@@ -223,8 +223,6 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
 
 }  // namespace
 
-void save_release(jxlh_ctx* ctx) { release(ctx->save_hook_in); }
-
 }  // namespace jxlh_host
 
 extern "C" {

@@ -66,12 +66,6 @@ jxlh_status run_splines(jxlh_ctx* ctx, float* const cur[3], size_t stride, int w
   return JXLH_OK;
 }
 
-void splines_release(jxlh_ctx* ctx) {
-  release(ctx->spline_desc);
-  release(ctx->spline_bins_dev);
-  release(ctx->spline_hook);
-}
-
 }  // namespace jxlh_host
 
 extern "C" {

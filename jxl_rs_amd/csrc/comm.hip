@@ -87,11 +87,10 @@ struct Comm {
   int rank = 0, nranks = 1;
   ncclComm_t nccl = nullptr;          // RCCL transport
   std::vector<jxlh_ctx*> peers;       // local transport (peers[rank] == the owning context)
-  hipEvent_t k1_ev = nullptr;         // local: this rank's transforms are done (the neighbours copy its edge rows)
-  hipEvent_t done_ev = nullptr;       // local: this rank's band is finished (the peers copy it in the gather)
-  hipEvent_t pulled_ev = nullptr;     // local: this rank has copied its neighbours' edge rows (they may overwrite them)
-  hipEvent_t gathered_ev = nullptr;   // local: this rank has copied the other bands (their owners may start the next frame)
-  bool gathered_valid = false;
+  Event k1_ev;                        // local: this rank's transforms are done (the neighbours copy its edge rows)
+  Event done_ev;                      // local: this rank's band is finished (the peers copy it in the gather)
+  Event pulled_ev;                    // local: this rank has copied its neighbours' edge rows (they may overwrite them)
+  Fence gathered_ev;                  // local: this rank has copied the other bands (their owners may start the next frame)
   // what was enqueued last on the stream through this communicator: named when a wait times out (comm_wait_stream)
   std::string last_op;
   double timeout_s = 120.0;           // JXLH_COMM_TIMEOUT_S; <= 0 waits forever
@@ -133,10 +132,6 @@ void comm_release(jxlh_ctx* ctx) {
       else (void)api->CommDestroy(c->nccl);
     }
   }
-  if (c->k1_ev) (void)hipEventDestroy(c->k1_ev);
-  if (c->done_ev) (void)hipEventDestroy(c->done_ev);
-  if (c->pulled_ev) (void)hipEventDestroy(c->pulled_ev);
-  if (c->gathered_ev) (void)hipEventDestroy(c->gathered_ev);
   delete c;
   ctx->comm = nullptr;
 }
@@ -286,10 +281,8 @@ jxlh_status jxlh_comm_init_local(jxlh_ctx* const peers[], int32_t nranks) {
     c->rank = i;
     c->nranks = nranks;
     c->peers.assign(peers, peers + nranks);
-    if (hipEventCreateWithFlags(&c->k1_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->pulled_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->gathered_ev, hipEventDisableTiming) != hipSuccess) {
+    if (c->k1_ev.create() != hipSuccess || c->done_ev.create() != hipSuccess || c->pulled_ev.create() != hipSuccess ||
+        c->gathered_ev.ev.create() != hipSuccess) {
       delete c;
       return JXLH_ERR_DEVICE;
     }
@@ -522,7 +515,7 @@ jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (int k = 0; k < n; k++)  // the previous frame's gather may still be reading this rank's band
-      if (k != i && peers[k]->comm->gathered_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, peers[k]->comm->gathered_ev, 0));
+      if (k != i) HIPCHK(ctx, peers[k]->comm->gathered_ev.wait(ctx->stream));
     if (jxlh_status st = shard_k1(ctx, &plan[i])) return st;
     HIPCHK(ctx, hipEventRecord(ctx->comm->k1_ev, ctx->stream));
   }
@@ -593,8 +586,7 @@ jxlh_status jxlh_frames_allgather_local(jxlh_ctx* const peers[], int32_t n) {
                                    dst->stream));
       }
     }
-    HIPCHK(dst, hipEventRecord(dst->comm->gathered_ev, dst->stream));
-    dst->comm->gathered_valid = true;
+    HIPCHK(dst, dst->comm->gathered_ev.record(dst->stream));
   }
   return JXLH_OK;
 }

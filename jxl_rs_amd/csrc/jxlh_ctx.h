@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "device_owned.h"
 #include "jxlh_internal.h"
 #include "run_plan.h"
 
@@ -27,29 +28,21 @@ using namespace jxlh;
 namespace jxlh_host {
 
 struct Slot {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
+  Stream stream;
+  Event done;
   // the last submission's host-to-device copies have landed -- recorded apart from `done` when device work follows the
   // copies on the slot's stream (the 12-bit entries' unpack kernel): jxlh_slot_wait / jxlh_slot_after are about the
-  // copies (host buffers, the bus), the frame waits for `done`
-  hipEvent_t copied = nullptr;
-  bool copied_valid = false;
+  // copies (host buffers, the bus), the frame waits for `done`.  Valid per submission: every one clears or records it.
+  Fence copied;
   bool used = false;
-  uint8_t* stage8 = nullptr;  // device staging of the 3-byte sparse form (positions | values), grown on demand
-  size_t stage8_cap = 0;
+  DevBuf<uint8_t> stage8;  // device staging of the 3-byte sparse form (positions | values), grown on demand
 };
 
 struct KernelTime {
   std::string name;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+  std::vector<std::pair<Event, Event>> pending;
   float total_ms = 0.f;
   int launches = 0;
-};
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;  // elements
 };
 
 }  // namespace jxlh_host
@@ -62,9 +55,9 @@ struct Comm;  // comm.hip
 struct jxlh_ctx {
   jxlh_host::Comm* comm = nullptr;  // multi-GPU: rank / transport of this context (null = single GPU)
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   std::vector<Slot> slots;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
+  Event t0, t1;
   std::string last_error;
   // frame state
   bool in_frame = false;
@@ -78,10 +71,8 @@ struct jxlh_ctx {
   // list; the descriptors go up from a pinned block, reused once local_copied (recorded behind its copy) has passed
   DevBuf<int32_t> local_arena;
   DevBuf<uint8_t> local_desc;
-  uint8_t* local_desc_host = nullptr;
-  size_t local_desc_host_cap = 0;
-  hipEvent_t local_copied = nullptr;
-  bool local_copied_valid = false;
+  Pinned<uint8_t> local_desc_host;
+  Fence local_copied;
   bool tables_set = false, lf_smoothed = false;
   jxlh_frame_params params;
   FrameDev fd;
@@ -96,7 +87,7 @@ struct jxlh_ctx {
   int tables_ok_host = 0;    // ... read back when the tables are set
   bool params_direct_ok = false;  // the frame parameters' share of FrameDev::se_direct_ok
   DevBuf<uint8_t> rgb8;  // jxlh_frame_read_rgb8 staging for host destinations
-  int* host_flag = nullptr;  // pinned
+  Pinned<int> host_flag;
   DevBuf<uint8_t> worklist;
   DevBuf<int> rerender_list;          // group ids of jxlh_frame_rerender_groups on the device
   std::vector<int> rerender_upload;   // ... and their host copy (alive until the copy has run)
@@ -131,7 +122,7 @@ struct jxlh_ctx {
   // word (zeroed when allocated and after an error was reported) is read back by the next jxlh_ctx_sync
   DevBuf<int> flow_words;
   bool flow_used = false;
-  int* host_flow_flag = nullptr;  // pinned, device-visible: the dataflow launches' error word (0 = none)
+  Pinned<int> host_flow_flag;  // device-visible: the dataflow launches' error word (0 = none)
   // jxlh_flow_profile (jxl_hip_dev.h): per-level timeline of the last dataflow launch
   DevBuf<unsigned long long> flow_prof;
   bool flow_prof_on = false;
@@ -143,11 +134,8 @@ struct jxlh_ctx {
   DevBuf<uint32_t> sp_pairs;
   DevBuf<SparseGroup> sp_groups_dev;
   DevBuf<uint2> sp_wide_dev;
-  hipEvent_t sp_expanded = nullptr;  // recorded behind what consumed the pair buffer (the next epoch's uploads wait)
-  bool sp_expanded_valid = false;
-  // recorded behind the transforms of every jxlh_frame_run: dense resubmissions wait for it
-  hipEvent_t k1_done = nullptr;
-  bool k1_done_valid = false;
+  Fence sp_expanded;  // recorded behind what consumed the pair buffer (the next epoch's uploads wait)
+  Fence k1_done;      // recorded behind the transforms of every jxlh_frame_run: dense resubmissions wait for it
   size_t worklist_nblocks = 0;  // the frame size the work list's fallback flags were last zeroed for
   uint32_t k1_launches = 0;  // parity selects the work-list counter set (vardct_worklist_reset / launch_vardct_groups)
   // Resident::kSortedPairs: the frame's pairs bucketed by varblock slot + slot tables
@@ -160,8 +148,7 @@ struct jxlh_ctx {
   DevBuf<uint16_t> se_entries[2];
   DevBuf<uint8_t> se_counts[2];
   DevBuf<uint2> se_runs[2];
-  hipEvent_t se_read[2] = {nullptr, nullptr};
-  bool se_read_valid[2] = {false, false};
+  Fence se_read[2];
   int se_live = 0;
   DevBuf<uint8_t> route_dev;  // Residence::route on the device (FrameDev::group_route)
   // extra channels inside the frame path (jxlh_frame_set_extra_channel): as handed over, converted, upsampled
@@ -253,8 +240,8 @@ struct jxlh_ctx {
   int placement_pick = -1;
   int strip_resident = 0;  // strip_resident_workgroups(cu_count), 0 = not asked yet
   // jxlh_ctx_mark / jxlh_ctx_wait_mark: a ring of events on the main stream
-  hipEvent_t handover = nullptr;  // jxlh_ctx_wait_stream: recorded on the caller's stream
-  hipEvent_t marks[JXLH_MAX_MARKS] = {};
+  Event handover;  // jxlh_ctx_wait_stream: recorded on the caller's stream
+  Event marks[JXLH_MAX_MARKS];
   uint32_t mark_seq = 0;
   // profiling
   bool timing = false;
@@ -283,28 +270,14 @@ jxlh_status probe_placement(jxlh_ctx* ctx, const int32_t* coeffs, size_t ngroups
 
 template <class T>
 jxlh_status ensure(jxlh_ctx* ctx, DevBuf<T>& b, size_t n) {
-  if (b.n >= n && b.p) return JXLH_OK;
-  if (b.p) {
-    HIPCHK(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.n = 0;
-  }
-  if (n == 0) return JXLH_OK;
-  HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T)));
-  b.n = n;
-  return JXLH_OK;
-}
-
-template <class T>
-void release(DevBuf<T>& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.n = 0;
+  const char* what = "";
+  const hipError_t e = b.ensure(n, &what);
+  return e == hipSuccess ? JXLH_OK : fail(ctx, e, what);
 }
 
 struct ScopedKernelTimer {
   jxlh_ctx* ctx;
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
   KernelTime* kt = nullptr;
   ScopedKernelTimer(jxlh_ctx* c, const char* name) : ctx(c) {
     if (!ctx->timing) return;
@@ -314,14 +287,14 @@ struct ScopedKernelTimer {
       ctx->ktimes.push_back(KernelTime{name, {}, 0.f, 0});
       kt = &ctx->ktimes.back();
     }
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
+    (void)a.create(true);
+    (void)b.create(true);
     (void)hipEventRecord(a, ctx->stream);
   }
   ~ScopedKernelTimer() {
     if (!kt) return;
     (void)hipEventRecord(b, ctx->stream);
-    kt->pending.emplace_back(a, b);
+    kt->pending.emplace_back(std::move(a), std::move(b));
   }
 };
 
@@ -334,8 +307,6 @@ inline void drain_timers(jxlh_ctx* ctx) {
         k.total_ms += ms;
         k.launches += 1;
       }
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
     }
     k.pending.clear();
   }
@@ -378,26 +349,20 @@ jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& stages, int y_lo, in
 jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsample of the channels handed over
 // abi_patches.hip: the patches stage on the colour planes `cur` (rows [y_lo, y_hi)) and, when stale, on every row of
-// the patched extra channels; the check a run makes before it launches anything; release of the context's buffers
+// the patched extra channels; the check a run makes before it launches anything
 jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y_lo, int y_hi);
 jxlh_status patches_check_run(const jxlh_ctx* ctx);
-void patches_release(jxlh_ctx* ctx);
-// abi_splines.hip: the splines stage on the colour planes `cur` (rows [y_lo, y_hi)); release of the context's buffers
+// abi_splines.hip: the splines stage on the colour planes `cur` (rows [y_lo, y_hi))
 jxlh_status run_splines(jxlh_ctx* ctx, float* const cur[3], size_t stride, int w, int h, int y_lo, int y_hi);
-void splines_release(jxlh_ctx* ctx);
 // patches and splines are drawn IN PLACE on the finished planes: whatever must not reach a pixel twice asks this
 inline bool draws_in_place(const jxlh_ctx* ctx) { return ctx->patch_n > 0 || ctx->spline_n > 0; }
 // abi_blend.hip.  blended(): the frame's result is the canvas jxlh_frame_blend composed (any render resets `result`).
 inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
-void blend_release(jxlh_ctx* ctx);
-void save_release(jxlh_ctx* ctx);  // abi_save.hip
-// ... and its argument checks, shared with jxlh_lf_preview: the descriptor's own (n_planes: pipeline channels that
+// abi_save.hip: the argument checks, shared with jxlh_lf_preview: the descriptor's own (n_planes: pipeline channels that
 // exist), `out` and its pitch against the oriented image of a w x h source, the colour stage named by `colour`
 jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes);
 jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row);
 jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a);
-void lf_frames_release(jxlh_ctx* ctx);  // abi_lf_frame.hip
-void modular_local_release(jxlh_ctx* ctx);  // abi_modular_local.hip
 // abi_lf_fill.hip.  lf_only_snapshot: ctx->lf_only_run <- the frame's marks (true = at least one group is marked).
 // lf_split_groups: the sorted `groups` of a run, the unmarked ones (all, without marks) first, on the device (rerender_list);
 // *n_k1 of them are K1's, the *n_fill behind them the fill's.  run_lf_fill: Upsample8x of the LF image into the planes

@@ -24,49 +24,36 @@ extern "C" jxlh_status jxlh_probe_copy_bandwidth(jxlh_ctx* ctx, size_t bytes, in
   if (!ctx || !gb_per_s || bytes < 16 || reps < 1) return JXLH_ERR_INVALID_ARGUMENT;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = bytes / 16;
-  float4 *a = nullptr, *b = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&a), n * 16) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
-  if (hipMalloc(reinterpret_cast<void**>(&b), n * 16) != hipSuccess) {
-    (void)hipFree(a);
-    return JXLH_ERR_OUT_OF_MEMORY;
+  DevBuf<float4> a, b;
+  if (a.alloc(n) != hipSuccess || b.alloc(n) != hipSuccess) return JXLH_ERR_OUT_OF_MEMORY;
+  Event e0, e1;
+  HIPCHK(ctx, hipMemsetAsync(a.p, 1, n * 16, ctx->stream));
+  HIPCHK(ctx, e0.create(true));
+  HIPCHK(ctx, e1.create(true));
+  size_t g = (n + 256 * 8 - 1) / (256 * 8);
+  if (g > 8192) g = 8192;
+  if (g < 1) g = 1;
+  // two cache policies, the better one counts: plain accesses, and `nt` on both streams (read once / not read again
+  // by this kernel), which copies a frame-sized buffer ~10 % faster on this device (4.8 vs 5.3 TB/s; a buffer that
+  // fits the Infinity Cache prefers plain: 6.5 vs 5.9)
+  double best = 0.0;
+  for (int mode = 0; mode < 2; mode++) {
+    auto launch = [&]() {
+      if (mode) hipLaunchKernelGGL(k_probe_copy<3>, dim3((unsigned)g), dim3(256), 0, ctx->stream, a.p, b.p, n);
+      else hipLaunchKernelGGL(k_probe_copy<0>, dim3((unsigned)g), dim3(256), 0, ctx->stream, a.p, b.p, n);
+    };
+    for (int i = 0; i < 2; i++) launch();
+    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+    for (int i = 0; i < reps; i++) launch();
+    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
+    const double rate = 2.0 * (double)(n * 16) * reps / ((double)ms * 1e-3) / 1e9;
+    if (rate > best) best = rate;
   }
-  jxlh_status st = JXLH_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto body = [&]() -> jxlh_status {
-    HIPCHK(ctx, hipMemsetAsync(a, 1, n * 16, ctx->stream));
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
-    size_t g = (n + 256 * 8 - 1) / (256 * 8);
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    // two cache policies, the better one counts: plain accesses, and `nt` on both streams (read once / not read again
-    // by this kernel), which copies a frame-sized buffer ~10 % faster on this device (4.8 vs 5.3 TB/s; a buffer that
-    // fits the Infinity Cache prefers plain: 6.5 vs 5.9)
-    double best = 0.0;
-    for (int mode = 0; mode < 2; mode++) {
-      auto launch = [&]() {
-        if (mode) hipLaunchKernelGGL(k_probe_copy<3>, dim3((unsigned)g), dim3(256), 0, ctx->stream, a, b, n);
-        else hipLaunchKernelGGL(k_probe_copy<0>, dim3((unsigned)g), dim3(256), 0, ctx->stream, a, b, n);
-      };
-      for (int i = 0; i < 2; i++) launch();
-      HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-      for (int i = 0; i < reps; i++) launch();
-      HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-      HIPCHK(ctx, hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-      const double rate = 2.0 * (double)(n * 16) * reps / ((double)ms * 1e-3) / 1e9;
-      if (rate > best) best = rate;
-    }
-    *gb_per_s = (float)best;
-    return JXLH_OK;
-  };
-  st = body();
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(a);
-  (void)hipFree(b);
-  return st;
+  *gb_per_s = (float)best;
+  return JXLH_OK;
 }
 
 // ---- placement probe (round 6, profiles/r06_q_context_placement.txt): the same kernels on the same data run up to 10 %
@@ -111,38 +98,31 @@ namespace jxlh_host {
 // average ms of the two movers on a candidate set of buffers (contents are overwritten / garbage is read: timing only)
 jxlh_status probe_placement(jxlh_ctx* ctx, const int32_t* coeffs, size_t ngroups, float* const planes[3], float* const tmp[3],
                             size_t plane_elems, float* k1_like_ms, float* filter_like_ms) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  jxlh_status st = JXLH_OK;
-  auto body = [&]() -> jxlh_status {
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
-    const int warm = 2, reps = 6;
-    float ms[2] = {0.f, 0.f};
-    for (int which = 0; which < 2; which++) {
-      auto launch = [&]() {
-        if (which == 0)
-          hipLaunchKernelGGL(k_probe_k1_like, dim3(2048), dim3(256), 0, ctx->stream, coeffs, ngroups, planes[0], planes[1],
-                             planes[2], plane_elems);
-        else
-          hipLaunchKernelGGL(k_probe_filter_like, dim3(4096), dim3(256), 0, ctx->stream, planes[0], planes[1], planes[2], tmp[0],
-                             tmp[1], tmp[2], plane_elems / 4);
-      };
-      for (int i = 0; i < warm; i++) launch();
-      HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-      for (int i = 0; i < reps; i++) launch();
-      HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-      HIPCHK(ctx, hipEventSynchronize(e1));
-      HIPCHK(ctx, hipEventElapsedTime(&ms[which], e0, e1));
-      ms[which] /= reps;
-    }
-    *k1_like_ms = ms[0];
-    *filter_like_ms = ms[1];
-    return JXLH_OK;
-  };
-  st = body();
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return st;
+  Event e0, e1;
+  HIPCHK(ctx, e0.create(true));
+  HIPCHK(ctx, e1.create(true));
+  const int warm = 2, reps = 6;
+  float ms[2] = {0.f, 0.f};
+  for (int which = 0; which < 2; which++) {
+    auto launch = [&]() {
+      if (which == 0)
+        hipLaunchKernelGGL(k_probe_k1_like, dim3(2048), dim3(256), 0, ctx->stream, coeffs, ngroups, planes[0], planes[1],
+                           planes[2], plane_elems);
+      else
+        hipLaunchKernelGGL(k_probe_filter_like, dim3(4096), dim3(256), 0, ctx->stream, planes[0], planes[1], planes[2], tmp[0],
+                           tmp[1], tmp[2], plane_elems / 4);
+    };
+    for (int i = 0; i < warm; i++) launch();
+    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+    for (int i = 0; i < reps; i++) launch();
+    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(e1));
+    HIPCHK(ctx, hipEventElapsedTime(&ms[which], e0, e1));
+    ms[which] /= reps;
+  }
+  *k1_like_ms = ms[0];
+  *filter_like_ms = ms[1];
+  return JXLH_OK;
 }
 }  // namespace jxlh_host
 

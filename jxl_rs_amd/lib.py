@@ -78,7 +78,7 @@ DEV_SYMBOLS = [
     "jxlh_timer_start", "jxlh_timer_stop", "jxlh_kernel_timing_enable", "jxlh_kernel_timing_get",
     "jxlh_kernel_timing_reset", "jxlh_selftest_recip", "jxlh_probe_copy_bandwidth", "jxlh_frame_path",
     "jxlh_flow_profile", "jxlh_frame_k1_counters", "jxlh_probe_placement", "jxlh_worklist_layout",
-    "jxlh_save_tile_layout", "jxlh_splines_set_batch_budget", "jxlh_splines_bin_layout",
+    "jxlh_save_tile_layout", "jxlh_splines_set_batch_budget", "jxlh_splines_bin_layout", "jxlh_live_resources",
 ]
 
 
@@ -458,6 +458,8 @@ def load():
     L.jxlh_frames_allgather_local.argtypes = [C.POINTER(vp), i32]
     L.jxlh_comm_allgather.argtypes = [vp, vp, sz]
     L.jxlh_probe_copy_bandwidth.argtypes = [vp, sz, i32, fp]
+    if hasattr(L, "jxlh_live_resources"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
+        L.jxlh_live_resources.argtypes = [C.POINTER(C.c_uint64)]
     if hasattr(L, "jxlh_frame_path"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
         L.jxlh_frame_path.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     if hasattr(L, "jxlh_frame_set_extra_channel"):
@@ -572,6 +574,16 @@ def worklist_layout(xblocks, yblocks):
     if st != 0:
         raise JxlHipError(st, "worklist_layout")
     return int(out[0]), [(int(out[1 + 2 * r]), int(out[2 + 2 * r])) for r in range(WORKLIST_REGIONS)]
+
+
+def live_resources():
+    """jxlh_live_resources (jxl_hip_dev.h, host only): (device buffers, pinned blocks, events, streams) the library
+    holds right now over all contexts of the process"""
+    out = (C.c_uint64 * 4)()
+    st = _lib().jxlh_live_resources(out)
+    if st != 0:
+        raise JxlHipError(st, "live_resources")
+    return tuple(int(v) for v in out)
 
 
 def host_pack_slots(group_coeffs, group_id=0, bits12=False, entries=None, slot_counts=None, wide_capacity=4096):
