@@ -74,26 +74,7 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
   if (!ctx->in_frame || !ctx->rendered || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
   if (jxlh_status st = check_desc(ctx, d)) return st;
   BlendLaunch a{};
-  a.mode = kModeNone;
-  if (colour) {
-    switch (colour->color) {
-      case JXLH_COLOR_XYB:
-        if (colour->transfer > JXLH_TF_GAMMA) return JXLH_ERR_INVALID_ARGUMENT;
-        a.mode = (int)colour->transfer;  // JXLH_TF_* share the values of the internal modes
-        for (int i = 0; i < 9; i++) a.xyb.mat[i] = colour->xyb.opsin_inverse_matrix[i];
-        for (int i = 0; i < 3; i++) {
-          a.xyb.bias_cbrt[i] = colour->xyb.bias_cbrt[i];
-          a.xyb.scaled_bias[i] = colour->xyb.scaled_bias[i];
-        }
-        a.xyb.intensity_scale = colour->xyb.intensity_scale;
-        break;
-      case JXLH_COLOR_YCBCR: a.mode = kModeYcbcr; break;
-      case JXLH_COLOR_NONE: break;
-      default: return JXLH_ERR_INVALID_ARGUMENT;
-    }
-    a.tf.param = colour->tf_param;
-    for (int i = 0; i < 3; i++) a.tf.lum[i] = colour->hlg_luminance_rgb[i];
-  }
+  if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
   // the frame's own planes: the render's result, also when an earlier composition has taken its place
   const bool again = blended(ctx);
   float* fr[3];

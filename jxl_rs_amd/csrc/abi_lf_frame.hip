@@ -39,10 +39,10 @@ jxlh_status lf_preview(jxlh_ctx* ctx, uint32_t slot, uint32_t image_w, uint32_t 
   const bool rgb = d->channels[0] == 0 && d->channels[1] == 1 && d->channels[2] == 2;
   const bool bgr = d->channels[0] == 2 && d->channels[1] == 1 && d->channels[2] == 0;
   if (d->n_channels != 3 || !(rgb || bgr) || d->premultiply || d->n_spot) return JXLH_ERR_INVALID_ARGUMENT;
-  SaveLaunch sl{};
-  if (jxlh_status st = save_colour_mode(colour, sl)) return st;
+  LfPreviewLaunch a{};
+  if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
   // the cases in which the reference shows no preview (lf_preview.rs: Ok(false))
-  if (!colour || colour->color != JXLH_COLOR_XYB || sl.mode == kTfLinear) return JXLH_ERR_UNSUPPORTED;
+  if (!colour || colour->color != JXLH_COLOR_XYB || a.mode == kTfLinear) return JXLH_ERR_UNSUPPORTED;
   const jxlh_ctx::LfSlot& s = ctx->lf_slots[slot];
   if (!s.set || image_w == 0 || image_h == 0 || s.w != (image_w + 7) / 8 || s.h != (image_h + 7) / 8)
     return JXLH_ERR_INVALID_ARGUMENT;
@@ -52,7 +52,6 @@ jxlh_status lf_preview(jxlh_ctx* ctx, uint32_t slot, uint32_t image_w, uint32_t 
   if (w == 0 || h == 0) return JXLH_OK;
   // checked: from here on only the device can fail
   if (jxlh_status st = upload_upsampling_kernels(ctx, 8)) return st;
-  LfPreviewLaunch a{};
   for (int c = 0; c < 3; c++) a.plane[c] = s.buf.p + (size_t)c * s.stride * s.h;
   a.stride = (uint32_t)s.stride;
   a.sw = (int)s.w;
@@ -64,55 +63,26 @@ jxlh_status lf_preview(jxlh_ctx* ctx, uint32_t slot, uint32_t image_w, uint32_t 
   a.iw = (int)image_w;
   a.ih = (int)image_h;
   a.kernels = ctx->ups_kernels.p;
-  a.mode = sl.mode;
-  a.xyb = sl.xyb;
-  a.tf = sl.tf;
-  a.format = (int)d->format;
+  save_format(d, a);
   a.spp = d->fill_opaque_alpha ? 4 : 3;
   a.bgr = bgr;
-  const uint32_t max_int = d->format <= JXLH_SAVE_U16 ? (1u << d->bit_depth) - 1 : 0;
-  a.maxv = (float)max_int;
-  a.big_endian = d->big_endian && d->format != JXLH_SAVE_U8;
-  a.fill_bits = d->format <= JXLH_SAVE_U16 ? max_int : d->format == JXLH_SAVE_F16 ? 0x3c00u : 0x3f800000u;
-  if (a.big_endian)
-    a.fill_bits = d->format == JXLH_SAVE_F32 ? __builtin_bswap32(a.fill_bits)
-                                             : (((a.fill_bits >> 8) | (a.fill_bits << 8)) & 0xffffu);
-  const uint32_t o = d->orientation;
-  a.transpose = o >= 5;
-  a.flip_x = o == 2 || o == 3 || o == 6 || o == 7;
-  a.flip_y = o == 3 || o == 4 || o == 7 || o == 8;
-  const size_t pb = (size_t)a.spp * (d->format == JXLH_SAVE_U8 ? 1 : d->format == JXLH_SAVE_F32 ? 4 : 2);
-  if (is_device_ptr(out)) {
-    a.out = static_cast<uint8_t*>(out);
-    a.out_stride = bytes_per_row;
-    {
-      ScopedKernelTimer t(ctx, "k_lf_preview");
-      launch_lf_preview(ctx->stream, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    if (wait) JXLH_SYNC(ctx);
-    return JXLH_OK;
-  }
-  // host memory: the staging buffer holds exactly the rectangle of the oriented image the rect's pixels land in
+  // the rectangle of the oriented image the rect's pixels land in
   const size_t ix0 = (size_t)x0 * 8, iy0 = (size_t)y0 * 8;
   const size_t ix1 = std::min<size_t>(((size_t)x0 + w) * 8, image_w), iy1 = std::min<size_t>(((size_t)y0 + h) * 8, image_h);
-  const size_t fx0 = a.flip_x ? (a.transpose ? image_h - iy1 : image_w - ix1) : (a.transpose ? iy0 : ix0);
-  const size_t fy0 = a.flip_y ? (a.transpose ? image_w - ix1 : image_h - iy1) : (a.transpose ? ix0 : iy0);
-  const size_t rect_w = a.transpose ? iy1 - iy0 : ix1 - ix0, rect_h = a.transpose ? ix1 - ix0 : iy1 - iy0;
-  const size_t row_bytes = rect_w * pb, pitch = round_up(row_bytes, 4);
-  if (jxlh_status st = ensure(ctx, ctx->rgb8, pitch * rect_h)) return st;
-  // the image origin that puts the rectangle at the start of the staging buffer (never dereferenced outside it)
-  a.out = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->rgb8.p) - fy0 * pitch - fx0 * pb);
-  a.out_stride = pitch;
-  {
-    ScopedKernelTimer t(ctx, "k_lf_preview");
-    launch_lf_preview(ctx->stream, a);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  if (jxlh_status st = copy2d(ctx, static_cast<uint8_t*>(out) + fy0 * bytes_per_row + fx0 * pb, bytes_per_row, ctx->rgb8.p,
-                              pitch, row_bytes, rect_h, ctx->stream))
+  OutRect r;
+  r.x0 = a.flip_x ? (a.transpose ? image_h - iy1 : image_w - ix1) : (a.transpose ? iy0 : ix0);
+  r.y0 = a.flip_y ? (a.transpose ? image_w - ix1 : image_h - iy1) : (a.transpose ? ix0 : iy0);
+  r.w = a.transpose ? iy1 - iy0 : ix1 - ix0;
+  r.h = a.transpose ? ix1 - ix0 : iy1 - iy0;
+  const size_t pb = (size_t)a.spp * (size_t)save_sample_bytes(d->format);
+  if (jxlh_status st = write_out(ctx, static_cast<uint8_t*>(out) + r.y0 * bytes_per_row + r.x0 * pb, bytes_per_row, pb, r,
+                                 "k_lf_preview", /*wait=*/false, [&](uint8_t* origin, size_t pitch) {
+                                   a.out = origin;
+                                   a.out_stride = pitch;
+                                   launch_lf_preview(ctx->stream, a);
+                                 }))
     return st;
-  if (wait) JXLH_SYNC(ctx);
+  if (wait) JXLH_SYNC(ctx);  // a device destination included
   return JXLH_OK;
 }
 

@@ -7,17 +7,6 @@
 extern "C" {
 
 namespace {
-const XybParamsDev* xyb_params_dev(const jxlh_xyb_params* p, XybParamsDev* d) {
-  if (!p) return nullptr;
-  for (int i = 0; i < 9; i++) d->mat[i] = p->opsin_inverse_matrix[i];
-  for (int i = 0; i < 3; i++) {
-    d->bias_cbrt[i] = p->bias_cbrt[i];
-    d->scaled_bias[i] = p->scaled_bias[i];
-  }
-  d->intensity_scale = p->intensity_scale;
-  return d;
-}
-
 SubPlanesDev sub_planes_dev(const jxlh_ctx* ctx) {
   const FrameDev& f = ctx->fd;
   SubPlanesDev sp;
@@ -32,115 +21,63 @@ SubPlanesDev sub_planes_dev(const jxlh_ctx* ctx) {
   return sp;
 }
 
-// mode: kTfLinear..kTfGamma = XybStage (p) + that transfer function (t); kModeYcbcr; kModeNone
-jxlh_status read_rgb8(jxlh_ctx* ctx, int mode, const jxlh_xyb_params* p, const TfParamsDev& tf, uint32_t channels,
-                      uint32_t y0, uint32_t y1, void* out, size_t bytes_per_row, bool wait = true) {
-  if (!ctx || !out || (channels != 3 && channels != 4)) return JXLH_ERR_INVALID_ARGUMENT;
+// Rows [y0, y1) of the result behind the colour stage `d` names, as interleaved 8- / 16-bit samples with an opaque fourth
+// one.  16 bit is the identity save (channels 0 1 2, orientation 1, native byte order) of k_save.hip; 8 bit, and a YCbCr
+// frame whose chroma is still sub-sampled, have the kernels of k_output.hip.  `out` is row y0.  Unlike jxlh_frame_save
+// this serves sharded contexts (a rank converts its band: convert_band_to_output) and results of any size.
+jxlh_status read_output(jxlh_ctx* ctx, const jxlh_output_desc* d, uint32_t y0, uint32_t y1, void* out,
+                        size_t bytes_per_row, bool wait) {
+  if (!ctx || !d || (d->bits != 8 && d->bits != 16)) return JXLH_ERR_INVALID_ARGUMENT;
+  SaveLaunch a{};
+  if (jxlh_status st = colour_stage(d, &a.mode, &a.xyb, &a.tf)) return st;
+  const uint32_t channels = d->channels;
+  if (!out || (channels != 3 && channels != 4)) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
-  if (blended(ctx) && mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
+  if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   if (y1 > (uint32_t)ctx->res_h) y1 = (uint32_t)ctx->res_h;
-  if (y0 >= y1 || bytes_per_row < (size_t)ctx->res_w * channels) return JXLH_ERR_INVALID_ARGUMENT;
-  XybParamsDev d = {};
-  xyb_params_dev(p, &d);
-  const int rows = (int)(y1 - y0);
-  const bool fused_chroma = ctx->chroma_lazy && mode == kModeYcbcr;
-  if (!fused_chroma) materialise_chroma(ctx);
-  const float* planes[3] = {ctx->result[0], ctx->result[1], ctx->result[2]};
-  if (fused_chroma) {
+  const size_t bps = d->bits / 8, pb = channels * bps;
+  if (y0 >= y1 || bytes_per_row < (size_t)ctx->res_w * pb || bytes_per_row % bps != 0 ||
+      reinterpret_cast<uintptr_t>(out) % bps != 0)
+    return JXLH_ERR_INVALID_ARGUMENT;
+  // the labels are the read-outs' names in jxlh_kernel_timing_get (tools and recorded profiles key on them), not kernels
+  const OutRect r = {0, y0, (size_t)ctx->res_w, y1 - y0};
+  if (ctx->chroma_lazy && a.mode == kModeYcbcr) {
     const SubPlanesDev sp = sub_planes_dev(ctx);
-    const size_t tight = ((size_t)ctx->res_w * channels + 3) & ~(size_t)3;
-    const bool dev = is_device_ptr(out);
-    if (!dev)
-      if (jxlh_status st = ensure(ctx, ctx->rgb8, tight * (size_t)rows)) return st;
-    {
-      ScopedKernelTimer t(ctx, "k_ycbcr_sub_to_rgb");
-      launch_ycbcr_sub_to_rgb(ctx->stream, sp, ctx->res_stride, ctx->res_w, (int)y0, rows, (int)channels, 8,
-                              dev ? out : (void*)ctx->rgb8.p, dev ? bytes_per_row : tight);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    if (dev) return JXLH_OK;
-    if (jxlh_status st = copy2d(ctx, out, bytes_per_row, ctx->rgb8.p, tight, (size_t)ctx->res_w * channels, (size_t)rows,
-                                ctx->stream))
-      return st;
-    if (wait) JXLH_SYNC(ctx);
-    return JXLH_OK;
+    return write_out(ctx, out, bytes_per_row, pb, r, "k_ycbcr_sub_to_rgb", wait, [&](uint8_t* origin, size_t pitch) {
+      launch_ycbcr_sub_to_rgb(ctx->stream, sp, ctx->res_stride, ctx->res_w, (int)y0, (int)(y1 - y0), (int)channels,
+                              (int)d->bits, origin, pitch);
+    });
   }
-  if (is_device_ptr(out)) {
-    ScopedKernelTimer t(ctx, "k_xyb_to_rgb8");
-    launch_xyb_to_rgb8(ctx->stream, planes, ctx->res_stride, ctx->res_w, (int)y0, rows, mode, d, tf, (int)channels,
-                       static_cast<uint8_t*>(out), bytes_per_row);
-    HIPCHK(ctx, hipGetLastError());
-    return JXLH_OK;
+  if (d->bits == 8) {  // a kernel of its own: measured faster than the save's identity case at this depth
+    materialise_chroma(ctx);
+    const float* planes[3] = {ctx->result[0], ctx->result[1], ctx->result[2]};
+    return write_out(ctx, out, bytes_per_row, pb, r, "k_xyb_to_rgb8", wait, [&](uint8_t* origin, size_t pitch) {
+      launch_xyb_to_rgb8(ctx->stream, planes, ctx->res_stride, ctx->res_w, (int)y0, (int)(y1 - y0), a.mode, a.xyb, a.tf,
+                         (int)channels, origin, pitch);
+    });
   }
-  // staging rows are dword aligned; when the caller's rows are tight and already aligned the D2H
-  // is one linear copy, otherwise a 2-D copy of exactly the pixel bytes (row padding is never written)
-  const size_t tight = ((size_t)ctx->res_w * channels + 3) & ~(size_t)3;
-  if (jxlh_status st = ensure(ctx, ctx->rgb8, tight * (size_t)rows)) return st;
-  {
-    ScopedKernelTimer t(ctx, "k_xyb_to_rgb8");
-    launch_xyb_to_rgb8(ctx->stream, planes, ctx->res_stride, ctx->res_w, (int)y0, rows, mode, d, tf, (int)channels, ctx->rgb8.p,
-                       tight);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  const size_t row_bytes = (size_t)ctx->res_w * channels;
-  if (jxlh_status st = copy2d(ctx, out, bytes_per_row, ctx->rgb8.p, tight, row_bytes, (size_t)rows, ctx->stream))
-    return st;
-  if (wait) JXLH_SYNC(ctx);
-  return JXLH_OK;
+  // 16 bit: the identity save
+  jxlh_save_desc save = {};
+  save.n_channels = 3;
+  for (uint32_t k = 0; k < 3; k++) save.channels[k] = k;
+  save.fill_opaque_alpha = channels == 4;
+  save.format = JXLH_SAVE_U16;
+  save.bit_depth = 16;
+  save.orientation = 1;
+  void* image = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(out) - (size_t)y0 * bytes_per_row);
+  return save_result_rows(ctx, a, &save, nullptr, nullptr, y0, y1, image, bytes_per_row, "k_xyb_to_rgb16", wait);
 }
 
-jxlh_status read_rgb16(jxlh_ctx* ctx, int mode, const jxlh_xyb_params* p, const TfParamsDev& tf, uint32_t channels,
-                       uint32_t y0, uint32_t y1, void* out, size_t bytes_per_row, bool wait = true) {
-  if (!ctx || !out || (channels != 3 && channels != 4)) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
-  if (blended(ctx) && mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
-  if (y1 > (uint32_t)ctx->res_h) y1 = (uint32_t)ctx->res_h;
-  const size_t row_bytes = (size_t)ctx->res_w * channels * sizeof(uint16_t);
-  if (y0 >= y1 || bytes_per_row < row_bytes || bytes_per_row % sizeof(uint16_t) != 0 ||
-      reinterpret_cast<uintptr_t>(out) % sizeof(uint16_t) != 0)
-    return JXLH_ERR_INVALID_ARGUMENT;
-  XybParamsDev d = {};
-  xyb_params_dev(p, &d);
-  const int rows = (int)(y1 - y0);
-  const bool fused_chroma = ctx->chroma_lazy && mode == kModeYcbcr;
-  if (!fused_chroma) materialise_chroma(ctx);
-  const float* planes[3] = {ctx->result[0], ctx->result[1], ctx->result[2]};
-  if (fused_chroma) {
-    const SubPlanesDev sp = sub_planes_dev(ctx);
-    const bool dev = is_device_ptr(out);
-    if (!dev)
-      if (jxlh_status st = ensure(ctx, ctx->rgb8, row_bytes * (size_t)rows)) return st;
-    {
-      ScopedKernelTimer t(ctx, "k_ycbcr_sub_to_rgb");
-      launch_ycbcr_sub_to_rgb(ctx->stream, sp, ctx->res_stride, ctx->res_w, (int)y0, rows, (int)channels, 16,
-                              dev ? out : (void*)ctx->rgb8.p,
-                              dev ? bytes_per_row / sizeof(uint16_t) : (size_t)ctx->res_w * channels);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    if (dev) return JXLH_OK;
-    if (jxlh_status st = copy2d(ctx, out, bytes_per_row, ctx->rgb8.p, row_bytes, row_bytes, (size_t)rows, ctx->stream))
-      return st;
-    if (wait) JXLH_SYNC(ctx);
-    return JXLH_OK;
-  }
-  if (is_device_ptr(out)) {
-    ScopedKernelTimer t(ctx, "k_xyb_to_rgb16");
-    launch_xyb_to_rgb16(ctx->stream, planes, ctx->res_stride, ctx->res_w, (int)y0, rows, mode, d, tf, (int)channels,
-                        static_cast<uint16_t*>(out), bytes_per_row / sizeof(uint16_t));
-    HIPCHK(ctx, hipGetLastError());
-    return JXLH_OK;
-  }
-  if (jxlh_status st = ensure(ctx, ctx->rgb8, row_bytes * (size_t)rows)) return st;
-  {
-    ScopedKernelTimer t(ctx, "k_xyb_to_rgb16");
-    launch_xyb_to_rgb16(ctx->stream, planes, ctx->res_stride, ctx->res_w, (int)y0, rows, mode, d, tf, (int)channels,
-                        reinterpret_cast<uint16_t*>(ctx->rgb8.p), (size_t)ctx->res_w * channels);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  if (jxlh_status st = copy2d(ctx, out, bytes_per_row, ctx->rgb8.p, row_bytes, row_bytes, (size_t)rows, ctx->stream))
-    return st;
-  if (wait) JXLH_SYNC(ctx);
-  return JXLH_OK;
+// the dedicated entry points are read_output with a descriptor of their own: XYB + sRGB (p) or YCbCr (no p)
+jxlh_status read_fixed(jxlh_ctx* ctx, const jxlh_xyb_params* p, uint32_t bits, uint32_t channels, uint32_t y0, uint32_t y1,
+                       void* out, size_t bytes_per_row, bool wait = true) {
+  jxlh_output_desc d = {};
+  d.color = p ? JXLH_COLOR_XYB : JXLH_COLOR_YCBCR;
+  d.transfer = JXLH_TF_SRGB;
+  if (p) d.xyb = *p;
+  d.bits = bits;
+  d.channels = channels;
+  return read_output(ctx, &d, y0, y1, out, bytes_per_row, wait);
 }
 }  // namespace
 
@@ -148,53 +85,30 @@ jxlh_status jxlh_frame_read_rgb8(jxlh_ctx* ctx, const jxlh_xyb_params* p, uint32
                                  uint32_t y1, void* out, size_t bytes_per_row) {
   JXLH_ON_DEVICE(ctx);
   if (!p) return JXLH_ERR_INVALID_ARGUMENT;
-  return read_rgb8(ctx, kTfSrgb, p, TfParamsDev{}, channels, y0, y1, out, bytes_per_row);
+  return read_fixed(ctx, p, 8, channels, y0, y1, out, bytes_per_row);
 }
 jxlh_status jxlh_frame_read_rgb8_async(jxlh_ctx* ctx, const jxlh_xyb_params* p, uint32_t channels, uint32_t y0,
                                        uint32_t y1, void* out, size_t bytes_per_row) {
   JXLH_ON_DEVICE(ctx);
   if (!p) return JXLH_ERR_INVALID_ARGUMENT;
-  return read_rgb8(ctx, kTfSrgb, p, TfParamsDev{}, channels, y0, y1, out, bytes_per_row, /*wait=*/false);
+  return read_fixed(ctx, p, 8, channels, y0, y1, out, bytes_per_row, /*wait=*/false);
 }
 jxlh_status jxlh_frame_read_rgb16(jxlh_ctx* ctx, const jxlh_xyb_params* p, uint32_t channels, uint32_t y0,
                                   uint32_t y1, void* out, size_t bytes_per_row) {
   JXLH_ON_DEVICE(ctx);
   if (!p) return JXLH_ERR_INVALID_ARGUMENT;
-  return read_rgb16(ctx, kTfSrgb, p, TfParamsDev{}, channels, y0, y1, out, bytes_per_row);
+  return read_fixed(ctx, p, 16, channels, y0, y1, out, bytes_per_row);
 }
 jxlh_status jxlh_frame_read_ycbcr_rgb8(jxlh_ctx* ctx, uint32_t channels, uint32_t y0, uint32_t y1, void* out,
                                        size_t bytes_per_row) {
   JXLH_ON_DEVICE(ctx);
-  return read_rgb8(ctx, kModeYcbcr, nullptr, TfParamsDev{}, channels, y0, y1, out, bytes_per_row);
+  return read_fixed(ctx, nullptr, 8, channels, y0, y1, out, bytes_per_row);
 }
 jxlh_status jxlh_frame_read_ycbcr_rgb16(jxlh_ctx* ctx, uint32_t channels, uint32_t y0, uint32_t y1, void* out,
                                         size_t bytes_per_row) {
   JXLH_ON_DEVICE(ctx);
-  return read_rgb16(ctx, kModeYcbcr, nullptr, TfParamsDev{}, channels, y0, y1, out, bytes_per_row);
+  return read_fixed(ctx, nullptr, 16, channels, y0, y1, out, bytes_per_row);
 }
-
-namespace {
-jxlh_status read_output(jxlh_ctx* ctx, const jxlh_output_desc* d, uint32_t y0, uint32_t y1, void* out,
-                        size_t bytes_per_row, bool wait) {
-  if (!ctx || !d || (d->bits != 8 && d->bits != 16)) return JXLH_ERR_INVALID_ARGUMENT;
-  int mode;
-  switch (d->color) {
-    case JXLH_COLOR_XYB:
-      if (d->transfer > JXLH_TF_GAMMA) return JXLH_ERR_INVALID_ARGUMENT;
-      mode = (int)d->transfer;  // JXLH_TF_* share the values of the internal modes
-      break;
-    case JXLH_COLOR_YCBCR: mode = kModeYcbcr; break;
-    case JXLH_COLOR_NONE: mode = kModeNone; break;
-    default: return JXLH_ERR_INVALID_ARGUMENT;
-  }
-  TfParamsDev t;
-  t.param = d->tf_param;
-  for (int i = 0; i < 3; i++) t.lum[i] = d->hlg_luminance_rgb[i];
-  const jxlh_xyb_params* xp = d->color == JXLH_COLOR_XYB ? &d->xyb : nullptr;
-  return d->bits == 8 ? read_rgb8(ctx, mode, xp, t, d->channels, y0, y1, out, bytes_per_row, wait)
-                      : read_rgb16(ctx, mode, xp, t, d->channels, y0, y1, out, bytes_per_row, wait);
-}
-}  // namespace
 
 }  // extern "C"
 // comm.hip: a rank's band of the converted image into its rows of `out` (device memory), queued on the context's stream

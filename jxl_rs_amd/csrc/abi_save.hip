@@ -12,7 +12,6 @@ namespace jxlh_host {
 
 namespace {
 
-int sample_bytes(uint32_t format) { return format == JXLH_SAVE_U8 ? 1 : format == JXLH_SAVE_F32 ? 4 : 2; }
 uint32_t samples_per_pixel(const jxlh_save_desc* d) { return d->n_channels + (d->fill_opaque_alpha ? 1 : 0); }
 bool is_extra(uint32_t ch, uint32_t n_planes) { return ch >= 3 && ch < n_planes; }
 
@@ -36,33 +35,33 @@ jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes) {
 
 // `out` and its pitch against the oriented image of a w x h source
 jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row) {
-  const size_t bps = (size_t)sample_bytes(d->format);
+  const size_t bps = (size_t)save_sample_bytes(d->format);
   const size_t row = (size_t)(d->orientation >= 5 ? h : w) * samples_per_pixel(d) * bps;
   if (!out || bytes_per_row < row || bytes_per_row % bps != 0 || reinterpret_cast<uintptr_t>(out) % bps != 0)
     return JXLH_ERR_INVALID_ARGUMENT;
   return JXLH_OK;
 }
 
-jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a) {
-  a.mode = kModeNone;
+jxlh_status colour_stage(const jxlh_output_desc* colour, int* mode, XybParamsDev* xyb, TfParamsDev* tf) {
+  *mode = kModeNone;
   if (!colour) return JXLH_OK;
   switch (colour->color) {
     case JXLH_COLOR_XYB:
       if (colour->transfer > JXLH_TF_GAMMA) return JXLH_ERR_INVALID_ARGUMENT;
-      a.mode = (int)colour->transfer;  // JXLH_TF_* share the values of the internal modes
-      for (int i = 0; i < 9; i++) a.xyb.mat[i] = colour->xyb.opsin_inverse_matrix[i];
+      *mode = (int)colour->transfer;  // JXLH_TF_* share the values of the internal modes
+      for (int i = 0; i < 9; i++) xyb->mat[i] = colour->xyb.opsin_inverse_matrix[i];
       for (int i = 0; i < 3; i++) {
-        a.xyb.bias_cbrt[i] = colour->xyb.bias_cbrt[i];
-        a.xyb.scaled_bias[i] = colour->xyb.scaled_bias[i];
+        xyb->bias_cbrt[i] = colour->xyb.bias_cbrt[i];
+        xyb->scaled_bias[i] = colour->xyb.scaled_bias[i];
       }
-      a.xyb.intensity_scale = colour->xyb.intensity_scale;
+      xyb->intensity_scale = colour->xyb.intensity_scale;
       break;
-    case JXLH_COLOR_YCBCR: a.mode = kModeYcbcr; break;
+    case JXLH_COLOR_YCBCR: *mode = kModeYcbcr; break;
     case JXLH_COLOR_NONE: break;
     default: return JXLH_ERR_INVALID_ARGUMENT;
   }
-  a.tf.param = colour->tf_param;
-  for (int i = 0; i < 3; i++) a.tf.lum[i] = colour->hlg_luminance_rgb[i];
+  tf->param = colour->tf_param;
+  for (int i = 0; i < 3; i++) tf->lum[i] = colour->hlg_luminance_rgb[i];
   return JXLH_OK;
 }
 
@@ -71,7 +70,7 @@ namespace {
 // everything of the launch the (checked) descriptor decides; plane(ch) / stride(ch) resolve a pipeline channel
 template <class PlaneOf, class StrideOf>
 void fill_desc(const jxlh_save_desc* d, PlaneOf plane, StrideOf stride, SaveLaunch& a) {
-  a.format = (int)d->format;  // JXLH_SAVE_* share the values of kSave*
+  save_format(d, a);
   a.spp = (int)samples_per_pixel(d);
   a.colour = 0;
   for (uint32_t k = 0; k < 4; k++) {
@@ -101,67 +100,24 @@ void fill_desc(const jxlh_save_desc* d, PlaneOf plane, StrideOf stride, SaveLaun
   const bool premul = a.colour && d->premultiply;
   a.premul_plane = premul ? plane(d->premultiply_alpha_channel) : nullptr;
   a.premul_stride = premul ? stride(d->premultiply_alpha_channel) : 0;
-  const uint32_t max_int = d->format <= JXLH_SAVE_U16 ? (1u << d->bit_depth) - 1 : 0;
-  a.maxv = (float)max_int;
-  a.big_endian = d->big_endian && d->format != JXLH_SAVE_U8;
-  a.fill_bits = d->format <= JXLH_SAVE_U16 ? max_int : d->format == JXLH_SAVE_F16 ? 0x3c00u : 0x3f800000u;
-  if (a.big_endian)
-    a.fill_bits = d->format == JXLH_SAVE_F32 ? __builtin_bswap32(a.fill_bits)
-                                             : (((a.fill_bits >> 8) | (a.fill_bits << 8)) & 0xffffu);
   a.clamp = d->format == JXLH_SAVE_F16 && d->f16_clamp;
   a.clamp_min = d->f16_clamp_min;
   a.clamp_max = d->f16_clamp_max;
-  const uint32_t o = d->orientation;  // headers/image_metadata.rs:85-96
-  a.transpose = o >= 5;
-  a.flip_x = o == 2 || o == 3 || o == 6 || o == 7;
-  a.flip_y = o == 3 || o == 4 || o == 7 || o == 8;
 }
 
 // Launches `a` (everything but out / out_stride filled) for source rows [a.y0, a.y0 + a.rows) into the oriented image at
-// `out`.  Device memory is written in place; host memory goes through the staging buffer, which holds exactly the
-// rectangle of the oriented image the band covers (whole rows of it for orientations 1-4, a column range of every row
-// for 5-8), and a 2-D copy of that rectangle -- bytes outside it are never touched.
-jxlh_status launch_to(jxlh_ctx* ctx, SaveLaunch& a, void* out, size_t bytes_per_row, bool wait) {
-  const size_t pb = (size_t)a.spp * (size_t)sample_bytes((uint32_t)a.format);
-  if (is_device_ptr(out)) {
-    a.out = static_cast<uint8_t*>(out);
-    a.out_stride = bytes_per_row;
-    {
-      ScopedKernelTimer t(ctx, "k_save");
-      launch_save(ctx->stream, a);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return JXLH_OK;
-  }
-  // the band's rectangle in the oriented image: rect_w pixels from column ox0 of rows [oy0, oy0 + rect_h)
+// `image`: the band's rectangle there is whole rows of it for orientations 1-4, a column range of every row for 5-8.
+jxlh_status launch_to(jxlh_ctx* ctx, SaveLaunch& a, void* image, size_t bytes_per_row, const char* label, bool wait) {
+  const size_t pb = (size_t)a.spp * (size_t)save_sample_bytes((uint32_t)a.format);
   const int y1 = a.y0 + a.rows;
-  size_t ox0, oy0, rect_w, rect_h;
-  if (a.transpose) {
-    ox0 = (size_t)(a.flip_x ? a.h - y1 : a.y0);
-    oy0 = 0;
-    rect_w = (size_t)a.rows;
-    rect_h = (size_t)a.w;
-  } else {
-    ox0 = 0;
-    oy0 = (size_t)(a.flip_y ? a.h - y1 : a.y0);
-    rect_w = (size_t)a.w;
-    rect_h = (size_t)a.rows;
-  }
-  const size_t row_bytes = rect_w * pb, pitch = round_up(row_bytes, 4);
-  if (jxlh_status st = ensure(ctx, ctx->rgb8, pitch * rect_h)) return st;
-  // the image origin that puts the rectangle at the start of the staging buffer (never dereferenced outside it)
-  a.out = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->rgb8.p) - oy0 * pitch - ox0 * pb);
-  a.out_stride = pitch;
-  {
-    ScopedKernelTimer t(ctx, "k_save");
+  const OutRect r = a.transpose ? OutRect{(size_t)(a.flip_x ? a.h - y1 : a.y0), 0, (size_t)a.rows, (size_t)a.w}
+                                : OutRect{0, (size_t)(a.flip_y ? a.h - y1 : a.y0), (size_t)a.w, (size_t)a.rows};
+  void* dst = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(image) + r.y0 * bytes_per_row + r.x0 * pb);
+  return write_out(ctx, dst, bytes_per_row, pb, r, label, wait, [&](uint8_t* origin, size_t pitch) {
+    a.out = origin;
+    a.out_stride = pitch;
     launch_save(ctx->stream, a);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  if (jxlh_status st = copy2d(ctx, static_cast<uint8_t*>(out) + oy0 * bytes_per_row + ox0 * pb, bytes_per_row, ctx->rgb8.p,
-                              pitch, row_bytes, rect_h, ctx->stream))
-    return st;
-  if (wait) JXLH_SYNC(ctx);
-  return JXLH_OK;
+  });
 }
 
 jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d, uint32_t y0, uint32_t y1,
@@ -170,7 +126,7 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
   if (jxlh_status st = save_check_desc(d, 3 + JXLH_MAX_EXTRA_CHANNELS)) return st;
   SaveLaunch a{};
-  if (jxlh_status st = save_colour_mode(colour, a)) return st;
+  if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
   if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
   if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
@@ -208,20 +164,29 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
     for (uint32_t i = 0; i < d->n_spot; i++)
       if (jxlh_status st = resolve(3 + d->spot[i].ec)) return st;
   }
-  // checked: from here on only the device can fail
+  return save_result_rows(ctx, a, d, ec_plane, ec_stride, y0, y1, out, bytes_per_row, "k_save", wait);
+}
+
+}  // namespace
+
+// checked: from here on only the device can fail.  launch_save's own precondition is ceil(w / 1024) * rows < 2^31
+// workgroups (fewer for the tiles of orientations 5-8).  The save entry points have refused w * h >= 2^31; a read-out
+// comes with any result: ceil(w / 1024) * h <= w * h / 1024 + h, where h <= 2^23 (a side of 2^20, upsampled eight times)
+// and w * h < 2^35 for three f32 planes that exist in device memory -- below 2^26
+jxlh_status save_result_rows(jxlh_ctx* ctx, SaveLaunch& a, const jxlh_save_desc* d, const float* const* ec_plane,
+                             const uint32_t* ec_stride, uint32_t y0, uint32_t y1, void* image, size_t bytes_per_row,
+                             const char* label, bool wait) {
   materialise_chroma(ctx);
   fill_desc(
       d, [&](uint32_t ch) { return ch < 3 ? (const float*)ctx->result[ch] : ec_plane[ch - 3]; },
       [&](uint32_t ch) { return ch < 3 ? (uint32_t)ctx->res_stride : ec_stride[ch - 3]; }, a);
-  a.w = (int)w;
-  a.h = (int)h;
+  a.w = ctx->res_w;
+  a.h = ctx->res_h;
   a.y0 = (int)y0;
   a.rows = (int)(y1 - y0);
   a.dx = a.dy = 0;
-  return launch_to(ctx, a, out, bytes_per_row, wait);
+  return launch_to(ctx, a, image, bytes_per_row, label, wait);
 }
-
-}  // namespace
 
 }  // namespace jxlh_host
 
@@ -259,7 +224,7 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
     if (!planes[c]) return JXLH_ERR_INVALID_ARGUMENT;
   if (jxlh_status st = save_check_desc(d, n_planes)) return st;
   SaveLaunch a{};
-  if (jxlh_status st = save_colour_mode(colour, a)) return st;
+  if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
   if (y1 > h) y1 = h;
   if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
   if (jxlh_status st = save_check_out(d, w, h, out, bytes_per_row)) return st;
@@ -284,7 +249,7 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
   a.rows = (int)(y1 - y0);
   a.dx = (int)(frame_x0 & 31);  // the table is 32 x 32
   a.dy = (int)(frame_y0 & 31);
-  if (jxlh_status st = launch_to(ctx, a, out, bytes_per_row, /*wait=*/false)) return st;
+  if (jxlh_status st = launch_to(ctx, a, out, bytes_per_row, "k_save", /*wait=*/false)) return st;
   JXLH_SYNC(ctx);
   return JXLH_OK;
 }

@@ -1,4 +1,4 @@
-// The colour stage of a frame on ONE pixel, shared by the read-out kernels (k_output.hip) and frame blending
+// The colour stage of a frame on ONE pixel, shared by the read-outs (k_output.hip), the save tail and frame blending
 // (k_blend.hip): XybStage (render/stages/xyb.rs:208-240), FromLinearStage with each of the reference's transfer functions
 // (render/stages/from_linear.rs:57-112; curves of color/tf.rs and util/fast_math.rs, operation for operation) and
 // YcbcrToRgbStage (render/stages/ycbcr.rs:35-78).  FMAs are explicit: the library builds with -ffp-contract=off.

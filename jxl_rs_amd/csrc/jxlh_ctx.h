@@ -86,7 +86,7 @@ struct jxlh_ctx {
   DevBuf<int> tables_ok;     // FrameDev::tables_ok
   int tables_ok_host = 0;    // ... read back when the tables are set
   bool params_direct_ok = false;  // the frame parameters' share of FrameDev::se_direct_ok
-  DevBuf<uint8_t> rgb8;  // jxlh_frame_read_rgb8 staging for host destinations
+  DevBuf<uint8_t> rgb8;  // write_out's staging for host destinations
   Pinned<int> host_flag;
   DevBuf<uint8_t> worklist;
   DevBuf<int> rerender_list;          // group ids of jxlh_frame_rerender_groups on the device
@@ -359,10 +359,38 @@ inline bool draws_in_place(const jxlh_ctx* ctx) { return ctx->patch_n > 0 || ctx
 // abi_blend.hip.  blended(): the frame's result is the canvas jxlh_frame_blend composed (any render resets `result`).
 inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
 // abi_save.hip: the argument checks, shared with jxlh_lf_preview: the descriptor's own (n_planes: pipeline channels that
-// exist), `out` and its pitch against the oriented image of a w x h source, the colour stage named by `colour`
+// exist), `out` and its pitch against the oriented image of a w x h source
 jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes);
 jxlh_status save_check_out(const jxlh_save_desc* d, uint32_t w, uint32_t h, const void* out, size_t bytes_per_row);
-jxlh_status save_colour_mode(const jxlh_output_desc* colour, SaveLaunch& a);
+// ... the colour stage `colour` names (null = none) as the kernels take it: every entry point with a jxlh_output_desc
+jxlh_status colour_stage(const jxlh_output_desc* colour, int* mode, XybParamsDev* xyb, TfParamsDev* tf);
+// ... and what a (checked) descriptor says about the samples and their place: a.format, maxv, big_endian, fill_bits,
+// transpose, flip_x, flip_y of a SaveLaunch / LfPreviewLaunch
+inline int save_sample_bytes(uint32_t format) { return format == JXLH_SAVE_U8 ? 1 : format == JXLH_SAVE_F32 ? 4 : 2; }
+template <class Launch>
+void save_format(const jxlh_save_desc* d, Launch& a) {
+  a.format = (int)d->format;  // JXLH_SAVE_* share the values of kSave*
+  const uint32_t max_int = d->format <= JXLH_SAVE_U16 ? (1u << d->bit_depth) - 1 : 0;
+  a.maxv = (float)max_int;
+  a.big_endian = d->big_endian && d->format != JXLH_SAVE_U8;
+  a.fill_bits = d->format <= JXLH_SAVE_U16 ? max_int : d->format == JXLH_SAVE_F16 ? 0x3c00u : 0x3f800000u;
+  if (a.big_endian)
+    a.fill_bits = d->format == JXLH_SAVE_F32 ? __builtin_bswap32(a.fill_bits)
+                                             : (((a.fill_bits >> 8) | (a.fill_bits << 8)) & 0xffffu);
+  const uint32_t o = d->orientation;  // headers/image_metadata.rs:85-96
+  a.transpose = o >= 5;
+  a.flip_x = o == 2 || o == 3 || o == 6 || o == 7;
+  a.flip_y = o == 3 || o == 4 || o == 7 || o == 8;
+}
+struct OutRect {
+  size_t x0, y0, w, h;  // pixels of an oriented output image
+};
+// the tail of jxlh_frame_save, which the integer read-outs (abi_output.hip) share: rows [y0, y1) of the frame's result
+// through the save `d` (checked; ec_plane / ec_stride: the extra channels it names, may be null when it names none)
+// behind the colour stage already in `a`, into the oriented image at `image`
+jxlh_status save_result_rows(jxlh_ctx* ctx, SaveLaunch& a, const jxlh_save_desc* d, const float* const* ec_plane,
+                             const uint32_t* ec_stride, uint32_t y0, uint32_t y1, void* image, size_t bytes_per_row,
+                             const char* label, bool wait);
 // abi_lf_fill.hip.  lf_only_snapshot: ctx->lf_only_run <- the frame's marks (true = at least one group is marked).
 // lf_split_groups: the sorted `groups` of a run, the unmarked ones (all, without marks) first, on the device (rerender_list);
 // *n_k1 of them are K1's, the *n_fill behind them the fill's.  run_lf_fill: Upsample8x of the LF image into the planes
@@ -412,6 +440,32 @@ jxlh_status stage_out(jxlh_ctx* ctx, T* dst, const T* src, size_t n) {
   return JXLH_OK;
 }
 int comm_rows_per_rank(const jxlh_ctx* ctx, int ygroups);
+
+// The one way interleaved samples leave the device.  `launch(origin, pitch)` writes the pixels of rectangle `r` of an
+// oriented output image whose pixel (0, 0) is at `origin`, rows `pitch` bytes apart; `dst` is where the rectangle's first
+// pixel goes, rows bytes_per_row apart.  Device memory is written in place and never waited for.  Host memory goes
+// through ctx->rgb8, which holds exactly the rectangle at a dword-rounded pitch (the origin is shifted so that the
+// rectangle starts the buffer; it is never dereferenced outside it), and a 2-D copy of exactly the pixel bytes -- row
+// padding and bytes outside the rectangle are never touched --, then a wait if `wait`.  `label` names the launch in
+// jxlh_kernel_timing_get.
+template <class Launch>
+jxlh_status write_out(jxlh_ctx* ctx, void* dst, size_t bytes_per_row, size_t pixel_bytes, const OutRect& r,
+                      const char* label, bool wait, Launch launch) {
+  const bool staged = !is_device_ptr(dst);
+  const size_t row_bytes = r.w * pixel_bytes, pitch = staged ? round_up(row_bytes, 4) : bytes_per_row;
+  if (staged)
+    if (jxlh_status st = ensure(ctx, ctx->rgb8, pitch * r.h)) return st;
+  const uintptr_t first = reinterpret_cast<uintptr_t>(staged ? ctx->rgb8.p : dst);
+  {
+    ScopedKernelTimer t(ctx, label);
+    launch(reinterpret_cast<uint8_t*>(first - r.y0 * pitch - r.x0 * pixel_bytes), pitch);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (!staged) return JXLH_OK;
+  if (jxlh_status st = copy2d(ctx, dst, bytes_per_row, ctx->rgb8.p, pitch, row_bytes, r.h, ctx->stream)) return st;
+  if (wait) JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
 
 }  // namespace jxlh_host
 using namespace jxlh_host;

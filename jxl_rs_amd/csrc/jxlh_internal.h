@@ -290,7 +290,7 @@ void launch_epf(hipStream_t s, int stage, const EpfArgs& a, int y0, int y1);
 // Gaborish/EPF1/EPF2 of the frame's stage list in one LDS-tiled pass, planes -> tmp, output rows [y0, y1).
 // Returns false when the stage list is not covered (EPF0, i.e. epf_iters == 3, or no stage at all).
 int launch_fused_filters(hipStream_t s, const FrameDev& f, int y0, int y1);
-// output stages (k_output.hip): XybParams of the reference (xyb.rs:147-163), same field order as
+// output stages (color_device.h): XybParams of the reference (xyb.rs:147-163), same field order as
 // jxlh_xyb_params
 struct XybParamsDev {
   float mat[9], bias_cbrt[3], scaled_bias[3], intensity_scale;
@@ -307,12 +307,14 @@ struct SubPlanesDev {
   const float* p[3];
   int hs[3], vs[3], cw[3], ch[3];
 };
+// k_output.hip: rows [y0, y0 + rows) of such a frame as interleaved 8- / 16-bit RGB(A) into the image whose origin is
+// `out`, rows out_stride bytes apart
 void launch_ycbcr_sub_to_rgb(hipStream_t s, const SubPlanesDev& sp, size_t stride, int w, int y0, int rows, int channels,
-                             int bits, void* out, size_t out_stride);
+                             int bits, uint8_t* out, size_t out_stride);
+// ... and rows [y0, y0 + rows) of full-size planes through colour stage `mode` (kTfLinear..kTfGamma behind XybStage,
+// kModeYcbcr, kModeNone) as interleaved 8-bit RGB(A), the same way
 void launch_xyb_to_rgb8(hipStream_t s, const float* const planes[3], size_t stride, int w, int y0, int rows, int mode,
                         const XybParamsDev& q, const TfParamsDev& t, int channels, uint8_t* out, size_t out_stride);
-void launch_xyb_to_rgb16(hipStream_t s, const float* const planes[3], size_t stride, int w, int y0, int rows, int mode,
-                         const XybParamsDev& q, const TfParamsDev& t, int channels, uint16_t* out, size_t out_stride_elems);
 // only_flagged (nullable): expand a group only if only_flagged[group] != 0
 void launch_pack_pairs8(hipStream_t s, const uint16_t* pos, const int8_t* val, size_t n, uint32_t* pairs);
 // the 2-byte form (jxlh_submit_groups_sparse4): n_runs = groups of the batch x 3, desc = 4 words per run, see k_coeffs.hip

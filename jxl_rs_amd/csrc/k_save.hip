@@ -1,5 +1,5 @@
 // The save tail of a frame in ONE pass over the finished planes, everything between load and store in registers:
-//   colour stage            color_device.h (XybStage + FromLinearStage / YcbcrToRgbStage), as the read-out kernels
+//   colour stage            color_device.h (XybStage + FromLinearStage / YcbcrToRgbStage), as the read-outs
 //   SpotColorStage          jxl/src/render/stages/spot.rs:40-67          (scalar loop: two products and a sum, no FMA)
 //   PremultiplyAlphaStage   jxl/src/render/stages/premultiply_alpha.rs:47-92
 //   ConvertF32ToU8Stage / ConvertF32ToU16Stage / ConvertF32ToF16Stage    jxl/src/render/stages/convert.rs:570-606,
@@ -324,7 +324,8 @@ void launch_fmt(hipStream_t s, const SaveLaunch& a) {
 
 }  // namespace
 
-// w * h < 2^31 (checked by the callers): the 1-D grids stay below 2^31 workgroups and no image axis is a grid dimension
+// No image axis is a grid dimension; the 1-D grids (row blocks x rows, tiles) must stay below 2^31 workgroups.  The save
+// entry points refuse w * h >= 2^31; the read-outs' case is argued at save_result_rows (abi_save.hip).
 void launch_save(hipStream_t s, const SaveLaunch& a) {
   if (a.w <= 0 || a.rows <= 0) return;
   switch (a.format) {
