@@ -118,7 +118,7 @@ jxlh_status jxlh_flow_profile(jxlh_ctx* ctx, int32_t enable, int32_t* n_levels, 
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
   if (rows && n_levels && ctx->flow_prof_on && ctx->flow_prof.p && ctx->flow_prof_levels > 0) {
-    const int cap = unsqueeze_flow_max_steps();
+    const int cap = kFlowMaxLevels;
     std::vector<unsigned long long> h(11 * (size_t)cap);
     HIPCHK(ctx, hipMemcpyAsync(h.data(), ctx->flow_prof.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     JXLH_SYNC(ctx);

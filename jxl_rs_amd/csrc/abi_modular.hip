@@ -1,8 +1,37 @@
 // C ABI, Modular transforms: RCT, Palette (plain, delta / predicted, Weighted), Squeeze (steps, fused chains,
 // progressive smooth steps) and the bridges from Modular channels to pixels.
 #include <algorithm>
+#include <optional>
 
 #include "jxlh_ctx.h"
+
+namespace {
+using namespace jxlh;
+
+// a single squeeze step as squeeze_plan.h and the launchers read it (res: already the planes the kernel reads)
+SqueezeStep step_of(int horizontal, int n_planes, const int32_t* const avg[], size_t avg_stride, const int32_t* const res[],
+                    size_t res_stride, uint32_t out_w, uint32_t out_h, int32_t* const out[], size_t out_stride) {
+  SqueezeStep s{horizontal != 0, n_planes, out_w, out_h, avg_stride, res_stride, out_stride, {}, {}, {}};
+  for (int p = 0; p < n_planes; p++) {
+    s.avg[p] = (uintptr_t)avg[p];
+    s.res[p] = (uintptr_t)res[p];
+    s.out[p] = (uintptr_t)out[p];
+  }
+  return s;
+}
+// one planned launch of a single level: the step, the step fused with the RCT, or the RCT on the step's output
+void issue_step(hipStream_t s, const SqueezeLaunch& L, const SqueezeStep& st, int rct_op, int rct_perm) {
+  int32_t* const o[3] = {(int32_t*)st.out[0], (int32_t*)st.out[1], (int32_t*)st.out[2]};
+  switch (L.kind) {
+    case SqueezeLaunch::kFusedRct: return launch_unsqueeze_rct(s, L, st, rct_op, rct_perm);
+    case SqueezeLaunch::kRctFlat: return launch_rct(s, o[0], o[1], o[2], (size_t)st.out_w * st.out_h, rct_op, rct_perm);
+    case SqueezeLaunch::kRctRows: return launch_rct_rows(s, o[0], o[1], o[2], st.out_w, st.out_h, st.out_stride, rct_op, rct_perm);
+    default: return launch_unsqueeze(s, L, st);
+  }
+}
+// JXLH_SEPARATE_RCT=1, JXLH_CHAIN_FLOW=0 (tests, A/B): read on every call
+bool env_is(const char* name, char v) { return getenv(name) && *getenv(name) == v; }
+}  // namespace
 
 extern "C" {
 
@@ -222,9 +251,6 @@ jxlh_status jxlh_palette_delta_wp(jxlh_ctx* ctx, const int32_t* index, uint32_t 
   return stage_out(ctx, out, (const int32_t*)ctx->hook_i[2].p, n * nb_channels);
 }
 
-// dimension bound of the squeeze entry points (the kernels take `int` line counts / lengths)
-static constexpr uint32_t kMaxModularDim = 1u << 20;
-
 jxlh_status jxlh_unsqueeze(jxlh_ctx* ctx, int32_t horizontal, const int32_t* avg, size_t avg_stride,
                            const int32_t* res, size_t res_stride, uint32_t out_w, uint32_t out_h, int32_t* out,
                            size_t out_stride) {
@@ -232,34 +258,31 @@ jxlh_status jxlh_unsqueeze(jxlh_ctx* ctx, int32_t horizontal, const int32_t* avg
   if (!ctx || !avg || !out || out_stride < out_w) return JXLH_ERR_INVALID_ARGUMENT;
   if (out_w == 0 || out_h == 0) return JXLH_OK;
   if (out_w > kMaxModularDim || out_h > kMaxModularDim) return JXLH_ERR_UNSUPPORTED;
-  const uint32_t avg_w = horizontal ? (out_w + 1) / 2 : out_w, avg_h = horizontal ? out_h : (out_h + 1) / 2;
-  const uint32_t res_w = horizontal ? out_w / 2 : out_w, res_h = horizontal ? out_h : out_h / 2;
-  const bool has_res = (size_t)res_w * res_h > 0;
-  if (avg_stride < avg_w || (has_res && (!res || res_stride < res_w))) return JXLH_ERR_INVALID_ARGUMENT;
-  if (is_device_ptr(avg) && is_device_ptr(out) && (!has_res || is_device_ptr(res))) {
+  const SqueezeExtents e = squeeze_extents(horizontal != 0, out_w, out_h);
+  if (avg_stride < e.avg_w || (e.has_res && (!res || res_stride < e.res_w))) return JXLH_ERR_INVALID_ARGUMENT;
+  auto run = [&](const int32_t* a, const int32_t* r, int32_t* o) {
+    const int32_t* av[1] = {a};
+    const int32_t* rv[1] = {r};
+    int32_t* ov[1] = {o};
+    const SqueezeStep st = step_of(horizontal, 1, av, avg_stride, rv, res_stride, out_w, out_h, ov, out_stride);
+    launch_unsqueeze(ctx->stream, plan_squeeze_step(st), st);
+  };
+  if (is_device_ptr(avg) && is_device_ptr(out) && (!e.has_res || is_device_ptr(res))) {
     ScopedKernelTimer t(ctx, horizontal ? "k6_unsqueeze_h" : "k6_unsqueeze_v");
-    const int32_t* av[1] = {avg};
-    const int32_t* rv[1] = {res ? res : avg};
-    int32_t* ov[1] = {out};
-    launch_unsqueeze(ctx->stream, horizontal, 1, av, avg_stride, rv, res_stride, out_w, out_h, ov, out_stride);
+    run(avg, res ? res : avg, out);
     HIPCHK(ctx, hipGetLastError());
     return JXLH_OK;
   }
   jxlh_status st;
-  if ((st = stage_in(ctx, ctx->hook_i[0], avg, avg_stride * avg_h))) return st;
-  const size_t res_n = has_res ? res_stride * res_h : 0;
+  if ((st = stage_in(ctx, ctx->hook_i[0], avg, avg_stride * e.avg_h))) return st;
+  const size_t res_n = e.has_res ? res_stride * e.res_h : 0;
   if (res_n) {
     if ((st = stage_in(ctx, ctx->hook_i[1], res, res_n))) return st;
   } else if ((st = ensure(ctx, ctx->hook_i[1], 1))) {
     return st;
   }
   if ((st = ensure(ctx, ctx->hook_i[2], out_stride * out_h))) return st;
-  {
-    const int32_t* av[1] = {ctx->hook_i[0].p};
-    const int32_t* rv[1] = {ctx->hook_i[1].p};
-    int32_t* ov[1] = {ctx->hook_i[2].p};
-    launch_unsqueeze(ctx->stream, horizontal, 1, av, avg_stride, rv, res_stride, out_w, out_h, ov, out_stride);
-  }
+  run(ctx->hook_i[0].p, ctx->hook_i[1].p, ctx->hook_i[2].p);
   HIPCHK(ctx, hipGetLastError());
   return stage_out(ctx, out, (const int32_t*)ctx->hook_i[2].p, out_stride * out_h);
 }
@@ -268,214 +291,72 @@ jxlh_status jxlh_unsqueeze_levels(jxlh_ctx* ctx, int32_t n_planes, int32_t n_lev
                                   const int32_t* const base[], size_t base_stride, uint32_t base_w, uint32_t base_h,
                                   int32_t* const out[], size_t out_stride) {
   JXLH_ON_DEVICE(ctx);
-  if (!ctx || !levels || !base || !out || n_planes < 1 || n_planes > 3 || n_levels < 1 || n_levels > 64 || base_w == 0 ||
-      base_h == 0 || base_stride < base_w)
-    return JXLH_ERR_INVALID_ARGUMENT;
-  // geometry: every level doubles (up to the odd sample) the axis it squeezes
-  uint32_t cw = base_w, ch = base_h;
-  for (int i = 0; i < n_levels; i++) {
-    const jxlh_squeeze_level& lv = levels[i];
-    if (lv.out_w == 0 || lv.out_h == 0 || lv.out_w > kMaxModularDim || lv.out_h > kMaxModularDim) return JXLH_ERR_INVALID_ARGUMENT;
-    const uint32_t aw = lv.horizontal ? (lv.out_w + 1) / 2 : lv.out_w, ah = lv.horizontal ? lv.out_h : (lv.out_h + 1) / 2;
-    if (aw != cw || ah != ch) return JXLH_ERR_INVALID_ARGUMENT;
-    const uint32_t rw = lv.horizontal ? lv.out_w / 2 : lv.out_w, rh = lv.horizontal ? lv.out_h : lv.out_h / 2;
-    for (int p = 0; p < n_planes; p++)
-      if ((size_t)rw * rh > 0 && (!lv.res[p] || !is_device_ptr(lv.res[p]) || lv.res_stride < rw))
-        return JXLH_ERR_INVALID_ARGUMENT;
-    cw = lv.out_w;
-    ch = lv.out_h;
-  }
-  if (out_stride < cw) return JXLH_ERR_INVALID_ARGUMENT;
-  for (int p = 0; p < n_planes; p++)
-    if (!base[p] || !out[p] || !is_device_ptr(base[p]) || !is_device_ptr(out[p])) return JXLH_ERR_INVALID_ARGUMENT;
-  if (n_levels <= 16) {
-    int hz[16];
-    uint32_t ow[16], oh[16];
-    size_t rs[16];
-    const int32_t* rp[16 * 3];
-    for (int i = 0; i < n_levels; i++) {
-      hz[i] = levels[i].horizontal ? 1 : 0;
-      ow[i] = levels[i].out_w;
-      oh[i] = levels[i].out_h;
-      rs[i] = levels[i].res_stride;
-      for (int p = 0; p < 3; p++) rp[i * 3 + p] = p < n_planes && levels[i].res[p] ? levels[i].res[p] : base[0];
-    }
+  if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_squeeze_chain(n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride,
+                                           is_device_ptr))
+    return st;
+  if (squeeze_levels_fit(n_levels, levels, base_w, base_h)) {
     ScopedKernelTimer t(ctx, "k6_unsqueeze_levels");
-    if (launch_unsqueeze_levels(ctx->stream, n_planes, n_levels, hz, ow, oh, rp, rs, base, base_stride, base_w, base_h,
-                                out, out_stride)) {
-      HIPCHK(ctx, hipGetLastError());
-      return JXLH_OK;
-    }
+    launch_unsqueeze_levels(ctx->stream, n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride);
+    HIPCHK(ctx, hipGetLastError());
+    return JXLH_OK;
   }
   // anything else: the chain's route without an RCT (LDS-resident prefix, the streamed levels as one dataflow launch)
   return jxlh_unsqueeze_chain(ctx, n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, -1, 0);
 }
 
-// The inverse of a whole squeeze transform as one call (+ the RCT that follows it in the transform list).
+// The inverse of a whole squeeze transform as one call (+ the RCT that follows it in the transform list): validate,
+// plan (squeeze_plan.h), issue.
 jxlh_status jxlh_unsqueeze_chain(jxlh_ctx* ctx, int32_t n_planes, int32_t n_levels, const jxlh_squeeze_level* levels,
                                  const int32_t* const base[], size_t base_stride, uint32_t base_w, uint32_t base_h,
                                  int32_t* const out[], size_t out_stride, int32_t rct_op, int32_t rct_perm) {
   JXLH_ON_DEVICE(ctx);
-  if (!ctx || !levels || !base || !out || n_planes < 1 || n_planes > 3 || n_levels < 1 || n_levels > 64 || base_w == 0 ||
-      base_h == 0 || base_stride < base_w)
-    return JXLH_ERR_INVALID_ARGUMENT;
   const bool with_rct = rct_op >= 0;
-  if (with_rct && (n_planes != 3 || rct_op > 6 || rct_perm < 0 || rct_perm > 5)) return JXLH_ERR_INVALID_ARGUMENT;
-  uint32_t cw = base_w, ch = base_h;
-  for (int i = 0; i < n_levels; i++) {
-    const jxlh_squeeze_level& lv = levels[i];
-    if (lv.out_w == 0 || lv.out_h == 0 || lv.out_w > kMaxModularDim || lv.out_h > kMaxModularDim)
-      return JXLH_ERR_INVALID_ARGUMENT;
-    const uint32_t aw = lv.horizontal ? (lv.out_w + 1) / 2 : lv.out_w, ah = lv.horizontal ? lv.out_h : (lv.out_h + 1) / 2;
-    if (aw != cw || ah != ch) return JXLH_ERR_INVALID_ARGUMENT;
-    const uint32_t rw = lv.horizontal ? lv.out_w / 2 : lv.out_w, rh = lv.horizontal ? lv.out_h : lv.out_h / 2;
-    for (int p = 0; p < n_planes; p++)
-      if ((size_t)rw * rh > 0 && (!lv.res[p] || !is_device_ptr(lv.res[p]) || lv.res_stride < rw))
-        return JXLH_ERR_INVALID_ARGUMENT;
-    cw = lv.out_w;
-    ch = lv.out_h;
-  }
-  if (out_stride < cw) return JXLH_ERR_INVALID_ARGUMENT;
-  for (int p = 0; p < n_planes; p++)
-    if (!base[p] || !out[p] || !is_device_ptr(base[p]) || !is_device_ptr(out[p])) return JXLH_ERR_INVALID_ARGUMENT;
-  // intermediate planes: every level but the last writes its own plane set in context scratch (levels overlap in
-  // the dataflow launch below, so no ping-pong; the sizes halve per level: about twice the largest one in all)
+  if (!ctx || (with_rct && (n_planes != 3 || rct_op > 6 || rct_perm < 0 || rct_perm > 5))) return JXLH_ERR_INVALID_ARGUMENT;
   jxlh_status st;
-  // Rows of the intermediate planes are padded to whole 16 bytes and every plane starts on a 256-byte line: with the
-  // caller's residual planes laid out the same way the tiled kernels move every level with 16-byte accesses whatever
-  // the image width is (tiled_vec_ok).
-  size_t level_off[64], level_stride[64], level_plane[64], arena = 0;
-  for (int i = 0; i < n_levels - 1; i++) {
-    level_off[i] = arena;
-    level_stride[i] = ((size_t)levels[i].out_w + 3) & ~(size_t)3;
-    level_plane[i] = (level_stride[i] * levels[i].out_h + 63) & ~(size_t)63;
-    arena += level_plane[i] * n_planes;
+  if ((st = check_squeeze_chain(n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, is_device_ptr)))
+    return st;
+  if ((st = ensure(ctx, ctx->hook_i[0], std::max<size_t>(squeeze_arena(n_planes, n_levels, levels).total, 1)))) return st;
+  SqueezeChainIn in{n_planes, n_levels, levels, base_w, base_h, base_stride, out_stride, {}, {}, (uintptr_t)ctx->hook_i[0].p,
+                    with_rct, env_is("JXLH_SEPARATE_RCT", '1'), !env_is("JXLH_CHAIN_FLOW", '0')};
+  for (int p = 0; p < n_planes; p++) {
+    in.base[p] = (uintptr_t)base[p];
+    in.out[p] = (uintptr_t)out[p];
   }
-  if ((st = ensure(ctx, ctx->hook_i[0], std::max<size_t>(arena, 1)))) return st;
+  const SqueezePlan plan = plan_squeeze_chain(in);
+  if (plan.flow_words) {
+    if ((st = ensure(ctx, ctx->flow_words, plan.flow_words))) return st;
+    if (!ctx->host_flow_flag.p) {
+      // the error word lives in pinned host memory (device-visible under the same address): jxlh_ctx_sync AND
+      // jxlh_ctx_wait_mark read it without queueing a copy behind later work
+      HIPCHK(ctx, ctx->host_flow_flag.alloc(1));
+      *ctx->host_flow_flag.p = 0;
+    }
+    if (ctx->flow_prof_on && (st = ensure(ctx, ctx->flow_prof, 11 * (size_t)kFlowMaxLevels))) return st;
+  }
   ScopedKernelTimer t(ctx, "k6_unsqueeze_chain");
-  const int32_t* cur[3];
-  size_t cur_stride = base_stride;
-  for (int p = 0; p < n_planes; p++) cur[p] = base[p];
-  auto dst_of = [&](int i, int32_t* dst[3], size_t* stride) {
-    const bool last = i == n_levels - 1;
-    for (int p = 0; p < n_planes; p++)
-      dst[p] = last ? out[p] : ctx->hook_i[0].p + level_off[i] + (size_t)p * level_plane[i];
-    *stride = last ? out_stride : level_stride[i];
-  };
-  int i = 0;
-  // ---- the first levels, while the planes fit LDS: one launch (the chain starts from <= 8 x 8)
-  {
-    int n_small = 0;
-    while (n_small < n_levels - (with_rct ? 1 : 0) && n_small < JXLH_SQL_LEVELS && levels[n_small].out_w <= JXLH_SQL_MAX &&
-           levels[n_small].out_h <= JXLH_SQL_MAX)
-      n_small++;
-    while (n_small >= 2) {
-      int hz[JXLH_SQL_LEVELS];
-      uint32_t ow[JXLH_SQL_LEVELS], oh[JXLH_SQL_LEVELS];
-      size_t rs[JXLH_SQL_LEVELS];
-      const int32_t* rp[JXLH_SQL_LEVELS * 3];
-      for (int k = 0; k < n_small; k++) {
-        hz[k] = levels[k].horizontal ? 1 : 0;
-        ow[k] = levels[k].out_w;
-        oh[k] = levels[k].out_h;
-        rs[k] = levels[k].res_stride;
-        for (int p = 0; p < 3; p++) rp[k * 3 + p] = p < n_planes && levels[k].res[p] ? levels[k].res[p] : base[0];
-      }
+  for (int k = 0; k < plan.n; k++) {
+    const SqueezeLaunch& L = plan.launch[k];
+    if (L.kind == SqueezeLaunch::kLevels) {
       int32_t* dst[3];
-      size_t dst_stride;
-      dst_of(n_small - 1, dst, &dst_stride);
-      if (launch_unsqueeze_levels(ctx->stream, n_planes, n_small, hz, ow, oh, rp, rs, base, base_stride, base_w, base_h, dst,
-                                  dst_stride)) {
-        for (int p = 0; p < n_planes; p++) cur[p] = dst[p];
-        cur_stride = dst_stride;
-        i = n_small;
-        break;
+      for (int p = 0; p < n_planes; p++) dst[p] = (int32_t*)squeeze_plane_addr(in, plan.arena, L.dst, p);
+      launch_unsqueeze_levels(ctx->stream, n_planes, L.n_levels, levels, base, base_stride, base_w, base_h, dst, L.dst.stride);
+    } else if (L.kind == SqueezeLaunch::kFlow) {
+      SqueezeStep steps[kFlowRunCap];
+      SqueezeLoc a = L.src;
+      for (int n = 0; n < L.n_levels; n++) {  // every level of the run but its last writes its own plane set
+        const int j = L.level0 + n;
+        const SqueezeLoc d = n == L.n_levels - 1 ? L.dst : SqueezeLoc{j, plan.arena.stride[j]};
+        steps[n] = squeeze_level_step(in, plan.arena, j, a, d);
+        a = d;
       }
-      n_small--;  // a level that does not fit the kernel's half-size buffer: try a shorter prefix
+      launch_unsqueeze_flow(ctx->stream, L.n_levels, steps, plan.vec + L.level0, ctx->flow_words.p, ctx->host_flow_flag.p, 4.0f,
+                            ctx->flow_prof_on ? ctx->flow_prof.p : nullptr);
+      ctx->flow_prof_levels = L.n_levels;
+      ctx->flow_used = true;
+    } else {
+      issue_step(ctx->stream, L, squeeze_level_step(in, plan.arena, L.level0, L.src, L.dst), rct_op, rct_perm);
     }
-  }
-  // JXLH_SEPARATE_RCT=1 (tests): take the two-pass route that planes of 2^31 samples and more need;
-  // JXLH_CHAIN_FLOW=0 (tests, A/B): one launch per streamed level instead of the dataflow launch
-  const char* sep = getenv("JXLH_SEPARATE_RCT");
-  const bool fuse_rct = with_rct && !(sep && *sep == '1');
-  const char* fl = getenv("JXLH_CHAIN_FLOW");
-  const bool flow = !(fl && *fl == '0');
-  // ---- the remaining levels: runs of streamed levels as ONE dataflow launch (levels overlap: k6_unsqueeze_flow),
-  // anything else one launch per level over the three planes; the last one fused with the RCT
-  while (i < n_levels) {
-    if (flow) {
-      FlowStep steps[16];
-      const int max_run = std::min(16, unsqueeze_flow_max_steps());
-      const int32_t* a[3];
-      size_t a_stride = cur_stride;
-      for (int p = 0; p < n_planes; p++) a[p] = cur[p];
-      int n = 0;
-      for (int j = i; j < n_levels && n < max_run; j++, n++) {
-        const jxlh_squeeze_level& lv = levels[j];
-        if (j == n_levels - 1 && with_rct) break;  // the fused kernel (or, without fusion, the level + RCT pair below) takes it
-        int32_t* dst[3];
-        size_t dst_stride;
-        dst_of(j, dst, &dst_stride);
-        if (!unsqueeze_tiled_eligible(lv.horizontal ? 1 : 0, lv.out_w, lv.out_h, a_stride, lv.res_stride, dst_stride)) break;
-        FlowStep& fs = steps[n];
-        fs.horizontal = lv.horizontal ? 1 : 0;
-        fs.avg_stride = a_stride;
-        fs.res_stride = lv.res_stride;
-        fs.out_w = lv.out_w;
-        fs.out_h = lv.out_h;
-        fs.out_stride = dst_stride;
-        for (int p = 0; p < 3; p++) {
-          const int q = p < n_planes ? p : 0;
-          fs.avg[p] = a[q];
-          fs.res[p] = lv.res[q] ? lv.res[q] : a[q];
-          fs.out[p] = dst[q];
-        }
-        for (int p = 0; p < n_planes; p++) a[p] = dst[p];
-        a_stride = dst_stride;
-      }
-      if (n >= 2) {
-        if ((st = ensure(ctx, ctx->flow_words, unsqueeze_flow_words(n_planes, n, steps)))) return st;
-        if (!ctx->host_flow_flag.p) {
-          // the error word lives in pinned host memory (device-visible under the same address): jxlh_ctx_sync AND
-          // jxlh_ctx_wait_mark read it without queueing a copy behind later work
-          HIPCHK(ctx, ctx->host_flow_flag.alloc(1));
-          *ctx->host_flow_flag.p = 0;
-        }
-        if (ctx->flow_prof_on && (st = ensure(ctx, ctx->flow_prof, 11 * (size_t)unsqueeze_flow_max_steps()))) return st;
-        launch_unsqueeze_flow(ctx->stream, n_planes, n, steps, ctx->flow_words.p, ctx->host_flow_flag.p, 4.0f,
-                              ctx->flow_prof_on ? ctx->flow_prof.p : nullptr);
-        ctx->flow_prof_levels = n;
-        ctx->flow_used = true;
-        for (int p = 0; p < n_planes; p++) cur[p] = a[p];
-        cur_stride = a_stride;
-        i += n;
-        continue;
-      }
-    }
-    const jxlh_squeeze_level& lv = levels[i];
-    const bool last = i == n_levels - 1;
-    int32_t* dst[3];
-    size_t dst_stride;
-    dst_of(i, dst, &dst_stride);
-    const int32_t* rv[3];
-    for (int p = 0; p < n_planes; p++) rv[p] = lv.res[p] ? lv.res[p] : cur[p];
-    bool fused = false;
-    if (last && fuse_rct)
-      fused = launch_unsqueeze_rct(ctx->stream, lv.horizontal ? 1 : 0, cur, cur_stride, rv, lv.res_stride, lv.out_w, lv.out_h,
-                                   dst, dst_stride, rct_op, rct_perm);
-    if (!fused)
-      launch_unsqueeze(ctx->stream, lv.horizontal ? 1 : 0, n_planes, cur, cur_stride, rv, lv.res_stride, lv.out_w, lv.out_h,
-                       dst, dst_stride);
-    if (last && with_rct && !fused) {
-      if (dst_stride == lv.out_w) {
-        launch_rct(ctx->stream, dst[0], dst[1], dst[2], (size_t)lv.out_w * lv.out_h, rct_op, rct_perm);
-      } else {
-        launch_rct_rows(ctx->stream, dst[0], dst[1], dst[2], lv.out_w, lv.out_h, dst_stride, rct_op, rct_perm);
-      }
-    }
-    for (int p = 0; p < n_planes; p++) cur[p] = dst[p];
-    cur_stride = dst_stride;
-    i++;
   }
   HIPCHK(ctx, hipGetLastError());
   return JXLH_OK;
@@ -488,32 +369,21 @@ jxlh_status jxlh_unsqueeze_rct(jxlh_ctx* ctx, int32_t horizontal, const int32_t*
   if (!ctx || !avg || !res || !out || out_stride < out_w || op < 0 || op > 6 || perm < 0 || perm > 5)
     return JXLH_ERR_INVALID_ARGUMENT;
   if (out_w == 0 || out_h == 0) return JXLH_OK;
-  const uint32_t avg_w = horizontal ? (out_w + 1) / 2 : out_w;
-  const uint32_t res_w = horizontal ? out_w / 2 : out_w, res_h = horizontal ? out_h : out_h / 2;
-  const bool has_res = (size_t)res_w * res_h > 0;
-  if (avg_stride < avg_w || (has_res && res_stride < res_w)) return JXLH_ERR_INVALID_ARGUMENT;
+  const SqueezeExtents e = squeeze_extents(horizontal != 0, out_w, out_h);
+  if (avg_stride < e.avg_w || (e.has_res && res_stride < e.res_w)) return JXLH_ERR_INVALID_ARGUMENT;
   const int32_t* rv[3];
   for (int i = 0; i < 3; i++) {
     if (!avg[i] || !out[i] || !is_device_ptr(avg[i]) || !is_device_ptr(out[i])) return JXLH_ERR_INVALID_ARGUMENT;
-    if (has_res && (!res[i] || !is_device_ptr(res[i]))) return JXLH_ERR_INVALID_ARGUMENT;
+    if (e.has_res && (!res[i] || !is_device_ptr(res[i]))) return JXLH_ERR_INVALID_ARGUMENT;
     rv[i] = res[i] ? res[i] : avg[i];
   }
-  const char* sep = getenv("JXLH_SEPARATE_RCT");
-  if (!(sep && *sep == '1')) {
-    ScopedKernelTimer t(ctx, horizontal ? "k6_unsqueeze_rct_h" : "k6_unsqueeze_rct_v");
-    if (launch_unsqueeze_rct(ctx->stream, horizontal, avg, avg_stride, rv, res_stride, out_w, out_h, out, out_stride, op,
-                             perm)) {
-      HIPCHK(ctx, hipGetLastError());
-      return JXLH_OK;
-    }
-  }
-  // planes of 2^31 samples or more: the two separate passes (the RCT with a row pitch when the rows are padded)
-  launch_unsqueeze(ctx->stream, horizontal, 3, avg, avg_stride, rv, res_stride, out_w, out_h, out, out_stride);
-  if (out_stride == out_w) {
-    launch_rct(ctx->stream, out[0], out[1], out[2], (size_t)out_w * out_h, op, perm);
-  } else {
-    launch_rct_rows(ctx->stream, out[0], out[1], out[2], out_w, out_h, out_stride, op, perm);
-  }
+  // fused, or (planes of 2^31 samples or more) the two separate passes
+  SqueezeLaunch L[2];
+  const SqueezeStep st = step_of(horizontal, 3, avg, avg_stride, rv, res_stride, out_w, out_h, out, out_stride);
+  const int n = plan_squeeze_step_rct(st, env_is("JXLH_SEPARATE_RCT", '1'), L);
+  std::optional<ScopedKernelTimer> t;  // (the fused launch only, as ever)
+  if (n == 1) t.emplace(ctx, horizontal ? "k6_unsqueeze_rct_h" : "k6_unsqueeze_rct_v");
+  for (int k = 0; k < n; k++) issue_step(ctx->stream, L[k], st, op, perm);
   HIPCHK(ctx, hipGetLastError());
   return JXLH_OK;
 }
@@ -562,18 +432,17 @@ jxlh_status jxlh_unsqueeze_planes(jxlh_ctx* ctx, int32_t horizontal, int32_t n_p
     return JXLH_ERR_INVALID_ARGUMENT;
   if (out_w == 0 || out_h == 0) return JXLH_OK;
   if (out_w > kMaxModularDim || out_h > kMaxModularDim) return JXLH_ERR_UNSUPPORTED;
-  const uint32_t avg_w = horizontal ? (out_w + 1) / 2 : out_w;
-  const uint32_t res_w = horizontal ? out_w / 2 : out_w, res_h = horizontal ? out_h : out_h / 2;
-  const bool has_res = (size_t)res_w * res_h > 0;
-  if (avg_stride < avg_w || (has_res && res_stride < res_w)) return JXLH_ERR_INVALID_ARGUMENT;
+  const SqueezeExtents e = squeeze_extents(horizontal != 0, out_w, out_h);
+  if (avg_stride < e.avg_w || (e.has_res && res_stride < e.res_w)) return JXLH_ERR_INVALID_ARGUMENT;
   const int32_t* rv[3];
   for (int i = 0; i < n_planes; i++) {
     if (!avg[i] || !out[i] || !is_device_ptr(avg[i]) || !is_device_ptr(out[i])) return JXLH_ERR_INVALID_ARGUMENT;
     rv[i] = res[i] ? res[i] : avg[i];
-    if (has_res && (!res[i] || !is_device_ptr(res[i]))) return JXLH_ERR_INVALID_ARGUMENT;
+    if (e.has_res && (!res[i] || !is_device_ptr(res[i]))) return JXLH_ERR_INVALID_ARGUMENT;
   }
   ScopedKernelTimer t(ctx, horizontal ? "k6_unsqueeze_h" : "k6_unsqueeze_v");
-  launch_unsqueeze(ctx->stream, horizontal, n_planes, avg, avg_stride, rv, res_stride, out_w, out_h, out, out_stride);
+  const SqueezeStep st = step_of(horizontal, n_planes, avg, avg_stride, rv, res_stride, out_w, out_h, out, out_stride);
+  launch_unsqueeze(ctx->stream, plan_squeeze_step(st), st);
   HIPCHK(ctx, hipGetLastError());
   return JXLH_OK;
 }

@@ -7,6 +7,7 @@
 #include "../../include/jxl_hip.h"
 #include "coeff_epoch.h"
 #include "splines_host.h"
+#include "squeeze_plan.h"
 
 namespace jxlh {
 // 16-byte global accesses with a selectable cache policy (NT = streamed once: `nt` loads / stores)
@@ -423,39 +424,18 @@ void launch_modular_local(hipStream_t s, const LocalLaunch& a);
 void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
 void launch_modular_xyb_to_f32(hipStream_t s, const int32_t* y, const int32_t* x, const int32_t* b, size_t n,
                                const float scale[3], float* ox, float* oy, float* ob);
-// n_planes (<= 3) planes of identical geometry in one launch (the channels of one squeeze step)
-void launch_unsqueeze(hipStream_t s, int horizontal, int n_planes, const int32_t* const avg[], size_t avg_stride,
-                      const int32_t* const res[], size_t res_stride, uint32_t out_w, uint32_t out_h,
-                      int32_t* const out[], size_t out_stride);
-// fused unsqueeze of three planes + inverse RCT; false = not applicable (plane too large), nothing launched
-// consecutive streamed unsqueeze steps as one dataflow launch (k6_unsqueeze_flow): step i + 1's averages are step i's
-// outputs (distinct planes per step); `scratch` holds unsqueeze_flow_words() ints, `error` one int that stays 0 unless a
-// wait inside the launch outlasted deadline_s
-struct FlowStep {
-  int horizontal;
-  const int32_t* avg[3];
-  size_t avg_stride;
-  const int32_t* res[3];
-  size_t res_stride;
-  uint32_t out_w, out_h;
-  int32_t* out[3];
-  size_t out_stride;
-};
-bool unsqueeze_tiled_eligible(int horizontal, uint32_t out_w, uint32_t out_h, size_t avg_stride, size_t res_stride,
-                              size_t out_stride);
-int unsqueeze_flow_max_steps();
-size_t unsqueeze_flow_words(int n_planes, int n_steps, const FlowStep* steps);
-void launch_unsqueeze_flow(hipStream_t s, int n_planes, int n_steps, const FlowStep* steps, int* scratch, int* error,
+// k_squeeze.hip: each launcher launches exactly the kernel and variant the plan names (squeeze_plan.h); a SqueezeStep's
+// addresses are the planes.  One step over its n_planes (<= 3) planes of one geometry: kTiled or kOneWave
+void launch_unsqueeze(hipStream_t s, const SqueezeLaunch& how, const SqueezeStep& st);
+// consecutive streamed steps as one dataflow launch (k6_unsqueeze_flow): step i + 1's averages are step i's outputs
+// (distinct planes per step), vec[i] = squeeze_tiled_vec; `scratch` holds squeeze_flow_words() ints, `error` one int that
+// stays 0 unless a wait inside the launch outlasted deadline_s
+void launch_unsqueeze_flow(hipStream_t s, int n_steps, const SqueezeStep* steps, const uint8_t* vec, int* scratch, int* error,
                            float deadline_s, unsigned long long* prof);
-bool launch_unsqueeze_rct(hipStream_t s, int horizontal, const int32_t* const avg[3], size_t avg_stride,
-                          const int32_t* const res[3], size_t res_stride, uint32_t out_w, uint32_t out_h,
-                          int32_t* const out[3], size_t out_stride, int op, int perm);
-// several consecutive squeeze steps of small planes (all sides <= 128) in one launch; res[i * 3 + p] = residual plane
-// of level i, plane p.  false = the chain does not qualify, nothing launched
-#define JXLH_SQL_MAX 128     // k6_unsqueeze_levels: largest plane side handled in LDS
-#define JXLH_SQL_LEVELS 16  // ... and the most levels one launch takes
-bool launch_unsqueeze_levels(hipStream_t s, int n_planes, int n_levels, const int* horizontal, const uint32_t* out_w,
-                             const uint32_t* out_h, const int32_t* const* res, const size_t* res_stride,
+// fused unsqueeze of three planes + inverse RCT (kFusedRct)
+void launch_unsqueeze_rct(hipStream_t s, const SqueezeLaunch& how, const SqueezeStep& st, int op, int perm);
+// the first n_levels levels of a chain in one launch, planes in LDS (kLevels: squeeze_levels_fit)
+void launch_unsqueeze_levels(hipStream_t s, int n_planes, int n_levels, const jxlh_squeeze_level* levels,
                              const int32_t* const base[], size_t base_stride, uint32_t base_w, uint32_t base_h,
                              int32_t* const out[], size_t out_stride);
 // smooth_{h,v,2d}_unsqueeze on a rectangle of the output channel; `in` is the whole average channel

@@ -993,7 +993,7 @@ def test_unsqueeze_rejects_dimensions_whose_product_wraps(ctx):
 
 @pytest.mark.parametrize("scale", [2**15, 2**24, 2**27, 2**28])
 def test_unsqueeze_large_magnitudes(ctx, oracle, scale):
-    """the device folds the reference's two parity clamps into min() operations (k_modular.hip); checked here
+    """the device folds the reference's two parity clamps into min() operations (k_squeeze.hip); checked here
     on large-magnitude data inside the range where the reference's i64 scalar definition and its wrapping
     i32 SIMD form agree (tests/test_oracle_pin.py proves the min() identity on the full i32 range)"""
     rng = np.random.default_rng(scale % 1000)

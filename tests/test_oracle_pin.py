@@ -224,7 +224,7 @@ def test_u8_conversion_dither_properties(oracle_any):
 
 
 def test_tendency_clamps_equal_min_form_on_full_i32_range(oracle_any):
-    """The device kernel (k_modular.hip) computes the reference's SIMD tendency (squeeze.rs:107-141) with its
+    """The device kernel (k_squeeze.hip) computes the reference's SIMD tendency (squeeze.rs:107-141) with its
     two parity clamps folded into x = min(x, 2|a-b|+1, 2|b-c|) and the sign applied as (x ^ s) - s.  Proved
     here against the oracle's line-by-line restatement, including wrapping extremes."""
     L = oracle_any.lib
@@ -569,7 +569,7 @@ def test_weighted_predictor_reproduces_flat_and_ramp_images(oracle):
 
 # ---------------------------------------------------------------- the unsqueeze step as the device computes it
 def _unsqueeze_step_d_state(avg, res, nx, d):
-    """numpy transcription of unsqueeze_step (jxl_rs_amd/csrc/k_modular.hip): the recurrence on d = prev - avg with the
+    """numpy transcription of unsqueeze_step (jxl_rs_amd/csrc/k_squeeze.hip): the recurrence on d = prev - avg with the
     sign of avg - next applied up front; wrapping i32 arithmetic as on the device"""
     i32, u32 = np.int32, np.uint32
     with np.errstate(over="ignore"):
