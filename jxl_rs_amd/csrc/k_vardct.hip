@@ -5,14 +5,9 @@
 // adjust_quant_bias (:85-96), the LF patch copy (:227-235), transform_to_pixels and
 // the copy into the group planes (:237-250).
 //
-// Varblock sizes and positions are data dependent, so the work is first *binned*:
+// Varblock sizes and positions are data dependent, so the work is first *binned* (k1_scan, k_vardct_scan.hip: one
+// frame-wide list of 16-byte work items per transform class).  This file holds the DCT classes with sides of 8..32:
 //
-//   k1_scan   one 256-thread workgroup per 256x256 group: loads the group's 32x32 transform
-//             map, prefix-scans the varblock sizes in raster order -> coefficient offset of
-//             every varblock (the reference lays varblocks back to back in decode order,
-//             group.rs:440, :612), evaluates the per-varblock scalars (inv_global_scale /
-//             raw_quant, the two chroma-from-luma multipliers) and appends one 32-byte work
-//             item per varblock to a frame-wide list per transform class.
 //   k1_dct*   one kernel per class family, sized for that family's registers/LDS: wavefronts
 //             stride over batches of same-shape varblocks; a batch's dequantised coefficients
 //             are staged channel by channel in the wave's private LDS tile with 16-byte
@@ -21,338 +16,24 @@
 //             weights stay in registers across batches; on dense slabs every shape's batch is
 //             sized to 16 coefficients per lane and channel or fewer, and all of them issue
 //             the three channels' loads up front.
-//   k1_special / k1_large  the 8x8 special transforms and the 64..256 transforms.
+//
+// The 8x8 special transforms are k_vardct_special.hip, the 64..256 transforms k_vardct_large.hip; which of all these
+// kernels a launch enqueues is k1_plan.h, issued by k1_launch.hip.
 //
 // HBM traffic is the compulsory 12 B/px in + 12 B/px out (+ maps, + 32 B per varblock of
 // work items); arithmetic is f32 in the reference's operation order (bit-exact vs the FMA
 // build of the oracle).  Output is independent of the order in which work items land in
 // the lists (each varblock is independent).
-#include <algorithm>
-#include <atomic>
+#include <type_traits>
 
 #include "k_vardct_common.h"
 
-// Cache policy of K1's two streams (round 3, profiles/r03_n_k1_policy.txt): the coefficient slabs are read exactly once
-// and the pixels are next touched by another kernel after 0.8 GB of other traffic -- `nt` on both keeps them from
-// displacing each other in L2: K1 0.448 -> 0.430 ms, pipelined step 0.824 -> 0.806 ms (alternating runs, one box).
-// (`nt` on the filter kernel's loads / stores measured 10-40 % SLOWER: its halo rows are re-read by the neighbour tile.)
-#ifndef JXLH_NT_COEF
-#define JXLH_NT_COEF true
-#endif
+// (the policy of K1's two streams: JXLH_NT_COEF, k_vardct_common.h)
 #ifndef JXLH_NT_K1_STORE
 #define JXLH_NT_K1_STORE true
 #endif
 namespace jxlh {
 namespace {
-
-// ------------------------------------------------------------------------------------------
-// One workgroup scans kScanGroups groups (one 256-thread quarter each).  Its duration is the serial head of K1 and is
-// one latency chain -- map bytes -> two block scans -> a returning global atomic per class -> item stores -- so (round 3)
-// every global input is requested up front, the type tables are register immediates, two classes share a 32-bit scan
-// word, and the quarters pool their counts: 256 workgroups' atomics meet on a class counter instead of 1024 (same-
-// address atomics serialise at ~12 ns each: 13 of the former 36 us).
-constexpr int kScanGroups = 4;
-constexpr int kScanThreads = kScanGroups * kThreads;
-// STRIP (the frame runs through k123_strip, k_strip.hip): the scan also decides per 64x64 tile who reconstructs it -- the
-// strip kernel, iff every varblock touching the tile lies inside one 32x32 quadrant of it and is a DCT with sides <= 32
-// (what aligning every varblock to its own size gives) -- writes a descriptor
-// per block of those tiles ({type | dx << 5 | dy << 7 | off64 << 9 | 1 << 31, raw_quant of the varblock}: everything the
-// strip kernel needs to find a block's varblock and its coefficients) and appends work items for the OTHER tiles only.
-// ENT (the frame is read in the slot-bucketed form, FrameDev::se_*): the scan also turns the group's slot counts into
-// the entry range of every varblock -- an exclusive prefix sum over the 1024 slots of each channel (a thread loads the
-// counts of four slots as one word, the three channels ride one 64-bit block scan, 17 bits each), kept in LDS and read
-// at the varblock's first slot -- and writes it beside the work item: the class kernels then go from the item straight
-// to the entries.  This replaces the unpack pass of round 4 (pair words + 4-byte slot tables: 69 + 12.6 MB written and
-// read again per 8K frame).
-// ROUTE (ENT only): some groups of the frame are read from their dense slabs (FrameDev::group_route): their DCT-class
-// varblocks go to WorkLists::ditems.  A frame without routed groups runs the instantiation without any of it.
-template <bool STRIP, bool ENT = false, bool ROUTE = false>
-__global__ __launch_bounds__(kScanThreads) void k1_scan(const FrameDev f, const WorkLists wl, const int group_row0,
-                                                         int* __restrict__ error_flag,
-                                                         const int* __restrict__ group_list, const int ngroups,
-                                                         int* __restrict__ next_counts) {
-  constexpr int kPairs = (kNumClasses + 1) / 2;
-  __shared__ int s_wave_sum[kScanGroups][kWaves];
-  __shared__ uint32_t s_wcls[kScanGroups][kWaves][kPairs];
-  __shared__ int s_count[kScanGroups][kNumClasses], s_base[kScanGroups][kNumClasses];
-  __shared__ int s_route[ROUTE ? kScanGroups : 1];  // != 0 = the quarter's group is read from its dense slab (FrameDev::group_route)
-  __shared__ int s_tmode[kScanGroups][16];  // STRIP: != 0 = a tile of the group (4 x 4 of them) the class kernels keep
-  // ENT: exclusive prefix of the slot counts, three channels packed (17 bits each; a run holds at most 65536 entries)
-  __shared__ uint64_t s_pref[ENT ? kScanGroups : 1][ENT ? kSlotsPerRun + 1 : 1];
-  __shared__ uint64_t s_wpref[ENT ? kScanGroups : 1][kWaves];
-  if constexpr (STRIP) {
-    if (threadIdx.x < kScanGroups * 16) s_tmode[threadIdx.x / 16][threadIdx.x % 16] = 0;
-    // progress flags + ticket counter of the strip kernel that follows
-    if (blockIdx.x == 0)
-      for (int i = threadIdx.x; i < f.strip_nflags; i += kScanThreads) f.strip_flags[i] = 0;
-    __syncthreads();
-  }
-  // the counters of the NEXT launch (the other set: its last readers finished before this kernel started)
-  if (blockIdx.x == 0 && threadIdx.x < kCountLines) next_counts[threadIdx.x * kCountPitch] = 0;
-  const int sub = threadIdx.x / kThreads, tid = threadIdx.x % kThreads, lane = tid & 63, wave = tid >> 6;
-  const int gi = blockIdx.x * kScanGroups + sub;
-  const bool live = gi < ngroups;  // a dead quarter walks through the barriers with an empty group
-  const int group = !live ? 0 : group_list ? group_list[gi] : group_row0 * f.xgroups + gi;
-  const int bx0 = (group % f.xgroups) * kGroupBlocks, by0 = (group / f.xgroups) * kGroupBlocks;
-  const int bw = live ? min(kGroupBlocks, f.xblocks - bx0) : 0, bh = live ? min(kGroupBlocks, f.yblocks - by0) : 0;
-  // 4 consecutive blocks of the 32x32 raster per thread
-  int sizes[4], types[4], rq4[4], local = 0;
-  const int by = tid >> 3, bx4 = (tid & 7) * 4;
-  const int gby = min(by0 + by, f.yblocks - 1);
-  uint8_t raw4[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const size_t at = (size_t)gby * f.xblocks + min(bx0 + bx4 + i, f.xblocks - 1);
-    raw4[i] = f.transform_map[at];
-    rq4[i] = f.raw_quant[at];
-  }
-  // the four blocks of a thread share one colour tile (8 blocks wide, bx4 % 4 == 0)
-  const int ci = (gby / kColorTileBlocks) * f.cmap_stride + min(bx0 + bx4, f.xblocks - 1) / kColorTileBlocks;
-  const uint32_t cc = (uint32_t)(uint8_t)f.ytox[ci] | (uint32_t)(uint8_t)f.ytob[ci] << 8;
-  // ENT: counts of slots 4 tid .. 4 tid + 3 of the three channels, {first entry, entries} of the three runs
-  uint32_t cw[3] = {0u, 0u, 0u};
-  uint2 run[3] = {make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};
-  bool dense_route = false;
-  if constexpr (ENT) {
-    if constexpr (ROUTE) {
-      dense_route = live && f.group_route[group] != 0;
-      if (tid == 0) s_route[sub] = dense_route ? 1 : 0;  // (published by the barriers below)
-    }
-    if (live && !dense_route) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        cw[c] = *reinterpret_cast<const uint32_t*>(f.se_counts + ((size_t)group * 3 + c) * kSlotsPerRun + 4 * tid);
-        run[c] = f.se_runs[group * 3 + c];
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int bx = bx4 + i;
-    const uint8_t raw = (bx < bw && by < bh) ? raw4[i] : 0;
-    const int type = raw & 127;
-    int sz = 0;
-    if (raw >= 128) {  // first (top-left) block of a varblock, group.rs:468-473
-      if (type < JXLH_NUM_TRANSFORMS) {
-        const int cx = 1 << log2_covered_x_reg(type), cy = 1 << log2_covered_y_reg(type);
-        sz = cx * cy;
-        // Error::InvalidBlockSizeForChromaSubsampling (frame/modular/mod.rs:1058-1060)
-        if (f.subsampled && sz > 1) atomicExch(error_flag, JXLH_ERR_INVALID_BLOCK_SIZE);
-        // Error::HFBlockOutOfBounds (frame/modular/mod.rs:1061-1064): the varblock must end inside its group
-        // and inside the frame.  Such an item is dropped: its pixel stores would leave the plane.
-        if (bx + cx > bw || by + cy > bh) {
-          atomicExch(error_flag, JXLH_ERR_BLOCK_OUT_OF_BOUNDS);
-          sz = 0;
-        }
-        if constexpr (STRIP) {
-          // tiles this varblock keeps away from the strip kernel: all it touches if it is not a small DCT or leaves
-          // its tile; every tile of the group if the map is broken
-          const bool closed = (bx & 3) + cx <= 4 && (by & 3) + cy <= 4 && class_of_type_reg(type) < kClsSpecial;
-          if (sz == 0 || f.subsampled) {
-            for (int k = 0; k < 16; k++) atomicOr(&s_tmode[sub][k], 1);
-          } else if (!closed) {
-            for (int ty = by >> 3; ty <= (by + cy - 1) >> 3; ty++)
-              for (int tx = bx >> 3; tx <= (bx + cx - 1) >> 3; tx++) atomicOr(&s_tmode[sub][ty * 4 + tx], 1);
-          }
-        }
-      } else {
-        atomicExch(error_flag, JXLH_ERR_INVALID_TRANSFORM);  // Error::InvalidVarDCTTransform
-        if constexpr (STRIP)
-          for (int k = 0; k < 16; k++) atomicOr(&s_tmode[sub][k], 1);
-      }
-    }
-    sizes[i] = sz;
-    types[i] = type;
-    local += sz;
-  }
-  // coefficient offsets (in 64-coefficient slots): prefix sum of the covered areas in raster order (group.rs:612)
-  int incl = local;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int n = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += n;
-  }
-  if (lane == 63) s_wave_sum[sub][wave] = incl;
-  uint64_t pmine = 0, pincl = 0;
-  if constexpr (ENT) {
-    auto bytes = [](uint32_t w) { return (uint64_t)((w & 0xffu) + ((w >> 8) & 0xffu) + ((w >> 16) & 0xffu) + (w >> 24)); };
-    pmine = bytes(cw[0]) | bytes(cw[1]) << 17 | bytes(cw[2]) << 34;
-    pincl = pmine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)pincl, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(pincl >> 32), d, 64);
-      if (lane >= d) pincl += (uint64_t)lo | (uint64_t)hi << 32;
-    }
-    if (lane == 63) s_wpref[sub][wave] = pincl;
-  }
-  // per-class rank of every varblock in raster order (stable: neighbouring blocks stay neighbours in the lists ->
-  // contiguous coefficient reads, full-line pixel writes).  Two classes share a 32-bit word, 16 bits each (a group
-  // holds at most 1024 varblocks).
-  int slot[4], cls4[4];
-  bool strip_tile = false;  // the thread's four blocks share a tile
-  if constexpr (STRIP) {
-    __syncthreads();
-    strip_tile = s_tmode[sub][(by >> 3) * 4 + (bx4 >> 3)] == 0;
-  }
-  uint32_t mine[kPairs], excl[kPairs];
-#pragma unroll
-  for (int w = 0; w < kPairs; w++) mine[w] = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int cls = sizes[i] > 0 && !strip_tile ? class_of_type_reg(types[i]) : -1;
-    cls4[i] = cls;
-    slot[i] = 0;
-    const int sh = (cls & 1) * 16;
-#pragma unroll
-    for (int w = 0; w < kPairs; w++) {
-      if ((cls >> 1) == w) {  // cls = -1 matches no pair
-        slot[i] = (int)((mine[w] >> sh) & 0xffffu);
-        mine[w] += 1u << sh;
-      }
-    }
-  }
-#pragma unroll
-  for (int w = 0; w < kPairs; w++) {
-    uint32_t inc = mine[w];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t n = (uint32_t)__shfl_up((int)inc, d, 64);
-      if (lane >= d) inc += n;
-    }
-    excl[w] = inc - mine[w];
-    if (lane == 63) s_wcls[sub][wave][w] = inc;
-  }
-  __syncthreads();
-  if constexpr (ENT) {
-    uint64_t base = pincl - pmine;
-#pragma unroll
-    for (int v = 0; v < kWaves; v++)
-      if (v < wave) base += s_wpref[sub][v];
-    uint64_t* P = s_pref[sub] + 4 * tid;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      P[k] = base;
-      base += (uint64_t)((cw[0] >> (8 * k)) & 0xffu) | (uint64_t)((cw[1] >> (8 * k)) & 0xffu) << 17 |
-              (uint64_t)((cw[2] >> (8 * k)) & 0xffu) << 34;
-    }
-    if (tid == kThreads - 1) P[4] = base;  // the run's total (entry kSlotsPerRun)
-  }
-  int off64 = incl - local;
-  int group_total = 0;
-#pragma unroll
-  for (int v = 0; v < kWaves; v++) {
-    if (v < wave) off64 += s_wave_sum[sub][v];
-    group_total += s_wave_sum[sub][v];
-  }
-  // first-block flags that claim more blocks than the group holds (overlapping varblocks; the reference cannot
-  // produce such a map, a caller-built one can): the 10-bit coefficient offset of the work items would overflow,
-  // K1 would read past the group's slab and the class lists (sized by area) could overflow.  Nothing of such a
-  // group is reconstructed.
-  const bool bad_group = group_total > bw * bh;
-  if (bad_group && tid == 0) atomicExch(error_flag, JXLH_ERR_BLOCK_OUT_OF_BOUNDS);
-#pragma unroll
-  for (int w = 0; w < kPairs; w++) {
-    uint32_t woff = 0, total = 0;
-#pragma unroll
-    for (int v = 0; v < kWaves; v++) {
-      if (v < wave) woff += s_wcls[sub][v][w];
-      total += s_wcls[sub][v][w];
-    }
-    excl[w] += woff;
-    if ((tid >> 1) == w && tid < kNumClasses)
-      s_count[sub][tid] = bad_group ? 0 : (int)((total >> ((tid & 1) * 16)) & 0xffffu);
-  }
-  __syncthreads();
-  // one atomic per class for the whole workgroup; the quarters take consecutive ranges in group order.  ENT: the DCT
-  // classes of a dense-route quarter count into the dense lists (threads 32 .. 32 + kClsSpecial) instead
-  if (threadIdx.x < kNumClasses || (ROUTE && threadIdx.x >= 32 && threadIdx.x < 32 + kClsSpecial)) {
-    const bool dlist = ROUTE && threadIdx.x >= 32;
-    const int c = dlist ? threadIdx.x - 32 : threadIdx.x;
-    auto mine_q = [&](int q) {
-      if constexpr (ROUTE) return c >= kClsSpecial || (s_route[q] != 0) == dlist;
-      else return true;
-    };
-    int total = 0;
-#pragma unroll
-    for (int q = 0; q < kScanGroups; q++) total += mine_q(q) ? s_count[q][c] : 0;
-    int base = total > 0 ? atomicAdd(&wl.counts[(dlist ? kCntDense0 + c : c) * kCountPitch], total) : 0;
-#pragma unroll
-    for (int q = 0; q < kScanGroups; q++) {
-      if (mine_q(q)) {
-        s_base[q][c] = base;
-        base += s_count[q][c];
-      }
-    }
-  }
-  // (a dense-route group's slab is already there: nothing to expand for its special / large varblocks)
-  if (live && tid == 0 && f.group_dense)
-    f.group_dense[group] = !dense_route && (s_count[sub][kClsSpecial] | s_count[sub][kClsLarge]) != 0;
-  if constexpr (STRIP) {
-    if (live && tid < 16) {
-      const int gtx = (group % f.xgroups) * 4 + (tid & 3), gty = (group / f.xgroups) * 4 + (tid >> 2);
-      if (gtx < f.strips && gty < f.tile_rows) f.strip_mode[gty * f.strips + gtx] = (bad_group || s_tmode[sub][tid]) ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  if (bad_group) return;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    if (sizes[i] > 0) {
-      WorkItem it;
-      it.packed = (uint32_t)(bx4 + i) | ((uint32_t)by << 5) | ((uint32_t)off64 << 10) | ((uint32_t)types[i] << 20);
-      it.group = (uint32_t)group;
-      it.raw_quant = rq4[i];
-      it.cc = cc;
-      const int cls = cls4[i];
-      if (cls >= 0) {
-        const int sh = (cls & 1) * 16;
-        int rank = slot[i];
-#pragma unroll
-        for (int w = 0; w < kPairs; w++)
-          if ((cls >> 1) == w) rank += (int)((excl[w] >> sh) & 0xffffu);
-        bool to_dense = false;
-        if constexpr (ENT) {
-          if (cls < kClsSpecial) {
-            if (dense_route) {
-              to_dense = true;
-              wl.ditems[cls][s_base[sub][cls] + rank] = it;
-            } else {
-              // (the prefixes were published by the barriers above.)  A count table that claims more than its run holds
-              // is cut at the run's end: no entry outside the run is ever read.  A DCT-class varblock has at most 16
-              // slots of at most 255 entries: the counts fit their 16 bits
-              const uint64_t p0 = s_pref[sub][off64], p1 = s_pref[sub][min(off64 + sizes[i], kSlotsPerRun)];
-              EntryItem ei;
-              uint32_t n[3];
-#pragma unroll
-              for (int c = 0; c < 3; c++) {
-                const uint32_t a0 = min((uint32_t)(p0 >> (17 * c)) & 0x1ffffu, run[c].y);
-                const uint32_t a1 = min((uint32_t)(p1 >> (17 * c)) & 0x1ffffu, run[c].y);
-                ei.e0[c] = run[c].x + a0;
-                n[c] = min(a1 - a0, 0xffffu);
-              }
-              ei.nxy = n[0] | n[1] << 16;
-              it.group |= n[2] << 16;
-              wl.eitems[cls][s_base[sub][cls] + rank] = ei;
-            }
-          }
-        }
-        if (!to_dense) wl.items[cls][s_base[sub][cls] + rank] = it;
-      }
-      if constexpr (STRIP) {
-        if (strip_tile) {
-          const int cx = 1 << log2_covered_x_reg(types[i]), cy = 1 << log2_covered_y_reg(types[i]);
-          const uint32_t d0 = (uint32_t)types[i] | ((uint32_t)off64 << 9) | (1u << 31);
-          for (int dy = 0; dy < cy; dy++)
-            for (int dx = 0; dx < cx; dx++)
-              f.strip_desc[(size_t)(by0 + by + dy) * f.xblocks + bx0 + bx4 + i + dx] =
-                  make_uint2(d0 | ((uint32_t)dx << 5) | ((uint32_t)dy << 7), (uint32_t)rq4[i]);
-        }
-      }
-    }
-    off64 += sizes[i];
-  }
-}
-
 template <class S>
 __device__ __forceinline__ void stage4(float* __restrict__ buf, int b, int k, float4 v) {
   if constexpr (S::kWide) {
@@ -1244,385 +925,20 @@ __global__ __launch_bounds__(kThreads, SPARSE == 3 ? JXLH_K1_DIRECT_WPE : SPARSE
   if constexpr (ALL) run(ShapeTag<S8x8>{}, std::true_type{}, std::integral_constant<int, kClsDct8>{}, 0);
 }
 
-// family D: the nine 8x8 special transform types (IDENTITY, DCT2X2, DCT4X4, DCT4X8, DCT8X4, AFV0-3).
-// Each lane transforms one block of one channel with the block's 64 coefficients in registers, so a wavefront must
-// hold blocks of ONE code path or the nine paths serialise.  The special work list is in raster order (mixed types): a
-// wave takes a (chunk of 512 items, type bin) pair, compacts the chunk's items of its bin through a ballot, and runs
-// them in batches of kSpecBlk = 21 blocks.  Round 3: the three channels of a batch are transformed TOGETHER -- lane =
-// (channel, block), 63 of 64 lanes busy in one pass of the (long, fully unrolled) per-type code -- where round 2 ran the
-// transform once per channel on 32 lanes; the tile is in place (a lane reads its row into registers, writes the
-// pixels over it) and the dequantised Y a batch's X / B rows need stays in 24 registers.  16K all types: 394 -> see
-// profiles/r03_d_large_path.txt.
-constexpr int kSpecWaves = 2;
-constexpr int kSpecThreads = kSpecWaves * 64;
-constexpr int kSpecChunk = 512;
-constexpr int kSpecBins = 9;
-constexpr int kSpecBlk = 21;                       // blocks per batch: 3 x 21 = 63 transform lanes
-constexpr int kSpecIters = (kSpecBlk * 16 + 63) / 64;  // 16-byte groups of one channel of a batch, per lane
-__device__ __forceinline__ int special_bin(int type) {  // 1, 2, 3, 12, 13, 14, 15, 16, 17 -> 0..8
-  return type <= 3 ? type - 1 : type - 9;
-}
-
-// one lane: its block's 64 coefficients into registers, pixels written over them
-template <int TYPE>
-__device__ __forceinline__ void special_8x8_inplace(float* __restrict__ row, const float* __restrict__ afv_basis = kAfvBasisDev) {
-  float c[64], o[64];
-#pragma unroll
-  for (int i = 0; i < 64; i++) c[i] = row[i];
-  special_8x8_t<TYPE>(c, o, afv_basis);
-#pragma unroll
-  for (int i = 0; i < 64; i++) row[i] = o[i];
-}
-
-// BIN0 .. BIN1: the type bins one instantiation handles.  Round 5: two launches -- IDENTITY / DCT2X2 / DCT4X4 / DCT4X8 /
-// DCT8X4 (bins 0-4) and AFV0-3 (bins 5-8) -- instead of one: the kernel's registers are the maximum over its bodies, and
-// the AFV bodies (a 16 x 16 basis product on top of the 4x4 and 4x8 transforms) set it for everybody (230 VGPRs, 355
-// spilled SGPRs, two waves per SIMD).
-template <int BIN0, int BIN1>
-__global__ __launch_bounds__(kSpecThreads) void k1_special(const FrameDev f, const WorkLists wl) {
-  __shared__ float s_tile[kSpecWaves][64 * kSpecPitch];
-  __shared__ BlockInfo s_binfo[kSpecWaves][kSpecBlk];
-  __shared__ int s_idx[kSpecWaves][kSpecChunk];
-  __shared__ AdjTable s_adj;
-  __shared__ float s_afv[BIN1 > 5 ? 256 : 1];  // the AFV basis (bins 5-8 only)
-  if constexpr (BIN1 > 5)
-    for (int i = threadIdx.x; i < 256; i += kSpecThreads) s_afv[i] = kAfvBasisDev[i];
-  build_adj_table(f, &s_adj, threadIdx.x, kSpecThreads);  // (ends with a workgroup barrier)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const WorkItem* __restrict__ items = wl.items[kClsSpecial];
-  const int count = wl.counts[(kClsSpecial) * kCountPitch];
-  float* tile = s_tile[wave];
-  BlockInfo* binfo = s_binfo[wave];
-  int* mine = s_idx[wave];
-  constexpr int kBins = BIN1 - BIN0;
-  const int npairs = ((count + kSpecChunk - 1) / kSpecChunk) * kBins;
-  for (int pair = blockIdx.x * kSpecWaves + wave; pair < npairs; pair += gridDim.x * kSpecWaves) {
-    const int chunk = pair / kBins, bin = BIN0 + pair % kBins;
-    // ---- this wave's items of the chunk: the ones whose type falls in `bin`
-    int nmine = 0;
-    uint32_t packed[kSpecChunk / 64];
-#pragma unroll
-    for (int i = 0; i < kSpecChunk / 64; i++) {  // all loads in flight before the first ballot
-      const int idx = chunk * kSpecChunk + i * 64 + lane;
-      packed[i] = items[min(idx, max(count - 1, 0))].packed;
-    }
-#pragma unroll
-    for (int i = 0; i < kSpecChunk / 64; i++) {
-      const int idx = chunk * kSpecChunk + i * 64 + lane;
-      const bool m = idx < count && special_bin((int)(packed[i] >> 20) & 31) == bin;
-      const unsigned long long mask = __ballot(m);
-      if (m) mine[nmine + __popcll(mask & ((1ull << lane) - 1ull))] = idx;
-      nmine += __popcll(mask);
-    }
-    wave_sync();
-    // every item of the pair has a type of this bin, and the types of a bin share one dequant table
-    // (quant_weights.rs:321-343): a wave-uniform pointer instead of a per-lane lookup
-    constexpr int kBinType[kSpecBins] = {1, 2, 3, 12, 13, 14, 15, 16, 17};
-    int bin_type = kBinType[0];
-#pragma unroll
-    for (int i = 1; i < kSpecBins; i++) bin_type = bin == i ? kBinType[i] : bin_type;
-    const float* __restrict__ bin_table = f.tables + f.table_offset[quant_table_for_type(bin_type)];
-    const int k0 = (lane & 15) * 4;  // the four coefficient positions this lane stages, in every block it touches
-    for (int b0 = 0; b0 < nmine; b0 += kSpecBlk) {
-      const int nb = min(kSpecBlk, nmine - b0);
-      if (lane < nb) {
-        const WorkItem it = items[mine[b0 + lane]];
-        decode_item(f, it, &binfo[lane]);
-      }
-      wave_sync();
-      // ---- stage the three channels: row = ch * kSpecBlk + block, reference order Y, X, B (group.rs:223)
-      float dy[4 * kSpecIters];
-      auto stage_channel = [&](auto ch_tag) {
-        constexpr int CH = decltype(ch_tag)::value;
-        const float4 tv = *reinterpret_cast<const float4*>(bin_table + CH * 64 + k0);
-        int4 qv[kSpecIters];
-        float b_sdy[kSpecIters], b_xcc[kSpecIters], b_bcc[kSpecIters];
-#pragma unroll
-        for (int j = 0; j < kSpecIters; j++) {  // every global load of the channel in flight first
-          const int b = min(j * 4 + (lane >> 4), nb - 1);  // lanes past the batch re-read its last block (discarded)
-          const BlockInfo* bp = &binfo[b];
-          b_sdy[j] = bp->sdy;
-          b_xcc[j] = bp->x_cc;
-          b_bcc[j] = bp->b_cc;
-          qv[j] = gload_i4<JXLH_NT_COEF>(f.coeffs + bp->coef_off + CH * kGroupArea + k0);
-        }
-#pragma unroll
-        for (int j = 0; j < kSpecIters; j++) {
-          const int b = j * 4 + (lane >> 4);
-          float d4[4] = {dy[j * 4], dy[j * 4 + 1], dy[j * 4 + 2], dy[j * 4 + 3]};
-          BlockInfo bi;
-          bi.sdy = b_sdy[j];
-          bi.x_cc = b_xcc[j];
-          bi.b_cc = b_bcc[j];
-          const float4 v = dequant4t<CH>(f, qv[j], tv, bi, &s_adj, d4);
-          if constexpr (CH == 1) {
-            dy[j * 4] = d4[0];
-            dy[j * 4 + 1] = d4[1];
-            dy[j * 4 + 2] = d4[2];
-            dy[j * 4 + 3] = d4[3];
-          }
-          if (b < nb) {
-            float* dst = tile + (CH * kSpecBlk + b) * kSpecPitch + k0;
-            dst[0] = v.x;
-            dst[1] = v.y;
-            dst[2] = v.z;
-            dst[3] = v.w;
-          }
-        }
-      };
-      stage_channel(std::integral_constant<int, 1>{});
-      stage_channel(std::integral_constant<int, 0>{});
-      stage_channel(std::integral_constant<int, 2>{});
-      // ---- transform: lane = (channel, block); transform_buffer[0] = lf[0] first
-      const int tch = lane / kSpecBlk, tb = lane % kSpecBlk;
-      const bool on = tch < 3 && tb < nb;
-      const float lf0 = f.lf[min(tch, 2)][binfo[min(tb, nb - 1)].lf_off[min(tch, 2)]];
-      wave_sync();
-      if (on) {
-        float* row = tile + lane * kSpecPitch;  // lane == tch * kSpecBlk + tb
-        row[0] = lf0;
-        auto in_range = [](int b) { return b >= BIN0 && b < BIN1; };
-        // (wave-uniform; only the bodies of this instantiation's bins are compiled in)
-        if (in_range(0) && bin == 0) special_8x8_inplace<1>(row);
-        if (in_range(1) && bin == 1) special_8x8_inplace<2>(row);
-        if (in_range(2) && bin == 2) special_8x8_inplace<3>(row);
-        if (in_range(3) && bin == 3) special_8x8_inplace<12>(row);
-        if (in_range(4) && bin == 4) special_8x8_inplace<13>(row);
-        if (in_range(5) && bin == 5) special_8x8_inplace<14>(row, s_afv);
-        if (in_range(6) && bin == 6) special_8x8_inplace<15>(row, s_afv);
-        if (in_range(7) && bin == 7) special_8x8_inplace<16>(row, s_afv);
-        if (in_range(8) && bin == 8) special_8x8_inplace<17>(row, s_afv);
-      }
-      wave_sync();
-      // ---- store: gather first, then store: all stores of the lane issue back to back
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) {
-        float* __restrict__ plane = f.planes[ch];
-        float4 ov[kSpecIters];
-        int oo[kSpecIters];
-#pragma unroll
-        for (int j = 0; j < kSpecIters; j++) {
-          const int b = min(j * 4 + (lane >> 4), nb - 1), p = k0;
-          const int px = binfo[b].px_off[ch];
-          const float* r = tile + (ch * kSpecBlk + b) * kSpecPitch;
-          if (f.tiled) {  // memory order inside the block is (y & 4) * 8 + x * 4 + (y & 3)
-            const int x = (p & 31) >> 2, y0 = (p >> 5) * 4;
-            const float* src = r + y0 * 8 + x;
-            ov[j] = make_float4(src[0], src[8], src[16], src[24]);
-            oo[j] = px + p;
-          } else {
-            ov[j] = make_float4(r[p], r[p + 1], r[p + 2], r[p + 3]);
-            oo[j] = px + (p / 8) * (int)f.plane_stride + (p % 8);
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < kSpecIters; j++)
-          if (j * 4 + (lane >> 4) < nb) *reinterpret_cast<float4*>(plane + oo[j]) = ov[j];
-      }
-      wave_sync();
-    }
-    wave_sync();  // `mine` is rewritten by the next pair
-  }
-}
+static_assert(S8x8::NB == kDct8Batch, "k1_plan.h sizes the 8x8 class's grid by its batch");
 
 }  // namespace
 
-// ---- host side -----------------------------------------------------------------------------
-// the two-pass units (nblocks / 32 + 16) and the three fused lists (/ 32, / 128, / 256, + 16 each), k_vardct_large.hip
-static size_t large_unit_capacity(size_t nblocks) { return nblocks / 8 + 64; }
-// k_vardct_large.hip
-void launch_vardct_large(hipStream_t s, const FrameDev& f, const WorkLists& wl, int nblk, uint32_t* large_units,
-                         size_t unit_capacity, size_t nblocks);
-
-static_assert(kWlEItems0 - kWlItems0 == kNumClasses && kWlDItems0 - kWlEItems0 == kClsSpecial &&
-              kWlFallback0 - kWlDItems0 == kClsSpecial && kWlFbAny - kWlFallback0 == kClsSpecial, "work-list regions");
-
-WorklistLayout vardct_worklist_layout(size_t nblocks) {
-  WorklistLayout L{};
-  size_t p = 0;
-  auto put = [&](int r, size_t len) {
-    L.off[r] = p;
-    L.len[r] = len;
-    p += len;
-  };
-  put(kWlCounts, 2 * kCountBytes);  // two sets of counters, one 128-byte line each
-  for (int c = 0; c < kNumClasses; c++) put(kWlItems0 + c, (nblocks / class_min_area(c) + 1) * sizeof(WorkItem));
-  // entry side items of the DCT classes + their dense-route lists
-  for (int c = 0; c < kClsSpecial; c++) put(kWlEItems0 + c, (nblocks / class_min_area(c) + 1) * sizeof(EntryItem));
-  for (int c = 0; c < kClsSpecial; c++) put(kWlDItems0 + c, (nblocks / class_min_area(c) + 1) * sizeof(WorkItem));
-  // the fallback flags: one word per batch of the class (at least 2 varblocks per batch)
-  for (int c = 0; c < kClsSpecial; c++) put(kWlFallback0 + c, (nblocks / (2 * class_min_area(c)) + 16) * sizeof(uint32_t));
-  put(kWlFbAny, (size_t)kFbAny * kFbAnyPitch * sizeof(uint32_t));  // the fallback launch's summary words
-  // the unit lists of the large transforms: one u32 per 4096 samples of a 256-pixel varblock (two-pass units) and one
-  // per varblock of the smaller types (three lists by slabs per channel; worst case one entry per 32 blocks)
-  put(kWlLargeUnits, large_unit_capacity(nblocks) * sizeof(uint32_t));
-  // the LLF planes of the large transforms (3 x nblocks floats, k1_large_llf): launch_vardct_large aligns their pointer
-  // to 64 bytes, which is this offset on a hipMalloc'ed (256-byte aligned) base
-  p = (p + 63) & ~(size_t)63;
-  put(kWlLlf, 3 * nblocks * sizeof(float));
-  L.bytes = p;
-  return L;
-}
-
-size_t vardct_worklist_bytes(const FrameDev& f) {
-  return vardct_worklist_layout((size_t)f.xblocks * f.yblocks).bytes;
-}
-
-void vardct_worklist_clear_flags(hipStream_t s, void* worklist_mem, size_t nblocks) {
-  const WorklistLayout L = vardct_worklist_layout(nblocks);
-  (void)hipMemsetAsync(reinterpret_cast<char*>(worklist_mem) + L.off[kWlFallback0], 0,
-                       L.off[kWlFbAny] + L.len[kWlFbAny] - L.off[kWlFallback0], s);
-}
-
-void vardct_worklist_reset(hipStream_t s, void* worklist_mem, uint32_t* launch_parity) {
-  (void)hipMemsetAsync(worklist_mem, 0, 2 * kCountBytes, s);
-  *launch_parity = 0;
-}
-
-const void* vardct_worklist_counters(const void* worklist_mem, uint32_t launch, size_t* bytes, int* lines) {
-  static_assert(kCntFallback0 == kNumClasses + 4 && kCntDense0 == kCntFallback0 + kClsSpecial && kNumClasses == 11,
-                "jxlh_frame_k1_counters maps the lines by position");
-  *bytes = kCountBytes;
-  *lines = kCountLines;
-  return reinterpret_cast<const char*>(worklist_mem) + (launch & 1u) * kCountBytes;
-}
-
-void launch_vardct_groups(hipStream_t s, const FrameDev& f_in, int group_row0, int group_row1,
-                          void* worklist_mem, uint32_t* launch_parity, int* error_flag, int32_t* dense_coeffs,
-                          const int* group_list, int n_list, bool has_special, bool has_large, int n_dense_route) {
-  const int ngroups = group_list ? n_list : (group_row1 - group_row0) * f_in.xgroups;
-  if (ngroups <= 0) return;
-  // The value that flags a batch for the fallback launch: unique per launch across the process, never 0.  The flag words
-  // are zeroed when the work list is allocated or its layout moves (vardct_worklist_clear_flags), so a stale word holds an
-  // earlier launch's epoch and never this one's.
-  static std::atomic<uint32_t> epoch_counter{0};
-  FrameDev f = f_in;
-  uint32_t epoch = ++epoch_counter;
-  if (epoch == 0) epoch = ++epoch_counter;
-  f.fb_epoch = (int)epoch;
-  // carve the work-list memory (vardct_worklist_layout): [two sets of counters, one 128-byte line each] [class 0 items] ...
-  WorkLists wl;
-  const uint32_t set = (*launch_parity)++ & 1u;
-  wl.counts = reinterpret_cast<int*>(reinterpret_cast<char*>(worklist_mem) + set * kCountBytes);
-  int* next_counts = reinterpret_cast<int*>(reinterpret_cast<char*>(worklist_mem) + (set ^ 1u) * kCountBytes);
-  char* const base = reinterpret_cast<char*>(worklist_mem);
-  const size_t nblocks = (size_t)f.xblocks * f.yblocks;
-  const WorklistLayout L = vardct_worklist_layout(nblocks);
-  for (int c = 0; c < kNumClasses; c++) wl.items[c] = reinterpret_cast<WorkItem*>(base + L.off[kWlItems0 + c]);
-  for (int c = 0; c < kClsSpecial; c++) {
-    wl.eitems[c] = reinterpret_cast<EntryItem*>(base + L.off[kWlEItems0 + c]);
-    wl.ditems[c] = reinterpret_cast<WorkItem*>(base + L.off[kWlDItems0 + c]);
-    wl.fallback[c] = reinterpret_cast<uint32_t*>(base + L.off[kWlFallback0 + c]);
-  }
-  wl.fb_any = reinterpret_cast<uint32_t*>(base + L.off[kWlFbAny]);
-  uint32_t* large_units = reinterpret_cast<uint32_t*>(base + L.off[kWlLargeUnits]);  // behind the last list
-  const dim3 gscan((ngroups + kScanGroups - 1) / kScanGroups);
-  if (f.strip_desc)
-    hipLaunchKernelGGL(k1_scan<true>, gscan, dim3(kScanThreads), 0, s, f, wl, group_row0, error_flag, group_list, ngroups,
-                       next_counts);
-  else if (f.se_entries && f.group_route)
-    hipLaunchKernelGGL((k1_scan<false, true, true>), gscan, dim3(kScanThreads), 0, s, f, wl, group_row0, error_flag, group_list,
-                       ngroups, next_counts);
-  else if (f.se_entries)
-    hipLaunchKernelGGL((k1_scan<false, true>), gscan, dim3(kScanThreads), 0, s, f, wl, group_row0, error_flag, group_list,
-                       ngroups, next_counts);
-  else
-    hipLaunchKernelGGL(k1_scan<false>, gscan, dim3(kScanThreads), 0, s, f, wl, group_row0, error_flag, group_list, ngroups,
-                       next_counts);
-  if (f.strip_desc && f.strip_all_closed) return;  // the host saw the whole map: no tile is left to the class kernels
-  // grids: enough waves to fill the chip; kernels stride over their lists (counts are device-side)
-  const int nblk = ngroups * kGroupBlocks * kGroupBlocks;
-  auto grid_for = [](long work_items, int items_per_wg, int cap) {
-    long g = (work_items + items_per_wg - 1) / items_per_wg;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-  };
-  // one stream: forking the class kernels onto side streams measured no gain on the d1 mix (event
-  // overhead ~ tail savings) and extra streams compete for the runtime's few hardware queues
-  // entries form: the direct kernels (+ the fallback launch) when a zero coefficient provably reconstructs to +0.0f
-  const int sparse = f.se_entries ? (f.se_direct_ok ? 3 : 2) : f.sp_sorted ? 1 : 0;
-  if (sparse && dense_coeffs && (has_special || has_large)) {
-    // groups that hold special / large varblocks (flagged by k1_scan) still get a dense slab
-    if (sparse >= 2)
-      launch_expand_entries(s, dense_coeffs, f.se_entries, f.se_counts, f.se_runs, f.group_dense, f.xgroups * f.ygroups);
-    else
-      launch_expand_sorted(s, dense_coeffs, f.sp_sorted, f.sp_slot_start, f.group_dense, f.xgroups * f.ygroups);
-  }
-  // caps measured flat between 768 and 8192 workgroups at 8K (tools/bench_variants.sh)
-  const dim3 g8(grid_for(nblk, kWaves * S8x8::NB * 2, 4096)), g16(grid_for(nblk / 2, kWaves * 8 * 2, 2048)),
-      g32(grid_for(nblk / 4, kWaves * 4 * 2, 2048));
-  bool inline8 = false, dense1632 = false;  // entries form: the dense-pass choices of a frame denser than d1 (se_dense_hint)
-  if (f.subsampled) {
-    // (the fallback launch has no sub-sampled form: such a frame always takes the inline fallback)
-    if (sparse == 3) hipLaunchKernelGGL((k1_dct8<3, true, true>), g8, dim3(kThreads), 0, s, f, wl);
-    else if (sparse == 2) hipLaunchKernelGGL((k1_dct8<2, true>), g8, dim3(kThreads), 0, s, f, wl);
-    else if (sparse == 1) hipLaunchKernelGGL((k1_dct8<1, true>), g8, dim3(kThreads), 0, s, f, wl);
-    else hipLaunchKernelGGL((k1_dct8<0, true>), g8, dim3(kThreads), 0, s, f, wl);
-    // the other DCT classes are empty in a sub-sampled frame (k1_scan reports larger varblocks as an error)
-  } else {
-    const dim3 g1632(std::min(4096u, g16.x + g32.x));
-    if (sparse == 3) {
-      static const int force_inline = [] {  // JXLH_K1_INLINE=0 / 1: A/B runs of the 8x8 class's two forms
-        const char* e = getenv("JXLH_K1_INLINE");
-        return e && *e ? atoi(e) : -1;
-      }();
-      static const int force_dense1632 = [] {  // JXLH_K1_DENSE1632=0 / 1: the same for the 16..32-point classes
-        const char* e = getenv("JXLH_K1_DENSE1632");
-        return e && *e ? atoi(e) : -1;
-      }();
-      inline8 = force_inline >= 0 ? force_inline != 0 : f.se_dense_hint >= 2;
-      dense1632 = force_dense1632 >= 0 ? force_dense1632 != 0 : f.se_dense_hint >= 1;
-      if (inline8) hipLaunchKernelGGL((k1_dct8<3, false, true>), g8, dim3(kThreads), 0, s, f, wl);
-      else hipLaunchKernelGGL(k1_dct8<3>, g8, dim3(kThreads), 0, s, f, wl);
-      if (dense1632) hipLaunchKernelGGL(k1_dct16_32<2>, g1632, dim3(kThreads), 0, s, f, wl);
-      else hipLaunchKernelGGL(k1_dct16_32<3>, g1632, dim3(kThreads), 0, s, f, wl);
-    } else if (sparse == 2) {
-      hipLaunchKernelGGL(k1_dct8<2>, g8, dim3(kThreads), 0, s, f, wl);
-      hipLaunchKernelGGL(k1_dct16_32<2>, g1632, dim3(kThreads), 0, s, f, wl);
-    } else if (sparse == 1) {
-      hipLaunchKernelGGL(k1_dct8<1>, g8, dim3(kThreads), 0, s, f, wl);
-      hipLaunchKernelGGL(k1_dct16_32<1>, g1632, dim3(kThreads), 0, s, f, wl);
-    } else {
-      hipLaunchKernelGGL(k1_dct8<0>, g8, dim3(kThreads), 0, s, f, wl);
-      hipLaunchKernelGGL(k1_dct16_32<0>, g1632, dim3(kThreads), 0, s, f, wl);
-    }
-  }
-  // what the direct form of k1_dct16_32 left (usually next to nothing: the workgroups read one counter and leave)
-  // (a sparse frame leaves a handful of batches: the workgroups read one counter and go; a frame denser than d1 gets
-  // the whole chip)
-  // (the fallback as TWO launches -- the classes without a 32-point side apart: 32 KB of LDS, three waves per SIMD --
-  // measured no better on the outlier frame and 4 % worse on dense ones: profiles/r06_c_density.txt)
-  // (nothing can be left when both choices were made)
-  if (sparse == 3 && !f.subsampled && !(inline8 && dense1632))
-    hipLaunchKernelGGL((k1_dct16_32<2, true>), dim3(std::min(512, std::max(1, nblk / 2048))), dim3(kThreads), 0, s, f, wl);
-  // entries form, groups routed to their dense slabs (FrameDev::group_route): the same class kernels in their dense
-  // form on those groups' lists; the grids follow the routed share of the frame
-  if (sparse >= 2 && n_dense_route > 0) {
-    WorkLists wd = wl;
-    for (int c = 0; c < kClsSpecial; c++) wd.items[c] = wl.ditems[c];
-    wd.counts = wl.counts + kCntDense0 * kCountPitch;
-    FrameDev fd = f;
-    fd.se_entries = nullptr;
-    const long dblk = (long)std::min(n_dense_route, ngroups) * kGroupBlocks * kGroupBlocks;
-    const dim3 d8(grid_for(dblk, kWaves * S8x8::NB * 2, 4096));
-    if (f.subsampled) {
-      hipLaunchKernelGGL((k1_dct8<0, true>), d8, dim3(kThreads), 0, s, fd, wd);
-    } else {
-      // (one launch for every DCT class of the routed groups)
-      hipLaunchKernelGGL((k1_dct16_32<0, false, true>), dim3(std::min(8192u, d8.x + (unsigned)grid_for(dblk / 2, kWaves * 8 * 2, 4096))),
-                         dim3(kThreads), 0, s, fd, wd);
-    }
-  }
-  // an empty special list (the d1 mix) pays for every launched workgroup: the grid follows the list's worst case
-  if (has_special)
-  {
-    hipLaunchKernelGGL((k1_special<0, 5>), dim3(grid_for((long)(nblk / kSpecChunk + 1) * 5, kSpecWaves, 2048)),
-                       dim3(kSpecThreads), 0, s, f, wl);
-    hipLaunchKernelGGL((k1_special<5, 9>), dim3(grid_for((long)(nblk / kSpecChunk + 1) * 4, kSpecWaves, 2048)),
-                       dim3(kSpecThreads), 0, s, f, wl);
-  }
-  // (the large transforms on a side stream next to the memory-bound DCT classes, one workgroup per CU: K1 of the 16K
-  // all-types frame 1.872 -> 1.847 ms, 1.937 with their usual two per CU -- inside the noise, not kept)
-  if (has_large) launch_vardct_large(s, f, wl, nblk, large_units, large_unit_capacity(nblocks), nblocks);
+void launch_k1_dct(hipStream_t s, const K1Step& step, const FrameDev& f, const WorkLists& wl) {
+  // in the order of K1Kernel (k1_plan.h)
+  static constexpr K1ClassKernel kTable[] = {
+      k1_dct8<kFormDense>,       k1_dct8<kFormSorted>,       k1_dct8<kFormEntries>,       k1_dct8<kFormDirect>,
+      k1_dct8<kFormDirect, false, true>,
+      k1_dct8<kFormDense, true>, k1_dct8<kFormSorted, true>, k1_dct8<kFormEntries, true>, k1_dct8<kFormDirect, true, true>,
+      k1_dct16_32<kFormDense>,   k1_dct16_32<kFormSorted>,   k1_dct16_32<kFormEntries>,   k1_dct16_32<kFormDirect>,
+      k1_dct16_32<kFormEntries, true>, k1_dct16_32<kFormDense, false, true>};
+  static_assert(sizeof(kTable) / sizeof(kTable[0]) == kK1Special0 - kK1Class0, "one kernel per id of k1_plan.h");
+  hipLaunchKernelGGL(kTable[step.kernel - kK1Class0], dim3(step.grid), dim3(step.block), 0, s, f, wl);
 }
 
 }  // namespace jxlh

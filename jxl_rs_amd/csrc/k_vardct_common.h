@@ -1,12 +1,22 @@
-// Shared by the K1 translation units (k_vardct.hip: scan + DCT8..32 classes + special transforms; k_vardct_large.hip:
-// the 64..256 transforms): the work-list types k1_scan writes and the per-item decoding.
+// Shared by the K1 translation units (k_vardct_scan.hip: the scan and the work-list memory; k_vardct.hip: the DCT8..32
+// classes; k_vardct_special.hip: the 8x8 special transforms; k_vardct_large.hip: the 64..256 transforms; k1_launch.hip:
+// the issuing loop): the work-list types k1_scan writes, the per-item decoding and the per-file launchers.
 #pragma once
+#include "k1_plan.h"
 #include "varblock_core.h"
+
+// Cache policy of K1's two streams (round 3, profiles/r03_n_k1_policy.txt): the coefficient slabs are read exactly once
+// and the pixels are next touched by another kernel after 0.8 GB of other traffic -- `nt` on both (JXLH_NT_K1_STORE,
+// k_vardct.hip) keeps them from displacing each other in L2: K1 0.448 -> 0.430 ms, pipelined step 0.824 -> 0.806 ms
+// (alternating runs, one box).
+// (`nt` on the filter kernel's loads / stores measured 10-40 % SLOWER: its halo rows are re-read by the neighbour tile.)
+#ifndef JXLH_NT_COEF
+#define JXLH_NT_COEF true
+#endif
 
 namespace jxlh {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = kWaves * 64;
+static_assert(kK1GroupBlocks == kGroupBlocks, "k1_plan.h sizes the grids by the blocks of a group");
 
 // class ids of the work lists
 enum : int {
@@ -109,6 +119,16 @@ struct WorkLists {
   int* counts;  // kCountLines counters at kCountPitch ints, zeroed before k1_scan: the classes, then the large
                 // transforms' unit lists (k_vardct_large.hip: two-pass slab units, fused lists of 1 / 2 / 4 slabs)
 };
+
+// One launcher per kernel-holding file: each launches exactly the kernel the step names, on the step's grid.
+using K1ClassKernel = void (*)(const FrameDev, const WorkLists);  // k1_dct8, k1_dct16_32, k1_special
+void launch_k1_scan(hipStream_t s, const K1Step& step, const FrameDev& f, const WorkLists& wl, int group_row0,
+                    int* error_flag, const int* group_list, int ngroups, int* next_counts);
+void launch_k1_dct(hipStream_t s, const K1Step& step, const FrameDev& f, const WorkLists& wl);
+void launch_k1_special(hipStream_t s, const K1Step& step, const FrameDev& f, const WorkLists& wl);
+// large_units: the kWlLargeUnits region of the work-list memory (k1_large_carve), the LLF planes behind it
+void launch_k1_large(hipStream_t s, const K1Step& step, int fuse, const FrameDev& f, const WorkLists& wl,
+                     uint32_t* large_units, size_t nblocks);
 
 __device__ __forceinline__ void decode_item(const FrameDev& f, const WorkItem& it, BlockInfo* bi) {
   const int bx = it.packed & 31, by = (it.packed >> 5) & 31, off64 = (it.packed >> 10) & 1023;

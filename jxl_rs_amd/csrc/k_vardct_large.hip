@@ -1,12 +1,8 @@
-// K1, family E: the 64..256-pixel transforms of a frame (see k_vardct.hip for the binning that feeds them).  Its own
+// K1, family E: the 64..256-pixel transforms of a frame (see k_vardct_scan.hip for the binning that feeds them).  Its own
 // translation unit: the register-resident length-64 leaves want no SLP packing (v_pk_* pairs cost moves and registers
-// on gfx950, Makefile), while the special-transform kernel of k_vardct.hip measured better with it.
+// on gfx950, Makefile), while the special-transform kernel of k_vardct_special.hip measured better with it.
 #include "k_vardct_common.h"
 #include "varblock_large.h"
-
-#ifndef JXLH_LLF_GRID
-#define JXLH_LLF_GRID 1024  // four 32 KB workgroups of k1_large_llf fit a CU
-#endif
 
 namespace jxlh {
 namespace {
@@ -31,7 +27,7 @@ namespace {
 //   k1_large_pass<2> unit = (slab of pixel columns, channel): vertical IDCT in place
 // Every body is instantiated per transform type (the geometry folds to constants); pass 1 keeps eight rounds of raw
 // coefficient loads in flight per lane.
-// unit lists behind each other in the `units` allocation (launch_vardct_large carves them the same way)
+// unit lists behind each other in the `units` allocation (k1_plan.h: k1_large_carve)
 struct LargeLists {
   uint32_t* two_pass;  // item | slab << 24 of the 256-pixel types, counter kNumClasses * kCountPitch
   uint32_t* fused[3];  // items of the types whose channel is 1 (64x64, 64x32, 32x64), 2 (128x64, 64x128) or 4 (128x128)
@@ -294,34 +290,24 @@ __global__ __launch_bounds__(kLargeThreads) __attribute__((amdgpu_waves_per_eu(2
 
 }  // namespace
 
-void launch_vardct_large(hipStream_t s, const FrameDev& f, const WorkLists& wl, int nblk, uint32_t* large_units,
-                         size_t unit_capacity, size_t nblocks) {
-  auto grid_for = [](long work_items, int items_per_wg, int cap) {
-    long g = (work_items + items_per_wg - 1) / items_per_wg;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-  };
-  // the large class: unit lists, LLF corners, the one-launch path, then one launch per separable pass of the 256-pixel
-  // types.  All five exit at once when the class is empty
-  const size_t nb = nblocks;
+static_assert(kLargeThreads == 256, "k1_large_units runs the same block size");
+
+void launch_k1_large(hipStream_t s, const K1Step& step, int fuse, const FrameDev& f, const WorkLists& wl,
+                     uint32_t* large_units, size_t nblocks) {
+  const K1LargeCarve c = k1_large_carve(nblocks);
   LargeLists ll;
-  ll.two_pass = large_units;
-  ll.fused[0] = ll.two_pass + (nb / 32 + 16);
-  ll.fused[1] = ll.fused[0] + (nb / 32 + 16);
-  ll.fused[2] = ll.fused[1] + (nb / 128 + 16);
+  ll.two_pass = large_units + c.two_pass;
+  for (int i = 0; i < 3; i++) ll.fused[i] = large_units + c.fused[i];
   float* llf_planes = reinterpret_cast<float*>(
-      (reinterpret_cast<uintptr_t>(large_units + unit_capacity) + 63) & ~(uintptr_t)63);
-  static const int fuse = [] {  // development switch: JXLH_LARGE_FUSED=0 sends every large type through the two passes
-    const char* e = getenv("JXLH_LARGE_FUSED");
-    return e ? atoi(e) : 1;
-  }();
-  hipLaunchKernelGGL(k1_large_units, dim3(grid_for(nblk / 64 + 1, 256, 64)), dim3(256), 0, s, wl, ll, fuse);
-  hipLaunchKernelGGL(k1_large_llf, dim3(grid_for(3L * (nblk / 32 + 1), kLargeWaves, JXLH_LLF_GRID)), dim3(kLargeThreads), 0, s, f, wl,
-                     llf_planes, nblocks);
-  // two 77 KiB workgroups fit a CU: 512 is the resident capacity
-  const dim3 glarge(grid_for(3L * (nblk / 32 + 1), kLargeWaves, 512));
-  if (fuse) hipLaunchKernelGGL(k1_large_fused, glarge, dim3(kLargeThreads), 0, s, f, wl, ll, llf_planes, nblocks);
-  hipLaunchKernelGGL(k1_large_pass<1>, glarge, dim3(kLargeThreads), 0, s, f, wl, ll.two_pass, llf_planes, nblocks);
-  hipLaunchKernelGGL(k1_large_pass<2>, glarge, dim3(kLargeThreads), 0, s, f, wl, ll.two_pass, llf_planes, nblocks);
+      (reinterpret_cast<uintptr_t>(large_units + c.capacity) + 63) & ~(uintptr_t)63);
+  const dim3 grid(step.grid), block(step.block);
+  switch (step.kernel) {
+    case kK1LargeUnits: hipLaunchKernelGGL(k1_large_units, grid, block, 0, s, wl, ll, fuse); break;
+    case kK1LargeLlf: hipLaunchKernelGGL(k1_large_llf, grid, block, 0, s, f, wl, llf_planes, nblocks); break;
+    case kK1LargeFused: hipLaunchKernelGGL(k1_large_fused, grid, block, 0, s, f, wl, ll, llf_planes, nblocks); break;
+    case kK1LargePass1: hipLaunchKernelGGL(k1_large_pass<1>, grid, block, 0, s, f, wl, ll.two_pass, llf_planes, nblocks); break;
+    default: hipLaunchKernelGGL(k1_large_pass<2>, grid, block, 0, s, f, wl, ll.two_pass, llf_planes, nblocks); break;
+  }
 }
 
 }  // namespace jxlh

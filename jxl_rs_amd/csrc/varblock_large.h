@@ -25,12 +25,12 @@
 // level-n sums rounded before level n/2 adds them, w_i butterflies with FMA), so results are bit-identical to the
 // oracle's FMA build.
 #pragma once
+#include "k1_plan.h"
 #include "varblock_core.h"
 
 namespace jxlh {
 
-constexpr int kLargeThreads = 256;                 // 4 independent waves per workgroup
-constexpr int kLargeWaves = kLargeThreads / 64;
+constexpr int kLargeThreads = kLargeWaves * 64;    // 4 independent waves per workgroup (k1_plan.h)
 constexpr int kLargeSlab = 4096;                   // samples per slab = per wave
 constexpr int kLargeTile = 64 * 65;
 #ifndef JXLH_LARGE_BULK
@@ -496,7 +496,7 @@ __device__ __forceinline__ void wave_large_pass2(const LargeGeom& g, int x0, flo
 }
 
 // One channel of one large varblock, both passes by one 256-thread workgroup (stage hook; the frame path runs the
-// passes as separate launches over slab units, k_vardct.hip).  lf points at the cy x cx LF patch (row pitch
+// passes as separate launches over slab units, k_vardct_large.hip).  lf points at the cy x cx LF patch (row pitch
 // lf_stride); plane at the top-left output pixel (addressing given by `lay`).  lds: kLargeWaves * kLargeTile + 2048
 // floats.  coef(k): the dequantised coefficient at stored index k.  All threads must call with identical arguments.
 template <class CoefFn>

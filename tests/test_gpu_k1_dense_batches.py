@@ -10,7 +10,8 @@ Every case compares helpers.run_gpu_frame with helpers.run_oracle_frame bit for 
     the counts asserted
   - the d1 mix with wide chroma-from-luma factors, a raw_quant spread and extreme coefficients at both ends of varblocks
   - both output layouts (8x8-tiled planes for the filters, raster planes read directly)
-  - a group routed to its dense slab inside a slot-form frame (k1_dct16_32<0, false, true>)
+  - a group routed to its dense slab inside a slot-form frame (k1_dct16_32<kFormDense, false, true>: kK1Dct1632DenseAll
+    of csrc/k1_plan.h)
 """
 import copy
 

@@ -1,4 +1,4 @@
-"""The transform stage's work-list memory (k_vardct.hip, vardct_worklist_layout): one layout gives both the bytes
+"""The transform stage's work-list memory (k_vardct_scan.hip, vardct_worklist_layout): one layout gives both the bytes
 jxlh_frame_begin allocates and the regions launch_vardct_groups carves from them.  Swept over every frame of
 1..512 x 1..512 blocks through the host-only jxlh_worklist_layout (jxl_hip_dev.h): each region holds the worst case
 a frame of that size can put in it, the regions follow each other without overlap and the last one ends inside the
