@@ -13,160 +13,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # JXLH_LIBRARY: developer override used to A/B kernel build variants (tools/build_variant.sh)
 LIB_PATH = os.environ.get("JXLH_LIBRARY") or os.path.join(_HERE, "libjxl_hip.so")
 
-NUM_TRANSFORMS = 27
-NUM_QUANT_TABLES = 17
-GROUP_DIM = 256
-NUM_LF_FRAMES = 4
+# The constants (JXLH_X -> X), the structs (jxlh_frame_params -> FrameParams), ABI_SYMBOLS / DEV_SYMBOLS and every entry
+# point's signature come from the headers by way of tools/gen_py_binding.py; below is only what the headers do not say.
+from . import _abi  # noqa: E402
+from ._abi import *  # noqa: E402,F401,F403
 
-OK = 0
-ERR_INVALID_ARGUMENT = -1
-ERR_OUT_OF_MEMORY = -2
-ERR_DEVICE = -3
-ERR_BAD_STATE = -4
-ERR_INVALID_TRANSFORM = -5
-ERR_UNSUPPORTED = -6
-ERR_INVALID_BLOCK_SIZE = -7
-ERR_BLOCK_OUT_OF_BOUNDS = -8
-FRAME_UNFUSED_FILTERS = 1
-FRAME_EXPAND_SPARSE = 2
-FRAME_STRIP = 4
-FRAME_DENSE_DEQUANT = 8
-FRAME_MODULAR = 16
-MODULAR_XYB = 1 << 16  # jxlh_frame_set_modular_channels: sample_format | MODULAR_XYB
-GROUP_COMPLETE = 1
-GROUP_ACCUMULATE = 2
-GROUP_ENTRIES12 = 4
-
-# every symbol include/jxl_hip.h declares (checked by tests/test_abi_symbols.py)
-ABI_SYMBOLS = [
-    "jxlh_default_frame_params", "jxlh_ctx_create", "jxlh_ctx_destroy", "jxlh_status_string", "jxlh_last_error",
-    "jxlh_alloc_pinned", "jxlh_free_pinned", "jxlh_frame_begin", "jxlh_frame_set_dequant_tables",
-    "jxlh_frame_set_lf_quantized", "jxlh_frame_set_lf", "jxlh_frame_set_hf_meta", "jxlh_submit_group",
-    "jxlh_submit_group_sparse", "jxlh_submit_groups_sparse", "jxlh_submit_groups_sparse8", "jxlh_submit_groups_sparse4",
-    "jxlh_submit_groups_slots", "jxlh_slot_wait", "jxlh_slot_after",
-    "jxlh_frame_coeff_buffer", "jxlh_frame_run", "jxlh_ctx_sync", "jxlh_ctx_mark", "jxlh_ctx_wait_mark", "jxlh_frame_read_planes",
-    "jxlh_frame_read_planes_rect", "jxlh_frame_read_planes_rect_async",
-    "jxlh_frame_device_planes", "jxlh_frame_set_extra_channel", "jxlh_frame_read_extra_channel", "jxlh_frame_read_lf", "jxlh_frame_read_rgb8", "jxlh_frame_read_rgb8_async",
-    "jxlh_frame_read_rgb16", "jxlh_frame_read_ycbcr_rgb8", "jxlh_frame_read_ycbcr_rgb16", "jxlh_frame_read_output",
-    "jxlh_frame_read_output_async", "jxlh_stage_chroma_upsample", "jxlh_stage_upsample",
-    "jxlh_set_upsampling_weights", "jxlh_stage_noise_generate", "jxlh_stage_noise_convolve", "jxlh_stage_noise_add",
-    "jxlh_stage_gaborish", "jxlh_stage_epf", "jxlh_stage_lf_smooth", "jxlh_stage_transform_to_pixels", "jxlh_rct",
-    "jxlh_palette", "jxlh_palette_delta", "jxlh_modular_to_rgb8", "jxlh_modular_to_f32", "jxlh_modular_xyb_to_f32",
-    "jxlh_unsqueeze", "jxlh_unsqueeze_planes", "jxlh_smooth_unsqueeze", "jxlh_unsqueeze_rct", "jxlh_palette_delta_wp",
-    "jxlh_unsqueeze_levels", "jxlh_unsqueeze_chain", "jxlh_abi_version", "jxlh_covered_blocks_x", "jxlh_covered_blocks_y",
-    "jxlh_quant_table_for_type", "jxlh_quant_table_size", "jxlh_comm_unique_id", "jxlh_comm_init",
-    "jxlh_comm_init_local", "jxlh_comm_destroy", "jxlh_comm_band", "jxlh_frame_run_sharded", "jxlh_frame_allgather",
-    "jxlh_frames_run_sharded_local", "jxlh_frames_allgather_local", "jxlh_comm_allgather",
-    "jxlh_frame_rerender_groups", "jxlh_comm_allgather_local", "jxlh_palette_strided", "jxlh_modular_frame_filters",
-    "jxlh_ctx_wait_stream", "jxlh_ctx_wait_event", "jxlh_ctx_tune_placement", "jxlh_ctx_record_event",
-    "jxlh_frame_allgather_output", "jxlh_frames_allgather_output_local",
-    "jxlh_host_pack_slots", "jxlh_host_pack_slots_many", "jxlh_slot_writer_create", "jxlh_slot_writer_destroy", "jxlh_slot_writer_begin_group",
-    "jxlh_slot_writer_begin_varblock", "jxlh_slot_writer_add", "jxlh_slot_writer_add_many", "jxlh_slot_writer_end_group",
-    "jxlh_ctx_set_reference", "jxlh_frame_save_reference", "jxlh_ctx_clear_reference", "jxlh_frame_set_patches",
-    "jxlh_stage_patches", "jxlh_frame_blend", "jxlh_stage_blend",
-    "jxlh_frame_save", "jxlh_frame_save_async", "jxlh_stage_save",
-    "jxlh_frame_set_splines", "jxlh_stage_splines", "jxlh_splines_build_segments",
-    "jxlh_frame_set_modular_channels",
-    "jxlh_ctx_set_lf_frame", "jxlh_frame_save_lf", "jxlh_ctx_clear_lf_frame", "jxlh_frame_set_lf_from_slot",
-    "jxlh_lf_preview", "jxlh_lf_preview_async",
-    "jxlh_frame_set_groups_lf_only",
-    "jxlh_modular_local_lower", "jxlh_modular_local_transforms", "jxlh_frame_set_modular_groups",
-    "jxlh_frame_set_modular_groups_async",
-]
-# developer / bench instruments: include/jxl_hip_dev.h (same library, not part of the drop-in boundary)
-DEV_SYMBOLS = [
-    "jxlh_timer_start", "jxlh_timer_stop", "jxlh_kernel_timing_enable", "jxlh_kernel_timing_get",
-    "jxlh_kernel_timing_reset", "jxlh_selftest_recip", "jxlh_probe_copy_bandwidth", "jxlh_frame_path",
-    "jxlh_flow_profile", "jxlh_frame_k1_counters", "jxlh_probe_placement", "jxlh_worklist_layout",
-    "jxlh_save_tile_layout", "jxlh_splines_set_batch_budget", "jxlh_splines_bin_layout", "jxlh_live_resources",
-]
-
-
-class FrameParams(C.Structure):
-    """jxlh_frame_params."""
-    _fields_ = [
-        ("abi_version", C.c_uint32),
-        ("xsize", C.c_uint32), ("ysize", C.c_uint32),
-        ("global_scale", C.c_uint32), ("quant_lf", C.c_uint32),
-        ("lf_quant_factors", C.c_float * 3),
-        ("quant_biases", C.c_float * 4),
-        ("x_qm_scale", C.c_uint32), ("b_qm_scale", C.c_uint32),
-        ("color_factor", C.c_uint32),
-        ("base_correlation_x", C.c_float), ("base_correlation_b", C.c_float),
-        ("ytox_lf", C.c_int32), ("ytob_lf", C.c_int32),
-        ("gab", C.c_uint32),
-        ("gab_w1", C.c_float * 3), ("gab_w2", C.c_float * 3),
-        ("epf_iters", C.c_uint32),
-        ("epf_sharp_lut", C.c_float * 8),
-        ("epf_channel_scale", C.c_float * 3),
-        ("epf_quant_mul", C.c_float), ("epf_pass0_sigma_scale", C.c_float),
-        ("epf_pass2_sigma_scale", C.c_float), ("epf_border_sad_mul", C.c_float),
-        ("do_lf_smoothing", C.c_uint32),
-        ("flags", C.c_uint32),
-        ("hshift", C.c_uint32 * 3), ("vshift", C.c_uint32 * 3),
-        ("epf_sigma_for_modular", C.c_float),
-        ("upsampling", C.c_uint32),
-        ("xsize_upsampled", C.c_uint32), ("ysize_upsampled", C.c_uint32),
-        ("noise", C.c_uint32), ("noise_lut", C.c_float * 8),
-        ("visible_frame_index", C.c_uint32), ("nonvisible_frame_index", C.c_uint32),
-    ]
-
-
-class OutputDesc(C.Structure):
-    """jxlh_output_desc."""
-    _fields_ = [("color", C.c_uint32), ("transfer", C.c_uint32), ("xyb", C.c_float * 16), ("tf_param", C.c_float),
-                ("hlg_luminance_rgb", C.c_float * 3), ("bits", C.c_uint32), ("channels", C.c_uint32)]
-
-
-COLOR_XYB, COLOR_YCBCR, COLOR_NONE = 0, 1, 2
-TF = {"linear": 0, "srgb": 1, "bt709": 2, "pq": 3, "hlg": 4, "gamma": 5}
-
-
-class Plane(C.Structure):
-    """jxlh_plane == RawImageBuffer."""
-    _fields_ = [("ptr", C.c_void_p), ("bytes_per_row", C.c_size_t), ("num_rows", C.c_size_t),
-                ("bytes_between_rows", C.c_size_t)]
-
-
-# patches (jxlh_frame_set_patches): PatchBlendMode values, ExtraChannelInfo flags
-PATCH_NONE, PATCH_REPLACE, PATCH_ADD, PATCH_MUL, PATCH_BLEND_ABOVE, PATCH_BLEND_BELOW, PATCH_AWA_ABOVE, PATCH_AWA_BELOW = range(8)
-EC_ALPHA = 1
-EC_ALPHA_ASSOCIATED = 2
-
-
-class Patch(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("x", "y", "ref_slot", "ref_x0", "ref_y0", "xsize", "ysize")]
-
-
-class PatchBlending(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("mode", "alpha_channel", "clamp")]
-
-
-class SplineSegment(C.Structure):
-    """jxlh_spline_segment."""
-    _fields_ = [("center_x", C.c_float), ("center_y", C.c_float), ("maximum_distance", C.c_float),
-                ("inv_sigma", C.c_float), ("sigma_over_4_times_intensity", C.c_float), ("color", C.c_float * 3)]
-
-
-class QuantizedSpline(C.Structure):
-    """jxlh_quantized_spline."""
-    _fields_ = [("control_points", C.c_void_p), ("n_points", C.c_uint32), ("color_dct", C.c_int32 * 96),
-                ("sigma_dct", C.c_int32 * 32), ("start_x", C.c_float), ("start_y", C.c_float)]
-
-
-# frame blending (jxlh_frame_blend): BlendingMode values
-BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = range(5)
-
-
-class BlendingInfo(C.Structure):
-    """jxlh_blending_info."""
-    _fields_ = [(n, C.c_uint32) for n in ("mode", "alpha_channel", "clamp", "source")]
-
-
-class BlendDesc(C.Structure):
-    """jxlh_blend_desc."""
-    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("image_w", C.c_uint32), ("image_h", C.c_uint32),
-                ("color", BlendingInfo), ("num_ec", C.c_uint32), ("ec", BlendingInfo * 8), ("ec_flags", C.c_uint32 * 8)]
+MODULAR_XYB = 1 << 16  # jxlh_frame_set_modular_channels: sample_format | MODULAR_XYB (a parenthesised #define)
+PATCH_AWA_ABOVE, PATCH_AWA_BELOW = PATCH_ALPHA_WEIGHTED_ADD_ABOVE, PATCH_ALPHA_WEIGHTED_ADD_BELOW
+TF = {"linear": TF_LINEAR, "srgb": TF_SRGB, "bt709": TF_BT709, "pq": TF_PQ, "hlg": TF_HLG, "gamma": TF_GAMMA}
 
 
 def blend_desc(x0, y0, image_w, image_h, color, ec=(), ec_flags=(), num_ec=None):
@@ -182,9 +36,7 @@ def blend_desc(x0, y0, image_w, image_h, color, ec=(), ec_flags=(), num_ec=None)
     return d
 
 
-# the save tail (jxlh_frame_save): sample formats
-SAVE_U8, SAVE_U16, SAVE_F16, SAVE_F32 = range(4)
-SAVE_SAMPLE_BYTES = {SAVE_U8: 1, SAVE_U16: 2, SAVE_F16: 2, SAVE_F32: 4}
+SAVE_SAMPLE_BYTES = {SAVE_U8: 1, SAVE_U16: 2, SAVE_F16: 2, SAVE_F32: 4}  # the save tail (jxlh_frame_save)
 
 
 def save_tile_layout(pixel_bytes):
@@ -197,18 +49,8 @@ def save_tile_layout(pixel_bytes):
     return c.value, r.value
 
 
-class SpotColor(C.Structure):
-    """jxlh_spot_color."""
-    _fields_ = [("ec", C.c_uint32), ("rgba", C.c_float * 4)]
-
-
-class SaveDesc(C.Structure):
-    """jxlh_save_desc."""
-    _fields_ = [("n_channels", C.c_uint32), ("channels", C.c_uint32 * 4), ("fill_opaque_alpha", C.c_uint32),
-                ("format", C.c_uint32), ("bit_depth", C.c_uint32), ("big_endian", C.c_uint32), ("orientation", C.c_uint32),
-                ("f16_clamp", C.c_uint32), ("f16_clamp_min", C.c_float), ("f16_clamp_max", C.c_float),
-                ("premultiply", C.c_uint32), ("premultiply_alpha_channel", C.c_uint32), ("n_spot", C.c_uint32),
-                ("spot", SpotColor * 8)]
+class SaveDesc(_abi.SaveDesc):
+    """jxlh_save_desc, with the sizes callers allocate by."""
 
     @property
     def samples_per_pixel(self):
@@ -244,33 +86,6 @@ def save_desc(channels, format=SAVE_U8, bit_depth=None, fill_opaque_alpha=False,
         for k in range(4):
             d.spot[i].rgba[k] = float(rgba[k])
     return d
-
-
-# group-local Modular transforms (jxlh_local_*)
-LOCAL_MAX_STEPS = 4
-LOCAL_MAX_CHANNELS = 4
-LOCAL_RCT, LOCAL_PALETTE = 0, 1
-
-
-class LocalStep(C.Structure):  # jxlh_local_step
-    _fields_ = [("kind", C.c_uint32), ("begin_c", C.c_uint32), ("rct_type", C.c_uint32), ("num_c", C.c_uint32),
-                ("num_colors", C.c_uint32), ("num_deltas", C.c_uint32), ("predictor", C.c_uint32),
-                ("palette_offset", C.c_uint64)]
-
-
-class LocalGroup(C.Structure):  # jxlh_local_group
-    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("n_channels", C.c_uint32),
-                ("n_steps", C.c_uint32), ("steps", LocalStep * LOCAL_MAX_STEPS), ("n_coded", C.c_uint32),
-                ("coded_offset", C.c_uint64 * LOCAL_MAX_CHANNELS), ("coded_stride", C.c_uint32)]
-
-
-class LocalOp(C.Structure):  # jxlh_local_op
-    _fields_ = [("kind", C.c_uint32), ("rct_op", C.c_uint32), ("n_slots", C.c_uint32), ("in_slot", C.c_uint32 * 3),
-                ("out_slot", C.c_uint32 * 4), ("num_colors", C.c_uint32), ("palette_offset", C.c_uint64)]
-
-
-class LocalProgram(C.Structure):  # jxlh_local_program
-    _fields_ = [("n_coded", C.c_uint32), ("coded_slot", C.c_uint32 * 4), ("n_ops", C.c_uint32), ("ops", LocalOp * 4)]
 
 
 def local_rct(begin_c, rct_type):
@@ -356,173 +171,7 @@ def load():
         raise ImportError(
             f"{LIB_PATH} is missing: build it with `make -C jxl_rs_amd/csrc` (or __graft_entry__.build()); "
             "there is no CPU fallback for the device path")
-    L = C.CDLL(LIB_PATH)
-    vp, i32, u32, sz, fp = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t, C.POINTER(C.c_float)
-    L.jxlh_default_frame_params.argtypes = [C.POINTER(FrameParams), u32, u32]
-    L.jxlh_ctx_create.argtypes = [i32, i32, C.POINTER(vp)]
-    L.jxlh_ctx_destroy.argtypes = [vp]
-    L.jxlh_ctx_destroy.restype = None
-    L.jxlh_status_string.argtypes = [i32]
-    L.jxlh_status_string.restype = C.c_char_p
-    L.jxlh_last_error.argtypes = [vp]
-    L.jxlh_last_error.restype = C.c_char_p
-    L.jxlh_alloc_pinned.argtypes = [vp, sz, C.POINTER(vp)]
-    L.jxlh_free_pinned.argtypes = [vp, vp]
-    L.jxlh_frame_begin.argtypes = [vp, C.POINTER(FrameParams)]
-    L.jxlh_frame_read_rgb8.argtypes = [vp, vp, u32, u32, u32, vp, sz]
-    L.jxlh_frame_read_rgb16.argtypes = [vp, vp, u32, u32, u32, vp, sz]
-    L.jxlh_frame_read_rgb8_async.argtypes = [vp, vp, u32, u32, u32, vp, sz]
-    L.jxlh_frame_read_output.argtypes = [vp, C.POINTER(OutputDesc), u32, u32, vp, sz]
-    L.jxlh_frame_read_output_async.argtypes = [vp, C.POINTER(OutputDesc), u32, u32, vp, sz]
-    L.jxlh_frame_read_ycbcr_rgb8.argtypes = [vp, u32, u32, u32, vp, sz]
-    L.jxlh_frame_read_ycbcr_rgb16.argtypes = [vp, u32, u32, u32, vp, sz]
-    L.jxlh_stage_chroma_upsample.argtypes = [vp, vp, vp, u32, u32, i32]
-    L.jxlh_stage_upsample.argtypes = [vp, i32, vp, vp, u32, u32]
-    L.jxlh_stage_noise_generate.argtypes = [vp, u32, u32, u32, u32, C.POINTER(vp)]
-    L.jxlh_stage_noise_convolve.argtypes = [vp, vp, vp, u32, u32]
-    L.jxlh_stage_noise_add.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), sz]
-    L.jxlh_set_upsampling_weights.argtypes = [vp, vp, vp, vp]
-    L.jxlh_selftest_recip.argtypes = [vp, u32, u32, C.POINTER(C.c_uint64)]
-    if hasattr(L, "jxlh_flow_profile"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_flow_profile.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64), i32]
-    if hasattr(L, "jxlh_frame_k1_counters"):
-        L.jxlh_frame_k1_counters.argtypes = [vp, vp, i32]
-    if hasattr(L, "jxlh_ctx_tune_placement"):
-        L.jxlh_ctx_tune_placement.argtypes = [vp, i32, vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    if hasattr(L, "jxlh_probe_placement"):
-        L.jxlh_probe_placement.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.jxlh_frame_set_dequant_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
-    L.jxlh_frame_set_lf_quantized.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, u32]
-    L.jxlh_frame_set_lf.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz]
-    L.jxlh_frame_set_hf_meta.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, vp, vp, sz]
-    if hasattr(L, "jxlh_frame_set_modular_channels"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_frame_set_modular_channels.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, sz, u32]
-    if hasattr(L, "jxlh_modular_local_lower"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        gp, u64, szp = C.POINTER(LocalGroup), C.c_uint64, C.POINTER(C.c_size_t)
-        L.jxlh_modular_local_lower.argtypes = [gp, sz, u32, u64, C.POINTER(LocalProgram), szp]
-        L.jxlh_modular_local_transforms.argtypes = [vp, vp, u64, gp, sz, u32, C.POINTER(vp), u32, u32, u32, sz, szp]
-        L.jxlh_frame_set_modular_groups.argtypes = [vp, vp, u64, gp, sz, u32, szp]
-        L.jxlh_frame_set_modular_groups_async.argtypes = [vp, vp, u64, gp, sz, u32, szp]
-    L.jxlh_submit_group.argtypes = [vp, i32, u32, vp, u32]
-    L.jxlh_slot_wait.argtypes = [vp, i32]
-    L.jxlh_submit_group_sparse.argtypes = [vp, i32, u32, vp, vp, vp, u32, u32]
-    L.jxlh_submit_groups_sparse.argtypes = [vp, i32, u32, vp, vp, vp, vp, u32, u32]
-    if hasattr(L, "jxlh_submit_groups_slots"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_submit_groups_sparse4.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, u32, u32]
-        L.jxlh_submit_groups_slots.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, u32, u32]
-    L.jxlh_submit_groups_sparse8.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, u32, u32]
-    L.jxlh_frame_coeff_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
-    L.jxlh_frame_run.argtypes = [vp, u32, u32]
-    L.jxlh_ctx_sync.argtypes = [vp]
-    if hasattr(L, "jxlh_slot_after"):
-        L.jxlh_slot_after.argtypes = [vp, i32, vp, i32]
-    if hasattr(L, "jxlh_ctx_mark"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_ctx_mark.argtypes = [vp, C.POINTER(u32)]
-        L.jxlh_ctx_wait_mark.argtypes = [vp, u32]
-    L.jxlh_frame_read_planes.argtypes = [vp, C.POINTER(Plane)]
-    L.jxlh_frame_read_planes_rect.argtypes = [vp, u32, u32, u32, u32, C.POINTER(Plane)]
-    L.jxlh_frame_read_planes_rect_async.argtypes = [vp, u32, u32, u32, u32, C.POINTER(Plane)]
-    L.jxlh_frame_device_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
-    L.jxlh_frame_read_lf.argtypes = [vp, vp, vp, vp, sz]
-    L.jxlh_timer_start.argtypes = [vp]
-    L.jxlh_timer_stop.argtypes = [vp, fp]
-    L.jxlh_kernel_timing_enable.argtypes = [vp, i32]
-    L.jxlh_kernel_timing_get.argtypes = [vp, i32, C.POINTER(C.c_char_p), fp, C.POINTER(i32)]
-    L.jxlh_kernel_timing_reset.argtypes = [vp]
-    L.jxlh_stage_gaborish.argtypes = [vp, vp, vp, u32, u32, sz, C.c_float, C.c_float]
-    L.jxlh_stage_epf.argtypes = [vp, i32, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32, sz, vp, sz]
-    L.jxlh_stage_lf_smooth.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32]
-    L.jxlh_stage_transform_to_pixels.argtypes = [vp, i32, u32, vp, vp, vp]
-    L.jxlh_rct.argtypes = [vp, vp, vp, vp, sz, i32, i32]
-    L.jxlh_palette.argtypes = [vp, vp, sz, vp, i32, sz, i32, i32, vp]
-    L.jxlh_palette_delta.argtypes = [vp, vp, u32, u32, vp, i32, i32, sz, i32, i32, i32, vp]
-    L.jxlh_unsqueeze_levels.argtypes = [vp, i32, i32, vp, C.POINTER(vp), sz, u32, u32, C.POINTER(vp), sz]
-    L.jxlh_unsqueeze_chain.argtypes = [vp, i32, i32, vp, C.POINTER(vp), sz, u32, u32, C.POINTER(vp), sz, i32, i32]
-    L.jxlh_palette_delta_wp.argtypes = [vp, vp, u32, u32, vp, i32, i32, sz, i32, i32, vp, vp]
-    L.jxlh_modular_to_rgb8.argtypes = [vp, C.POINTER(vp), sz, u32, u32, i32, i32, u32, vp, sz]
-    L.jxlh_modular_to_f32.argtypes = [vp, vp, sz, u32, vp]
-    L.jxlh_modular_xyb_to_f32.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
-    L.jxlh_unsqueeze.argtypes = [vp, i32, vp, sz, vp, sz, u32, u32, vp, sz]
-    L.jxlh_unsqueeze_rct.argtypes = [vp, i32, C.POINTER(vp), sz, C.POINTER(vp), sz, u32, u32, C.POINTER(vp), sz, i32, i32]
-    L.jxlh_smooth_unsqueeze.argtypes = [vp, i32, vp, sz, u32, u32, u32, u32, vp, sz, u32, u32]
-    L.jxlh_unsqueeze_planes.argtypes = [vp, i32, i32, C.POINTER(vp), sz, C.POINTER(vp), sz, u32, u32, C.POINTER(vp), sz]
-    L.jxlh_abi_version.restype = u32
-    L.jxlh_comm_unique_id.argtypes = [vp]
-    L.jxlh_comm_init.argtypes = [vp, vp, i32, i32]
-    L.jxlh_comm_init_local.argtypes = [C.POINTER(vp), i32]
-    L.jxlh_comm_destroy.argtypes = [vp]
-    L.jxlh_comm_band.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]
-    L.jxlh_frame_run_sharded.argtypes = [vp]
-    L.jxlh_frame_allgather.argtypes = [vp]
-    L.jxlh_frames_run_sharded_local.argtypes = [C.POINTER(vp), i32]
-    L.jxlh_frames_allgather_local.argtypes = [C.POINTER(vp), i32]
-    L.jxlh_comm_allgather.argtypes = [vp, vp, sz]
-    L.jxlh_probe_copy_bandwidth.argtypes = [vp, sz, i32, fp]
-    if hasattr(L, "jxlh_live_resources"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_live_resources.argtypes = [C.POINTER(C.c_uint64)]
-    if hasattr(L, "jxlh_frame_path"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_frame_path.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    if hasattr(L, "jxlh_frame_set_extra_channel"):
-        L.jxlh_frame_set_extra_channel.argtypes = [vp, u32, vp, sz, u32, u32, u32, u32]
-        L.jxlh_frame_read_extra_channel.argtypes = [vp, u32, C.POINTER(Plane)]
-    L.jxlh_frame_rerender_groups.argtypes = [vp, vp, u32]
-    L.jxlh_ctx_set_reference.argtypes = [vp, u32, u32, u32, u32, C.POINTER(vp), sz]
-    L.jxlh_frame_save_reference.argtypes = [vp, u32]
-    L.jxlh_ctx_clear_reference.argtypes = [vp, u32]
-    L.jxlh_frame_set_patches.argtypes = [vp, vp, u32, vp, u32, vp]
-    L.jxlh_stage_patches.argtypes = [vp, C.POINTER(vp), u32, u32, u32, sz]
-    if hasattr(L, "jxlh_frame_blend"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_frame_blend.argtypes = [vp, C.POINTER(BlendDesc), C.POINTER(OutputDesc)]
-        L.jxlh_stage_blend.argtypes = [vp, C.POINTER(BlendDesc), C.POINTER(vp), u32, u32, u32, sz, C.POINTER(vp), sz]
-    if hasattr(L, "jxlh_frame_save"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_frame_save.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), u32, u32, vp, sz]
-        L.jxlh_frame_save_async.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), u32, u32, vp, sz]
-        L.jxlh_stage_save.argtypes = [vp, C.POINTER(OutputDesc), C.POINTER(SaveDesc), C.POINTER(vp), u32, u32, u32, sz,
-                                      u32, u32, u32, u32, vp, sz]
-    if hasattr(L, "jxlh_lf_preview"):
-        L.jxlh_ctx_set_lf_frame.argtypes = [vp, u32, u32, u32, vp, vp, vp, sz]
-        L.jxlh_frame_save_lf.argtypes = [vp, u32]
-        L.jxlh_ctx_clear_lf_frame.argtypes = [vp, u32]
-        L.jxlh_frame_set_lf_from_slot.argtypes = [vp, u32]
-        for fn in (L.jxlh_lf_preview, L.jxlh_lf_preview_async):
-            fn.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, C.POINTER(OutputDesc), C.POINTER(SaveDesc), vp, sz]
-    if hasattr(L, "jxlh_frame_set_groups_lf_only"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_frame_set_groups_lf_only.argtypes = [vp, vp, u32]
-    if hasattr(L, "jxlh_frame_set_splines"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_frame_set_splines.argtypes = [vp, vp, u32]
-        L.jxlh_stage_splines.argtypes = [vp, C.POINTER(vp), u32, u32, sz]
-        L.jxlh_splines_build_segments.argtypes = [vp, u32, i32, C.c_float, C.c_float, C.c_uint64, C.c_uint64, u32, vp,
-                                                  sz, C.POINTER(sz)]
-        L.jxlh_splines_set_batch_budget.argtypes = [vp, C.c_uint64]
-        L.jxlh_splines_bin_layout.argtypes = [C.POINTER(u32), C.POINTER(u32)]
-    L.jxlh_comm_allgather_local.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), sz]
-    L.jxlh_palette_strided.argtypes = [vp, vp, sz, vp, i32, sz, i32, i32, vp, sz]
-    L.jxlh_modular_frame_filters.argtypes = [vp, C.POINTER(FrameParams), C.POINTER(vp), C.POINTER(vp), u32, u32, sz]
-    # host side of the slot-bucketed form (csrc/host_pack.hip): plain CPU code, no context
-    if hasattr(L, "jxlh_frame_allgather_output"):
-        L.jxlh_frame_allgather_output.argtypes = [vp, C.POINTER(OutputDesc), vp, sz]
-        L.jxlh_frames_allgather_output_local.argtypes = [C.POINTER(vp), i32, C.POINTER(OutputDesc), C.POINTER(vp), sz]
-    if hasattr(L, "jxlh_ctx_wait_stream"):
-        L.jxlh_ctx_wait_stream.argtypes = [vp, vp]
-        L.jxlh_ctx_wait_event.argtypes = [vp, vp]
-        L.jxlh_ctx_record_event.argtypes = [vp, vp]
-    if hasattr(L, "jxlh_host_pack_slots"):  # absent from older builds used in A/B runs (JXLH_LIBRARY)
-        L.jxlh_host_pack_slots.argtypes = [vp, u32, u32, vp, sz, vp, vp, vp, u32, C.POINTER(u32)]
-    if hasattr(L, "jxlh_host_pack_slots_many"):
-        L.jxlh_host_pack_slots_many.argtypes = [vp, vp, u32, u32, vp, sz, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(sz)]
-        L.jxlh_slot_writer_create.argtypes = [C.POINTER(vp)]
-        L.jxlh_slot_writer_destroy.argtypes = [vp]
-        L.jxlh_slot_writer_destroy.restype = None
-        L.jxlh_slot_writer_begin_group.argtypes = [vp, u32, u32, vp, sz, vp, vp, u32]
-        L.jxlh_slot_writer_begin_varblock.argtypes = [vp, u32, u32]
-        L.jxlh_slot_writer_add.argtypes = [vp, u32, u32, i32]
-        L.jxlh_slot_writer_add_many.argtypes = [vp, u32, vp, vp, sz]
-        L.jxlh_slot_writer_end_group.argtypes = [vp, vp, C.POINTER(u32)]
-    for name in ("jxlh_covered_blocks_x", "jxlh_covered_blocks_y", "jxlh_quant_table_for_type",
-                 "jxlh_quant_table_size"):
-        getattr(L, name).argtypes = [i32]
-        getattr(L, name).restype = i32
-    return L
+    return _abi.bind(C.CDLL(LIB_PATH))
 
 
 def splines_bin_layout():
@@ -868,11 +517,6 @@ def _rect_planes(arrs, dtype, w, h, stride):
     if not (w is None and h is None and stride is None):
         raise ValueError("w, h and stride of host arrays come from the arrays themselves")
     return _rect_planes_mixed(arrs, (dtype,) * len(arrs))
-
-
-class SqueezeLevel(C.Structure):  # jxlh_squeeze_level
-    _fields_ = [("horizontal", C.c_int32), ("out_w", C.c_uint32), ("out_h", C.c_uint32), ("res", C.c_void_p * 3),
-                ("res_stride", C.c_size_t)]
 
 
 class Context:
@@ -1513,8 +1157,7 @@ class Context:
         d = OutputDesc()
         d.color, d.transfer, d.bits, d.channels, d.tf_param = color, TF[transfer], bits, channels, tf_param
         if xyb_params is not None:
-            for i, v in enumerate(np.asarray(xyb_params, dtype=np.float32).ravel()):
-                d.xyb[i] = float(v)
+            d.xyb = XybParams.from_buffer_copy(np.ascontiguousarray(xyb_params, dtype=np.float32))
         for i in range(3):
             d.hlg_luminance_rgb[i] = lum[i]
         return d

@@ -1,6 +1,31 @@
 """Shared helpers for the parity tests: run the same workload through the CPU oracle and
 through the HIP path (via the C ABI), and forward-squeeze for round-trip properties."""
+import os
+import subprocess
+
 import numpy as np
+
+
+def c_struct_layouts(tmp_path, structs):
+    """What the C compiler lays out for structs of include/jxl_hip.h.  structs: {C name: [field names]}; returns
+    {(C name, "size"): sizeof, (C name, field): offsetof, (C name, field + ".size"): the field's sizeof}.  The yardstick of the generated bindings' layout tests."""
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "jxl_hip.h"', "int main(void) {"]
+    for n, fields in structs.items():
+        lines.append(f'  printf("{n} size %zu\\n", sizeof({n}));')
+        for f in fields:
+            lines.append(f'  printf("{n} {f} %zu\\n", offsetof({n}, {f}));')
+            lines.append(f'  printf("{n} {f}.size %zu\\n", sizeof((({n}*)0)->{f}));')
+    lines +=["  return 0;", "}"]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    subprocess.run(["gcc", "-std=c99", "-I", include, str(src), "-o", str(exe)], check=True)
+    got = {}
+    for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
+        n, f, v = ln.split()
+        got[(n, f)] = int(v)
+    return got
 
 
 def _set_shifts(p, wl):

@@ -1668,8 +1668,7 @@ def test_rgb8_async_read_equals_blocking_read(ctx, oracle, kat):
     want16 = ctx.read_output(lib.COLOR_XYB, "pq", params, 4000.0, bits=16, channels=3)
     d = lib.OutputDesc()
     d.color, d.transfer, d.bits, d.channels, d.tf_param = lib.COLOR_XYB, lib.TF["pq"], 16, 3, 4000.0
-    for i, v in enumerate(np.asarray(params, dtype=np.float32).ravel()):
-        d.xyb[i] = float(v)
+    d.xyb = lib.XybParams.from_buffer_copy(pr)  # the header's jxlh_xyb_params: the 16 floats of `params`
     pinned16, addr16 = ctx.alloc_pinned(w * h * 3 * 2)
     ctx._chk(ctx.L.jxlh_frame_read_output_async(ctx._ctx, C.byref(d), 0, h, C.c_void_p(addr16), w * 3 * 2),
              "frame_read_output_async")

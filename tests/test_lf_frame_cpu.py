@@ -29,13 +29,14 @@ def test_symbols_are_exported_and_bound():
 
 
 def c_to_ctypes(param):
-    """the ctypes type lib.py should bind a C parameter declaration with"""
+    """the ctypes type lib.py should bind a C parameter declaration with; a pointer to a struct of the header is bound
+    as lib.StructPtr(that struct) and stands here as ("struct*", that struct)"""
     p = param.strip()
     if "*" in p:
         if re.match(r"const jxlh_output_desc\s*\*", p):
-            return C.POINTER(lib.OutputDesc)
+            return "struct*", lib.OutputDesc
         if re.match(r"const jxlh_save_desc\s*\*", p):
-            return C.POINTER(lib.SaveDesc)
+            return "struct*", lib.SaveDesc.__base__  # lib.SaveDesc adds two properties to the header's struct
         return C.c_void_p
     ty = p.rsplit(None, 1)[0]
     return {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "size_t": C.c_size_t}[ty]
@@ -48,7 +49,8 @@ def test_python_prototypes_agree_with_the_header():
         m = re.search(r"jxlh_status\s+" + n + r"\s*\(([^)]*)\)", src)
         assert m, n
         want = [c_to_ctypes(p) for p in m.group(1).split(",")]
-        assert list(getattr(L, n).argtypes) == want, n
+        got = [("struct*", t.struct) if isinstance(t, lib.StructPtr) else t for t in getattr(L, n).argtypes]
+        assert got == want, n
     assert re.search(r"#define\s+JXLH_NUM_LF_FRAMES\s+4\b", src) and lib.NUM_LF_FRAMES == 4
     # additions only: the ABI version and the parameter struct are what they were
     assert re.search(r"#define\s+JXLH_ABI_VERSION\s+6\b", src) and L.jxlh_abi_version() == 6

@@ -5,7 +5,6 @@ header's fields in the header's order; their sizes and offsets, computed with Ru
 the C compiler lays out; every exported symbol has a binding."""
 import os
 import re
-import subprocess
 import sys
 
 import pytest
@@ -54,20 +53,8 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
     structs = rust_structs(open(g.OUT).read())
     names = [n for n in structs if structs[n] and structs[n][0][0] != "_private"]
     assert {"jxlh_frame_params", "jxlh_output_desc", "jxlh_xyb_params", "jxlh_plane", "jxlh_coeff16", "jxlh_coeff32"} <= set(names)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "jxl_hip.h"', "int main(void) {"]
-    for n in names:
-        lines.append(f'  printf("{n} size %zu\\n", sizeof({n}));')
-        for f, _ in structs[n]:
-            lines.append(f'  printf("{n} {f} %zu\\n", offsetof({n}, {f}));')
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = {}
-    for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
-        n, f, v = ln.split()
-        got[(n, f)] = int(v)
+    from helpers import c_struct_layouts
+    got = c_struct_layouts(tmp_path, {n: [f for f, _ in structs[n]] for n in names})
     for n in names:
         size, _, offs = layout(structs[n], structs)
         assert got[(n, "size")] == size, n
