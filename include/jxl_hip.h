@@ -1201,6 +1201,10 @@ jxlh_status jxlh_smooth_unsqueeze(jxlh_ctx* ctx, int32_t kind, const int32_t* av
                                   uint32_t avg_h, uint32_t x0, uint32_t y0, int32_t* out, size_t out_stride,
                                   uint32_t out_w, uint32_t out_h);
 
+/* Progressive previews of a WHOLE squeeze transform in one call -- jxlh_unsqueeze_chain for an image whose finest
+ * residual channels have not arrived: jxlh_unsqueeze_chain_preview and jxlh_squeeze_preview_kinds, declared in
+ * jxl_hip_preview.h, which this header includes at its end. */
+
 /* ---------------------------------------------------------------- multi-GPU
  * The reference renders a frame's groups on a pool of host threads and joins them in the pipeline's output buffers
  * (frame/render.rs:395-479).  Here a frame is cut into contiguous bands of group rows, one per GPU ("rank"):
@@ -1285,4 +1289,7 @@ int32_t jxlh_quant_table_size(int32_t table);
 #ifdef __cplusplus
 }
 #endif
+/* entry points added since ABI version 6 was recorded, in headers of their own: part of this interface all the same */
+#include "jxl_hip_preview.h"
+
 #endif /* JXL_HIP_H_ */

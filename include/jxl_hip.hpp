@@ -77,11 +77,47 @@ class Context {
   void stage_splines(float* const planes[3], uint32_t w, uint32_t h, size_t stride) {
     check(jxlh_stage_splines(c_, planes, w, h, stride), "jxlh_stage_splines");
   }
+  // the inverse of a whole squeeze transform on device planes (levels smallest first; base / out: one pointer per
+  // channel, 1..3), with the RCT that follows it fused into the last level (rct_op < 0: none): jxlh_unsqueeze_chain
+  void unsqueeze_chain(const std::vector<jxlh_squeeze_level>& levels, const std::vector<const int32_t*>& base, size_t base_stride,
+                       uint32_t base_w, uint32_t base_h, const std::vector<int32_t*>& out, size_t out_stride, int32_t rct_op = -1,
+                       int32_t rct_perm = 0) {
+    if (base.size() != out.size()) throw Error(JXLH_ERR_INVALID_ARGUMENT, "Context::unsqueeze_chain", "base and out planes differ in number");
+    check(jxlh_unsqueeze_chain(c_, (int32_t)base.size(), (int32_t)levels.size(), levels.data(), base.data(), base_stride, base_w,
+                               base_h, out.data(), out_stride, rct_op, rct_perm),
+          "jxlh_unsqueeze_chain");
+  }
+  // ... while the finest residual channels have not arrived: a level with res[] all null runs the reference's smooth step
+  // (SqueezeStepKind::Upsample1D / Upsample2D, transforms/step.rs:138-150).  nearest_even: the preview of an x86 reference
+  // build (JXLH_SMOOTH_CVT_NEAREST_EVEN)
+  void unsqueeze_chain_preview(const std::vector<jxlh_squeeze_level>& levels, const std::vector<const int32_t*>& base,
+                               size_t base_stride, uint32_t base_w, uint32_t base_h, const std::vector<int32_t*>& out,
+                               size_t out_stride, int32_t rct_op = -1, int32_t rct_perm = 0, bool nearest_even = false) {
+    if (base.size() != out.size())
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "Context::unsqueeze_chain_preview", "base and out planes differ in number");
+    check(jxlh_unsqueeze_chain_preview(c_, (int32_t)base.size(), (int32_t)levels.size(), levels.data(), base.data(), base_stride,
+                                       base_w, base_h, out.data(), out_stride, rct_op, rct_perm,
+                                       nearest_even ? (uint32_t)JXLH_SMOOTH_CVT_NEAREST_EVEN : 0u),
+          "jxlh_unsqueeze_chain_preview");
+  }
 
  private:
   jxlh_ctx* c_ = nullptr;
   int n_slots_ = 1;
 };
+
+// what each level of a preview chain runs (JXLH_PREVIEW_*) and whether the final planes depend on it: host only
+struct SqueezePreviewKinds {
+  std::vector<uint8_t> kinds, live;
+};
+inline SqueezePreviewKinds squeeze_preview_kinds(int n_planes, const std::vector<jxlh_squeeze_level>& levels, uint32_t base_w,
+                                                 uint32_t base_h) {
+  SqueezePreviewKinds r{std::vector<uint8_t>(levels.size()), std::vector<uint8_t>(levels.size())};
+  const jxlh_status st =
+      jxlh_squeeze_preview_kinds(n_planes, (int32_t)levels.size(), levels.data(), base_w, base_h, r.kinds.data(), r.live.data());
+  if (st != JXLH_OK) throw Error(st, "jxlh_squeeze_preview_kinds", "");
+  return r;
+}
 
 // One VarDCT frame on the device: the order of calls is the order of Frame's sections in the codestream.
 class VarDctFrame {

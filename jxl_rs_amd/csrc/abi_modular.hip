@@ -4,6 +4,7 @@
 #include <optional>
 
 #include "jxlh_ctx.h"
+#include "squeeze_preview_plan.h"
 
 namespace {
 using namespace jxlh;
@@ -31,6 +32,61 @@ void issue_step(hipStream_t s, const SqueezeLaunch& L, const SqueezeStep& st, in
 }
 // JXLH_SEPARATE_RCT=1, JXLH_CHAIN_FLOW=0 (tests, A/B): read on every call
 bool env_is(const char* name, char v) { return getenv(name) && *getenv(name) == v; }
+// a planned chain (squeeze_plan.h) onto the context's stream; in.arena is the context's hook_i[0]
+jxlh_status issue_chain(jxlh_ctx* ctx, const SqueezeChainIn& in, const SqueezePlan& plan, int rct_op, int rct_perm) {
+  jxlh_status st;
+  const int n_planes = in.n_planes;
+  const jxlh_squeeze_level* levels = in.levels;
+  const int32_t* base[3];
+  for (int p = 0; p < n_planes; p++) base[p] = (const int32_t*)in.base[p];
+  if (plan.flow_words) {
+    if ((st = ensure(ctx, ctx->flow_words, plan.flow_words))) return st;
+    if (!ctx->host_flow_flag.p) {
+      // the error word lives in pinned host memory (device-visible under the same address): jxlh_ctx_sync AND
+      // jxlh_ctx_wait_mark read it without queueing a copy behind later work (ADVICE r05)
+      HIPCHK(ctx, ctx->host_flow_flag.alloc(1));
+      *ctx->host_flow_flag.p = 0;
+    }
+    if (ctx->flow_prof_on && (st = ensure(ctx, ctx->flow_prof, 11 * (size_t)kFlowMaxLevels))) return st;
+  }
+  ScopedKernelTimer t(ctx, "k6_unsqueeze_chain");
+  for (int k = 0; k < plan.n; k++) {
+    const SqueezeLaunch& L = plan.launch[k];
+    if (L.kind == SqueezeLaunch::kLevels) {
+      int32_t* dst[3];
+      for (int p = 0; p < n_planes; p++) dst[p] = (int32_t*)squeeze_plane_addr(in, plan.arena, L.dst, p);
+      launch_unsqueeze_levels(ctx->stream, n_planes, L.n_levels, levels, base, in.base_stride, in.base_w, in.base_h, dst, L.dst.stride);
+    } else if (L.kind == SqueezeLaunch::kFlow) {
+      SqueezeStep steps[kFlowRunCap];
+      SqueezeLoc a = L.src;
+      for (int n = 0; n < L.n_levels; n++) {  // every level of the run but its last writes its own plane set
+        const int j = L.level0 + n;
+        const SqueezeLoc d = n == L.n_levels - 1 ? L.dst : SqueezeLoc{j, plan.arena.stride[j]};
+        steps[n] = squeeze_level_step(in, plan.arena, j, a, d);
+        a = d;
+      }
+      launch_unsqueeze_flow(ctx->stream, L.n_levels, steps, plan.vec + L.level0, ctx->flow_words.p, ctx->host_flow_flag.p, 4.0f,
+                            ctx->flow_prof_on ? ctx->flow_prof.p : nullptr);
+      ctx->flow_prof_levels = L.n_levels;
+      ctx->flow_used = true;
+    } else {
+      issue_step(ctx->stream, L, squeeze_level_step(in, plan.arena, L.level0, L.src, L.dst), rct_op, rct_perm);
+    }
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return JXLH_OK;
+}
+// what the two chain calls plan from, once the arguments are checked and the arena is there
+SqueezeChainIn chain_in(jxlh_ctx* ctx, int n_planes, int n_levels, const jxlh_squeeze_level* levels, const int32_t* const base[],
+                        size_t base_stride, uint32_t base_w, uint32_t base_h, int32_t* const out[], size_t out_stride, bool with_rct) {
+  SqueezeChainIn in{n_planes, n_levels, levels, base_w, base_h, base_stride, out_stride, {}, {}, (uintptr_t)ctx->hook_i[0].p,
+                    with_rct, env_is("JXLH_SEPARATE_RCT", '1'), !env_is("JXLH_CHAIN_FLOW", '0')};
+  for (int p = 0; p < n_planes; p++) {
+    in.base[p] = (uintptr_t)base[p];
+    in.out[p] = (uintptr_t)out[p];
+  }
+  return in;
+}
 }  // namespace
 
 extern "C" {
@@ -317,46 +373,60 @@ jxlh_status jxlh_unsqueeze_chain(jxlh_ctx* ctx, int32_t n_planes, int32_t n_leve
   if ((st = check_squeeze_chain(n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, is_device_ptr)))
     return st;
   if ((st = ensure(ctx, ctx->hook_i[0], std::max<size_t>(squeeze_arena(n_planes, n_levels, levels).total, 1)))) return st;
-  SqueezeChainIn in{n_planes, n_levels, levels, base_w, base_h, base_stride, out_stride, {}, {}, (uintptr_t)ctx->hook_i[0].p,
-                    with_rct, env_is("JXLH_SEPARATE_RCT", '1'), !env_is("JXLH_CHAIN_FLOW", '0')};
-  for (int p = 0; p < n_planes; p++) {
-    in.base[p] = (uintptr_t)base[p];
-    in.out[p] = (uintptr_t)out[p];
-  }
-  const SqueezePlan plan = plan_squeeze_chain(in);
-  if (plan.flow_words) {
-    if ((st = ensure(ctx, ctx->flow_words, plan.flow_words))) return st;
-    if (!ctx->host_flow_flag.p) {
-      // the error word lives in pinned host memory (device-visible under the same address): jxlh_ctx_sync AND
-      // jxlh_ctx_wait_mark read it without queueing a copy behind later work (ADVICE r05)
-      HIPCHK(ctx, ctx->host_flow_flag.alloc(1));
-      *ctx->host_flow_flag.p = 0;
-    }
-    if (ctx->flow_prof_on && (st = ensure(ctx, ctx->flow_prof, 11 * (size_t)kFlowMaxLevels))) return st;
-  }
-  ScopedKernelTimer t(ctx, "k6_unsqueeze_chain");
+  const SqueezeChainIn in = chain_in(ctx, n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, with_rct);
+  return issue_chain(ctx, in, plan_squeeze_chain(in), rct_op, rct_perm);
+}
+
+jxlh_status jxlh_squeeze_preview_kinds(int32_t n_planes, int32_t n_levels, const jxlh_squeeze_level* levels, uint32_t base_w,
+                                       uint32_t base_h, uint8_t* kinds, uint8_t* live) {
+  if (!kinds) return JXLH_ERR_INVALID_ARGUMENT;
+  // the chain's geometry and NULL rules; no planes are named here, so every pointer passes for a device one
+  static const int32_t some = 0;
+  const int32_t* const base[3] = {&some, &some, &some};
+  int32_t* const out[3] = {const_cast<int32_t*>(&some), const_cast<int32_t*>(&some), const_cast<int32_t*>(&some)};
+  if (jxlh_status st = check_squeeze_chain(n_planes, n_levels, levels, base, base_w, base_w, base_h, out, (size_t)kMaxModularDim,
+                                           [](const void*) { return true; }, true))
+    return st;
+  squeeze_preview_kinds(n_planes, n_levels, levels, kinds, live);
+  return JXLH_OK;
+}
+
+// A progressive preview of a whole squeeze transform: validate, plan (squeeze_preview_plan.h), issue -- the regular
+// prefix as the chain it is, then one launch group per live level, in stream order.
+jxlh_status jxlh_unsqueeze_chain_preview(jxlh_ctx* ctx, int32_t n_planes, int32_t n_levels, const jxlh_squeeze_level* levels,
+                                         const int32_t* const base[], size_t base_stride, uint32_t base_w, uint32_t base_h,
+                                         int32_t* const out[], size_t out_stride, int32_t rct_op, int32_t rct_perm, uint32_t flags) {
+  JXLH_ON_DEVICE(ctx);
+  const bool with_rct = rct_op >= 0;
+  if (!ctx || (with_rct && (n_planes != 3 || rct_op > 6 || rct_perm < 0 || rct_perm > 5)) ||
+      (flags != 0 && flags != JXLH_SMOOTH_CVT_NEAREST_EVEN))
+    return JXLH_ERR_INVALID_ARGUMENT;
+  jxlh_status st;
+  if ((st = check_squeeze_chain(n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, is_device_ptr, true)))
+    return st;
+  if ((st = ensure(ctx, ctx->hook_i[0], std::max<size_t>(squeeze_arena(n_planes, n_levels, levels).total, 1)))) return st;
+  const SqueezeChainIn in = chain_in(ctx, n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, with_rct);
+  const SqueezePreviewPlan plan = plan_squeeze_preview(in);
+  if (plan.n_prefix > 0 && (st = issue_chain(ctx, plan.prefix_in, plan.prefix, rct_op, rct_perm))) return st;
+  if (plan.n == 0) return JXLH_OK;
+  ScopedKernelTimer t(ctx, "k6_unsqueeze_chain_preview");
   for (int k = 0; k < plan.n; k++) {
-    const SqueezeLaunch& L = plan.launch[k];
-    if (L.kind == SqueezeLaunch::kLevels) {
-      int32_t* dst[3];
-      for (int p = 0; p < n_planes; p++) dst[p] = (int32_t*)squeeze_plane_addr(in, plan.arena, L.dst, p);
-      launch_unsqueeze_levels(ctx->stream, n_planes, L.n_levels, levels, base, base_stride, base_w, base_h, dst, L.dst.stride);
-    } else if (L.kind == SqueezeLaunch::kFlow) {
-      SqueezeStep steps[kFlowRunCap];
-      SqueezeLoc a = L.src;
-      for (int n = 0; n < L.n_levels; n++) {  // every level of the run but its last writes its own plane set
-        const int j = L.level0 + n;
-        const SqueezeLoc d = n == L.n_levels - 1 ? L.dst : SqueezeLoc{j, plan.arena.stride[j]};
-        steps[n] = squeeze_level_step(in, plan.arena, j, a, d);
-        a = d;
-      }
-      launch_unsqueeze_flow(ctx->stream, L.n_levels, steps, plan.vec + L.level0, ctx->flow_words.p, ctx->host_flow_flag.p, 4.0f,
-                            ctx->flow_prof_on ? ctx->flow_prof.p : nullptr);
-      ctx->flow_prof_levels = L.n_levels;
-      ctx->flow_used = true;
-    } else {
-      issue_step(ctx->stream, L, squeeze_level_step(in, plan.arena, L.level0, L.src, L.dst), rct_op, rct_perm);
+    const PreviewEntry& e = plan.entry[k];
+    const jxlh_squeeze_level& lv = levels[e.level];
+    if (e.kind == JXLH_PREVIEW_REGULAR) {
+      const SqueezeStep step = squeeze_level_step(in, plan.arena, e.level, e.src, e.dst);
+      for (int j = 0; j < e.n_launch; j++) issue_step(ctx->stream, e.launch[j], step, rct_op, rct_perm);
+      continue;
     }
+    const int32_t* src[3] = {};
+    int32_t* dst[3] = {};
+    for (int p = 0; p < n_planes; p++) {
+      src[p] = (const int32_t*)squeeze_plane_addr(in, plan.arena, e.src, p);
+      dst[p] = (int32_t*)squeeze_plane_addr(in, plan.arena, e.dst, p);
+    }
+    const int kind = e.kind == JXLH_PREVIEW_SMOOTH_2D ? JXLH_SMOOTH_2D : lv.horizontal ? JXLH_SMOOTH_H : JXLH_SMOOTH_V;
+    launch_smooth_unsqueeze_planes(ctx->stream, kind, n_planes, src, e.src.stride, (int)e.src_w, (int)e.src_h, dst, e.dst.stride,
+                                   (int)lv.out_w, (int)lv.out_h, flags != 0, e.rct ? rct_op : -1, rct_perm);
   }
   HIPCHK(ctx, hipGetLastError());
   return JXLH_OK;

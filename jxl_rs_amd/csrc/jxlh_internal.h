@@ -441,6 +441,11 @@ void launch_unsqueeze_levels(hipStream_t s, int n_planes, int n_levels, const jx
 // smooth_{h,v,2d}_unsqueeze on a rectangle of the output channel; `in` is the whole average channel
 void launch_smooth_unsqueeze(hipStream_t s, int kind, const int32_t* in, size_t in_stride, int in_w, int in_h, int x0,
                              int y0, int32_t* out, size_t out_stride, int out_w, int out_h, bool cvt_rne);
+// ... on whole channels, n_planes (<= 3) planes of one geometry in one launch; op >= 0: three planes with the inverse
+// RCT (op, perm as launch_rct) applied in registers before the store
+void launch_smooth_unsqueeze_planes(hipStream_t s, int kind, int n_planes, const int32_t* const in[], size_t in_stride, int in_w,
+                                    int in_h, int32_t* const out[], size_t out_stride, int out_w, int out_h, bool cvt_rne, int op,
+                                    int perm);
 
 // patches stage (k_patches.hip): one patch as the kernel reads it (wave-uniform, scalar loads)
 struct PatchDev {

@@ -1,12 +1,15 @@
 // Smooth unsqueeze: what a squeeze step runs while its residual channel has not arrived (progressive previews;
 // transforms/step.rs:138-150 picks the kind, :841-851 dispatches): smooth_h / smooth_v / smooth_2d_unsqueeze
 // (squeeze.rs:908-1225).  A pure 5x5 stencil on the average channel -- unlike the regular step there is no
-// recurrence, so it is one thread per column of a 64 x 16 tile of average samples, walking four rows with a sliding window; the
-// tile's 68 x 20 window is staged through LDS once.
+// recurrence, so it is one thread per column of a 64 x 32 tile of average samples, walking eight rows with a sliding window; the
+// tile's 68 x 36 window is staged through LDS once.  Three kernels over one tile body: a rectangle of one plane
+// (jxlh_smooth_unsqueeze), whole channels with the plane in blockIdx.z, and three channels with the inverse RCT applied
+// in registers (jxlh_unsqueeze_chain_preview).
 // Arithmetic order is the reference's (four partial sums of <= 4 FMAs from zero, (a + b) + (c + d), +-0.5,
 // truncating convert: the scalar / NEON / wasm as_i32; the x86 back-ends' cvtps rounds a second time, see
 // DESIGN.md 4).
 #include "jxlh_internal.h"
+#include "modular_ops_device.h"  // rct_op, rct_permute
 
 namespace jxlh {
 
@@ -70,81 +73,168 @@ __device__ __forceinline__ int32_t smooth_eval(const float (&n)[25]) {
 #define JXLH_SM_TX 64
 #define JXLH_SM_WAVES 4
 #define JXLH_SM_RPT 8                                 // consecutive rows one thread walks with a sliding window
-#define JXLH_SM_TY (JXLH_SM_WAVES * JXLH_SM_RPT)      // average rows per workgroup: 20 window rows for 16 (1.25x)
+#define JXLH_SM_TY (JXLH_SM_WAVES * JXLH_SM_RPT)      // average rows per workgroup: 36 window rows for 32 (1.125x)
 // KIND 0: horizontal (out = 2 in_x), 1: vertical, 2: both.  nx x ny = average samples the rectangle covers.
+// One workgroup's tile of NCH planes of one geometry: NCH == 1 is a plane on its own; NCH == 3 stages the three
+// channels' windows, a thread produces the same output samples of all three, and the inverse RCT (`op`, the planes of
+// `out` already permuted: out[k] receives w_k) runs on them in registers before the one store.
+// pair: base and stride keep every sample pair 8-byte aligned
+struct SmoothGeom {
+  size_t in_stride, out_stride;
+  int in_w, in_h, cx0, cy0, out_w, out_h, nx, ny;
+};
+__device__ __forceinline__ void smooth_rct(int op, int32_t& a, int32_t& b, int32_t& c) {
+  const int32_t v0 = a, v1 = b, v2 = c;
+  switch (op) {  // wave-uniform
+    case 0: break;
+    case 1: rct_op<1>(v0, v1, v2, a, b, c); break;
+    case 2: rct_op<2>(v0, v1, v2, a, b, c); break;
+    case 3: rct_op<3>(v0, v1, v2, a, b, c); break;
+    case 4: rct_op<4>(v0, v1, v2, a, b, c); break;
+    case 5: rct_op<5>(v0, v1, v2, a, b, c); break;
+    default: rct_op<6>(v0, v1, v2, a, b, c); break;
+  }
+}
+template <int KIND, bool RNE, int NCH>
+__device__ __forceinline__ void smooth_tile(float (&tile)[NCH][JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1], const int32_t* const (&in)[NCH],
+                                            int32_t* const (&out)[NCH], const SmoothGeom& g, bool pair, int op) {
+  const int tid = threadIdx.x;
+  const int bx = blockIdx.x * JXLH_SM_TX, by = blockIdx.y * JXLH_SM_TY;
+  // The window, (TY + 4) x (TX + 4) samples per plane, is fetched as a flat list, thread t taking samples t, t + 256, ...:
+  // no branch between the loads, so all of a thread's fetches are in flight before the first is written to LDS (one
+  // wave per row with lanes 0..3 fetching the extra columns under a branch waited for every load in turn).  The last
+  // round's surplus threads repeat the last sample.  Rows mirror ( -1 -> 0, h -> h - 1 ), columns clamp:
+  // load_row_to_scratch, step.rs:386-416
+  const int wave = __builtin_amdgcn_readfirstlane(tid / JXLH_SM_TX), lane = tid % JXLH_SM_TX;
+  constexpr int WIN_W = JXLH_SM_TX + 4, WIN_N = WIN_W * (JXLH_SM_TY + 4), NT = JXLH_SM_TX * JXLH_SM_WAVES;
+  constexpr int ROUNDS = (WIN_N + NT - 1) / NT;
+  int32_t fetched[ROUNDS][NCH];
+#pragma unroll
+  for (int i = 0; i < ROUNDS; i++) {
+    const int idx = min(tid + i * NT, WIN_N - 1), r = idx / WIN_W, c = idx - r * WIN_W;
+    int y = g.cy0 + by + r - 2;
+    y = g.in_h == 1 ? 0 : (y < 0 ? -y - 1 : (y >= g.in_h ? 2 * g.in_h - 1 - y : y));
+    y = min(max(y, 0), g.in_h - 1);  // only rows no live thread reads can still be outside
+    const int x = min(max(g.cx0 + bx + c - 2, 0), g.in_w - 1);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) fetched[i][ch] = in[ch][(size_t)y * g.in_stride + x];
+  }
+#pragma unroll
+  for (int i = 0; i < ROUNDS; i++) {
+    const int idx = min(tid + i * NT, WIN_N - 1), r = idx / WIN_W, c = idx - r * WIN_W;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) tile[ch][r][c] = (float)fetched[i][ch];
+  }
+  __syncthreads();
+  const int ix = bx + lane;
+  if (ix >= g.nx) return;
+  const bool both = 2 * ix + 1 < g.out_w;
+  float win[NCH][5][5];  // window rows; the first four are loaded once, then one new row per step
+#pragma unroll
+  for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+      for (int c = 0; c < 5; c++) win[ch][r][c] = tile[ch][wave * JXLH_SM_RPT + r][lane + c];
+#pragma unroll
+  for (int k = 0; k < JXLH_SM_RPT; k++) {
+    const int ly = wave * JXLH_SM_RPT + k, iy = by + ly;
+    if (iy >= g.ny) return;  // wave-uniform
+    // v[ch]: KIND 2: the 2 x 2 outputs row by row; KIND 0: the pair along x; KIND 1: the pair along y
+    int32_t v[NCH][KIND == 2 ? 4 : 2];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+#pragma unroll
+      for (int c = 0; c < 5; c++) win[ch][4][c] = tile[ch][ly + 4][lane + c];
+      float n[25];
+#pragma unroll
+      for (int r = 0; r < 5; r++)
+#pragma unroll
+        for (int c = 0; c < 5; c++) n[KIND == 1 ? 5 * c + r : 5 * r + c] = win[ch][r][c];
+      if constexpr (KIND == 2) {
+        v[ch][0] = smooth_eval<true, 0, RNE>(n);
+        v[ch][1] = smooth_eval<true, 1, RNE>(n);
+        v[ch][2] = smooth_eval<true, 2, RNE>(n);
+        v[ch][3] = smooth_eval<true, 3, RNE>(n);
+      } else {
+        v[ch][0] = smooth_eval<false, 0, RNE>(n);
+        v[ch][1] = smooth_eval<false, 1, RNE>(n);
+      }
+    }
+    if constexpr (NCH == 3) {
+#pragma unroll
+      for (int j = 0; j < (KIND == 2 ? 4 : 2); j++) smooth_rct(op, v[0][j], v[1][j], v[2][j]);
+    }
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+      if constexpr (KIND == 2) {
+        int32_t* p0 = out[ch] + (size_t)(2 * iy) * g.out_stride + 2 * ix;
+        if (pair && both) {
+          *(int2*)p0 = make_int2(v[ch][0], v[ch][1]);
+          if (2 * iy + 1 < g.out_h) *(int2*)(p0 + g.out_stride) = make_int2(v[ch][2], v[ch][3]);
+        } else {
+          p0[0] = v[ch][0];
+          if (both) p0[1] = v[ch][1];
+          if (2 * iy + 1 < g.out_h) {
+            p0[g.out_stride] = v[ch][2];
+            if (both) p0[g.out_stride + 1] = v[ch][3];
+          }
+        }
+      } else if constexpr (KIND == 0) {
+        int32_t* p = out[ch] + (size_t)iy * g.out_stride + 2 * ix;
+        if (pair && both) {
+          *(int2*)p = make_int2(v[ch][0], v[ch][1]);
+        } else {
+          p[0] = v[ch][0];
+          if (both) p[1] = v[ch][1];
+        }
+      } else {
+        int32_t* p = out[ch] + (size_t)(2 * iy) * g.out_stride + ix;
+        p[0] = v[ch][0];
+        if (2 * iy + 1 < g.out_h) p[g.out_stride] = v[ch][1];
+      }
+    }
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int c = 0; c < 5; c++) win[ch][r][c] = win[ch][r + 1][c];
+  }
+}
+
+// a rectangle of one plane (jxlh_smooth_unsqueeze)
 template <int KIND, bool PAIR, bool RNE>
 __global__ __launch_bounds__(JXLH_SM_TX* JXLH_SM_WAVES) void k6_smooth_unsqueeze(
     const int32_t* __restrict__ in, size_t in_stride, int in_w, int in_h, int cx0, int cy0, int32_t* __restrict__ out,
     size_t out_stride, int out_w, int out_h, int nx, int ny) {
-  __shared__ float tile[JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1];
-  const int tid = threadIdx.x;
-  const int bx = blockIdx.x * JXLH_SM_TX, by = blockIdx.y * JXLH_SM_TY;
-  // one wave per window row (row arithmetic is wave-uniform), lane = column; lanes 0..3 also fetch the 4 extra columns.
-  // rows mirror ( -1 -> 0, h -> h - 1 ), columns clamp: load_row_to_scratch, step.rs:386-416
-  const int wave = __builtin_amdgcn_readfirstlane(tid / JXLH_SM_TX), lane = tid % JXLH_SM_TX;
-  for (int r = wave; r < JXLH_SM_TY + 4; r += JXLH_SM_WAVES) {
-    int y = cy0 + by + r - 2;
-    y = in_h == 1 ? 0 : (y < 0 ? -y - 1 : (y >= in_h ? 2 * in_h - 1 - y : y));
-    y = min(max(y, 0), in_h - 1);  // only rows no live thread reads can still be outside
-    const int32_t* row = in + (size_t)y * in_stride;
-    const int x = cx0 + bx + lane - 2;
-    tile[r][lane] = (float)row[min(max(x, 0), in_w - 1)];
-    if (lane < 4) tile[r][JXLH_SM_TX + lane] = (float)row[min(max(x + JXLH_SM_TX, 0), in_w - 1)];
-  }
-  __syncthreads();
-  const int ix = bx + lane;
-  if (ix >= nx) return;
-  const bool both = 2 * ix + 1 < out_w;
-  float win[5][5];  // window rows; the first four are loaded once, then one new row per step
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-#pragma unroll
-    for (int c = 0; c < 5; c++) win[r][c] = tile[wave * JXLH_SM_RPT + r][lane + c];
-#pragma unroll
-  for (int k = 0; k < JXLH_SM_RPT; k++) {
-    const int ly = wave * JXLH_SM_RPT + k, iy = by + ly;
-    if (iy >= ny) return;  // wave-uniform
-#pragma unroll
-    for (int c = 0; c < 5; c++) win[4][c] = tile[ly + 4][lane + c];
-    float n[25];
-#pragma unroll
-    for (int r = 0; r < 5; r++)
-#pragma unroll
-      for (int c = 0; c < 5; c++) n[KIND == 1 ? 5 * c + r : 5 * r + c] = win[r][c];
-    if (KIND == 2) {
-      const int32_t o00 = smooth_eval<true, 0, RNE>(n), o01 = smooth_eval<true, 1, RNE>(n);
-      const int32_t o10 = smooth_eval<true, 2, RNE>(n), o11 = smooth_eval<true, 3, RNE>(n);
-      int32_t* p0 = out + (size_t)(2 * iy) * out_stride + 2 * ix;
-      if (PAIR && both) {  // PAIR: base and stride keep every sample pair 8-byte aligned
-        *(int2*)p0 = make_int2(o00, o01);
-        if (2 * iy + 1 < out_h) *(int2*)(p0 + out_stride) = make_int2(o10, o11);
-      } else {
-        p0[0] = o00;
-        if (both) p0[1] = o01;
-        if (2 * iy + 1 < out_h) {
-          p0[out_stride] = o10;
-          if (both) p0[out_stride + 1] = o11;
-        }
-      }
-    } else if (KIND == 0) {
-      int32_t* p = out + (size_t)iy * out_stride + 2 * ix;
-      const int32_t e = smooth_eval<false, 0, RNE>(n), o = smooth_eval<false, 1, RNE>(n);
-      if (PAIR && both) {
-        *(int2*)p = make_int2(e, o);
-      } else {
-        p[0] = e;
-        if (both) p[1] = o;
-      }
-    } else {
-      int32_t* p = out + (size_t)(2 * iy) * out_stride + ix;
-      p[0] = smooth_eval<false, 0, RNE>(n);
-      if (2 * iy + 1 < out_h) p[out_stride] = smooth_eval<false, 1, RNE>(n);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int c = 0; c < 5; c++) win[r][c] = win[r + 1][c];
-  }
+  __shared__ float tile[1][JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1];
+  const int32_t* const iv[1] = {in};
+  int32_t* const ov[1] = {out};
+  smooth_tile<KIND, RNE, 1>(tile, iv, ov, SmoothGeom{in_stride, out_stride, in_w, in_h, cx0, cy0, out_w, out_h, nx, ny}, PAIR, 0);
+}
+
+// whole channels of a preview chain (jxlh_unsqueeze_chain_preview): the plane in blockIdx.z
+struct SmoothPlanes {
+  const int32_t* in[3];
+  int32_t* out[3];
+};
+template <int KIND, bool RNE>
+__global__ __launch_bounds__(JXLH_SM_TX* JXLH_SM_WAVES) void k6_smooth_unsqueeze_planes(const SmoothPlanes pl, const SmoothGeom g,
+                                                                                         int pair) {
+  __shared__ float tile[1][JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1];
+  const int32_t* const iv[1] = {pl.in[blockIdx.z]};
+  int32_t* const ov[1] = {pl.out[blockIdx.z]};
+  smooth_tile<KIND, RNE, 1>(tile, iv, ov, g, pair != 0, 0);
+}
+// ... the last level with the RCT behind it: three planes, 3 x 36 x 69 floats of LDS
+template <int KIND, bool RNE>
+__global__ __launch_bounds__(JXLH_SM_TX* JXLH_SM_WAVES) void k6_smooth_unsqueeze_rct(const SmoothPlanes pl, const SmoothGeom g, int pair,
+                                                                                      int op) {
+  __shared__ float tile[3][JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1];
+  const int32_t* const iv[3] = {pl.in[0], pl.in[1], pl.in[2]};
+  int32_t* const ov[3] = {pl.out[0], pl.out[1], pl.out[2]};
+  smooth_tile<KIND, RNE, 3>(tile, iv, ov, g, pair != 0, op);
 }
 
 void launch_smooth_unsqueeze(hipStream_t s, int kind, const int32_t* in, size_t in_stride, int in_w, int in_h, int x0,
@@ -174,6 +264,39 @@ void launch_smooth_unsqueeze(hipStream_t s, int kind, const int32_t* in, size_t 
   }
 #undef JXLH_SM_LAUNCH
 #undef JXLH_SM_LAUNCH1
+}
+
+// whole channels: kind JXLH_SMOOTH_*; op < 0: n_planes (<= 3) planes on their own; else three planes + the inverse RCT
+void launch_smooth_unsqueeze_planes(hipStream_t s, int kind, int n_planes, const int32_t* const in[], size_t in_stride, int in_w,
+                                    int in_h, int32_t* const out[], size_t out_stride, int out_w, int out_h, bool cvt_rne, int op,
+                                    int perm) {
+  const bool fx = kind != 1, fy = kind != 0;
+  if ((fx ? out_w / 2 : out_w) == 0 || (fy ? out_h / 2 : out_h) == 0) return;
+  const SmoothGeom g{in_stride, out_stride, in_w, in_h, 0, 0, out_w, out_h, fx ? (out_w + 1) / 2 : out_w, fy ? (out_h + 1) / 2 : out_h};
+  SmoothPlanes pl{};
+  bool pair = out_stride % 2 == 0 && kind != 1;
+  for (int p = 0; p < n_planes; p++) {
+    pl.in[p] = in[p];
+    pl.out[p] = out[p];
+    pair = pair && (uintptr_t)out[p] % 8 == 0;
+  }
+  if (op >= 0) rct_permute<int32_t*>(perm, out[0], out[1], out[2], pl.out);  // which plane receives w0 / w1 / w2 (as k4_rct)
+  const dim3 grid((g.nx + JXLH_SM_TX - 1) / JXLH_SM_TX, (g.ny + JXLH_SM_TY - 1) / JXLH_SM_TY, op >= 0 ? 1 : n_planes);
+  const dim3 block(JXLH_SM_TX * JXLH_SM_WAVES);
+#define JXLH_SM_LAUNCH(K, R)                                                                                      \
+  do {                                                                                                            \
+    if (op >= 0) hipLaunchKernelGGL((k6_smooth_unsqueeze_rct<K, R>), grid, block, 0, s, pl, g, (int)pair, op);    \
+    else hipLaunchKernelGGL((k6_smooth_unsqueeze_planes<K, R>), grid, block, 0, s, pl, g, (int)pair);             \
+  } while (0)
+  switch (kind * 2 + (cvt_rne ? 1 : 0)) {
+    case 0: JXLH_SM_LAUNCH(0, false); break;
+    case 1: JXLH_SM_LAUNCH(0, true); break;
+    case 2: JXLH_SM_LAUNCH(1, false); break;
+    case 3: JXLH_SM_LAUNCH(1, true); break;
+    case 4: JXLH_SM_LAUNCH(2, false); break;
+    default: JXLH_SM_LAUNCH(2, true); break;
+  }
+#undef JXLH_SM_LAUNCH
 }
 
 }  // namespace jxlh

@@ -28,12 +28,22 @@ inline SqueezeExtents squeeze_extents(bool horizontal, uint32_t out_w, uint32_t 
   return {horizontal ? (out_w + 1) / 2 : out_w, horizontal ? out_h : (out_h + 1) / 2, rw, rh, (size_t)rw * rh > 0};
 }
 
+// a level whose residuals have not arrived (progressive previews, squeeze_preview_plan.h): it has residual samples and
+// names no plane of them
+inline bool squeeze_level_missing(int n_planes, const jxlh_squeeze_level& lv) {
+  if (!squeeze_extents(lv.horizontal != 0, lv.out_w, lv.out_h).has_res) return false;
+  for (int p = 0; p < n_planes; p++)
+    if (lv.res[p]) return false;
+  return true;
+}
+
 // ---- a chain's arguments: every level doubles (up to the odd sample) the axis it squeezes, starting from the base;
-// every plane that is read or written is a device pointer (is_dev)
+// every plane that is read or written is a device pointer (is_dev).  allow_missing: a level may leave out ALL its
+// residual planes (jxlh_unsqueeze_chain_preview); one that leaves out some is refused either way
 template <class IsDev>
 jxlh_status check_squeeze_chain(int n_planes, int n_levels, const jxlh_squeeze_level* levels, const int32_t* const base[],
                                 size_t base_stride, uint32_t base_w, uint32_t base_h, int32_t* const out[],
-                                size_t out_stride, IsDev is_dev) {
+                                size_t out_stride, IsDev is_dev, bool allow_missing = false) {
   if (!levels || !base || !out || n_planes < 1 || n_planes > 3 || n_levels < 1 || n_levels > kSqueezeMaxLevels ||
       base_w == 0 || base_h == 0 || base_stride < base_w)
     return JXLH_ERR_INVALID_ARGUMENT;
@@ -44,7 +54,8 @@ jxlh_status check_squeeze_chain(int n_planes, int n_levels, const jxlh_squeeze_l
       return JXLH_ERR_INVALID_ARGUMENT;
     const SqueezeExtents e = squeeze_extents(lv.horizontal != 0, lv.out_w, lv.out_h);
     if (e.avg_w != cw || e.avg_h != ch) return JXLH_ERR_INVALID_ARGUMENT;
-    for (int p = 0; p < n_planes; p++)
+    const bool missing = allow_missing && squeeze_level_missing(n_planes, lv);
+    for (int p = 0; p < n_planes && !missing; p++)
       if (e.has_res && (!lv.res[p] || !is_dev(lv.res[p]) || lv.res_stride < e.res_w)) return JXLH_ERR_INVALID_ARGUMENT;
     cw = lv.out_w;
     ch = lv.out_h;

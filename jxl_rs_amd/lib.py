@@ -211,6 +211,32 @@ def try_build_spline_segments(splines, quantization_adjustment, y_to_x_lf, y_to_
     return st, out
 
 
+def _squeeze_levels(levels, n_planes):
+    """[(horizontal, out_w, out_h, [res planes], res_stride)] as a jxlh_squeeze_level array; a level whose planes are
+    all None is a missing one (progressive previews)"""
+    arr = (SqueezeLevel * max(len(levels), 1))()
+    for i, (hz, ow, oh, res, rstride) in enumerate(levels):
+        arr[i].horizontal = 1 if hz else 0
+        arr[i].out_w, arr[i].out_h = ow, oh
+        for p in range(3):
+            arr[i].res[p] = _addr(res[p]).value if p < n_planes and p < len(res) and res[p] is not None else None
+        arr[i].res_stride = rstride
+    return arr
+
+
+def squeeze_preview_kinds(levels, base_w, base_h, n_planes=1):
+    """jxlh_squeeze_preview_kinds (host only): what each level of a preview chain runs (PREVIEW_REGULAR / _SMOOTH_1D /
+    _SMOOTH_2D) and whether the final planes depend on it -> (kinds, live), two uint8 arrays.  levels as for
+    Context.unsqueeze_chain; any non-zero integer stands for a present plane."""
+    arr = _squeeze_levels(levels, n_planes)
+    kinds, live = np.zeros(max(len(levels), 1), np.uint8), np.zeros(max(len(levels), 1), np.uint8)
+    st = _lib().jxlh_squeeze_preview_kinds(n_planes, len(levels), C.cast(arr, C.c_void_p), base_w, base_h, _addr(kinds),
+                                           _addr(live))
+    if st != OK:
+        raise JxlHipError(st, "squeeze_preview_kinds")
+    return kinds[:len(levels)], live[:len(levels)]
+
+
 WORKLIST_REGIONS = 42  # jxlh_worklist_layout: counters, 11 class lists, 9 + 9 + 9 DCT-class regions, fb_any, units, LLF
 
 
@@ -1442,6 +1468,22 @@ class Context:
         op, perm = rct if rct is not None else (-1, 0)
         self._chk(self.L.jxlh_unsqueeze_chain(self._ctx, n_planes, len(levels), C.cast(arr, C.c_void_p), bv, base_stride,
                                               base_w, base_h, ov, out_stride, op, perm), "unsqueeze_chain")
+
+    def unsqueeze_chain_preview(self, levels, base, base_stride, base_w, base_h, out, out_stride, rct=None, cvt_rne=False,
+                                flags=None):
+        """A progressive preview of a whole squeeze transform in one call (jxlh_unsqueeze_chain_preview): arguments as
+        unsqueeze_chain; a level whose residual planes are all None has not arrived and runs the reference's smooth
+        step (squeeze_preview_kinds says which).  cvt_rne: the x86 reference builds' float-to-int conversion."""
+        n_planes = len(base)
+        arr = _squeeze_levels(levels, n_planes)
+        bv = (C.c_void_p * n_planes)(*[_addr(a).value for a in base])
+        ov = (C.c_void_p * n_planes)(*[_addr(a).value for a in out])
+        op, perm = rct if rct is not None else (-1, 0)
+        if flags is None:
+            flags = self.SMOOTH_CVT_NEAREST_EVEN if cvt_rne else 0
+        self._chk(self.L.jxlh_unsqueeze_chain_preview(self._ctx, n_planes, len(levels), C.cast(arr, C.c_void_p), bv,
+                                                      base_stride, base_w, base_h, ov, out_stride, op, perm, flags),
+                  "unsqueeze_chain_preview")
 
     def unsqueeze_rct(self, horizontal, avg, res, out, out_w, out_h, avg_stride, res_stride, out_stride, op, perm):
         """Unsqueeze of three device-resident planes fused with the inverse RCT on them."""

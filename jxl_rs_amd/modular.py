@@ -41,6 +41,16 @@ class ModularChain:
         self.ctx.unsqueeze_chain(self.levels, [d.ptr for d in self.d_base], self.base_w, self.base_w, self.base_h,
                                  [d.ptr for d in self.d_out], self.w, rct=self.rct)
 
+    def preview(self, missing_from_level, cvt_rne=False):
+        """the progressive preview with the residuals of levels [missing_from_level, end) not arrived yet: one
+        jxlh_unsqueeze_chain_preview call (smooth steps for the missing levels, the RCT fused into the last one),
+        asynchronous.  Returns the three device planes (w x h, stride w): what set_modular_channels / feed_frame take."""
+        levels = [(hz, ow, oh, res if i < missing_from_level else [None] * len(res), rs)
+                  for i, (hz, ow, oh, res, rs) in enumerate(self.levels)]
+        self.ctx.unsqueeze_chain_preview(levels, [d.ptr for d in self.d_base], self.base_w, self.base_w, self.base_h,
+                                         [d.ptr for d in self.d_out], self.w, rct=self.rct, cvt_rne=cvt_rne)
+        return self.d_out
+
     # ---- BASELINE configs[3] across GPUs: "Squeeze + RCT + Palette, group shard + all-gather".  The squeeze
     # recurrence is serial along whole lines (DESIGN.md section 6: replicas only), so every rank runs the chain; the
     # per-sample transforms behind it are sharded -- rank r runs the RCT in place on ITS share of the chain's output
