@@ -71,16 +71,16 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !d) return JXLH_ERR_INVALID_ARGUMENT;
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
-  if (!ctx->in_frame || !ctx->rendered || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.rendered || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   if (jxlh_status st = check_desc(ctx, d)) return st;
   BlendLaunch a{};
   if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
   // the frame's own planes: the render's result, also when an earlier composition has taken its place
   const bool again = blended(ctx);
   float* fr[3];
-  for (int c = 0; c < 3; c++) fr[c] = again ? ctx->blend_frame[c] : ctx->result[c];
-  const int fw = again ? ctx->blend_fw : ctx->res_w, fh = again ? ctx->blend_fh : ctx->res_h;
-  const size_t fstride = again ? ctx->blend_fstride : ctx->res_stride;
+  for (int c = 0; c < 3; c++) fr[c] = again ? ctx->frame.blend_frame[c] : ctx->frame.result[c];
+  const int fw = again ? ctx->frame.blend_fw : ctx->res_w, fh = again ? ctx->frame.blend_fh : ctx->res_h;
+  const size_t fstride = again ? ctx->frame.blend_fstride : ctx->res_stride;
   if (!sides_ok(d, (uint32_t)fw, (uint32_t)fh)) return JXLH_ERR_UNSUPPORTED;
   // the extra channels handed over: 0 .. nec - 1, converted, at the frame's size (as jxlh_frame_save_reference)
   uint32_t nec = 0;
@@ -109,7 +109,7 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
   }
   const size_t ostride = round_up(d->image_w, 64), plane = ostride * d->image_h;
   if (again && ctx->blend_canvas.n < plane * (3 + nec)) {  // the canvas is about to be replaced: un-blend first
-    for (int c = 0; c < 3; c++) ctx->result[c] = fr[c];
+    for (int c = 0; c < 3; c++) ctx->frame.result[c] = fr[c];
     ctx->res_w = fw;
     ctx->res_h = fh;
     ctx->res_stride = fstride;
@@ -123,13 +123,13 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
   }
   HIPCHK(ctx, hipGetLastError());
   for (int c = 0; c < 3; c++) {
-    ctx->blend_frame[c] = fr[c];
-    ctx->result[c] = a.out[c];
+    ctx->frame.blend_frame[c] = fr[c];
+    ctx->frame.result[c] = a.out[c];
   }
-  ctx->blend_fw = fw;
-  ctx->blend_fh = fh;
-  ctx->blend_fstride = fstride;
-  ctx->blend_nec = nec;
+  ctx->frame.blend_fw = fw;
+  ctx->frame.blend_fh = fh;
+  ctx->frame.blend_fstride = fstride;
+  ctx->frame.blend_nec = nec;
   ctx->res_w = (int)d->image_w;
   ctx->res_h = (int)d->image_h;
   ctx->res_stride = ostride;

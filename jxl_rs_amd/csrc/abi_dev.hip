@@ -74,9 +74,9 @@ jxlh_status jxlh_worklist_layout(int32_t xblocks, int32_t yblocks, uint64_t* out
 jxlh_status jxlh_frame_path(jxlh_ctx* ctx, int32_t* strip, int32_t* tiles, int32_t* tiles_by_class_kernels) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
-  if (strip) *strip = ctx->strip_ran ? 1 : 0;
+  if (strip) *strip = ctx->frame.strip_ran ? 1 : 0;
   int32_t n = 0, k = 0;
-  if (ctx->strip_ran && ctx->strip_mode.p) {
+  if (ctx->frame.strip_ran && ctx->strip_mode.p) {
     n = (int32_t)(strip_strips(ctx->fd) * strip_tile_rows(ctx->fd));
     std::vector<uint8_t> m((size_t)n);
     HIPCHK(ctx, hipMemcpyAsync(m.data(), ctx->strip_mode.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

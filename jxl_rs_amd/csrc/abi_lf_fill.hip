@@ -1,5 +1,5 @@
 // C ABI, groups whose HF has not arrived (jxl_hip.h "GROUPS WITHOUT HF"): jxlh_frame_set_groups_lf_only marks them, and
-// jxlh_frame_run / jxlh_frame_rerender_groups (abi_frame.hip) hand a marked group to the fill kernel (k_lf_fill.hip)
+// jxlh_frame_run / jxlh_frame_rerender_groups (frame_run.hip) hand a marked group to the fill kernel (k_lf_fill.hip)
 // instead of the transforms -- upsample_lf_group of the reference (frame/decode.rs:51-158, taken at :744-752).  The marks
 // live beside the coefficient epoch (CoeffEpoch::lf_only, under sp_mutex): a submission on any slot thread clears its
 // group's mark where it records the submission.

@@ -116,14 +116,14 @@ jxlh_status jxlh_frame_save_lf(jxlh_ctx* ctx, uint32_t slot) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || slot >= JXLH_NUM_LF_FRAMES) return JXLH_ERR_INVALID_ARGUMENT;
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;
-  if (!ctx->in_frame || !ctx->rendered || !ctx->result[0] || blended(ctx)) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.rendered || !ctx->frame.result[0] || blended(ctx)) return JXLH_ERR_BAD_STATE;
   materialise_chroma(ctx);
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
   jxlh_ctx::LfSlot& s = ctx->lf_slots[slot];
   size_t dstride;
   if (jxlh_status st = slot_reserve(ctx, s, w, h, &dstride)) return st;
   for (int c = 0; c < 3; c++)
-    HIPCHK(ctx, hipMemcpy2DAsync(s.buf.p + (size_t)c * dstride * h, dstride * sizeof(float), ctx->result[c],
+    HIPCHK(ctx, hipMemcpy2DAsync(s.buf.p + (size_t)c * dstride * h, dstride * sizeof(float), ctx->frame.result[c],
                                  ctx->res_stride * sizeof(float), (size_t)w * sizeof(float), h, hipMemcpyDeviceToDevice,
                                  ctx->stream));
   slot_commit(s, w, h, dstride);
@@ -144,7 +144,7 @@ jxlh_status jxlh_frame_set_lf_from_slot(jxlh_ctx* ctx, uint32_t slot) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || slot >= JXLH_NUM_LF_FRAMES) return JXLH_ERR_INVALID_ARGUMENT;
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;
-  if (!ctx->in_frame || ctx->modular || ctx->lf_from_caller) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || ctx->modular || ctx->frame.lf_from_caller) return JXLH_ERR_BAD_STATE;
   const FrameDev& f = ctx->fd;
   if (f.subsampled) return JXLH_ERR_UNSUPPORTED;  // size_blocks rounds past the LF frame's size
   const jxlh_ctx::LfSlot& s = ctx->lf_slots[slot];
@@ -153,8 +153,8 @@ jxlh_status jxlh_frame_set_lf_from_slot(jxlh_ctx* ctx, uint32_t slot) {
     HIPCHK(ctx, hipMemcpy2DAsync(ctx->lf_raw[c].p, (size_t)f.xblocks * sizeof(float), s.buf.p + (size_t)c * s.stride * s.h,
                                  s.stride * sizeof(float), (size_t)f.xblocks * sizeof(float), (size_t)f.yblocks,
                                  hipMemcpyDeviceToDevice, ctx->stream));
-  ctx->lf_from_slot = true;
-  ctx->lf_smoothed = false;
+  ctx->frame.lf_from_slot = true;
+  ctx->frame.lf_smoothed = false;
   for (int c = 0; c < 3; c++) ctx->fd.lf[c] = ctx->lf_raw[c].p;
   return JXLH_OK;
 }

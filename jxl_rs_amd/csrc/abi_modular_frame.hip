@@ -2,47 +2,40 @@
 // samples the inverse transforms left go in rect by rect (jxlh_frame_set_modular_channels); jxlh_frame_run takes a
 // band of them into the frame layout (k_modular_intake: the conversion stages that open the reference's render list,
 // frame/render.rs:554-563), and from there the frame is a VarDCT frame's: chroma upsampling, Gaborish / EPF with the
-// constant sigma of features/epf.rs:81-84, run_post_stages, and every call that reads ctx->result / ctx->extra.
+// constant sigma of features/epf.rs:81-84, run_post_stages, and every call that reads ctx->frame.result / ctx->extra.
 #include <algorithm>
 
 #include "jxlh_ctx.h"
 
 namespace jxlh_host {
 
-// jxlh_frame_begin of a Modular frame, behind the argument checks and the geometry (ctx->params, ctx->fd)
-jxlh_status modular_frame_begin(jxlh_ctx* ctx) {
+// jxlh_frame_begin's commit of a Modular frame, behind the plan, the per-frame state and the geometry (ctx->params,
+// ctx->fd): the buffers at the plan's sizes
+jxlh_status modular_frame_begin(jxlh_ctx* ctx, const FramePlan& pl) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
-  const size_t plane_elems = f.plane_stride * (size_t)f.yblocks * 8;
-  const size_t nblocks = (size_t)f.xblocks * f.yblocks;
   jxlh_status st;
   for (int c = 0; c < 3; c++) {
-    if ((st = ensure(ctx, ctx->planes[c], plane_elems)) != JXLH_OK) return st;
-    if ((st = ensure(ctx, ctx->tmp[c], plane_elems)) != JXLH_OK) return st;
-    // the samples take the coefficient buffer's place in the budget (12 B/px); rows at the planes' stride: 256-byte
-    // aligned, and sample (x, y) of a full-resolution channel sits where pixel (x, y) of its plane will
-    if ((st = ensure(ctx, ctx->mod_src[c], plane_elems)) != JXLH_OK) return st;
+    if ((st = ensure(ctx, ctx->planes[c], pl.planes_n)) != JXLH_OK) return st;
+    if ((st = ensure(ctx, ctx->tmp[c], pl.tmp_n)) != JXLH_OK) return st;
+    if ((st = ensure(ctx, ctx->mod_src[c], pl.mod_src_n)) != JXLH_OK) return st;
   }
-  if ((st = ensure(ctx, ctx->sigma, nblocks)) != JXLH_OK) return st;
+  if ((st = ensure(ctx, ctx->sigma, pl.sigma_n)) != JXLH_OK) return st;
   if ((st = ensure(ctx, ctx->error_flag, 1)) != JXLH_OK) return st;
   HIPCHK(ctx, hipMemsetAsync(ctx->error_flag.p, 0, sizeof(int), ctx->stream));
   // rows never set read as zero samples
   for (int c = 0; c < 3; c++)
-    HIPCHK(ctx, hipMemsetAsync(ctx->mod_src[c].p, 0, plane_elems * sizeof(int32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->mod_src[c].p, 0, pl.mod_src_n * sizeof(int32_t), ctx->stream));
   for (int c = 0; c < 3; c++) {
     f.planes[c] = ctx->planes[c].p;
     f.tmp[c] = ctx->tmp[c].p;
   }
-  f.scrap_off = (int)plane_elems;
   f.inv_sigma = ctx->sigma.p;
   f.tiled = 0;
   set_filter_params(f, p);
   // SigmaSource::Constant (features/epf.rs:81-84): one value for every block, once per frame
-  if (f.epf_iters > 0) launch_fill_f32(ctx->stream, ctx->sigma.p, nblocks, kInvSigmaNum / p.epf_sigma_for_modular);
+  if (f.epf_iters > 0) launch_fill_f32(ctx->stream, ctx->sigma.p, pl.sigma_n, kInvSigmaNum / p.epf_sigma_for_modular);
   HIPCHK(ctx, hipGetLastError());
-  ctx->mod_format = 0;
-  ctx->in_frame = true;
-  reset_frame_state(ctx);
   return JXLH_OK;
 }
 
@@ -54,12 +47,12 @@ jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group
   // (a band whose halo rows would undo the neighbouring band's finished rows is rendered whole: run_plan.h)
   const RunPlan plan = plan_run(run_inputs(ctx), (int)group_row0, (int)group_row1);
   f.tiled = plan.tiled ? 1 : 0;  // the intake writes raster planes
-  ctx->strip_ran = false;
-  ctx->chroma_lazy = plan.chroma_lazy;
+  ctx->frame.strip_ran = false;
+  ctx->frame.chroma_lazy = plan.chroma_lazy;
   const int ya = plan.intake_y0, yb = plan.intake_y1;
   {
     IntakeLaunch a{};
-    const uint32_t fmt = ctx->mod_format ? ctx->mod_format : 8u;  // (no rect was set: zero samples in any format)
+    const uint32_t fmt = ctx->frame.mod_format ? ctx->frame.mod_format : 8u;  // (no rect was set: zero samples in any format)
     const uint32_t depth = fmt & 0xffffu;
     a.form = (fmt & JXLH_MODULAR_XYB) ? kIntakeXyb : (depth >> 8) ? kIntakeFloat : kIntakeInt;
     a.bits = depth & 0xffu;
@@ -81,7 +74,7 @@ jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group
     launch_modular_intake(ctx->stream, a);
   }
   if (f.subsampled) run_chroma_upsample_rows(ctx, ya, yb);  // frame/render.rs:569-576, in front of the filters
-  if (plan.whole) ctx->rendered = true;
+  if (plan.whole) ctx->frame.rendered = true;
   return run_stages_rows(ctx, plan.stages, plan.y_lo, plan.y_hi, plan.whole);
 }
 
@@ -101,7 +94,7 @@ jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t
   // (the XYB form does not read the bit depth: it may be left out)
   if (!(xyb && depth == 0) && !bit_depth_ok(depth, 31)) return JXLH_ERR_INVALID_ARGUMENT;
   if (xyb && f.subsampled) return JXLH_ERR_INVALID_ARGUMENT;
-  if (ctx->mod_format && ctx->mod_format != sample_format) return JXLH_ERR_INVALID_ARGUMENT;
+  if (ctx->frame.mod_format && ctx->frame.mod_format != sample_format) return JXLH_ERR_INVALID_ARGUMENT;
   if ((uint64_t)x0 + w > (uint64_t)f.xsize || (uint64_t)y0 + h > (uint64_t)f.ysize) return JXLH_ERR_INVALID_ARGUMENT;
   int maxhs = 0, maxvs = 0;
   for (int c = 0; c < 3; c++) {
@@ -120,7 +113,7 @@ jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t
       return st;
   }
   JXLH_SYNC(ctx);  // like the other setters: the caller's buffers may be reused as soon as the call returns
-  ctx->mod_format = sample_format;
+  ctx->frame.mod_format = sample_format;
   return JXLH_OK;
 }
 

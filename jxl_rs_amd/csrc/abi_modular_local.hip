@@ -138,7 +138,7 @@ jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
   const bool xyb = (sample_format & JXLH_MODULAR_XYB) != 0;
   const uint32_t depth = sample_format & ~(uint32_t)JXLH_MODULAR_XYB;
   if (!(xyb && depth == 0) && !bit_depth_ok(depth, 31)) return JXLH_ERR_INVALID_ARGUMENT;
-  if (ctx->mod_format && ctx->mod_format != sample_format) return JXLH_ERR_INVALID_ARGUMENT;
+  if (ctx->frame.mod_format && ctx->frame.mod_format != sample_format) return JXLH_ERR_INVALID_ARGUMENT;
   LocalDest d;
   for (int c = 0; c < 3; c++) d.out[c] = ctx->mod_src[c].p;
   d.n_out = 3;
@@ -147,7 +147,7 @@ jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
   d.frame = true;
   // the palettes' bit depth is the samples' (a palette on 32-bit float samples is refused: no bit depth of 1..31)
   if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, depth & 0xffu, d, first_bad)) return st;
-  ctx->mod_format = sample_format;
+  ctx->frame.mod_format = sample_format;
   if (wait) JXLH_SYNC(ctx);
   return JXLH_OK;
 }

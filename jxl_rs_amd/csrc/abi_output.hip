@@ -32,7 +32,7 @@ jxlh_status read_output(jxlh_ctx* ctx, const jxlh_output_desc* d, uint32_t y0, u
   if (jxlh_status st = colour_stage(d, &a.mode, &a.xyb, &a.tf)) return st;
   const uint32_t channels = d->channels;
   if (!out || (channels != 3 && channels != 4)) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   if (y1 > (uint32_t)ctx->res_h) y1 = (uint32_t)ctx->res_h;
   const size_t bps = d->bits / 8, pb = channels * bps;
@@ -41,7 +41,7 @@ jxlh_status read_output(jxlh_ctx* ctx, const jxlh_output_desc* d, uint32_t y0, u
     return JXLH_ERR_INVALID_ARGUMENT;
   // the labels are the read-outs' names in jxlh_kernel_timing_get (tools and recorded profiles key on them), not kernels
   const OutRect r = {0, y0, (size_t)ctx->res_w, y1 - y0};
-  if (ctx->chroma_lazy && a.mode == kModeYcbcr) {
+  if (ctx->frame.chroma_lazy && a.mode == kModeYcbcr) {
     const SubPlanesDev sp = sub_planes_dev(ctx);
     return write_out(ctx, out, bytes_per_row, pb, r, "k_ycbcr_sub_to_rgb", wait, [&](uint8_t* origin, size_t pitch) {
       launch_ycbcr_sub_to_rgb(ctx->stream, sp, ctx->res_stride, ctx->res_w, (int)y0, (int)(y1 - y0), (int)channels,
@@ -50,7 +50,7 @@ jxlh_status read_output(jxlh_ctx* ctx, const jxlh_output_desc* d, uint32_t y0, u
   }
   if (d->bits == 8) {  // a kernel of its own: measured faster than the save's identity case at this depth
     materialise_chroma(ctx);
-    const float* planes[3] = {ctx->result[0], ctx->result[1], ctx->result[2]};
+    const float* planes[3] = {ctx->frame.result[0], ctx->frame.result[1], ctx->frame.result[2]};
     return write_out(ctx, out, bytes_per_row, pb, r, "k_xyb_to_rgb8", wait, [&](uint8_t* origin, size_t pitch) {
       launch_xyb_to_rgb8(ctx->stream, planes, ctx->res_stride, ctx->res_w, (int)y0, (int)(y1 - y0), a.mode, a.xyb, a.tf,
                          (int)channels, origin, pitch);
@@ -134,13 +134,13 @@ jxlh_status jxlh_frame_read_output_async(jxlh_ctx* ctx, const jxlh_output_desc* 
 jxlh_status jxlh_frame_read_planes(jxlh_ctx* ctx, const jxlh_plane out[3]) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !out) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   materialise_chroma(ctx);
   for (int c = 0; c < 3; c++) {
     if (!out[c].ptr || out[c].bytes_per_row < (size_t)ctx->res_w * sizeof(float) || out[c].num_rows < (size_t)ctx->res_h ||
         out[c].bytes_between_rows < out[c].bytes_per_row)
       return JXLH_ERR_INVALID_ARGUMENT;
-    jxlh_status st = copy2d(ctx, out[c].ptr, out[c].bytes_between_rows, ctx->result[c],
+    jxlh_status st = copy2d(ctx, out[c].ptr, out[c].bytes_between_rows, ctx->frame.result[c],
                             ctx->res_stride * sizeof(float), (size_t)ctx->res_w * sizeof(float), ctx->res_h, ctx->stream);
     if (st != JXLH_OK) return st;
   }
@@ -152,7 +152,7 @@ namespace {
 jxlh_status read_planes_rect(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const jxlh_plane out[3],
                              bool wait) {
   if (!ctx || !out || w == 0 || h == 0) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   if (x0 >= (uint32_t)ctx->res_w || y0 >= (uint32_t)ctx->res_h) return JXLH_ERR_INVALID_ARGUMENT;
   const size_t cw = std::min<size_t>(w, (size_t)ctx->res_w - x0), ch = std::min<size_t>(h, (size_t)ctx->res_h - y0);
   for (int c = 0; c < 3; c++)
@@ -161,7 +161,7 @@ jxlh_status read_planes_rect(jxlh_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w
       return JXLH_ERR_INVALID_ARGUMENT;
   materialise_chroma(ctx);
   for (int c = 0; c < 3; c++) {
-    const float* src = ctx->result[c] + (size_t)y0 * ctx->res_stride + x0;
+    const float* src = ctx->frame.result[c] + (size_t)y0 * ctx->res_stride + x0;
     if (jxlh_status st = copy2d(ctx, out[c].ptr, out[c].bytes_between_rows, src, ctx->res_stride * sizeof(float),
                                 cw * sizeof(float), ch, ctx->stream))
       return st;
@@ -184,9 +184,9 @@ jxlh_status jxlh_frame_read_planes_rect_async(jxlh_ctx* ctx, uint32_t x0, uint32
 jxlh_status jxlh_frame_device_planes(jxlh_ctx* ctx, float* planes[3], size_t* stride) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !planes) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   materialise_chroma(ctx);
-  for (int c = 0; c < 3; c++) planes[c] = ctx->result[c];
+  for (int c = 0; c < 3; c++) planes[c] = ctx->frame.result[c];
   if (stride) *stride = ctx->res_stride;
   return JXLH_OK;
 }

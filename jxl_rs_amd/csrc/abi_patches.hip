@@ -1,6 +1,6 @@
 // C ABI of the patches stage: the reference-frame slots of a context, the frame's patch dictionary (validated like
 // PatchesDictionary::read, jxl/src/features/patches.rs:362-620, and binned into tiles once), the stage hook, and the
-// piece of the frame pipeline that launches k_patches (run_post_stages, abi_frame.hip).
+// piece of the frame pipeline that launches k_patches (run_post_stages, frame_run.hip).
 #include <algorithm>
 
 #include "blend_device.h"
@@ -82,9 +82,9 @@ jxlh_status build_bins(jxlh_ctx* ctx, jxlh_ctx::PatchBins& b, int w, int h) {
 // the slots the dictionary reads still hold what it was checked against
 bool slots_ok(const jxlh_ctx* ctx) {
   for (int s = 0; s < JXLH_MAX_REFERENCE_FRAMES; s++) {
-    if (!(ctx->patch_slots_used >> s & 1u)) continue;
+    if (!(ctx->frame.patch_slots_used >> s & 1u)) continue;
     const jxlh_ctx::RefSlot& r = ctx->refs[s];
-    if (!r.set || r.n_channels != 3 + ctx->patch_nec || r.w < ctx->patch_need_w[s] || r.h < ctx->patch_need_h[s])
+    if (!r.set || r.n_channels != 3 + ctx->frame.patch_nec || r.w < ctx->frame.patch_need_w[s] || r.h < ctx->frame.patch_need_h[s])
       return false;
   }
   return true;
@@ -119,7 +119,7 @@ void launch_bins(jxlh_ctx* ctx, const jxlh_ctx::PatchBins& b, PatchLaunch& a, in
   a.tile0 = first;
   const uint32_t* tiles = b.dev.p;
   ScopedKernelTimer t(ctx, "k_patches");
-  launch_patches(ctx->stream, (int)ctx->patch_nec, a, last - first, tiles, tiles + b.ntiles, tiles + 2 * b.ntiles + 1,
+  launch_patches(ctx->stream, (int)ctx->frame.patch_nec, a, last - first, tiles, tiles + b.ntiles, tiles + 2 * b.ntiles + 1,
                  ctx->patch_desc.p);
 }
 
@@ -128,12 +128,12 @@ const float* ec_base(const jxlh_ctx::ExtraChannel& e) { return e.up > 1 ? e.out.
 }  // namespace
 
 jxlh_status patches_check_run(const jxlh_ctx* ctx) {
-  if (ctx->patch_n == 0) return JXLH_OK;
+  if (ctx->frame.patch_n == 0) return JXLH_OK;
   if (!slots_ok(ctx)) return JXLH_ERR_BAD_STATE;
   // the dictionary's extra channels are exactly the ones handed over, each covering the whole frame
   for (uint32_t i = 0; i < JXLH_MAX_EXTRA_CHANNELS; i++) {
     const jxlh_ctx::ExtraChannel& e = ctx->extra[i];
-    if (e.set != (i < ctx->patch_nec)) return JXLH_ERR_BAD_STATE;
+    if (e.set != (i < ctx->frame.patch_nec)) return JXLH_ERR_BAD_STATE;
     if (e.set && (std::min(e.w * e.up, (uint32_t)ctx->fd.xsize) != (uint32_t)ctx->fd.xsize ||
                   std::min(e.h * e.up, (uint32_t)ctx->fd.ysize) != (uint32_t)ctx->fd.ysize))
       return JXLH_ERR_BAD_STATE;
@@ -149,11 +149,11 @@ jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y
   a.h = ctx->fd.ysize;
   a.cy0 = y_lo;
   a.cy1 = y_hi;
-  a.ec_alpha = ctx->patch_ec_alpha;
-  a.ec_assoc = ctx->patch_ec_assoc;
+  a.ec_alpha = ctx->frame.patch_ec_alpha;
+  a.ec_assoc = ctx->frame.patch_ec_assoc;
   fill_refs(ctx, a);
-  const bool ec_rebuild = ctx->patch_nec > 0 && ctx->patch_ec_stale;
-  for (uint32_t i = 0; i < ctx->patch_nec; i++) {
+  const bool ec_rebuild = ctx->frame.patch_nec > 0 && ctx->frame.patch_ec_stale;
+  for (uint32_t i = 0; i < ctx->frame.patch_nec; i++) {
     jxlh_ctx::ExtraChannel& e = ctx->extra[i];
     const size_t n = e.out_stride * e.out_h;
     if (ec_rebuild) {  // the patched plane starts as a copy of the channel; the kernel writes the covered pixels
@@ -170,8 +170,8 @@ jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y
   launch_bins(ctx, ctx->patch_bins, a, r0, r1);
   HIPCHK(ctx, hipGetLastError());
   if (ec_rebuild) {
-    ctx->patch_ec_stale = false;
-    for (uint32_t i = 0; i < ctx->patch_nec; i++) ctx->extra[i].pat_ready = true;
+    ctx->frame.patch_ec_stale = false;
+    for (uint32_t i = 0; i < ctx->frame.patch_nec; i++) ctx->extra[i].pat_ready = true;
   }
   return JXLH_OK;
 }
@@ -208,12 +208,12 @@ jxlh_status jxlh_ctx_set_reference(jxlh_ctx* ctx, uint32_t slot, uint32_t n_chan
 jxlh_status jxlh_frame_save_reference(jxlh_ctx* ctx, uint32_t slot) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || slot >= JXLH_MAX_REFERENCE_FRAMES) return JXLH_ERR_INVALID_ARGUMENT;
-  if (!ctx->in_frame || !ctx->rendered || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.rendered || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   materialise_chroma(ctx);
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
   if (blended(ctx)) {  // the composed image (jxlh_frame_blend): the canvas has the slot's layout, one linear copy
     jxlh_ctx::RefSlot& r = ctx->refs[slot];
-    const uint32_t nch = 3 + ctx->blend_nec;
+    const uint32_t nch = 3 + ctx->frame.blend_nec;
     const size_t n = ctx->res_stride * h * nch;
     if (jxlh_status st = ensure(ctx, r.buf, n)) return st;
     HIPCHK(ctx, hipMemcpyAsync(r.buf.p, ctx->blend_canvas.p, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
@@ -242,7 +242,7 @@ jxlh_status jxlh_frame_save_reference(jxlh_ctx* ctx, uint32_t slot) {
     const float* src;
     size_t sstride;
     if (c < 3) {
-      src = ctx->result[c];
+      src = ctx->frame.result[c];
       sstride = ctx->res_stride;
     } else {
       const jxlh_ctx::ExtraChannel& e = ctx->extra[c - 3];
@@ -308,16 +308,16 @@ jxlh_status jxlh_frame_set_patches(jxlh_ctx* ctx, const jxlh_patch* patches, uin
     }
   }
   // checked: nothing below fails on the arguments
-  ctx->patch_n = 0;
-  ctx->patch_nec = 0;
-  ctx->patch_slots_used = 0;
-  ctx->patch_ec_stale = true;
+  ctx->frame.patch_n = 0;
+  ctx->frame.patch_nec = 0;
+  ctx->frame.patch_slots_used = 0;
+  ctx->frame.patch_ec_stale = true;
   for (auto& e : ctx->extra) e.pat_ready = false;
   ctx->patch_desc_host.clear();
   if (n == 0) return JXLH_OK;
   const uint32_t stride = 1 + num_ec;
   ctx->patch_desc_host.resize(n);
-  for (int s = 0; s < JXLH_MAX_REFERENCE_FRAMES; s++) ctx->patch_need_w[s] = ctx->patch_need_h[s] = 0;
+  for (int s = 0; s < JXLH_MAX_REFERENCE_FRAMES; s++) ctx->frame.patch_need_w[s] = ctx->frame.patch_need_h[s] = 0;
   for (uint32_t i = 0; i < n; i++) {
     const jxlh_patch& p = patches[i];
     PatchDev& d = ctx->patch_desc_host[i];
@@ -335,14 +335,14 @@ jxlh_status jxlh_frame_set_patches(jxlh_ctx* ctx, const jxlh_patch* patches, uin
       const uint32_t alpha = uses_alpha(b.mode) && num_ec > 1 ? b.alpha_channel : 0;
       d.blend[k] = pack_blending(b.mode, alpha, b.clamp != 0);
     }
-    ctx->patch_slots_used |= 1u << p.ref_slot;
-    ctx->patch_need_w[p.ref_slot] = std::max(ctx->patch_need_w[p.ref_slot], p.ref_x0 + p.xsize);
-    ctx->patch_need_h[p.ref_slot] = std::max(ctx->patch_need_h[p.ref_slot], p.ref_y0 + p.ysize);
+    ctx->frame.patch_slots_used |= 1u << p.ref_slot;
+    ctx->frame.patch_need_w[p.ref_slot] = std::max(ctx->frame.patch_need_w[p.ref_slot], p.ref_x0 + p.xsize);
+    ctx->frame.patch_need_h[p.ref_slot] = std::max(ctx->frame.patch_need_h[p.ref_slot], p.ref_y0 + p.ysize);
   }
-  ctx->patch_ec_alpha = ctx->patch_ec_assoc = 0;
+  ctx->frame.patch_ec_alpha = ctx->frame.patch_ec_assoc = 0;
   for (uint32_t k = 0; k < num_ec; k++) {
-    if (ec_flags[k] & JXLH_EC_ALPHA) ctx->patch_ec_alpha |= 1u << k;
-    if (ec_flags[k] & JXLH_EC_ALPHA_ASSOCIATED) ctx->patch_ec_assoc |= 1u << k;
+    if (ec_flags[k] & JXLH_EC_ALPHA) ctx->frame.patch_ec_alpha |= 1u << k;
+    if (ec_flags[k] & JXLH_EC_ALPHA_ASSOCIATED) ctx->frame.patch_ec_assoc |= 1u << k;
   }
   if (jxlh_status st = ensure(ctx, ctx->patch_desc, n)) return st;
   HIPCHK(ctx, hipMemcpyAsync(ctx->patch_desc.p, ctx->patch_desc_host.data(), n * sizeof(PatchDev),
@@ -350,8 +350,8 @@ jxlh_status jxlh_frame_set_patches(jxlh_ctx* ctx, const jxlh_patch* patches, uin
   if (jxlh_status st = build_bins(ctx, ctx->patch_bins, ctx->fd.xsize, ctx->fd.ysize)) return st;
   ctx->patch_hook_bins.w = ctx->patch_hook_bins.h = 0;  // (binned again for the next stage-hook size)
   JXLH_SYNC(ctx);  // the host copies may change with the next call
-  ctx->patch_n = n;
-  ctx->patch_nec = num_ec;
+  ctx->frame.patch_n = n;
+  ctx->frame.patch_nec = num_ec;
   return JXLH_OK;
 }
 
@@ -359,8 +359,8 @@ jxlh_status jxlh_stage_patches(jxlh_ctx* ctx, float* const planes[], uint32_t n_
                                size_t stride) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !planes || w == 0 || h == 0 || stride < w) return JXLH_ERR_INVALID_ARGUMENT;
-  if (ctx->patch_n == 0) return n_channels >= 3 ? JXLH_OK : JXLH_ERR_INVALID_ARGUMENT;
-  if (n_channels != 3 + ctx->patch_nec) return JXLH_ERR_INVALID_ARGUMENT;
+  if (ctx->frame.patch_n == 0) return n_channels >= 3 ? JXLH_OK : JXLH_ERR_INVALID_ARGUMENT;
+  if (n_channels != 3 + ctx->frame.patch_nec) return JXLH_ERR_INVALID_ARGUMENT;
   for (uint32_t c = 0; c < n_channels; c++)
     if (!planes[c]) return JXLH_ERR_INVALID_ARGUMENT;
   if ((uint64_t)stride * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
@@ -381,7 +381,7 @@ jxlh_status jxlh_stage_patches(jxlh_ctx* ctx, float* const planes[], uint32_t n_
   PatchLaunch a{};
   for (int c = 0; c < 3; c++) a.col[c] = hp + c * plane;
   a.col_stride = stride;
-  for (uint32_t i = 0; i < ctx->patch_nec; i++) {
+  for (uint32_t i = 0; i < ctx->frame.patch_nec; i++) {
     a.ec_in[i] = a.ec_out[i] = hp + (3 + i) * plane;
     a.ec_stride[i] = (uint32_t)stride;
   }
@@ -389,8 +389,8 @@ jxlh_status jxlh_stage_patches(jxlh_ctx* ctx, float* const planes[], uint32_t n_
   a.h = (int)h;
   a.cy0 = a.ey0 = 0;
   a.cy1 = a.ey1 = (int)h;
-  a.ec_alpha = ctx->patch_ec_alpha;
-  a.ec_assoc = ctx->patch_ec_assoc;
+  a.ec_alpha = ctx->frame.patch_ec_alpha;
+  a.ec_assoc = ctx->frame.patch_ec_assoc;
   fill_refs(ctx, a);
   launch_bins(ctx, *b, a, 0, (int)h);
   HIPCHK(ctx, hipGetLastError());

@@ -127,7 +127,7 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
   if (jxlh_status st = save_check_desc(d, 3 + JXLH_MAX_EXTRA_CHANNELS)) return st;
   SaveLaunch a{};
   if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
-  if (!ctx->in_frame || !ctx->result[0]) return JXLH_ERR_BAD_STATE;
+  if (!ctx->in_frame || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
   if (y1 > h) y1 = h;
@@ -143,7 +143,7 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
     const jxlh_ctx::ExtraChannel& e = ctx->extra[ec];
     if (!e.set || !e.done) return JXLH_ERR_BAD_STATE;
     if (blended(ctx)) {  // the composed channel, image-sized
-      if (ec >= ctx->blend_nec) return JXLH_ERR_BAD_STATE;
+      if (ec >= ctx->frame.blend_nec) return JXLH_ERR_BAD_STATE;
       ec_plane[ec] = ctx->blend_canvas.p + (size_t)(3 + ec) * ctx->res_stride * h;
       ec_stride[ec] = (uint32_t)ctx->res_stride;
       return JXLH_OK;
@@ -178,7 +178,7 @@ jxlh_status save_result_rows(jxlh_ctx* ctx, SaveLaunch& a, const jxlh_save_desc*
                              const char* label, bool wait) {
   materialise_chroma(ctx);
   fill_desc(
-      d, [&](uint32_t ch) { return ch < 3 ? (const float*)ctx->result[ch] : ec_plane[ch - 3]; },
+      d, [&](uint32_t ch) { return ch < 3 ? (const float*)ctx->frame.result[ch] : ec_plane[ch - 3]; },
       [&](uint32_t ch) { return ch < 3 ? (uint32_t)ctx->res_stride : ec_stride[ch - 3]; }, a);
   a.w = ctx->res_w;
   a.h = ctx->res_h;

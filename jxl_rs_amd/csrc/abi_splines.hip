@@ -1,6 +1,6 @@
 // C ABI of the splines stage: the frame's segments (bounds worked out and batches planned once per set call,
 // splines_host.h), the stage hook, the host-only builder from the bitstream's form, and the piece of the frame pipeline
-// that launches k_splines (run_post_stages, abi_frame.hip).
+// that launches k_splines (run_post_stages, frame_run.hip).
 #include <algorithm>
 
 #include "../../include/jxl_hip_dev.h"
@@ -13,17 +13,17 @@ namespace {
 // the batches of the current segments for a w x h plane
 void plan(jxlh_ctx* ctx, int w, int h) {
   if (ctx->spline_plan_w == w && ctx->spline_plan_h == h && !ctx->spline_first.empty()) return;
-  spline_plan_batches(ctx->spline_desc_host.data(), ctx->spline_n, w, h, ctx->spline_budget, ctx->spline_first);
+  spline_plan_batches(ctx->spline_desc_host.data(), ctx->frame.spline_n, w, h, ctx->spline_budget, ctx->spline_first);
   ctx->spline_plan_w = w;
   ctx->spline_plan_h = h;
-  ctx->spline_resident = -1;
+  ctx->frame.spline_resident = -1;
 }
 
 // batch b's bin list on the device.  A set that fits one batch keeps its list from call to call; with more batches each
 // one is binned and uploaded when its turn comes, so the device never holds more than one batch's entries.
 jxlh_status bins_on_device(jxlh_ctx* ctx, int b, int w, int h) {
-  if (ctx->spline_resident == b) return JXLH_OK;
-  ctx->spline_resident = -1;
+  if (ctx->frame.spline_resident == b) return JXLH_OK;
+  ctx->frame.spline_resident = -1;
   // (the list a queued launch reads is replaced in stream order; the host copy must outlive its upload)
   spline_build_bins(ctx->spline_desc_host.data(), ctx->spline_first[b], ctx->spline_first[b + 1], w, h, ctx->spline_bins);
   const std::vector<uint32_t>& words = ctx->spline_bins.words;
@@ -31,7 +31,7 @@ jxlh_status bins_on_device(jxlh_ctx* ctx, int b, int w, int h) {
   HIPCHK(ctx, hipMemcpyAsync(ctx->spline_bins_dev.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                              ctx->stream));
   JXLH_SYNC(ctx);
-  ctx->spline_resident = b;
+  ctx->frame.spline_resident = b;
   return JXLH_OK;
 }
 
@@ -40,7 +40,7 @@ jxlh_status bins_on_device(jxlh_ctx* ctx, int b, int w, int h) {
 jxlh_status run_splines(jxlh_ctx* ctx, float* const cur[3], size_t stride, int w, int h, int y_lo, int y_hi) {
   y_lo = std::max(0, y_lo);
   y_hi = std::min(h, y_hi);
-  if (ctx->spline_n == 0 || y_lo >= y_hi) return JXLH_OK;
+  if (ctx->frame.spline_n == 0 || y_lo >= y_hi) return JXLH_OK;
   plan(ctx, w, h);
   SplineLaunch a{};
   for (int c = 0; c < 3; c++) a.col[c] = cur[c];
@@ -75,9 +75,9 @@ jxlh_status jxlh_frame_set_splines(jxlh_ctx* ctx, const jxlh_spline_segment* seg
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
   if (n > 0 && !segments) return JXLH_ERR_INVALID_ARGUMENT;
-  ctx->spline_n = 0;
+  ctx->frame.spline_n = 0;
   ctx->spline_first.clear();
-  ctx->spline_resident = -1;
+  ctx->frame.spline_resident = -1;
   ctx->spline_desc_host.resize(n);
   if (n == 0) return JXLH_OK;
   for (uint32_t i = 0; i < n; i++) ctx->spline_desc_host[i] = spline_dev(segments[i]);
@@ -85,7 +85,7 @@ jxlh_status jxlh_frame_set_splines(jxlh_ctx* ctx, const jxlh_spline_segment* seg
   HIPCHK(ctx, hipMemcpyAsync(ctx->spline_desc.p, ctx->spline_desc_host.data(), n * sizeof(SplineDev),
                              hipMemcpyHostToDevice, ctx->stream));
   JXLH_SYNC(ctx);
-  ctx->spline_n = n;
+  ctx->frame.spline_n = n;
   // binned once per set call for the frame's size (a set of several batches: their ranges; the lists follow per draw)
   plan(ctx, ctx->fd.xsize, ctx->fd.ysize);
   if (ctx->spline_first.size() == 2) return bins_on_device(ctx, 0, ctx->fd.xsize, ctx->fd.ysize);
@@ -98,7 +98,7 @@ jxlh_status jxlh_stage_splines(jxlh_ctx* ctx, float* const planes[3], uint32_t w
   for (int c = 0; c < 3; c++)
     if (!planes[c]) return JXLH_ERR_INVALID_ARGUMENT;
   if ((uint64_t)stride * h >= (1ull << 31) || w >= kSplineMaxAxis || h >= kSplineMaxAxis) return JXLH_ERR_UNSUPPORTED;
-  if (ctx->spline_n == 0) return JXLH_OK;
+  if (ctx->frame.spline_n == 0) return JXLH_OK;
   // the rows' first w values travel; what lies beyond them is neither read nor written
   const size_t dstride = round_up(w, 64), plane = dstride * h;
   if (jxlh_status st = ensure(ctx, ctx->spline_hook, plane * 3)) return st;
@@ -142,7 +142,7 @@ jxlh_status jxlh_splines_set_batch_budget(jxlh_ctx* ctx, uint64_t entries) {
   if (!ctx) return JXLH_ERR_INVALID_ARGUMENT;
   ctx->spline_budget = entries ? entries : kSplineDefaultBudget;
   ctx->spline_first.clear();  // planned again by the next draw
-  ctx->spline_resident = -1;
+  ctx->frame.spline_resident = -1;
   return JXLH_OK;
 }
 

@@ -1,5 +1,5 @@
 // The coefficient epoch: the submissions between two jxlh_frame_run calls, the form the frame is resident in, and the
-// plan that takes the one to the other at the next run (abi_frame.hip: apply_coeff_epoch issues it).  Plain C++: the
+// plan that takes the one to the other at the next run (frame_run.hip: apply_coeff_epoch issues it).  Plain C++: the
 // planner is host logic, tested without a device (tests/cpp/coeff_epoch_plan.cc).
 #pragma once
 #include <algorithm>

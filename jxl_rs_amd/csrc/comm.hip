@@ -184,14 +184,11 @@ int comm_nranks(const jxlh_ctx* ctx) { return ctx->comm ? ctx->comm->nranks : 1;
 
 // contiguous bands: ceil(ygroups / nranks) group rows per rank; trailing ranks may own nothing
 static void band_of(int ygroups, int nranks, int rank, int* r0, int* r1) {
-  const int per = (ygroups + nranks - 1) / nranks;
+  const int per = rows_per_rank(ygroups, nranks);
   *r0 = std::min(rank * per, ygroups);
   *r1 = std::min((rank + 1) * per, ygroups);
 }
-int comm_rows_per_rank(const jxlh_ctx* ctx, int ygroups) {
-  const int n = comm_nranks(ctx);
-  return (ygroups + n - 1) / n;
-}
+int comm_rows_per_rank(const jxlh_ctx* ctx, int ygroups) { return rows_per_rank(ygroups, comm_nranks(ctx)); }
 
 // one block row (8 pixel rows) of plane c in the layout K1 just wrote: offset and length in floats
 static void block_row_span(const FrameDev& f, int by, size_t* off, size_t* count) {
@@ -379,7 +376,7 @@ jxlh_status jxlh_frame_run_sharded(jxlh_ctx* ctx) {
 // where the result lives) + the geometry the read-out stages use
 static void set_band_result(jxlh_ctx* ctx) {
   const FrameDev& f = ctx->fd;
-  for (int ch = 0; ch < 3; ch++) ctx->result[ch] = stage_list(ctx).result_in_tmp() ? f.tmp[ch] : f.planes[ch];
+  for (int ch = 0; ch < 3; ch++) ctx->frame.result[ch] = stage_list(ctx).result_in_tmp() ? f.tmp[ch] : f.planes[ch];
   ctx->res_w = f.xsize;
   ctx->res_h = f.ysize;
   ctx->res_stride = f.plane_stride;
@@ -398,7 +395,7 @@ jxlh_status jxlh_frame_allgather(jxlh_ctx* ctx) {
   c->last_op = "ncclAllGather of the finished planes (" + std::to_string(count * 4) + " bytes per rank and plane)";
   NCCLCHK(ctx, api, api->GroupStart());
   for (int ch = 0; ch < 3; ch++)
-    NCCLCHK_IN_GROUP(ctx, api, api->AllGather(ctx->result[ch] + (size_t)c->rank * count, ctx->result[ch], count, ncclFloat32, c->nccl, ctx->stream));
+    NCCLCHK_IN_GROUP(ctx, api, api->AllGather(ctx->frame.result[ch] + (size_t)c->rank * count, ctx->frame.result[ch], count, ncclFloat32, c->nccl, ctx->stream));
   NCCLCHK(ctx, api, api->GroupEnd());
   return JXLH_OK;
 }
@@ -582,7 +579,7 @@ jxlh_status jxlh_frames_allgather_local(jxlh_ctx* const peers[], int32_t n) {
       const size_t rows = (size_t)std::min(r1 * kGroupDim, f.ysize) - (size_t)r0 * kGroupDim;
       for (int c = 0; c < 3; c++) {
         const float* s = (which ? src->fd.tmp[c] : src->fd.planes[c]) + off;
-        HIPCHK(dst, hipMemcpyAsync(dst->result[c] + off, s, rows * f.plane_stride * sizeof(float), hipMemcpyDefault,
+        HIPCHK(dst, hipMemcpyAsync(dst->frame.result[c] + off, s, rows * f.plane_stride * sizeof(float), hipMemcpyDefault,
                                    dst->stream));
       }
     }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "device_owned.h"
+#include "frame_plan.h"
 #include "jxlh_internal.h"
 #include "run_plan.h"
 
@@ -52,6 +53,48 @@ namespace jxlh_host {
 struct Comm;  // comm.hip
 }
 
+// The per-frame state: every field that each jxlh_frame_begin must start from the same value, and only those --
+// `ctx->frame = FrameState{}` starts them (start_frame, abi_frame.hip, which also takes the steps that are no plain
+// value: the extra channels' flags, slots[].used, the host vectors, the coefficient epoch).  Resources and settings of
+// the context, what a begin takes from its parameters (params, fd, ngroups, modular, params_direct_ok) and decoder state
+// that outlives a frame (refs, lf_slots, the epoch's resident form, se_live, ...) are members of jxlh_ctx.
+struct FrameState {
+  uint32_t mod_format = 0;  // a Modular frame's sample format (0 = no rect set yet)
+  bool lf_smoothed = false;
+  // lf_from_slot: this frame's LF image is a copy of an LF slot (no K0b, no jxlh_frame_set_lf*); lf_from_caller: a
+  // jxlh_frame_set_lf* call has written into it
+  bool lf_from_slot = false, lf_from_caller = false;
+  bool rendered = false;                        // a full jxlh_frame_run has happened in this frame
+  bool has_special = false, has_large = false;  // transform families seen in the frame's maps (jxlh_frame_set_hf_meta)
+  // strip_all_closed: every rect of the transform map came from host memory and every varblock in it is a small DCT
+  // inside its 64x64 tile (jxlh_frame_set_hf_meta); strip_ran: the last jxlh_frame_run went through the strip kernel
+  // (`planes` then hold no unfiltered pixels)
+  bool strip_all_closed = true, strip_ran = false;
+  float* result[3] = {nullptr, nullptr, nullptr};  // the planes the last run left the frame in (res_w, res_h, res_stride)
+  // chroma-subsampled frame with nothing between the transforms and the output: the upsampling into planes[] is
+  // deferred until somebody asks for the planes (the YCbCr output calls read the sub-sampled channels directly);
+  // lazy_gr0 / 1: the group rows it is owed on (written whenever chroma_lazy is)
+  bool chroma_lazy = false;
+  int lazy_gr0 = 0, lazy_gr1 = 0;
+  // the patch dictionary (jxlh_frame_set_patches; the reference slots are not per frame).  patch_slots_used bit s: the
+  // dictionary reads slot s, up to patch_need_w / _h[s] of it; patch_ec_stale: the patched extra channels must be
+  // rebuilt from their base planes on all rows
+  uint32_t patch_n = 0, patch_nec = 0;  // 0 patches: no dictionary
+  uint32_t patch_ec_alpha = 0, patch_ec_assoc = 0;
+  uint32_t patch_need_w[JXLH_MAX_REFERENCE_FRAMES] = {}, patch_need_h[JXLH_MAX_REFERENCE_FRAMES] = {};
+  uint32_t patch_slots_used = 0;
+  bool patch_ec_stale = true;
+  // the splines (jxlh_frame_set_splines): segment count, and which batch's bin list the device holds (-1: none)
+  uint32_t spline_n = 0;
+  int spline_resident = -1;
+  // jxlh_frame_blend: while the frame's result points at the canvas (blended()), blend_frame / blend_f* keep the frame's
+  // own planes and geometry, blend_nec the canvas's extra channels
+  uint32_t blend_nec = 0;
+  float* blend_frame[3] = {nullptr, nullptr, nullptr};
+  int blend_fw = 0, blend_fh = 0;
+  size_t blend_fstride = 0;
+};
+
 struct jxlh_ctx {
   jxlh_host::Comm* comm = nullptr;  // multi-GPU: rank / transport of this context (null = single GPU)
   int device = 0;
@@ -62,20 +105,19 @@ struct jxlh_ctx {
   // frame state
   bool in_frame = false;
   // a Modular frame (JXLH_FRAME_MODULAR, abi_modular_frame.hip): the i32 samples of the three colour channels as
-  // jxlh_frame_set_modular_channels handed them over, at the planes' row stride (rows 256-byte aligned), and their format
-  // (0 = no rect set yet)
+  // jxlh_frame_set_modular_channels handed them over, at the planes' row stride (rows 256-byte aligned)
   bool modular = false;
   DevBuf<int32_t> mod_src[3];
-  uint32_t mod_format = 0;
   // group-local transforms (abi_modular_local.hip): device scratch of a host arena and of a batch's descriptors + work
   // list; the descriptors go up from a pinned block, reused once local_copied (recorded behind its copy) has passed
   DevBuf<int32_t> local_arena;
   DevBuf<uint8_t> local_desc;
   Pinned<uint8_t> local_desc_host;
   Fence local_copied;
-  bool tables_set = false, lf_smoothed = false;
+  bool tables_set = false;
   jxlh_frame_params params;
   FrameDev fd;
+  FrameState frame;  // what every jxlh_frame_begin starts from its defaults (start_frame, abi_frame.hip)
   size_t ngroups = 0;
   DevBuf<float> planes[3], tmp[3], lf_raw[3], lf_sm[3], sigma, tables;
   int table_offset[JXLH_NUM_QUANT_TABLES] = {0};
@@ -96,16 +138,9 @@ struct jxlh_ctx {
   // K1 transforms, then the ones the fill writes -- as it is copied to rerender_list
   std::vector<uint8_t> lf_only_run;
   std::vector<int> lf_split_upload;
-  bool rendered = false;              // a full jxlh_frame_run has happened in this frame
-  bool has_special = false, has_large = false;  // transform families seen in the frame's maps (jxlh_frame_set_hf_meta)
-  float* result[3] = {nullptr, nullptr, nullptr};
-  // geometry of `result`: the frame itself, or its upsampled image (frame_header.upsampling > 1)
+  // geometry of frame.result (written with it): the frame itself, or its upsampled image (frame_header.upsampling > 1)
   int res_w = 0, res_h = 0;
   size_t res_stride = 0;
-  // chroma-subsampled frame with nothing between the transforms and the output: the upsampling into planes[] is
-  // deferred until somebody asks for the planes (the YCbCr output calls read the sub-sampled channels directly)
-  bool chroma_lazy = false;
-  int lazy_gr0 = 0, lazy_gr1 = 0;
   DevBuf<float> noise[3];      // random planes of the noise synthesis
   DevBuf<uint64_t> xs_jump;    // xorshift128+ jump matrices T^(2^j), uploaded on first use
   DevBuf<float> ups[3];        // upsampled planes
@@ -174,8 +209,7 @@ struct jxlh_ctx {
   };
   RefSlot refs[JXLH_MAX_REFERENCE_FRAMES];
   // LF frames (DecoderState::lf_frames, abi_lf_frame.hip): the X, Y, B planes of w x h at `stride` (rows 256-byte
-  // aligned), channel c at c * stride * h.  lf_from_slot: this frame's LF image is a copy of a slot (no K0b, no
-  // jxlh_frame_set_lf*); lf_from_caller: a jxlh_frame_set_lf* call has written into it
+  // aligned), channel c at c * stride * h
   struct LfSlot {
     bool set = false;
     uint32_t w = 0, h = 0;
@@ -183,7 +217,6 @@ struct jxlh_ctx {
     DevBuf<float> buf;
   };
   LfSlot lf_slots[JXLH_NUM_LF_FRAMES];
-  bool lf_from_slot = false, lf_from_caller = false;
   // the frame's patch dictionary (jxlh_frame_set_patches), binned into 64 x 4 tiles: words = tile ids | starts | patch
   // indices; row_first[r] = first listed tile of tile row r
   struct PatchBins {
@@ -192,46 +225,32 @@ struct jxlh_ctx {
     std::vector<uint32_t> words, row_first;
     DevBuf<uint32_t> dev;
   };
-  uint32_t patch_n = 0, patch_nec = 0;  // 0 patches: no dictionary
-  uint32_t patch_ec_alpha = 0, patch_ec_assoc = 0;
   std::vector<PatchDev> patch_desc_host;
   DevBuf<PatchDev> patch_desc;
-  uint32_t patch_need_w[JXLH_MAX_REFERENCE_FRAMES] = {}, patch_need_h[JXLH_MAX_REFERENCE_FRAMES] = {};
-  uint32_t patch_slots_used = 0;  // bit s: the dictionary reads slot s
   PatchBins patch_bins, patch_hook_bins;
-  bool patch_ec_stale = true;  // the patched extra channels must be rebuilt from their base planes on all rows
   DevBuf<float> patch_hook;    // jxlh_stage_patches staging
   // the frame's spline segments (jxlh_frame_set_splines, abi_splines.hip): as the kernel reads them, host and device;
   // spline_first = the batches of consecutive segments planned for spline_plan_w x _h under spline_budget entries;
-  // spline_bins = the bin list of batch spline_resident for that size, also on the device (-1: none)
-  uint32_t spline_n = 0;
+  // spline_bins = the bin list of batch frame.spline_resident for that size, also on the device
   std::vector<SplineDev> spline_desc_host;
   DevBuf<SplineDev> spline_desc;
   std::vector<uint32_t> spline_first;
   int spline_plan_w = 0, spline_plan_h = 0;
   SplineBins spline_bins;
   DevBuf<uint32_t> spline_bins_dev;
-  int spline_resident = -1;
   uint64_t spline_budget = kSplineDefaultBudget;
   DevBuf<float> spline_hook;  // jxlh_stage_splines staging
-  // frame blending (abi_blend.hip): the image-sized canvas of 3 + blend_nec planes, channel c at c * res_stride * res_h.
-  // While the frame's result points at it (blended()), blend_frame / blend_f* keep the frame's own planes and geometry.
+  // frame blending (abi_blend.hip): the image-sized canvas of 3 + frame.blend_nec planes, channel c at
+  // c * res_stride * res_h
   DevBuf<float> blend_canvas;
-  uint32_t blend_nec = 0;
-  float* blend_frame[3] = {nullptr, nullptr, nullptr};
-  int blend_fw = 0, blend_fh = 0;
-  size_t blend_fstride = 0;
   DevBuf<float> blend_hook_in, blend_hook_out;  // jxlh_stage_blend staging
   DevBuf<float> save_hook_in;                   // jxlh_stage_save staging of host planes (abi_save.hip)
   // strip path (k_strip.hip): block descriptors / tile modes written by k1_scan, the strips' edge-column exchange
-  // buffer, progress flags + ticket.  strip_all_closed: every rect of the transform map came from host memory and
-  // every varblock in it is a small DCT inside its 64x64 tile (jxlh_frame_set_hf_meta); strip_ran: the last
-  // jxlh_frame_run went through the strip kernel (`planes` then hold no unfiltered pixels).
+  // buffer, progress flags + ticket
   DevBuf<uint2> strip_desc;
   DevBuf<uint8_t> strip_mode;
   DevBuf<float> strip_xchg;
   DevBuf<int> strip_flags;
-  bool strip_all_closed = true, strip_ran = false;
   int cu_count = 0;
   // jxlh_ctx_tune_placement: candidate sets the first allocation of the large buffers is picked from (<= 1: plain
   // allocation); what the last pick saw (k1-like ms, filter-like ms per candidate) and took
@@ -355,9 +374,9 @@ jxlh_status patches_check_run(const jxlh_ctx* ctx);
 // abi_splines.hip: the splines stage on the colour planes `cur` (rows [y_lo, y_hi))
 jxlh_status run_splines(jxlh_ctx* ctx, float* const cur[3], size_t stride, int w, int h, int y_lo, int y_hi);
 // patches and splines are drawn IN PLACE on the finished planes: whatever must not reach a pixel twice asks this
-inline bool draws_in_place(const jxlh_ctx* ctx) { return ctx->patch_n > 0 || ctx->spline_n > 0; }
+inline bool draws_in_place(const jxlh_ctx* ctx) { return ctx->frame.patch_n > 0 || ctx->frame.spline_n > 0; }
 // abi_blend.hip.  blended(): the frame's result is the canvas jxlh_frame_blend composed (any render resets `result`).
-inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->result[0] == ctx->blend_canvas.p; }
+inline bool blended(const jxlh_ctx* ctx) { return ctx->blend_canvas.p && ctx->frame.result[0] == ctx->blend_canvas.p; }
 // abi_save.hip: the argument checks, shared with jxlh_lf_preview: the descriptor's own (n_planes: pipeline channels that
 // exist), `out` and its pitch against the oriented image of a w x h source
 jxlh_status save_check_desc(const jxlh_save_desc* d, uint32_t n_planes);
@@ -399,17 +418,19 @@ bool lf_only_snapshot(jxlh_ctx* ctx);
 jxlh_status lf_split_groups(jxlh_ctx* ctx, const std::vector<int>& groups, int* n_k1, int* n_fill);
 jxlh_status run_lf_fill(jxlh_ctx* ctx, const FrameDev& f, const int* groups_dev, int n);
 jxlh_status run_strip(jxlh_ctx* ctx);
-void set_filter_params(FrameDev& f, const jxlh_frame_params& p);
-// abi_modular_frame.hip: jxlh_frame_begin / jxlh_frame_run of a Modular frame (behind the shared argument checks)
-void reset_frame_state(jxlh_ctx* ctx);  // abi_frame.hip: the per-frame state every jxlh_frame_begin starts from
-jxlh_status modular_frame_begin(jxlh_ctx* ctx);
+void set_filter_params(FrameDev& f, const jxlh_frame_params& p);  // abi_frame.hip
+// jxlh_frame_begin's commit takes its sizes from the plan (frame_plan.h).  abi_ctx.hip: the first allocation of the
+// large buffers as a pick among candidate sets (jxlh_ctx_tune_placement)
+jxlh_status choose_placement(jxlh_ctx* ctx, const FramePlan& pl);
+// abi_modular_frame.hip: the commit / jxlh_frame_run of a Modular frame
+jxlh_status modular_frame_begin(jxlh_ctx* ctx, const FramePlan& pl);
 jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_row1);
-void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1);  // abi_frame.hip: ... of the rows that cover [y0, y1)
-// abi_frame.hip: pieces of the frame pipeline the read-out and stage-hook entry points share
+void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1);  // frame_run.hip: ... of the rows that cover [y0, y1)
+// frame_run.hip: pieces of the frame pipeline the read-out and stage-hook entry points share
 bool noise_lut_is_zero(const float lut[8]);
 void materialise_chroma(jxlh_ctx* ctx);          // deferred chroma upsampling of a sub-sampled frame, if still pending
 jxlh_status ensure_jump_table(jxlh_ctx* ctx);    // xorshift128+ jump matrices of the noise generator
-jxlh_status upload_upsampling_kernels(jxlh_ctx* ctx, int n);
+jxlh_status upload_upsampling_kernels(jxlh_ctx* ctx, int n);  // abi_frame.hip
 
 // host or device source -> context-owned device scratch / back, on the main stream (stage hooks, Modular entry points)
 template <class T>

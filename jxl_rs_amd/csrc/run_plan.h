@@ -1,5 +1,5 @@
 // The routing of a frame run: what jxlh_frame_run, jxlh_frame_rerender_groups, a Modular frame's run and a sharded run
-// launch, on which rows, and where the result ends up -- decided here, issued by abi_frame.hip, abi_modular_frame.hip
+// launch, on which rows, and where the result ends up -- decided here, issued by frame_run.hip, abi_modular_frame.hip
 // and comm.hip.  Plain C++: the planner is host logic, tested without a device (tests/cpp/run_plan.cc).
 #pragma once
 #include <algorithm>
@@ -43,7 +43,7 @@ struct StageList {
   int fused_where() const { return count() == 0 ? 0 : epf_iters >= 3 ? 2 : 1; }
 };
 
-// What the decisions read from the context and the frame parameters (abi_frame.hip: run_inputs), and nothing else.
+// What the decisions read from the context and the frame parameters (frame_run.hip: run_inputs), and nothing else.
 // noise: the flag is set and the LUT is not all zero.  draws_in_place: patches or splines, drawn IN PLACE on the finished
 // planes.  strip_requested: JXLH_FRAME_STRIP, or the JXLH_STRIP environment hook.  lf_only: a group is marked
 // (jxlh_frame_set_groups_lf_only).  rendered: a whole-frame run has happened in this frame; strip_ran: the last run went

@@ -29,7 +29,8 @@ def test_roofline_traffic_resolves_for_the_default_config():
 def test_kernel_byte_table_matches_the_library_timer_names():
     b = _bench()
     import glob
-    srcs = "".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "jxl_rs_amd", "csrc", "abi_*.hip")))
+    csrc = os.path.join(ROOT, "jxl_rs_amd", "csrc")  # the host files that name timers: the ABI files and the frame run
+    srcs = "".join(open(f).read() for f in glob.glob(os.path.join(csrc, "abi_*.hip")) + [os.path.join(csrc, "frame_run.hip")])
     for name in b.ALGO_BYTES_PER_PX:
         assert f'"{name}"' in srcs or name.startswith("k3"), name  # k3a_/k3b_/k3c_ names are composed at run time
 

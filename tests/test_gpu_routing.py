@@ -2,7 +2,7 @@
 
   - per-group routing: groups that arrive in another form (dense slab, plain pairs), carry a value in `wide`, or add a
     pass to earlier content are read from their dense slabs while the rest of the frame is still read in place
-    (csrc/abi_frame.hip:run_prologue, the dense-route lists of k1_scan, csrc/k_vardct_scan.hip, which csrc/k1_plan.h gives
+    (csrc/frame_run.hip:run_prologue, the dense-route lists of k1_scan, csrc/k_vardct_scan.hip, which csrc/k1_plan.h gives
     their own launch) -- the reference's `current_coeffs[idx] += coeff` on
     arbitrary i32 (frame/group.rs:568-572) must not cost the whole frame its fast path;
   - wide values split into repeated in-range entries by the C packer (jxlh_host_pack_slots) stay in place;
