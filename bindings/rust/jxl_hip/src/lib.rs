@@ -94,6 +94,28 @@ impl Context {
                                  frame_origin.1, y0, y1, out.as_mut_ptr() as *mut c_void, bytes_per_row)
         })
     }
+    /// `jxlh_stage_save_rects`: `stage_save` for a list of rectangles of the planes instead of a row band.
+    #[allow(clippy::too_many_arguments)]
+    pub fn stage_save_rects(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc, planes: &[&[f32]],
+                            w: u32, h: u32, stride: usize, frame_origin: (u32, u32), rects: &[sys::save_rects::jxlh_rect],
+                            out: &mut [u8], bytes_per_row: usize) -> Result<()> {
+        if w == 0 || h == 0 || stride < w as usize || !save_fits(desc, w, h, bytes_per_row, out.len()) {
+            return Err(HipError::InvalidArgument);
+        }
+        let need = (h as usize - 1).checked_mul(stride).and_then(|n| n.checked_add(w as usize));
+        match need {
+            Some(n) if planes.iter().all(|p| p.len() >= n) => {}
+            _ => return Err(HipError::InvalidArgument),
+        }
+        let ptrs: Vec<*const f32> = planes.iter().map(|p| p.as_ptr()).collect();
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        // SAFETY: every plane holds h rows of w samples at `stride`, `out` the whole oriented image; the call waits
+        self.ok(unsafe {
+            sys::save_rects::jxlh_stage_save_rects(self.raw, colour, desc, ptrs.as_ptr(), ptrs.len() as u32, w, h, stride,
+                                                   frame_origin.0, frame_origin.1, rects.as_ptr(), rects.len() as u32,
+                                                   out.as_mut_ptr() as *mut c_void, bytes_per_row)
+        })
+    }
     /// `jxlh_frame_set_modular_groups`: the group-local transforms of a Modular frame on the device.  `arena` holds
     /// every group's coded channels and palettes (host memory), `groups` each group's rect, transform list in bitstream
     /// order and offsets into the arena (what `decode_modular_section` leaves instead of running `local_apply`).  All
@@ -213,6 +235,26 @@ impl Drop for PinnedBuf<'_> {
     fn drop(&mut self) {
         unsafe { sys::jxlh_free_pinned(self.ctx.raw, self.ptr) };
     }
+}
+
+/// `jxlh_changed_rects` (host code, no context): the rectangles of the frame's result, in the frame's coordinates,
+/// outside which re-rendering `groups` leaves every pixel as it was -- what `VarDctFrame::save_rects` repaints after a
+/// pass.  After `blend`, shift them by the frame's origin in the image and clip them to it.
+pub fn changed_rects(params: &sys::jxlh_frame_params, groups: &[u32]) -> Result<Vec<sys::save_rects::jxlh_rect>> {
+    let mut n = 0u32;
+    // SAFETY: cap = 0 writes no rect; *n is the number needed (the call then reports the missing room)
+    let st = unsafe {
+        sys::save_rects::jxlh_changed_rects(params, groups.as_ptr(), groups.len() as u32, std::ptr::null_mut(), 0, &mut n)
+    };
+    if n == 0 {
+        return check(std::ptr::null(), st).map(|_| Vec::new());
+    }
+    let mut rects = vec![sys::save_rects::jxlh_rect { x0: 0, y0: 0, w: 0, h: 0 }; n as usize];
+    // SAFETY: `rects` holds the n entries asked for
+    check(std::ptr::null(), unsafe {
+        sys::save_rects::jxlh_changed_rects(params, groups.as_ptr(), groups.len() as u32, rects.as_mut_ptr(), n, &mut n)
+    })?;
+    Ok(rects)
 }
 
 /// A VarDCT frame on the device.  Call order = the reference's frame flow.
@@ -389,6 +431,39 @@ impl<'a> VarDctFrame<'a> {
                              out: *mut c_void, bytes_per_row: usize) -> Result<()> {
         let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
         self.ctx.ok(sys::jxlh_frame_save_async(self.ctx.raw, colour, desc, y0, y1, out, bytes_per_row))
+    }
+    /// `save` for a list of rectangles of the result instead of a row band (`jxlh_frame_save_rects`): only the pixels
+    /// inside a rect (cut at the result's edge) are written, each at its display position in the whole oriented image at
+    /// `out`, with the samples `save` gives them; a device destination in one launch, a host destination with one copy
+    /// of exactly its pixel bytes per rect.
+    ///
+    /// # Safety
+    /// As `save`.
+    pub unsafe fn save_rects(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc,
+                             rects: &[sys::save_rects::jxlh_rect], out: *mut c_void, bytes_per_row: usize) -> Result<()> {
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        self.ctx.ok(sys::save_rects::jxlh_frame_save_rects(self.ctx.raw, colour, desc, rects.as_ptr(), rects.len() as u32, out,
+                                                           bytes_per_row))
+    }
+    /// `save_rects` into host memory, checked as `save_to_slice` is; returns after the copies have completed.
+    pub fn save_rects_to_slice(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc,
+                               rects: &[sys::save_rects::jxlh_rect], out: &mut [u8], bytes_per_row: usize) -> Result<()> {
+        let (w, h) = self.out_size.get();
+        if !save_fits(desc, w, h, bytes_per_row, out.len()) {
+            return Err(HipError::InvalidArgument);
+        }
+        // SAFETY: the slice holds every byte the oriented image can touch, and the call waits for the copies
+        unsafe { self.save_rects(colour, desc, rects, out.as_mut_ptr() as *mut c_void, bytes_per_row) }
+    }
+    /// `save_rects` without the final wait (`jxlh_frame_save_rects_async`).
+    ///
+    /// # Safety
+    /// As `save_async`.
+    pub unsafe fn save_rects_async(&self, colour: Option<&sys::jxlh_output_desc>, desc: &sys::jxlh_save_desc,
+                                   rects: &[sys::save_rects::jxlh_rect], out: *mut c_void, bytes_per_row: usize) -> Result<()> {
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        self.ctx.ok(sys::save_rects::jxlh_frame_save_rects_async(self.ctx.raw, colour, desc, rects.as_ptr(),
+                                                                 rects.len() as u32, out, bytes_per_row))
     }
     /// `mark_group_to_rerender` + re-render (render/mod.rs:143-146): after more passes arrived for `groups`
     pub fn rerender_groups(&self, groups: &[u32]) -> Result<()> {

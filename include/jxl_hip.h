@@ -971,6 +971,11 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
                             uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
                             size_t bytes_per_row);
 
+/* Save rectangles -- the same save for a LIST of rectangles of the source in one launch, so that a repaint moves only
+ * the pixels a group re-render can have changed, and the host function that names those rectangles:
+ * jxlh_frame_save_rects, jxlh_frame_save_rects_async, jxlh_stage_save_rects and jxlh_changed_rects (jxlh_rect,
+ * JXLH_MAX_SAVE_RECTS), declared in jxl_hip_save_rects.h, which this header includes at its end. */
+
 /* ---------------------------------------------------------------- LF frames
  * A frame with lf_level = L >= 1 (the layers of a progressive_dc file) is an ordinary frame of ceil(size / 8^L) pixels,
  * usually Modular XYB, sometimes VarDCT (FrameHeader::size_upsampled, headers/frame_header.rs:584-589): begin, fill and
@@ -1291,5 +1296,6 @@ int32_t jxlh_quant_table_size(int32_t table);
 #endif
 /* entry points added since ABI version 6 was recorded, in headers of their own: part of this interface all the same */
 #include "jxl_hip_preview.h"
+#include "jxl_hip_save_rects.h"
 
 #endif /* JXL_HIP_H_ */

@@ -100,11 +100,29 @@ class Context {
                                        nearest_even ? (uint32_t)JXLH_SMOOTH_CVT_NEAREST_EVEN : 0u),
           "jxlh_unsqueeze_chain_preview");
   }
+  // the save tail on caller planes (3 + num_ec, host or device) for a list of source rectangles: jxlh_stage_save_rects
+  void stage_save_rects(const jxlh_output_desc* colour, const jxlh_save_desc& save, const std::vector<const float*>& planes,
+                        uint32_t w, uint32_t h, size_t stride, uint32_t frame_x0, uint32_t frame_y0,
+                        const std::vector<jxlh_rect>& rects, void* out, size_t bytes_per_row) {
+    check(jxlh_stage_save_rects(c_, colour, &save, planes.data(), (uint32_t)planes.size(), w, h, stride, frame_x0, frame_y0,
+                                rects.data(), (uint32_t)rects.size(), out, bytes_per_row),
+          "jxlh_stage_save_rects");
+  }
 
  private:
   jxlh_ctx* c_ = nullptr;
   int n_slots_ = 1;
 };
+
+// the rectangles of a frame's result that re-rendering `groups` can change (jxlh_changed_rects): host only
+inline std::vector<jxlh_rect> changed_rects(const jxlh_frame_params& p, const std::vector<uint32_t>& groups) {
+  uint32_t n = 0;
+  jxlh_status st = jxlh_changed_rects(&p, groups.data(), (uint32_t)groups.size(), nullptr, 0, &n);
+  std::vector<jxlh_rect> rects(n);
+  if (n) st = jxlh_changed_rects(&p, groups.data(), (uint32_t)groups.size(), rects.data(), n, &n);
+  if (st != JXLH_OK) throw Error(st, "jxlh_changed_rects", "");
+  return rects;
+}
 
 // what each level of a preview chain runs (JXLH_PREVIEW_*) and whether the final planes depend on it: host only
 struct SqueezePreviewKinds {
@@ -272,6 +290,20 @@ class VarDctFrame {
             uint32_t y1 = 0xFFFFFFFFu) {
     ctx_.check(jxlh_frame_save(ctx_.raw(), colour, &desc, y0, y1, out, bytes_per_row), "jxlh_frame_save");
   }
+  // ... for a list of rectangles of the result instead of a row band (jxlh_frame_save_rects): only their pixels are
+  // written, each at its display position in the whole oriented image at `out`; _async: without the final wait
+  void save_rects(const jxlh_output_desc* colour, const jxlh_save_desc& desc, const std::vector<jxlh_rect>& rects, void* out,
+                  size_t bytes_per_row) {
+    ctx_.check(jxlh_frame_save_rects(ctx_.raw(), colour, &desc, rects.data(), (uint32_t)rects.size(), out, bytes_per_row),
+               "jxlh_frame_save_rects");
+  }
+  void save_rects_async(const jxlh_output_desc* colour, const jxlh_save_desc& desc, const std::vector<jxlh_rect>& rects,
+                        void* out, size_t bytes_per_row) {
+    ctx_.check(jxlh_frame_save_rects_async(ctx_.raw(), colour, &desc, rects.data(), (uint32_t)rects.size(), out, bytes_per_row),
+               "jxlh_frame_save_rects_async");
+  }
+  // the rectangles of this frame's result that re-rendering `groups` can change (before blend(): frame coordinates)
+  std::vector<jxlh_rect> changed_rects(const std::vector<uint32_t>& groups) const { return jxlh::changed_rects(p_, groups); }
   uint32_t out_width() const {
     if (blend_w_) return blend_w_;
     const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;

@@ -935,6 +935,10 @@ class GpuFramePipeline {
   void save(size_t buffer_index, void* out, size_t bytes_per_row, uint32_t y0 = 0, uint32_t y1 = 0xFFFFFFFFu) {
     frame_.save(&lp_.output, save_desc(buffer_index), out, bytes_per_row, y0, y1);
   }
+  // ... only the pixels of `rects` (source rectangles of the result), e.g. what changed_rects() names after a pass
+  void save_rects(size_t buffer_index, const std::vector<jxlh_rect>& rects, void* out, size_t bytes_per_row) {
+    frame_.save_rects(&lp_.output, save_desc(buffer_index), rects, out, bytes_per_row);
+  }
   void save_planes(float* c0, float* c1, float* c2) { frame_.read_planes(c0, c1, c2); }
   // an LF frame's result (lf_level = L) into LF slot L - 1, where the reference's list has its three Grayscale f32 save
   // stages (frame/render.rs:699-710); those stages are not lowered
@@ -984,6 +988,10 @@ class GpuRenderPipeline : public GpuFramePipeline {
   }
   // render/mod.rs:146
   void mark_group_to_rerender(uint32_t g) { rerender_.push_back(g); }
+  // The rectangles of the frame's result that re-rendering `groups` can change (jxlh_changed_rects): what save_rects
+  // repaints after the do_render() of a pass that touched them.  Frame coordinates: with a BlendingStage in the list,
+  // shift them by the frame's origin and clip them to the image.
+  std::vector<jxlh_rect> changed_rects(const std::vector<uint32_t>& groups) const { return frame_.changed_rects(groups); }
   // A group that must be rendered while its HF has not arrived (force_render with DataStatus::Zero, frame/decode.rs:
   // 744-752): the reference hands the pipeline the LF image upsampled 8x as the group's buffers; here the group is marked
   // and the next do_render() fills it on the device.  set_buffer_for_group on the group later clears the mark.

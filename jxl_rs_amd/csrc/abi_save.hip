@@ -1,7 +1,8 @@
 // C ABI of the save tail (frame/render.rs:793-903): spot colours, premultiplication, the conversions to u8 / u16 / f16 /
 // f32 at any bit depth and the save stage with its channel order, endianness, opaque-alpha fill and orientation, behind
 // the frame's colour stage.  jxlh_frame_save runs it on the frame's result, jxlh_stage_save on caller planes; both launch
-// k_save.hip.
+// k_save.hip.  jxlh_frame_save_rects / jxlh_stage_save_rects are the same two for a list of source rectangles
+// (save_rects_plan.h decides, k_save_rects.hip runs it in one launch); jxlh_changed_rects is that header's host function.
 #include <algorithm>
 #include <cmath>
 
@@ -120,9 +121,63 @@ jxlh_status launch_to(jxlh_ctx* ctx, SaveLaunch& a, void* image, size_t bytes_pe
   });
 }
 
+// the frame's result and the extra channels the save names as the launch reads them, and the result's geometry
+void fill_result_launch(jxlh_ctx* ctx, SaveLaunch& a, const jxlh_save_desc* d, const float* const* ec_plane,
+                        const uint32_t* ec_stride) {
+  fill_desc(
+      d, [&](uint32_t ch) { return ch < 3 ? (const float*)ctx->frame.result[ch] : ec_plane[ch - 3]; },
+      [&](uint32_t ch) { return ch < 3 ? (uint32_t)ctx->res_stride : ec_stride[ch - 3]; }, a);
+  a.w = ctx->res_w;
+  a.h = ctx->res_h;
+  a.y0 = a.rows = 0;
+  a.dx = a.dy = 0;
+}
+
+// The rect-list tail (save_rects_plan.h decides, this issues): the work list goes up on the stream, ONE launch writes
+// every rect -- into the caller's device image, or into the rects' packed blocks of ctx->rgb8, which then leave with one
+// 2-D copy of exactly the pixel bytes per rect.  `a`: everything but out filled.
+jxlh_status issue_save_rects(jxlh_ctx* ctx, SaveLaunch& a, SaveRectsPlan& plan, bool staged, void* image,
+                             size_t bytes_per_row, bool wait) {
+  if (plan.work.empty()) return JXLH_OK;
+  const size_t pb = (size_t)a.spp * (size_t)save_sample_bytes((uint32_t)a.format);
+  const uint32_t n = (uint32_t)plan.work.size();
+  if (staged)
+    if (jxlh_status st = ensure(ctx, ctx->rgb8, (size_t)plan.staging_bytes)) return st;
+  if (jxlh_status st = ensure(ctx, ctx->save_rects_dev, n)) return st;
+  HIPCHK(ctx, ctx->save_rects_copied.sync());  // the pinned block's previous list is on its way
+  ctx->save_rects_copied.clear();
+  if (ctx->save_rects_host.n < n) {
+    HIPCHK(ctx, ctx->save_rects_host.reset());
+    HIPCHK(ctx, ctx->save_rects_host.alloc(n + n / 2));
+  }
+  std::memcpy(ctx->save_rects_host.p, plan.work.data(), n * sizeof(SaveRectWork));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->save_rects_dev.p, ctx->save_rects_host.p, n * sizeof(SaveRectWork), hipMemcpyHostToDevice,
+                             ctx->stream));
+  HIPCHK(ctx, ctx->save_rects_copied.record(ctx->stream));
+  a.out = staged ? ctx->rgb8.p : static_cast<uint8_t*>(image);
+  a.out_stride = 0;  // every rect carries its own
+  {
+    ScopedKernelTimer t(ctx, "k_save_rects");
+    launch_save_rects(ctx->stream, a, ctx->save_rects_dev.p, n, plan.groups);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (!staged) return JXLH_OK;
+  for (const SaveRectOut& o : plan.out) {
+    void* dst = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(image) + o.oy0 * bytes_per_row + o.ox0 * pb);
+    if (jxlh_status st = copy2d(ctx, dst, bytes_per_row, ctx->rgb8.p + o.stage_off, o.stage_pitch, o.row_bytes, o.oh,
+                                ctx->stream))
+      return st;
+  }
+  if (wait) JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+// jxlh_frame_save (rects == nullptr && !by_rects: rows [y0, y1)) and jxlh_frame_save_rects (by_rects: the list)
 jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d, uint32_t y0, uint32_t y1,
-                       void* out, size_t bytes_per_row, bool wait) {
+                       void* out, size_t bytes_per_row, bool wait, bool by_rects = false, const jxlh_rect* rects = nullptr,
+                       uint32_t n_rects = 0) {
   if (!ctx || !d || !out) return JXLH_ERR_INVALID_ARGUMENT;
+  if (by_rects && (n_rects > JXLH_MAX_SAVE_RECTS || (n_rects && !rects))) return JXLH_ERR_INVALID_ARGUMENT;
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
   if (jxlh_status st = save_check_desc(d, 3 + JXLH_MAX_EXTRA_CHANNELS)) return st;
   SaveLaunch a{};
@@ -130,8 +185,12 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
   if (!ctx->in_frame || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
   if (blended(ctx) && a.mode != kModeNone) return JXLH_ERR_BAD_STATE;  // jxlh_frame_blend has run the colour stage already
   const uint32_t w = (uint32_t)ctx->res_w, h = (uint32_t)ctx->res_h;
-  if (y1 > h) y1 = h;
-  if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (by_rects) {
+    if (jxlh_status st = check_save_rects(rects, n_rects, w, h)) return st;
+  } else {
+    if (y1 > h) y1 = h;
+    if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
+  }
   if (jxlh_status st = save_check_out(d, w, h, out, bytes_per_row)) return st;
   if ((uint64_t)w * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
   // the extra channels the save reads, as jxlh_frame_read_extra_channel resolves them
@@ -164,7 +223,15 @@ jxlh_status frame_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh
     for (uint32_t i = 0; i < d->n_spot; i++)
       if (jxlh_status st = resolve(3 + d->spot[i].ec)) return st;
   }
-  return save_result_rows(ctx, a, d, ec_plane, ec_stride, y0, y1, out, bytes_per_row, "k_save", wait);
+  if (!by_rects) return save_result_rows(ctx, a, d, ec_plane, ec_stride, y0, y1, out, bytes_per_row, "k_save", wait);
+  const bool staged = !is_device_ptr(out);
+  SaveRectsPlan plan = plan_save_rects(rects, n_rects, w, h, d->orientation,
+                                       samples_per_pixel(d) * (uint32_t)save_sample_bytes(d->format), staged, bytes_per_row);
+  if (plan.status != JXLH_OK) return plan.status;
+  if (plan.work.empty()) return JXLH_OK;  // nothing to write: nothing enqueued
+  materialise_chroma(ctx);
+  fill_result_launch(ctx, a, d, ec_plane, ec_stride);
+  return issue_save_rects(ctx, a, plan, staged, out, bytes_per_row, wait);
 }
 
 }  // namespace
@@ -212,23 +279,62 @@ jxlh_status jxlh_frame_save_async(jxlh_ctx* ctx, const jxlh_output_desc* colour,
   return frame_save(ctx, colour, save, y0, y1, out, bytes_per_row, /*wait=*/false);
 }
 
-jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d,
-                            const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
-                            uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
-                            size_t bytes_per_row) {
+jxlh_status jxlh_frame_save_rects(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save,
+                                  const jxlh_rect* rects, uint32_t n, void* out, size_t bytes_per_row) {
+  JXLH_ON_DEVICE(ctx);
+  return frame_save(ctx, colour, save, 0, 0, out, bytes_per_row, /*wait=*/true, /*by_rects=*/true, rects, n);
+}
+
+jxlh_status jxlh_frame_save_rects_async(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* save,
+                                        const jxlh_rect* rects, uint32_t n, void* out, size_t bytes_per_row) {
+  JXLH_ON_DEVICE(ctx);
+  return frame_save(ctx, colour, save, 0, 0, out, bytes_per_row, /*wait=*/false, /*by_rects=*/true, rects, n);
+}
+
+// pure host code (save_rects_plan.h)
+jxlh_status jxlh_changed_rects(const jxlh_frame_params* p, const uint32_t* group_ids, uint32_t count, jxlh_rect* rects,
+                               uint32_t cap, uint32_t* n) {
+  if (!p || !n || (count && !group_ids) || (cap && !rects)) return JXLH_ERR_INVALID_ARGUMENT;
+  std::vector<jxlh_rect> need;
+  if (jxlh_status st = plan_changed_rects(*p, group_ids, count, need)) return st;
+  *n = (uint32_t)need.size();
+  if (need.size() > cap) return JXLH_ERR_INVALID_ARGUMENT;
+  std::copy(need.begin(), need.end(), rects);
+  return JXLH_OK;
+}
+
+// jxlh_stage_save (rows [y0, y1)) and jxlh_stage_save_rects (by_rects: the list)
+static jxlh_status stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d,
+                              const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
+                              uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
+                              size_t bytes_per_row, bool by_rects, const jxlh_rect* rects, uint32_t n_rects) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !d || !planes || !out || w == 0 || h == 0 || stride < w || stride > 0xffffffffu)
     return JXLH_ERR_INVALID_ARGUMENT;
+  if (by_rects && (n_rects > JXLH_MAX_SAVE_RECTS || (n_rects && !rects))) return JXLH_ERR_INVALID_ARGUMENT;
   if (n_planes < 3 || n_planes > 3 + JXLH_MAX_EXTRA_CHANNELS) return JXLH_ERR_INVALID_ARGUMENT;
   for (uint32_t c = 0; c < n_planes; c++)
     if (!planes[c]) return JXLH_ERR_INVALID_ARGUMENT;
   if (jxlh_status st = save_check_desc(d, n_planes)) return st;
   SaveLaunch a{};
   if (jxlh_status st = colour_stage(colour, &a.mode, &a.xyb, &a.tf)) return st;
-  if (y1 > h) y1 = h;
-  if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (by_rects) {
+    if (jxlh_status st = check_save_rects(rects, n_rects, w, h)) return st;
+  } else {
+    if (y1 > h) y1 = h;
+    if (y0 >= y1) return JXLH_ERR_INVALID_ARGUMENT;
+  }
   if (jxlh_status st = save_check_out(d, w, h, out, bytes_per_row)) return st;
   if ((uint64_t)w * h >= (1ull << 31)) return JXLH_ERR_UNSUPPORTED;
+  const bool staged_out = by_rects && !is_device_ptr(out);
+  SaveRectsPlan plan;
+  if (by_rects) {
+    plan = plan_save_rects(rects, n_rects, w, h, d->orientation,
+                           (d->n_channels + (d->fill_opaque_alpha ? 1 : 0)) * (uint32_t)save_sample_bytes(d->format),
+                           staged_out, bytes_per_row);
+    if (plan.status != JXLH_OK) return plan.status;
+    if (plan.work.empty()) return JXLH_OK;  // nothing to write: nothing enqueued
+  }
   // host planes are staged whole, rows 16-byte aligned; device planes are read where they are
   const size_t sstride = round_up(w, 4), splane = sstride * h;
   bool all_device = true;
@@ -249,9 +355,29 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
   a.rows = (int)(y1 - y0);
   a.dx = (int)(frame_x0 & 31);  // the table is 32 x 32
   a.dy = (int)(frame_y0 & 31);
-  if (jxlh_status st = launch_to(ctx, a, out, bytes_per_row, "k_save", /*wait=*/false)) return st;
+  if (by_rects) {
+    if (jxlh_status st = issue_save_rects(ctx, a, plan, staged_out, out, bytes_per_row, /*wait=*/false)) return st;
+  } else {
+    if (jxlh_status st = launch_to(ctx, a, out, bytes_per_row, "k_save", /*wait=*/false)) return st;
+  }
   JXLH_SYNC(ctx);
   return JXLH_OK;
+}
+
+jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d,
+                            const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
+                            uint32_t frame_x0, uint32_t frame_y0, uint32_t y0, uint32_t y1, void* out,
+                            size_t bytes_per_row) {
+  return stage_save(ctx, colour, d, planes, n_planes, w, h, stride, frame_x0, frame_y0, y0, y1, out, bytes_per_row,
+                    /*by_rects=*/false, nullptr, 0);
+}
+
+jxlh_status jxlh_stage_save_rects(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d,
+                                  const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,
+                                  uint32_t frame_x0, uint32_t frame_y0, const jxlh_rect* rects, uint32_t n, void* out,
+                                  size_t bytes_per_row) {
+  return stage_save(ctx, colour, d, planes, n_planes, w, h, stride, frame_x0, frame_y0, 0, 0, out, bytes_per_row,
+                    /*by_rects=*/true, rects, n);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "frame_plan.h"
 #include "jxlh_internal.h"
 #include "run_plan.h"
+#include "save_rects_plan.h"
 
 using namespace jxlh;
 
@@ -129,6 +130,11 @@ struct jxlh_ctx {
   int tables_ok_host = 0;    // ... read back when the tables are set
   bool params_direct_ok = false;  // the frame parameters' share of FrameDev::se_direct_ok
   DevBuf<uint8_t> rgb8;  // write_out's staging for host destinations
+  // jxlh_frame_save_rects: the work list on the device; it goes up from a pinned block, reused once save_rects_copied
+  // (recorded behind its copy) has passed -- an _async call returns while the copy is still queued
+  DevBuf<SaveRectWork> save_rects_dev;
+  Pinned<SaveRectWork> save_rects_host;
+  Fence save_rects_copied;
   Pinned<int> host_flag;
   DevBuf<uint8_t> worklist;
   DevBuf<int> rerender_list;          // group ids of jxlh_frame_rerender_groups on the device

@@ -545,6 +545,9 @@ struct SaveLaunch {
   size_t out_stride;                // bytes
 };
 void launch_save(hipStream_t s, const SaveLaunch& a);
+// ... and the pixels of a list of source rectangles instead of a row band (save_rects_plan.h), in one launch
+struct SaveRectWork;
+void launch_save_rects(hipStream_t s, const SaveLaunch& a, const SaveRectWork* work, uint32_t n, uint32_t groups);
 
 // the LF-frame preview (k_lf_preview.hip): Upsample8x of a rect of an LF slot, the colour stage, the conversion at
 // pipeline position (channel 0, row 0) and the oriented interleaved store, one pass.  The kernel indexes the structure

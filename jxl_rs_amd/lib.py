@@ -49,6 +49,35 @@ def save_tile_layout(pixel_bytes):
     return c.value, r.value
 
 
+def _rect_array(rects):
+    """rects as the C ABI takes them: (x0, y0, w, h) rows as a contiguous uint32 array [n, 4] (the layout of jxlh_rect)"""
+    r = np.ascontiguousarray(rects, dtype=np.uint32).reshape(-1, 4)
+    return r, len(r)
+
+
+def try_changed_rects(params, group_ids, cap=None):
+    """jxlh_changed_rects (host only), returning (status, rects [n, 4] as (x0, y0, w, h) or None, n needed).  cap: room
+    offered (None: as many as needed -- asked for first, as a C caller would)"""
+    ids = np.ascontiguousarray(group_ids, dtype=np.uint32)
+    L, n = load(), C.c_uint32(0)
+    if cap is None:
+        st = L.jxlh_changed_rects(C.byref(params), _addr(ids), len(ids), None, 0, C.byref(n))
+        if st != OK and n.value == 0:
+            return st, None, 0
+        cap = n.value
+    out = np.zeros((max(int(cap), 1), 4), dtype=np.uint32)
+    st = L.jxlh_changed_rects(C.byref(params), _addr(ids), len(ids), _addr(out) if cap else None, int(cap), C.byref(n))
+    return st, (out[:n.value].copy() if st == OK else None), n.value
+
+
+def changed_rects(params, group_ids):
+    """the rectangles of the frame's result that re-rendering `group_ids` can change, [n, 4] rows (x0, y0, w, h)"""
+    st, rects, _ = try_changed_rects(params, group_ids)
+    if st != OK:
+        raise JxlHipError(st, "jxlh_changed_rects")
+    return rects
+
+
 class SaveDesc(_abi.SaveDesc):
     """jxlh_save_desc, with the sizes callers allocate by."""
 
@@ -1001,6 +1030,65 @@ class Context:
                    size=None, stride=None):
         st, out = self.try_stage_save(desc, planes, colour, origin, y0, y1, out, bytes_per_row, size, stride)
         self._chk(st, "stage_save")
+        return out
+
+    # ---- save rectangles ----
+    def changed_rects(self, group_ids):
+        """jxlh_changed_rects for the current frame's parameters"""
+        return changed_rects(self.params, group_ids)
+
+    def try_frame_save_rects(self, desc, rects, colour=None, out=None, bytes_per_row=None, wait=True):
+        """jxlh_frame_save_rects (_async when not `wait`), returning (status, out).  rects: rows (x0, y0, w, h) of the
+        result; out as in try_frame_save (the WHOLE oriented image; a zeroed one is made when None)"""
+        w, h = self.out_size
+        if out is None:
+            out = np.zeros(self.save_shape(desc, w, h), dtype=self._save_dtype(desc))
+        if bytes_per_row is None:
+            bytes_per_row = out.strides[0]
+        r, n = _rect_array(rects)
+        fn = self.L.jxlh_frame_save_rects if wait else self.L.jxlh_frame_save_rects_async
+        st = fn(self._ctx, None if colour is None else C.byref(colour), C.byref(desc), _addr(r) if n else None, n,
+                _addr(out), int(bytes_per_row))
+        return st, out
+
+    def frame_save_rects(self, desc, rects, colour=None, out=None, bytes_per_row=None):
+        """jxlh_frame_save_rects: only the pixels of `rects` of the frame's result, each at its display position in `out`"""
+        st, out = self.try_frame_save_rects(desc, rects, colour, out, bytes_per_row, True)
+        self._chk(st, "frame_save_rects")
+        return out
+
+    def frame_save_rects_async(self, desc, rects, colour=None, out=None, bytes_per_row=None):
+        """... without the final wait (sync() or a mark before `out` is read)"""
+        st, out = self.try_frame_save_rects(desc, rects, colour, out, bytes_per_row, False)
+        self._chk(st, "frame_save_rects_async")
+        return out
+
+    def try_stage_save_rects(self, desc, planes, rects, colour=None, origin=(0, 0), out=None, bytes_per_row=None,
+                             size=None, stride=None):
+        """jxlh_stage_save_rects on 3 + num_ec planes, as try_stage_save with the row band replaced by `rects`"""
+        if size is None:
+            pl = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+            h, w = pl[0].shape
+            stride = w
+        else:
+            pl = list(planes)
+            w, h = size
+            stride = w if stride is None else stride
+        if out is None:
+            out = np.zeros(self.save_shape(desc, w, h), dtype=self._save_dtype(desc))
+        if bytes_per_row is None:
+            bytes_per_row = out.strides[0]
+        r, n = _rect_array(rects)
+        pp = (C.c_void_p * len(pl))(*[_addr(a).value for a in pl])
+        st = self.L.jxlh_stage_save_rects(self._ctx, None if colour is None else C.byref(colour), C.byref(desc), pp, len(pl),
+                                          w, h, stride, int(origin[0]), int(origin[1]), _addr(r) if n else None, n,
+                                          _addr(out), int(bytes_per_row))
+        return st, out
+
+    def stage_save_rects(self, desc, planes, rects, colour=None, origin=(0, 0), out=None, bytes_per_row=None, size=None,
+                         stride=None):
+        st, out = self.try_stage_save_rects(desc, planes, rects, colour, origin, out, bytes_per_row, size, stride)
+        self._chk(st, "stage_save_rects")
         return out
 
     # ---- LF frames ----
