@@ -135,10 +135,10 @@ static void lf_smoothing_rows(const JxloFrameParams* p, const float* const in[3]
         mc[c] = m[0];
         sm[c] = corner * kWCorner + side * kWSide + mc[c] * w_center;
         const float g = fabsf((mc[c] - sm[c]) / lf_factors[c]);
-        gap = gap > g ? gap : g; /* f32::max(gap, g) */
+        gap = g > gap ? g : gap; /* f32::max(gap, g): a NaN g is dropped, gap keeps its 0.5 floor */
       }
       float factor = 3.0f - 4.0f * gap;
-      factor = factor > 0.0f ? factor : 0.0f;
+      factor = factor > 0.0f ? factor : 0.0f; /* (3.0 - 4.0 * gap).max(0.0): gap is never a NaN */
       for (int c = 0; c < 3; c++) out[c][i] = (sm[c] - mc[c]) * factor + mc[c];
     }
   }

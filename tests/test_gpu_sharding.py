@@ -34,15 +34,25 @@ def band_groups(wl, rank, n, extra=0):
     return {gy * wl.xgroups + gx for gy in range(r0, r1) for gx in range(wl.xgroups)}
 
 
+DITHERED_LF = "dithered_lf"  # flags 0, and an LF image adaptive LF smoothing acts on (tests/lf_smoothing_cases.py)
+
+
 @pytest.mark.parametrize("n", [2, 3, 6])
 @pytest.mark.parametrize("epf_iters,gab,flags", [(2, True, 0), (0, True, 0), (3, True, 0), (1, False, 0), (2, True, 1),
-                                                 (3, True, 1), (0, False, 0)])
+                                                 (3, True, 1), (0, False, 0), (2, True, DITHERED_LF)])
 def test_local_sharded_frame_equals_whole(oracle, n, epf_iters, gab, flags):
     import jxl_rs_amd
     from jxl_rs_amd import lib, synth
     wl = synth.make_vardct(520, 1000, mix=synth.MIX_ALL, seed=31 + n, epf_iters=epf_iters, gab=gab)
+    idle = None
+    if flags == DITHERED_LF:
+        import lf_smoothing_cases
+        wl, flags = lf_smoothing_cases.dithered(wl), 0
+        idle, _ = run_oracle_frame(oracle, wl, do_lf_smoothing=0)
     assert wl.ygroups == 4
     want, _ = run_oracle_frame(oracle, wl)
+    if idle is not None:  # the smoothing of a band's first and last LF rows reads the neighbouring bands' rows
+        assert (idle[1].view(np.uint32) != want[1].view(np.uint32)).mean() > 0.05, "smoothing is idle on this frame"
     ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(n)]
     try:
         lib.comm_init_local(ctxs)
