@@ -1208,7 +1208,8 @@ jxlh_status jxlh_smooth_unsqueeze(jxlh_ctx* ctx, int32_t kind, const int32_t* av
 
 /* Progressive previews of a WHOLE squeeze transform in one call -- jxlh_unsqueeze_chain for an image whose finest
  * residual channels have not arrived: jxlh_unsqueeze_chain_preview and jxlh_squeeze_preview_kinds, declared in
- * jxl_hip_preview.h, which this header includes at its end. */
+ * jxl_hip_preview.h, which this header includes at its end.  jxl_hip_preview_tiles.h (included there too) is the same per
+ * grid cell, for levels whose residual groups have partly arrived. */
 
 /* ---------------------------------------------------------------- multi-GPU
  * The reference renders a frame's groups on a pool of host threads and joins them in the pipeline's output buffers
@@ -1297,5 +1298,6 @@ int32_t jxlh_quant_table_size(int32_t table);
 /* entry points added since ABI version 6 was recorded, in headers of their own: part of this interface all the same */
 #include "jxl_hip_preview.h"
 #include "jxl_hip_save_rects.h"
+#include "jxl_hip_preview_tiles.h"
 
 #endif /* JXL_HIP_H_ */

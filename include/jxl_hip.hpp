@@ -100,6 +100,19 @@ class Context {
                                        nearest_even ? (uint32_t)JXLH_SMOOTH_CVT_NEAREST_EVEN : 0u),
           "jxlh_unsqueeze_chain_preview");
   }
+  // ... while the residual GROUPS of some levels have partly arrived: tiles[L] is level L's grid and the host mask of the
+  // cells whose residuals are there (jxl_hip_preview_tiles.h); the reference's per-cell choice (SqueezeInfo::new)
+  void unsqueeze_chain_preview_tiles(const std::vector<jxlh_squeeze_level>& levels, const std::vector<jxlh_squeeze_tiles>& tiles,
+                                     const std::vector<const int32_t*>& base, size_t base_stride, uint32_t base_w, uint32_t base_h,
+                                     const std::vector<int32_t*>& out, size_t out_stride, int32_t rct_op = -1, int32_t rct_perm = 0,
+                                     bool nearest_even = false) {
+    if (base.size() != out.size() || tiles.size() != levels.size())
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "Context::unsqueeze_chain_preview_tiles", "planes or grids differ in number");
+    check(jxlh_unsqueeze_chain_preview_tiles(c_, (int32_t)base.size(), (int32_t)levels.size(), levels.data(), tiles.data(), base.data(),
+                                             base_stride, base_w, base_h, out.data(), out_stride, rct_op, rct_perm,
+                                             nearest_even ? (uint32_t)JXLH_SMOOTH_CVT_NEAREST_EVEN : 0u),
+          "jxlh_unsqueeze_chain_preview_tiles");
+  }
   // the save tail on caller planes (3 + num_ec, host or device) for a list of source rectangles: jxlh_stage_save_rects
   void stage_save_rects(const jxlh_output_desc* colour, const jxlh_save_desc& save, const std::vector<const float*>& planes,
                         uint32_t w, uint32_t h, size_t stride, uint32_t frame_x0, uint32_t frame_y0,
@@ -135,6 +148,20 @@ inline SqueezePreviewKinds squeeze_preview_kinds(int n_planes, const std::vector
       jxlh_squeeze_preview_kinds(n_planes, (int32_t)levels.size(), levels.data(), base_w, base_h, r.kinds.data(), r.live.data());
   if (st != JXLH_OK) throw Error(st, "jxlh_squeeze_preview_kinds", "");
   return r;
+}
+// ... per grid cell: the kinds of the tiles_x * tiles_y cells of `level`, row by row: host only
+inline std::vector<uint8_t> squeeze_tile_kinds(int n_planes, const std::vector<jxlh_squeeze_level>& levels,
+                                               const std::vector<jxlh_squeeze_tiles>& tiles, uint32_t base_w, uint32_t base_h, int32_t level) {
+  if (tiles.size() != levels.size() || level < 0 || (size_t)level >= levels.size())
+    throw Error(JXLH_ERR_INVALID_ARGUMENT, "squeeze_tile_kinds", "one grid per level, and a level of the chain");
+  const jxlh_squeeze_tiles& t = tiles[level];
+  const uint32_t tw = t.tile_w ? t.tile_w : levels[level].out_w, th = t.tile_h ? t.tile_h : levels[level].out_h;
+  const uint64_t cells = tw && th ? (uint64_t)((levels[level].out_w + tw - 1) / tw) * ((levels[level].out_h + th - 1) / th) : 1;
+  if (cells > (1u << 20)) throw Error(JXLH_ERR_INVALID_ARGUMENT, "squeeze_tile_kinds", "more than 2^20 cells in a level");
+  std::vector<uint8_t> kinds((size_t)cells);
+  const jxlh_status st = jxlh_squeeze_tile_kinds(n_planes, (int32_t)levels.size(), levels.data(), tiles.data(), base_w, base_h, level, kinds.data());
+  if (st != JXLH_OK) throw Error(st, "jxlh_squeeze_tile_kinds", "");
+  return kinds;
 }
 
 // One VarDCT frame on the device: the order of calls is the order of Frame's sections in the codestream.

@@ -32,7 +32,7 @@ extern "C" {
  * asynchronous on the context's stream, no host round trip; the RCT is fused into the last level, smooth or regular.
  * flags: 0, or JXLH_SMOOTH_CVT_NEAREST_EVEN for the float-to-int conversion of an x86 reference build (see
  * jxlh_smooth_unsqueeze).  With no missing level the result and the launches are jxlh_unsqueeze_chain's.  Channels
- * whose residual GROUPS have partly arrived (per-tile mixtures) stay with jxlh_smooth_unsqueeze on rects. */
+ * whose residual GROUPS have partly arrived (per-tile mixtures): jxlh_unsqueeze_chain_preview_tiles, jxl_hip_preview_tiles.h. */
 enum { JXLH_PREVIEW_REGULAR = 0, JXLH_PREVIEW_SMOOTH_1D = 1, JXLH_PREVIEW_SMOOTH_2D = 2 };
 jxlh_status jxlh_squeeze_preview_kinds(int32_t n_planes, int32_t n_levels, const jxlh_squeeze_level* levels,
                                        uint32_t base_w, uint32_t base_h, uint8_t* kinds, uint8_t* live);

@@ -432,6 +432,115 @@ jxlh_status jxlh_unsqueeze_chain_preview(jxlh_ctx* ctx, int32_t n_planes, int32_
   return JXLH_OK;
 }
 
+jxlh_status jxlh_squeeze_tile_kinds(int32_t n_planes, int32_t n_levels, const jxlh_squeeze_level* levels,
+                                    const jxlh_squeeze_tiles* tiles, uint32_t base_w, uint32_t base_h, int32_t level, uint8_t* kinds) {
+  if (!kinds) return JXLH_ERR_INVALID_ARGUMENT;
+  // as jxlh_squeeze_preview_kinds: no planes are named here, so every pointer passes for a device one
+  static const int32_t some = 0;
+  const int32_t* const base[3] = {&some, &some, &some};
+  int32_t* const out[3] = {const_cast<int32_t*>(&some), const_cast<int32_t*>(&some), const_cast<int32_t*>(&some)};
+  if (jxlh_status st = check_squeeze_chain(n_planes, n_levels, levels, base, base_w, base_w, base_h, out, (size_t)kMaxModularDim,
+                                           [](const void*) { return true; }, true))
+    return st;
+  if (jxlh_status st = check_squeeze_tiles(n_levels, levels, tiles)) return st;
+  if (level < 0 || level >= n_levels) return JXLH_ERR_INVALID_ARGUMENT;
+  squeeze_tile_kinds(n_planes, levels, tiles, level, kinds);
+  return JXLH_OK;
+}
+
+// A progressive preview per grid cell: validate, plan (squeeze_tiles_plan.h), issue.  With no mixed level the call is
+// jxlh_unsqueeze_chain_preview; else the regular prefix as the chain it is, the work lists in one copy, then per needed
+// level its whole-level launch or its two list launches, in stream order.
+jxlh_status jxlh_unsqueeze_chain_preview_tiles(jxlh_ctx* ctx, int32_t n_planes, int32_t n_levels, const jxlh_squeeze_level* levels,
+                                               const jxlh_squeeze_tiles* tiles, const int32_t* const base[], size_t base_stride,
+                                               uint32_t base_w, uint32_t base_h, int32_t* const out[], size_t out_stride,
+                                               int32_t rct_op, int32_t rct_perm, uint32_t flags) {
+  JXLH_ON_DEVICE(ctx);
+  const bool with_rct = rct_op >= 0;
+  if (!ctx || (with_rct && (n_planes != 3 || rct_op > 6 || rct_perm < 0 || rct_perm > 5)) ||
+      (flags != 0 && flags != JXLH_SMOOTH_CVT_NEAREST_EVEN))
+    return JXLH_ERR_INVALID_ARGUMENT;
+  jxlh_status st;
+  if ((st = check_squeeze_chain(n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, is_device_ptr, true)))
+    return st;
+  if ((st = check_squeeze_tiles(n_levels, levels, tiles))) return st;
+  if ((st = ensure(ctx, ctx->hook_i[0], std::max<size_t>(squeeze_arena(n_planes, n_levels, levels).total, 1)))) return st;
+  const SqueezeChainIn in = chain_in(ctx, n_planes, n_levels, levels, base, base_stride, base_w, base_h, out, out_stride, with_rct);
+  const SqueezeTilesPlan plan = plan_squeeze_tiles(in, tiles);
+  if (!plan.mixed)
+    return jxlh_unsqueeze_chain_preview(ctx, n_planes, n_levels, plan.folded.data(), base, base_stride, base_w, base_h, out, out_stride,
+                                        rct_op, rct_perm, flags);
+  if (plan.too_large) return JXLH_ERR_UNSUPPORTED;
+  // the lists: one pinned block, one copy
+  const size_t n_rec = plan.upload_records;
+  if ((st = ensure(ctx, ctx->sq_tiles_dev, std::max<size_t>(n_rec, 1)))) return st;
+  Pinned<int4>& host = ctx->sq_tiles_host[ctx->sq_tiles_next];
+  Fence& copied = ctx->sq_tiles_copied[ctx->sq_tiles_next];
+  ctx->sq_tiles_next = (ctx->sq_tiles_next + 1) % jxlh_ctx::kSqTilesRing;
+  HIPCHK(ctx, copied.sync());  // the block's previous lists are on the device
+  copied.clear();
+  if (host.n < n_rec) {
+    HIPCHK(ctx, host.reset());
+    HIPCHK(ctx, host.alloc(n_rec + n_rec / 2));
+  }
+  static_assert(sizeof(SqTileSmoothCell) == sizeof(int4) && sizeof(SqTileRun) == sizeof(int4), "the lists are 16-byte records");
+  for (const SqTilesEntry& e : plan.entry) {
+    if (!e.smooth.empty()) std::memcpy(host.p + e.smooth_off, e.smooth.data(), e.smooth.size() * sizeof(int4));
+    if (!e.runs.empty()) std::memcpy(host.p + e.runs_off, e.runs.data(), e.runs.size() * sizeof(int4));
+  }
+  if (n_rec) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sq_tiles_dev.p, host.p, n_rec * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, copied.record(ctx->stream));
+  }
+  if (plan.n_prefix > 0 && (st = issue_chain(ctx, plan.prefix_in, plan.prefix, rct_op, rct_perm))) return st;
+  // one timer per launch: whole levels under the preview call's name, the list launches under their kernels'
+  for (const SqTilesEntry& e : plan.entry) {
+    const jxlh_squeeze_level& lv = levels[e.level];
+    const SqueezeStep step = squeeze_level_step(in, plan.arena, e.level, e.src, e.dst);
+    if (e.kind == JXLH_PREVIEW_REGULAR) {
+      ScopedKernelTimer t(ctx, "k6_unsqueeze_chain_preview");
+      for (int j = 0; j < e.n_launch; j++) issue_step(ctx->stream, e.launch[j], step, rct_op, rct_perm);
+      continue;
+    }
+    const int32_t* src[3] = {};
+    const int32_t* src2[3] = {};
+    int32_t* dst[3] = {};
+    for (int p = 0; p < n_planes; p++) {
+      src[p] = (const int32_t*)squeeze_plane_addr(in, plan.arena, e.src, p);
+      src2[p] = (const int32_t*)squeeze_plane_addr(in, plan.arena, e.src2, p);
+      dst[p] = (int32_t*)squeeze_plane_addr(in, plan.arena, e.dst, p);
+    }
+    if (e.kind >= 0) {  // every cell smooth, of one kind: the whole-level launch
+      const bool two_d = e.kind == JXLH_PREVIEW_SMOOTH_2D;
+      ScopedKernelTimer t(ctx, "k6_unsqueeze_chain_preview");
+      launch_smooth_unsqueeze_planes(ctx->stream, two_d ? JXLH_SMOOTH_2D : lv.horizontal ? JXLH_SMOOTH_H : JXLH_SMOOTH_V, n_planes,
+                                     two_d ? src2 : src, two_d ? e.src2.stride : e.src.stride, (int)(two_d ? e.src2_w : e.src_w),
+                                     (int)(two_d ? e.src2_h : e.src_h), dst, e.dst.stride, (int)lv.out_w, (int)lv.out_h, flags != 0,
+                                     e.rct ? rct_op : -1, rct_perm);
+      continue;
+    }
+    if (!e.smooth.empty()) {
+      ScopedKernelTimer t(ctx, "k6_smooth_unsqueeze_cells");
+      launch_smooth_unsqueeze_cells(ctx->stream, e.horizontal, n_planes, src, e.src.stride, (int)e.src_w, (int)e.src_h, src2, e.src2.stride,
+                                    (int)e.src2_w, (int)e.src2_h, dst, e.dst.stride,
+                                    reinterpret_cast<const SqTileSmoothCell*>(ctx->sq_tiles_dev.p + e.smooth_off), (uint32_t)e.smooth.size(),
+                                    e.tiles_x, e.tiles_per_cell, flags != 0);
+    }
+    if (!e.runs.empty()) {
+      ScopedKernelTimer t(ctx, "k6_unsqueeze_runs");
+      launch_unsqueeze_runs(ctx->stream, step, reinterpret_cast<const SqTileRun*>(ctx->sq_tiles_dev.p + e.runs_off), (uint32_t)e.runs.size(),
+                            e.groups_per_run);
+    }
+    if (e.rct) {
+      ScopedKernelTimer t(ctx, "k4_rct");
+      if (e.dst.stride == lv.out_w) launch_rct(ctx->stream, dst[0], dst[1], dst[2], (size_t)lv.out_w * lv.out_h, rct_op, rct_perm);
+      else launch_rct_rows(ctx->stream, dst[0], dst[1], dst[2], lv.out_w, lv.out_h, e.dst.stride, rct_op, rct_perm);
+    }
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return JXLH_OK;
+}
+
 jxlh_status jxlh_unsqueeze_rct(jxlh_ctx* ctx, int32_t horizontal, const int32_t* const avg[3], size_t avg_stride,
                                const int32_t* const res[3], size_t res_stride, uint32_t out_w, uint32_t out_h,
                                int32_t* const out[3], size_t out_stride, int32_t op, int32_t perm) {

@@ -162,6 +162,14 @@ struct jxlh_ctx {
   // jxlh_unsqueeze_chain's dataflow launches (k6_unsqueeze_flow): ticket + progress words, zeroed per launch; the error
   // word (zeroed when allocated and after an error was reported) is read back by the next jxlh_ctx_sync
   DevBuf<int> flow_words;
+  // jxlh_unsqueeze_chain_preview_tiles: the call's work lists (16-byte records) on the device; they go up from a pinned
+  // block, reused once its fence (recorded behind the copy) has passed.  The call returns while the copy is queued, and
+  // a caller paints again at once: a ring of blocks, so that a call waits for the copy of the fourth call before it
+  static constexpr int kSqTilesRing = 4;
+  DevBuf<int4> sq_tiles_dev;
+  Pinned<int4> sq_tiles_host[kSqTilesRing];
+  Fence sq_tiles_copied[kSqTilesRing];
+  int sq_tiles_next = 0;
   bool flow_used = false;
   Pinned<int> host_flow_flag;  // device-visible: the dataflow launches' error word (0 = none)
   // jxlh_flow_profile (jxl_hip_dev.h): per-level timeline of the last dataflow launch

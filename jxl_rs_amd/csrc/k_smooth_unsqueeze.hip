@@ -78,7 +78,8 @@ __device__ __forceinline__ int32_t smooth_eval(const float (&n)[25]) {
 // One workgroup's tile of NCH planes of one geometry: NCH == 1 is a plane on its own; NCH == 3 stages the three
 // channels' windows, a thread produces the same output samples of all three, and the inverse RCT (`op`, the planes of
 // `out` already permuted: out[k] receives w_k) runs on them in registers before the one store.
-// pair: base and stride keep every sample pair 8-byte aligned
+// pair: base and stride keep every sample pair 8-byte aligned.  The tile's first average sample in the rectangle comes
+// from blockIdx.x / .y (whole planes, rectangles) or, LISTED, from the caller (listed cells: the cell's own tile count)
 struct SmoothGeom {
   size_t in_stride, out_stride;
   int in_w, in_h, cx0, cy0, out_w, out_h, nx, ny;
@@ -95,11 +96,12 @@ __device__ __forceinline__ void smooth_rct(int op, int32_t& a, int32_t& b, int32
     default: rct_op<6>(v0, v1, v2, a, b, c); break;
   }
 }
-template <int KIND, bool RNE, int NCH>
+template <int KIND, bool RNE, int NCH, bool LISTED = false>
 __device__ __forceinline__ void smooth_tile(float (&tile)[NCH][JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1], const int32_t* const (&in)[NCH],
-                                            int32_t* const (&out)[NCH], const SmoothGeom& g, bool pair, int op) {
+                                            int32_t* const (&out)[NCH], const SmoothGeom& g, bool pair, int op, int listed_bx = 0,
+                                            int listed_by = 0) {
   const int tid = threadIdx.x;
-  const int bx = blockIdx.x * JXLH_SM_TX, by = blockIdx.y * JXLH_SM_TY;
+  const int bx = LISTED ? listed_bx : blockIdx.x * JXLH_SM_TX, by = LISTED ? listed_by : blockIdx.y * JXLH_SM_TY;
   // The window, (TY + 4) x (TX + 4) samples per plane, is fetched as a flat list, thread t taking samples t, t + 256, ...:
   // no branch between the loads, so all of a thread's fetches are in flight before the first is written to LDS (one
   // wave per row with lanes 0..3 fetching the extra columns under a branch waited for every load in turn).  The last
@@ -297,6 +299,85 @@ void launch_smooth_unsqueeze_planes(hipStream_t s, int kind, int n_planes, const
     default: JXLH_SM_LAUNCH(2, true); break;
   }
 #undef JXLH_SM_LAUNCH
+}
+
+// The smooth cells of a partly arrived level (jxlh_unsqueeze_chain_preview_tiles, squeeze_tiles_plan.h): one launch over
+// the listed cells, tiles_per_cell workgroups each (what a full 1-D cell needs; a cell that needs fewer -- a 2-D one, a
+// ragged last one -- sends the surplus home), the plane in blockIdx.y.  A cell is jxlh_smooth_unsqueeze on its rect: 1-D
+// along the level's axis from the level's average (in1), or 2-D from the average the level before reads (in2).  A cell
+// without one complete pair on a doubled axis is what the reference leaves of a fresh buffer: zero.
+static_assert(JXLH_SQC_TX == JXLH_SM_TX && JXLH_SQC_TY == JXLH_SM_TY, "squeeze_tiles_plan.h counts the workgroups of a cell");
+struct SmoothCellsArgs {
+  const int32_t* in1[3];
+  const int32_t* in2[3];
+  int32_t* out[3];
+  size_t in1_stride, in2_stride, out_stride;
+  int in1_w, in1_h, in2_w, in2_h;
+  const SqTileSmoothCell* cells;
+  uint32_t tiles_x, tiles_per_cell;
+};
+template <bool HORIZ, bool RNE>
+__global__ __launch_bounds__(JXLH_SM_TX* JXLH_SM_WAVES) void k6_smooth_unsqueeze_cells(const SmoothCellsArgs A) {
+  __shared__ float tile[1][JXLH_SM_TY + 4][JXLH_SM_TX + 4 + 1];
+  const uint32_t cell = blockIdx.x / A.tiles_per_cell, t = blockIdx.x - cell * A.tiles_per_cell;
+  const SqTileSmoothCell c = A.cells[cell];
+  const bool two_d = (c.h_kind & 3) == JXLH_PREVIEW_SMOOTH_2D;
+  const int w = c.w, h = c.h_kind >> 2;
+  const bool fx = two_d || HORIZ, fy = two_d || !HORIZ;
+  const int nx = fx ? (w + 1) / 2 : w, ny = fy ? (h + 1) / 2 : h;
+  const int bx = (int)(t % A.tiles_x) * JXLH_SM_TX, by = (int)(t / A.tiles_x) * JXLH_SM_TY;
+  if (bx >= nx || by >= ny) return;  // workgroup-uniform, in front of every barrier
+  int32_t* const o = A.out[blockIdx.y] + (size_t)c.y0 * A.out_stride + c.x0;
+  if ((fx ? w / 2 : w) == 0 || (fy ? h / 2 : h) == 0) {
+    const int ox0 = fx ? 2 * bx : bx, oy0 = fy ? 2 * by : by;
+    const int ow = min(w - ox0, fx ? 2 * JXLH_SM_TX : JXLH_SM_TX), oh = min(h - oy0, fy ? 2 * JXLH_SM_TY : JXLH_SM_TY);
+    for (int i = threadIdx.x; i < ow * oh; i += JXLH_SM_TX * JXLH_SM_WAVES) o[(size_t)(oy0 + i / ow) * A.out_stride + ox0 + i % ow] = 0;
+    return;
+  }
+  int32_t* const ov[1] = {o};
+  const bool pair = ((uintptr_t)o & 7) == 0 && (A.out_stride & 1) == 0;
+  if (two_d) {
+    const int32_t* const iv[1] = {A.in2[blockIdx.y]};
+    smooth_tile<2, RNE, 1, true>(tile, iv, ov, SmoothGeom{A.in2_stride, A.out_stride, A.in2_w, A.in2_h, c.x0 / 2, c.y0 / 2, w, h, nx, ny}, pair, 0,
+                           bx, by);
+  } else {
+    const int32_t* const iv[1] = {A.in1[blockIdx.y]};
+    smooth_tile<HORIZ ? 0 : 1, RNE, 1, true>(tile, iv, ov,
+                                       SmoothGeom{A.in1_stride, A.out_stride, A.in1_w, A.in1_h, HORIZ ? c.x0 / 2 : c.x0,
+                                                  HORIZ ? c.y0 : c.y0 / 2, w, h, nx, ny},
+                                       pair, 0, bx, by);
+  }
+}
+
+void launch_smooth_unsqueeze_cells(hipStream_t s, bool horizontal, int n_planes, const int32_t* const in1[], size_t in1_stride,
+                                   int in1_w, int in1_h, const int32_t* const in2[], size_t in2_stride, int in2_w, int in2_h,
+                                   int32_t* const out[], size_t out_stride, const SqTileSmoothCell* cells, uint32_t n_cells,
+                                   uint32_t tiles_x, uint32_t tiles_per_cell, bool cvt_rne) {
+  if (n_cells == 0) return;
+  SmoothCellsArgs A{};
+  for (int p = 0; p < n_planes; p++) {
+    A.in1[p] = in1[p];
+    A.in2[p] = in2[p];
+    A.out[p] = out[p];
+  }
+  A.in1_stride = in1_stride;
+  A.in2_stride = in2_stride;
+  A.out_stride = out_stride;
+  A.in1_w = in1_w;
+  A.in1_h = in1_h;
+  A.in2_w = in2_w;
+  A.in2_h = in2_h;
+  A.cells = cells;
+  A.tiles_x = tiles_x;
+  A.tiles_per_cell = tiles_per_cell;
+  const dim3 grid(n_cells * tiles_per_cell, n_planes), block(JXLH_SM_TX * JXLH_SM_WAVES);
+  if (horizontal) {
+    if (cvt_rne) hipLaunchKernelGGL((k6_smooth_unsqueeze_cells<true, true>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((k6_smooth_unsqueeze_cells<true, false>), grid, block, 0, s, A);
+  } else {
+    if (cvt_rne) hipLaunchKernelGGL((k6_smooth_unsqueeze_cells<false, true>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((k6_smooth_unsqueeze_cells<false, false>), grid, block, 0, s, A);
+  }
 }
 
 }  // namespace jxlh

@@ -1079,6 +1079,92 @@ void launch_unsqueeze(hipStream_t s, const SqueezeLaunch& how, const SqueezeStep
 #undef JXLH_SQ_LAUNCH
 }
 
+// ---- the regular runs of a partly arrived level (jxlh_unsqueeze_chain_preview_tiles, squeeze_tiles_plan.h).  A run is a
+// stretch of pairs [pair0, pair0 + n_pairs) of the lines [line0, line0 + n_lines): regular cells side by side along the
+// squeezed axis.  One launch over the listed runs, groups_per_run workgroups each (a ragged last cell row sends the
+// surplus home), lanes are lines in groups of 64, the plane in blockIdx.y.  The recurrence starts from the output sample
+// in front of the run -- the smooth launch ahead in the stream wrote it -- or from avg[0] at the channel's start, and ends
+// on the average across the run's edge (avg[x + 1]; at the channel's end avg[x] itself).  Residuals outside the run are
+// never read.  Loads of the next U steps are in flight while the current U run, as in k6_unsqueeze.
+namespace {
+static_assert(JXLH_SQC_LINES == 64, "squeeze_tiles_plan.h counts the workgroups of a run");
+template <bool HORIZ>
+__global__ __launch_bounds__(64) void k6_unsqueeze_runs(const SqueezePlanes pl, size_t avg_stride, size_t res_stride, size_t out_stride,
+                                                        int n_out, const SqTileRun* __restrict__ runs, uint32_t groups_per_run) {
+  const uint32_t run = blockIdx.x / groups_per_run, grp = blockIdx.x - run * groups_per_run;
+  const SqTileRun rn = runs[run];
+  const int l = (int)grp * 64 + (int)threadIdx.x;
+  if (l >= (rn.n_lines_tail >> 1)) return;
+  const size_t line = (size_t)(rn.line0 + l);
+  const size_t alp = HORIZ ? avg_stride : 1, aep = HORIZ ? 1 : avg_stride;
+  const size_t rlp = HORIZ ? res_stride : 1, rep = HORIZ ? 1 : res_stride;
+  const size_t olp = HORIZ ? out_stride : 1, oep = HORIZ ? 1 : out_stride;
+  const int32_t* __restrict__ a = pl.avg[blockIdx.y] + line * alp;
+  const int32_t* __restrict__ r = pl.res[blockIdx.y] + line * rlp;
+  int32_t* o = pl.out[blockIdx.y] + line * olp;
+  const int last_avg = n_out - n_out / 2 - 1;
+  int i = rn.pair0;
+  const int end = rn.pair0 + rn.n_pairs;
+  if (rn.n_pairs > 0) {
+    int32_t cur = a[(size_t)i * aep];
+    const int32_t prev = i == 0 ? cur : o[(size_t)(2 * i - 1) * oep];
+    int32_t d = wsub(prev, cur);
+    constexpr int U = 8;
+    int32_t na[U], rr[U], nb[U], rb[U];
+    auto load_block = [&](int i0, int32_t(&xa)[U], int32_t(&xr)[U]) {
+#pragma unroll
+      for (int k = 0; k < U; k++) {
+        xa[k] = a[(size_t)min(i0 + k + 1, last_avg) * aep];
+        xr[k] = r[(size_t)(i0 + k) * rep];
+      }
+    };
+    auto run_block = [&](int i0, const int32_t(&xa)[U], const int32_t(&xr)[U]) {
+#pragma unroll
+      for (int k = 0; k < U; k++) {
+        int32_t va, vb;
+        unsqueeze_step(cur, xr[k], xa[k], d, va, vb);
+        o[(size_t)(2 * (i0 + k)) * oep] = va;
+        o[(size_t)(2 * (i0 + k) + 1) * oep] = vb;
+        cur = xa[k];
+      }
+    };
+    const int n_blocks = rn.n_pairs / U;
+    if (n_blocks > 0) {
+      load_block(i, na, rr);
+      int blk = 0;
+      for (; blk + 2 <= n_blocks; blk += 2) {
+        load_block(i + (blk + 1) * U, nb, rb);
+        run_block(i + blk * U, na, rr);
+        if (blk + 2 < n_blocks) load_block(i + (blk + 2) * U, na, rr);
+        run_block(i + (blk + 1) * U, nb, rb);
+      }
+      if (blk < n_blocks) run_block(i + blk * U, na, rr);
+      i += n_blocks * U;
+    }
+    for (; i < end; i++) {
+      const int32_t nxt = a[(size_t)min(i + 1, last_avg) * aep];
+      int32_t va, vb;
+      unsqueeze_step(cur, r[(size_t)i * rep], nxt, d, va, vb);
+      o[(size_t)(2 * i) * oep] = va;
+      o[(size_t)(2 * i + 1) * oep] = vb;
+      cur = nxt;
+    }
+  }
+  if (rn.n_lines_tail & 1) o[(size_t)(2 * end) * oep] = a[(size_t)end * aep];  // odd size: the trailing average is copied
+}
+}  // namespace
+void launch_unsqueeze_runs(hipStream_t s, const SqueezeStep& st, const SqTileRun* runs, uint32_t n_runs, uint32_t groups_per_run) {
+  if (n_runs == 0 || st.n_planes <= 0) return;
+  const SqueezePlanes pl = planes_of(st);
+  const dim3 grid(n_runs * groups_per_run, st.n_planes);
+  if (st.horizontal)
+    hipLaunchKernelGGL(k6_unsqueeze_runs<true>, grid, dim3(64), 0, s, pl, st.avg_stride, st.res_stride, st.out_stride, (int)st.out_w, runs,
+                       groups_per_run);
+  else
+    hipLaunchKernelGGL(k6_unsqueeze_runs<false>, grid, dim3(64), 0, s, pl, st.avg_stride, st.res_stride, st.out_stride, (int)st.out_h, runs,
+                       groups_per_run);
+}
+
 // ---- dataflow launch of consecutive tiled steps (see k6_unsqueeze_flow)
 static_assert(sizeof(FlowArgs) <= 4096, "kFlowMaxLevels levels (squeeze_plan.h) travel as kernel arguments");
 void launch_unsqueeze_flow(hipStream_t s, int n_steps, const SqueezeStep* steps, const uint8_t* vec, int* scratch, int* error,

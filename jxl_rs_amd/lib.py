@@ -266,6 +266,43 @@ def squeeze_preview_kinds(levels, base_w, base_h, n_planes=1):
     return kinds[:len(levels)], live[:len(levels)]
 
 
+def _squeeze_tiles(levels, tiles):
+    """[(tile_w, tile_h, present)] per level as a jxlh_squeeze_tiles array (+ what keeps the masks alive): present is
+    None or a [tiles_y, tiles_x] array, non-zero where the cell's residuals have arrived; (0, 0, ...) is one cell"""
+    assert len(tiles) == len(levels), "one grid per level"
+    arr, keep = (SqueezeTiles * max(len(levels), 1))(), []
+    for i, ((_, ow, oh, _, _), (tw, th, present)) in enumerate(zip(levels, tiles)):
+        arr[i].tile_w, arr[i].tile_h = tw, th
+        if present is not None:
+            m = np.ascontiguousarray(present, dtype=np.uint8)
+            if tw and th:
+                assert m.shape == (-(-oh // th), -(-ow // tw)), f"level {i}: the mask is [tiles_y, tiles_x]"
+            keep.append(m)
+            arr[i].present = m.ctypes.data
+    return arr, keep
+
+
+def squeeze_tile_grid(level, tile):
+    """(tiles_x, tiles_y) of a level (horizontal, out_w, out_h, ...) under a grid (tile_w, tile_h, ...)"""
+    tw, th = (tile[0], tile[1]) if tile[0] and tile[1] else (level[1], level[2])
+    return -(-level[1] // tw), -(-level[2] // th)
+
+
+def squeeze_tile_kinds(levels, tiles, base_w, base_h, level, n_planes=1):
+    """jxlh_squeeze_tile_kinds (host only): the kind of every grid cell of `level` (PREVIEW_REGULAR / _SMOOTH_1D /
+    _SMOOTH_2D) -> uint8 [tiles_y, tiles_x].  levels as for squeeze_preview_kinds, tiles as for
+    Context.unsqueeze_chain_preview_tiles."""
+    arr = _squeeze_levels(levels, n_planes)
+    tarr, keep = _squeeze_tiles(levels, tiles)
+    nx, ny = squeeze_tile_grid(levels[level], tiles[level]) if 0 <= level < len(levels) else (1, 1)
+    kinds = np.zeros((ny, nx), np.uint8)
+    st = _lib().jxlh_squeeze_tile_kinds(n_planes, len(levels), C.cast(arr, C.c_void_p), C.cast(tarr, C.c_void_p), base_w, base_h,
+                                        level, _addr(kinds))
+    if st != OK:
+        raise JxlHipError(st, "squeeze_tile_kinds")
+    return kinds
+
+
 WORKLIST_REGIONS = 42  # jxlh_worklist_layout: counters, 11 class lists, 9 + 9 + 9 DCT-class regions, fb_any, units, LLF
 
 
@@ -1572,6 +1609,25 @@ class Context:
         self._chk(self.L.jxlh_unsqueeze_chain_preview(self._ctx, n_planes, len(levels), C.cast(arr, C.c_void_p), bv,
                                                       base_stride, base_w, base_h, ov, out_stride, op, perm, flags),
                   "unsqueeze_chain_preview")
+
+    def unsqueeze_chain_preview_tiles(self, levels, tiles, base, base_stride, base_w, base_h, out, out_stride, rct=None,
+                                      cvt_rne=False, flags=None):
+        """A progressive preview per grid cell in one call (jxlh_unsqueeze_chain_preview_tiles): arguments as
+        unsqueeze_chain_preview plus tiles = [(tile_w, tile_h, present)] per level -- present None, or a [tiles_y,
+        tiles_x] array that is non-zero where the cell's residual samples have arrived (squeeze_tile_kinds says what
+        each cell runs).  The residual planes of a partly arrived level are whole planes; samples of missing cells are
+        not read."""
+        n_planes = len(base)
+        arr = _squeeze_levels(levels, n_planes)
+        tarr, keep = _squeeze_tiles(levels, tiles)
+        bv = (C.c_void_p * n_planes)(*[_addr(a).value for a in base])
+        ov = (C.c_void_p * n_planes)(*[_addr(a).value for a in out])
+        op, perm = rct if rct is not None else (-1, 0)
+        if flags is None:
+            flags = self.SMOOTH_CVT_NEAREST_EVEN if cvt_rne else 0
+        self._chk(self.L.jxlh_unsqueeze_chain_preview_tiles(self._ctx, n_planes, len(levels), C.cast(arr, C.c_void_p),
+                                                            C.cast(tarr, C.c_void_p), bv, base_stride, base_w, base_h, ov,
+                                                            out_stride, op, perm, flags), "unsqueeze_chain_preview_tiles")
 
     def unsqueeze_rct(self, horizontal, avg, res, out, out_w, out_h, avg_stride, res_stride, out_stride, op, perm):
         """Unsqueeze of three device-resident planes fused with the inverse RCT on them."""

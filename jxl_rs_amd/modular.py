@@ -51,6 +51,14 @@ class ModularChain:
                                          [d.ptr for d in self.d_out], self.w, rct=self.rct, cvt_rne=cvt_rne)
         return self.d_out
 
+    def preview_tiles(self, tiles, cvt_rne=False):
+        """the progressive preview with the residual GROUPS partly arrived: tiles = [(tile_w, tile_h, present)] per level
+        (Context.unsqueeze_chain_preview_tiles), one jxlh_unsqueeze_chain_preview_tiles call, asynchronous.  The residual
+        planes stay where they are: cells whose byte of `present` is 0 are not read.  Returns the three device planes."""
+        self.ctx.unsqueeze_chain_preview_tiles(self.levels, tiles, [d.ptr for d in self.d_base], self.base_w, self.base_w,
+                                               self.base_h, [d.ptr for d in self.d_out], self.w, rct=self.rct, cvt_rne=cvt_rne)
+        return self.d_out
+
     # ---- BASELINE configs[3] across GPUs: "Squeeze + RCT + Palette, group shard + all-gather".  The squeeze
     # recurrence is serial along whole lines (DESIGN.md section 6: replicas only), so every rank runs the chain; the
     # per-sample transforms behind it are sharded -- rank r runs the RCT in place on ITS share of the chain's output

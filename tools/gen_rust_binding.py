@@ -20,6 +20,8 @@ PREVIEW_HEADER = os.path.join(ROOT, "include", "jxl_hip_preview.h")
 OUT_PREVIEW = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "preview.rs")
 SAVE_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_save_rects.h")
 OUT_SAVE_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "save_rects.rs")
+PREVIEW_TILES_HEADER = os.path.join(ROOT, "include", "jxl_hip_preview_tiles.h")
+OUT_PREVIEW_TILES = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "preview_tiles.rs")
 
 SCALARS = {"uint8_t": "u8", "int8_t": "i8", "uint16_t": "u16", "int16_t": "i16", "uint32_t": "u32", "int32_t": "i32",
            "uint64_t": "u64", "int64_t": "i64", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -154,6 +156,8 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod preview;")
     w("// include/jxl_hip_save_rects.h (... src/save_rects.rs)")
     w("pub mod save_rects;")
+    w("// include/jxl_hip_preview_tiles.h (... src/preview_tiles.rs)")
+    w("pub mod preview_tiles;")
     return "\n".join(out) + "\n"
 
 
@@ -198,8 +202,13 @@ def generate_save_rects():
     return emit_extension(os.path.basename(SAVE_RECTS_HEADER), *parse_header(open(SAVE_RECTS_HEADER).read()))
 
 
+def generate_preview_tiles():
+    return emit_extension(os.path.basename(PREVIEW_TILES_HEADER), *parse_header(open(PREVIEW_TILES_HEADER).read()))
+
+
 def main():
-    for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects())):
+    for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
+                      (OUT_PREVIEW_TILES, generate_preview_tiles())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
             if cur != text:
