@@ -8,7 +8,7 @@
 #include "coeff_epoch.h"
 #include "splines_host.h"
 #include "squeeze_plan.h"
-#include "squeeze_tiles_plan.h"
+#include "squeeze_preview_plan.h"
 
 namespace jxlh {
 // 16-byte global accesses with a selectable cache policy (NT = streamed once: `nt` loads / stores)
@@ -447,7 +447,7 @@ void launch_smooth_unsqueeze(hipStream_t s, int kind, const int32_t* in, size_t 
 void launch_smooth_unsqueeze_planes(hipStream_t s, int kind, int n_planes, const int32_t* const in[], size_t in_stride, int in_w,
                                     int in_h, int32_t* const out[], size_t out_stride, int out_w, int out_h, bool cvt_rne, int op,
                                     int perm);
-// the two launches of a partly arrived level (squeeze_tiles_plan.h; the lists are device memory).  Smooth cells: 1-D
+// the two launches of a partly arrived level (squeeze_preview_plan.h; the lists are device memory).  Smooth cells: 1-D
 // cells along the level's axis from in1 (the level's average), 2-D cells from in2 (what the level before reads)
 void launch_smooth_unsqueeze_cells(hipStream_t s, bool horizontal, int n_planes, const int32_t* const in1[], size_t in1_stride,
                                    int in1_w, int in1_h, const int32_t* const in2[], size_t in2_stride, int in2_w, int in2_h,

@@ -301,12 +301,12 @@ void launch_smooth_unsqueeze_planes(hipStream_t s, int kind, int n_planes, const
 #undef JXLH_SM_LAUNCH
 }
 
-// The smooth cells of a partly arrived level (jxlh_unsqueeze_chain_preview_tiles, squeeze_tiles_plan.h): one launch over
+// The smooth cells of a partly arrived level (jxlh_unsqueeze_chain_preview_tiles, squeeze_preview_plan.h): one launch over
 // the listed cells, tiles_per_cell workgroups each (what a full 1-D cell needs; a cell that needs fewer -- a 2-D one, a
 // ragged last one -- sends the surplus home), the plane in blockIdx.y.  A cell is jxlh_smooth_unsqueeze on its rect: 1-D
 // along the level's axis from the level's average (in1), or 2-D from the average the level before reads (in2).  A cell
 // without one complete pair on a doubled axis is what the reference leaves of a fresh buffer: zero.
-static_assert(JXLH_SQC_TX == JXLH_SM_TX && JXLH_SQC_TY == JXLH_SM_TY, "squeeze_tiles_plan.h counts the workgroups of a cell");
+static_assert(JXLH_SQC_TX == JXLH_SM_TX && JXLH_SQC_TY == JXLH_SM_TY, "squeeze_preview_plan.h counts the workgroups of a cell");
 struct SmoothCellsArgs {
   const int32_t* in1[3];
   const int32_t* in2[3];

@@ -1079,7 +1079,7 @@ void launch_unsqueeze(hipStream_t s, const SqueezeLaunch& how, const SqueezeStep
 #undef JXLH_SQ_LAUNCH
 }
 
-// ---- the regular runs of a partly arrived level (jxlh_unsqueeze_chain_preview_tiles, squeeze_tiles_plan.h).  A run is a
+// ---- the regular runs of a partly arrived level (jxlh_unsqueeze_chain_preview_tiles, squeeze_preview_plan.h).  A run is a
 // stretch of pairs [pair0, pair0 + n_pairs) of the lines [line0, line0 + n_lines): regular cells side by side along the
 // squeezed axis.  One launch over the listed runs, groups_per_run workgroups each (a ragged last cell row sends the
 // surplus home), lanes are lines in groups of 64, the plane in blockIdx.y.  The recurrence starts from the output sample
@@ -1087,7 +1087,7 @@ void launch_unsqueeze(hipStream_t s, const SqueezeLaunch& how, const SqueezeStep
 // on the average across the run's edge (avg[x + 1]; at the channel's end avg[x] itself).  Residuals outside the run are
 // never read.  Loads of the next U steps are in flight while the current U run, as in k6_unsqueeze.
 namespace {
-static_assert(JXLH_SQC_LINES == 64, "squeeze_tiles_plan.h counts the workgroups of a run");
+static_assert(JXLH_SQC_LINES == 64, "squeeze_preview_plan.h counts the workgroups of a run");
 template <bool HORIZ>
 __global__ __launch_bounds__(64) void k6_unsqueeze_runs(const SqueezePlanes pl, size_t avg_stride, size_t res_stride, size_t out_stride,
                                                         int n_out, const SqTileRun* __restrict__ runs, uint32_t groups_per_run) {

@@ -1,5 +1,5 @@
 // The route of an inverse squeeze: which kernel takes which levels of a chain (or a single step), in which variant,
-// from which planes to which -- decided here, issued by abi_modular.hip through the launchers of k_squeeze.hip.
+// from which planes to which -- decided here, issued by abi_squeeze.hip through the launchers of k_squeeze.hip.
 // Plain C++, fixed-size arrays, no heap: host logic, tested without a device (tests/cpp/squeeze_plan.cc).
 #pragma once
 #include <stddef.h>

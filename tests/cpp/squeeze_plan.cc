@@ -117,7 +117,7 @@ bool old_launch_unsqueeze_levels(int n_planes, int n_levels, const int* horizont
   }
   return true;
 }
-// ---- abi_modular.hip: the geometry check of jxlh_unsqueeze_levels and jxlh_unsqueeze_chain (every pointer a device one)
+// ---- abi_squeeze.hip: the geometry check of jxlh_unsqueeze_levels and jxlh_unsqueeze_chain (every pointer a device one)
 jxlh_status old_check(int n_planes, int n_levels, const jxlh_squeeze_level* levels, const cptr base[], size_t base_stride,
                       uint32_t base_w, uint32_t base_h, const mptr out[], size_t out_stride) {
   if (!levels || !base || !out || n_planes < 1 || n_planes > 3 || n_levels < 1 || n_levels > 64 || base_w == 0 ||
@@ -140,7 +140,7 @@ jxlh_status old_check(int n_planes, int n_levels, const jxlh_squeeze_level* leve
     if (!base[p] || !out[p]) return JXLH_ERR_INVALID_ARGUMENT;
   return JXLH_OK;
 }
-// ---- abi_modular.hip: jxlh_unsqueeze_chain between the check and the return, launches recorded instead of issued
+// ---- abi_squeeze.hip: jxlh_unsqueeze_chain between the check and the return, launches recorded instead of issued
 struct Chain {
   int n_planes, n_levels;
   std::vector<jxlh_squeeze_level> levels;

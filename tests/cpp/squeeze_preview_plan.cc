@@ -1,44 +1,12 @@
-// The preview planner (jxl_rs_amd/csrc/squeeze_preview_plan.h) on its own, over random chains: directions, sizes,
+// The preview planner (jxl_rs_amd/csrc/squeeze_preview_plan.h) without grids, over random chains: directions, sizes,
 // plane counts, missing sets with holes, strides and addresses.  Checked: the argument rule for missing levels; kinds and
 // liveness by their definitions; the regular prefix is the chain plan of exactly those levels; behind it one entry per
 // live level and none for a dead one; every entry reads a plane set that was written before it, of the size it expects,
-// and writes its own; nothing reaches past the arena; the RCT rides on the last level only.  Host only, no device:
-// addresses are numbers.  Built plain and with -fsanitize=address,undefined (tests/test_squeeze_preview_cpu.py).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#include "../../jxl_rs_amd/csrc/squeeze_preview_plan.h"
-
-using namespace jxlh;
+// and writes its own; nothing reaches past the arena; the RCT rides on the last level only (the entry checks are
+// squeeze_preview_checks.h's, shared with squeeze_tiles_plan.cc).  Host only, no device: addresses are numbers.  Built plain and with -fsanitize=address,undefined (tests/test_squeeze_preview_cpu.py).
+#include "squeeze_preview_checks.h"
 
 namespace {
-
-int g_fail = 0;
-#define CHECK(c, ...)                          \
-  do {                                         \
-    if (!(c)) {                                \
-      if (g_fail++ < 20) {                     \
-        std::printf("FAIL %s: ", #c);          \
-        std::printf(__VA_ARGS__);              \
-        std::printf("\n");                     \
-      }                                        \
-    }                                          \
-  } while (0)
-
-uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-uint32_t rnd() {
-  g_rng ^= g_rng << 13;
-  g_rng ^= g_rng >> 7;
-  g_rng ^= g_rng << 17;
-  return (uint32_t)(g_rng >> 24);
-}
-uint32_t rnd(uint32_t lo, uint32_t hi) { return lo + rnd() % (hi - lo + 1); }
-
-bool same_launch(const SqueezeLaunch& a, const SqueezeLaunch& b) {
-  return a.kind == b.kind && a.level0 == b.level0 && a.n_levels == b.n_levels && a.vec == b.vec && a.ncw == b.ncw &&
-         a.src.where == b.src.where && a.src.stride == b.src.stride && a.dst.where == b.dst.where && a.dst.stride == b.dst.stride;
-}
 
 void one_chain(int id) {
   // ---- a chain: final size, directions from the last level down, sizes halving towards the base
@@ -110,10 +78,12 @@ void one_chain(int id) {
   }
 
   // ---- kinds and liveness, by their definitions
-  const SqueezePreviewPlan P = plan_squeeze_preview(in);
+  const SqueezePreviewPlan P = plan_squeeze_preview(in, nullptr);
   uint8_t kinds[kSqueezeMaxLevels], live[kSqueezeMaxLevels];
   squeeze_preview_kinds(n_planes, nl, lv, kinds, live);
-  CHECK(!std::memcmp(kinds, P.kinds, nl) && !std::memcmp(live, P.live, nl), "chain %d: the plan's kinds are the public ones", id);
+  for (int i = 0; i < nl; i++)
+    CHECK(P.kind[i] == (int)kinds[i] && P.live[i] == live[i], "chain %d level %d: the plan's kinds are the public ones", id, i);
+  CHECK(P.records.empty() && !P.too_large, "chain %d: lists without a grid", id);
   int reads[kSqueezeMaxLevels];  // the level whose output a level reads
   for (int i = 0; i < nl; i++) {
     const bool two_d = missing[i] && i > 0 && missing[i - 1] && (lv[i].horizontal != 0) != (lv[i - 1].horizontal != 0);
@@ -165,45 +135,10 @@ void one_chain(int id) {
     if (k >= P.n) break;
     const PreviewEntry& e = P.entry[k++];
     CHECK(e.level == i && e.kind == kinds[i], "chain %d entry %d: level %d kind %d", id, k - 1, e.level, e.kind);
-    CHECK(e.src_level == reads[i], "chain %d level %d reads %d, expected %d", id, i, e.src_level, reads[i]);
-    const int s = e.src_level;
-    CHECK(s == -1 || (s >= n_pre - 1 && s < i && written[s]), "chain %d level %d reads level %d before it is written", id, i, s);
-    // where: the base, or the arena's plane set of the level read; never `out` (only the last level writes it)
-    if (s < 0) CHECK(e.src.where == kSqBase && e.src.stride == in.base_stride, "chain %d level %d: base", id, i);
-    else CHECK(e.src.where == s && s < nl - 1 && e.src.stride == A.stride[s], "chain %d level %d: source plane set", id, i);
-    const uint32_t sw = s < 0 ? base_w : lv[s].out_w, sh = s < 0 ? base_h : lv[s].out_h;
-    CHECK(e.src_w == sw && e.src_h == sh, "chain %d level %d: reads %u x %u of a %u x %u plane", id, i, e.src_w, e.src_h, sw, sh);
-    // the smooth kernels' geometry: the doubled axes halve (rounding up) to the source
-    const bool fx = e.kind == JXLH_PREVIEW_SMOOTH_2D || lv[i].horizontal, fy = e.kind == JXLH_PREVIEW_SMOOTH_2D || !lv[i].horizontal;
-    CHECK(sw == (fx ? (lv[i].out_w + 1) / 2 : lv[i].out_w) && sh == (fy ? (lv[i].out_h + 1) / 2 : lv[i].out_h), "chain %d level %d: geometry", id, i);
-    if (e.kind != JXLH_PREVIEW_REGULAR)  // a complete pair on every doubled axis: the kernels write every sample
-      CHECK((fx ? lv[i].out_w / 2 : lv[i].out_w) > 0 && (fy ? lv[i].out_h / 2 : lv[i].out_h) > 0, "chain %d level %d: no pair", id, i);
-    if (i == nl - 1) CHECK(e.dst.where == kSqOut && e.dst.stride == in.out_stride, "chain %d: the last level writes out", id);
-    else CHECK(e.dst.where == i && e.dst.stride == A.stride[i], "chain %d level %d: destination", id, i);
-    // arena extents
-    for (const SqueezeLoc* l : {&e.src, &e.dst}) {
-      if (l->where < 0) continue;
-      const int a = l->where;
-      CHECK(a < nl - 1 && lv[a].out_w <= A.stride[a] && A.stride[a] * (size_t)lv[a].out_h <= A.plane[a] &&
-                A.off[a] + (size_t)n_planes * A.plane[a] <= A.total, "chain %d level %d: plane set %d leaves the arena", id, i, a);
-      for (int p = 0; p < n_planes; p++)
-        CHECK(squeeze_plane_addr(in, A, *l, p) == arena_addr(a, p) && arena_addr(a, p) + 4 * A.plane[a] <= in.arena + 4 * A.total, "chain %d", id);
-    }
-    // the RCT: on the last level alone, by the kernel that fits it
-    const bool last_rct = i == nl - 1 && in.with_rct;
-    if (e.kind == JXLH_PREVIEW_REGULAR) {
-      CHECK(!e.rct, "chain %d level %d", id, i);
-      const SqueezeStep st = squeeze_level_step(in, A, i, e.src, e.dst);
-      SqueezeLaunch L[2];
-      const int n = last_rct ? plan_squeeze_step_rct(st, in.separate_rct, L) : (L[0] = plan_squeeze_step(st), 1);
-      CHECK(e.n_launch == n, "chain %d level %d: %d launches", id, i, e.n_launch);
-      for (int j = 0; j < n && j < e.n_launch; j++) CHECK(same_launch(e.launch[j], L[j]), "chain %d level %d launch %d", id, i, j);
-      const bool has_rct = e.launch[0].kind == SqueezeLaunch::kFusedRct ||
-                           (e.n_launch == 2 && (e.launch[1].kind == SqueezeLaunch::kRctFlat || e.launch[1].kind == SqueezeLaunch::kRctRows));
-      CHECK(has_rct == last_rct, "chain %d level %d: RCT", id, i);
-    } else {
-      CHECK(e.rct == last_rct && e.n_launch == 0, "chain %d level %d: smooth RCT", id, i);
-    }
+    // (check_whole_entry holds the level read against the kind; reads[] is the definition's)
+    const int s = e.kind == JXLH_PREVIEW_SMOOTH_2D ? e.src2.where : e.src.where;
+    CHECK((s == kSqBase ? -1 : s) == reads[i], "chain %d level %d reads %d, expected %d", id, i, s, reads[i]);
+    check_whole_entry(id, in, e, n_pre, written);
     written[i] = true;
   }
   CHECK(k == P.n, "chain %d: %d entries, %d live levels behind the prefix", id, P.n, k);
@@ -229,7 +164,7 @@ int main(int argc, char** argv) {
     SqueezeChainIn in{};
     in.n_planes = 1; in.n_levels = kSqueezeMaxLevels; in.levels = lv; in.base_w = 1; in.base_h = 3; in.base_stride = 1; in.out_stride = 1;
     in.base[0] = in.out[0] = 64; in.arena = 4096;
-    const SqueezePreviewPlan P = plan_squeeze_preview(in);  // no residual samples anywhere: all regular
+    const SqueezePreviewPlan P = plan_squeeze_preview(in, nullptr);  // no residual samples anywhere: all regular
     CHECK(P.n_prefix == kSqueezeMaxLevels && P.n == 0, "64 levels without residuals");
   }
   if (g_fail) {

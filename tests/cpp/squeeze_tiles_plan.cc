@@ -1,43 +1,46 @@
-// The tile planner (jxl_rs_amd/csrc/squeeze_tiles_plan.h) on its own: the geometries of the tile tests and random chains,
-// grids and masks.  Checked: kinds by their definition; with every mask uniform the plan is "not mixed" and the folded
-// levels name the missing ones; else the prefix ends in front of the first level with a missing cell, levels the final
-// planes do not depend on have no entry, and in a mixed entry every cell is in exactly one list -- the smooth list, or
-// exactly one regular run; runs are maximal (a smooth cell or the channel's edge on either side), disjoint, start on a
-// pair, carry the tail only at the channel's odd end, and every sample offset a run or a smooth cell touches stays
-// inside the planes.  Host only, no device: addresses are numbers.  Built plain and with -fsanitize=address,undefined
-// (tests/test_squeeze_tiles_cpu.py).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#include "../../jxl_rs_amd/csrc/squeeze_tiles_plan.h"
-
-using namespace jxlh;
+// The preview planner (jxl_rs_amd/csrc/squeeze_preview_plan.h) with grids: the geometries of the tile tests and random
+// chains, grids and masks.  Checked: kinds by their definition; a level goes cell by cell exactly when its kinds are mixed
+// or a smooth cell is ragged; a chain without such a level plans as the same chain without grids whose all-missing levels
+// name no residuals, field by field; the prefix ends in front of the first level with a missing cell, levels the final
+// planes do not depend on have no entry, every whole-level entry -- beside cell-wise ones too -- passes the checks of a
+// plan without grids (squeeze_preview_checks.h), and in a cell-wise entry every cell is in exactly one list -- the smooth
+// list, or exactly one regular run; runs are maximal (a smooth cell or the channel's edge on either side), disjoint,
+// start on a pair, carry the tail only at the channel's odd end, and every sample offset a run or a smooth cell touches
+// stays inside the planes.  Host only, no device: addresses are numbers.  Built plain and with
+// -fsanitize=address,undefined (tests/test_squeeze_tiles_cpu.py).
+#include "squeeze_preview_checks.h"
 
 namespace {
 
-int g_fail = 0;
-#define CHECK(c, ...)                          \
-  do {                                         \
-    if (!(c)) {                                \
-      if (g_fail++ < 20) {                     \
-        std::printf("FAIL %s: ", #c);          \
-        std::printf(__VA_ARGS__);              \
-        std::printf("\n");                     \
-      }                                        \
-    }                                          \
-  } while (0)
-
-uint64_t g_rng = 0x9E3779B97F4A7C15ull;
-uint32_t rnd() {
-  g_rng ^= g_rng << 13;
-  g_rng ^= g_rng >> 7;
-  g_rng ^= g_rng << 17;
-  return (uint32_t)(g_rng >> 24);
-}
-uint32_t rnd(uint32_t lo, uint32_t hi) { return lo + rnd() % (hi - lo + 1); }
-
 int g_mixed = 0, g_runs = 0, g_smooth = 0;
+int g_equal = 0;                                // chains without a cell-wise level, held against the plan without grids
+int g_whole_smooth = 0, g_whole_regular = 0;    // whole-level entries behind a cell-wise level
+
+// P, planned with grids and no cell-wise level, against Q: the chain with res[] cleared where every cell is missing,
+// planned without grids
+void check_same_plan(int id, const SqueezePreviewPlan& P, const SqueezePreviewPlan& Q, int nl) {
+  CHECK(P.n_prefix == Q.n_prefix && P.n == Q.n && P.records.empty() && Q.records.empty() && !P.too_large && !Q.too_large,
+        "chain %d: prefix %d / %d, entries %d / %d", id, P.n_prefix, Q.n_prefix, P.n, Q.n);
+  CHECK(!std::memcmp(&P.arena, &Q.arena, sizeof P.arena), "chain %d: arena", id);
+  for (int i = 0; i < nl; i++) CHECK(P.kind[i] == Q.kind[i] && P.live[i] == Q.live[i], "chain %d level %d: kind, live", id, i);
+  if (P.n_prefix > 0) {
+    const SqueezeChainIn &a = P.prefix_in, &b = Q.prefix_in;
+    CHECK(a.n_planes == b.n_planes && a.n_levels == b.n_levels && a.base_w == b.base_w && a.base_h == b.base_h && a.base_stride == b.base_stride &&
+              a.out_stride == b.out_stride && !std::memcmp(a.base, b.base, sizeof a.base) && !std::memcmp(a.out, b.out, sizeof a.out) &&
+              a.arena == b.arena && a.with_rct == b.with_rct && a.separate_rct == b.separate_rct && a.flow == b.flow,
+          "chain %d: the prefix's chain", id);
+    CHECK(P.prefix.n == Q.prefix.n && P.prefix.flow_words == Q.prefix.flow_words && !std::memcmp(P.prefix.vec, Q.prefix.vec, sizeof P.prefix.vec) &&
+              !std::memcmp(&P.prefix.arena, &Q.prefix.arena, sizeof P.prefix.arena), "chain %d: the prefix's plan", id);
+    for (int k = 0; k < P.prefix.n && k < Q.prefix.n; k++) CHECK(same_launch(P.prefix.launch[k], Q.prefix.launch[k]), "chain %d: prefix launch %d", id, k);
+  }
+  for (int k = 0; k < P.n && k < Q.n; k++) {
+    const PreviewEntry &a = P.entry[k], &b = Q.entry[k];
+    CHECK(a.level == b.level && a.kind == b.kind && a.kind >= 0 && same_loc(a.src, b.src) && same_loc(a.src2, b.src2) && same_loc(a.dst, b.dst) &&
+              a.src_w == b.src_w && a.src_h == b.src_h && a.src2_w == b.src2_w && a.src2_h == b.src2_h && a.rct == b.rct && a.n_launch == b.n_launch &&
+              a.n_smooth == 0 && a.n_runs == 0 && b.n_smooth == 0 && b.n_runs == 0, "chain %d entry %d (level %d / %d)", id, k, a.level, b.level);
+    for (int j = 0; j < a.n_launch && j < b.n_launch; j++) CHECK(same_launch(a.launch[j], b.launch[j]), "chain %d entry %d launch %d", id, k, j);
+  }
+}
 
 // w x h, nl levels alternating from `first_hz` at the finest; finest cell tw x th halved per level (0: one cell);
 // density: per cent of present cells
@@ -99,12 +102,14 @@ void one_chain(int id, uint32_t w, uint32_t h, int nl, bool finest_hz, uint32_t 
     in.base[p] = (uintptr_t)base[p];
     in.out[p] = (uintptr_t)out[p];
   }
-  const SqueezeTilesPlan P = plan_squeeze_tiles(in, tl);
+  const SqueezePreviewPlan P = plan_squeeze_preview(in, tl);
 
   // ---- kinds by definition, and what "mixed" means
   std::vector<std::vector<uint8_t>> kinds(nl);
   bool mixed = false;
   std::vector<uint8_t> cellwise(nl, 0);
+  jxlh_squeeze_level folded[kSqueezeMaxLevels];  // res[] cleared where every cell is missing
+  std::memcpy(folded, lv, sizeof folded);
   int first_missing = nl;
   for (int i = 0; i < nl; i++) {
     const SqTileGrid g = squeeze_tile_grid(lv[i], tl[i]);
@@ -130,6 +135,7 @@ void one_chain(int id, uint32_t w, uint32_t h, int nl, bool finest_hz, uint32_t 
         (missing ? any_s : any_r) = true;
       }
     if (any_r && any_s) mixed = true;
+    for (uint8_t k : kinds[i]) cellwise[i] = cellwise[i] || k != kinds[i][0];  // (1-D beside 2-D: level i - 1 is mixed)
     // a smooth cell without a complete pair on a doubled axis is zero: the level goes cell by cell
     bool ragged = false;
     for (uint32_t ty = 0; ty < g.ny; ty++)
@@ -140,19 +146,27 @@ void one_chain(int id, uint32_t w, uint32_t h, int nl, bool finest_hz, uint32_t 
         if (k != JXLH_PREVIEW_REGULAR && ((fx && cw_ < 2) || (fy && ch_ < 2))) ragged = true;
       }
     if (ragged) mixed = true;
-    cellwise[i] = ragged;
+    cellwise[i] = cellwise[i] || ragged;
     if (any_s && first_missing == nl) first_missing = i;
-    if (!any_r) CHECK(!P.folded[i].res[0] && !P.folded[i].res[1] && !P.folded[i].res[2], "chain %d level %d: not folded", id, i);
-    else CHECK(P.folded[i].res[0] == lv[i].res[0], "chain %d level %d: folded away", id, i);
+    if (!any_r)
+      for (int p = 0; p < 3; p++) folded[i].res[p] = nullptr;
+    CHECK(P.kind[i] == (cellwise[i] ? -1 : (int)kinds[i][0]), "chain %d level %d: kind %d", id, i, P.kind[i]);
   }
-  CHECK(P.mixed == mixed, "chain %d: mixed %d, want %d", id, P.mixed, mixed);
-  if (!P.mixed) {
-    CHECK(P.entry.empty() && P.upload_records == 0, "chain %d: a plan without a mixed level", id);
-    return;
+  bool any_cellwise = false;
+  for (int i = 0; i < nl; i++) any_cellwise = any_cellwise || cellwise[i];
+  CHECK(any_cellwise == mixed, "chain %d: a cell-wise level %d, mixed %d", id, any_cellwise, mixed);
+  if (!mixed) {
+    // no level goes cell by cell: the plan is the plan without grids of the folded chain
+    SqueezeChainIn fin = in;
+    fin.levels = folded;
+    check_same_plan(id, P, plan_squeeze_preview(fin, nullptr), nl);
+    CHECK(P.records.empty(), "chain %d: a plan without a cell-wise level", id);
+    g_equal++;
+  } else {
+    g_mixed++;
   }
-  g_mixed++;
   CHECK(P.n_prefix == first_missing, "chain %d: prefix %d, first level with a missing cell %d", id, P.n_prefix, first_missing);
-  CHECK(P.n_prefix == 0 || (!P.prefix_in.with_rct && P.prefix_in.n_levels == P.n_prefix), "chain %d: the prefix", id);
+  CHECK(P.n_prefix == 0 || P.n_prefix == nl || (!P.prefix_in.with_rct && P.prefix_in.n_levels == P.n_prefix), "chain %d: the prefix", id);
 
   // ---- need: the last level, and what a needed level reads
   std::vector<uint8_t> need(nl, 0);
@@ -164,32 +178,50 @@ void one_chain(int id, uint32_t w, uint32_t h, int nl, bool finest_hz, uint32_t 
       else if (i >= 1) need[i - 1] = 1;
     }
   }
-  size_t e_at = 0, records = 0;
+  for (int i = 0; i < nl; i++) CHECK(P.live[i] == need[i], "chain %d level %d: live %d", id, i, P.live[i]);
+  // some entry goes cell by cell exactly when a cell-wise level is needed (one may be dead)
+  bool plan_mixed = false, want_mixed = false;
+  for (int k = 0; k < P.n; k++) plan_mixed = plan_mixed || P.entry[k].kind < 0;
+  for (int i = 0; i < nl; i++) want_mixed = want_mixed || (need[i] && cellwise[i]);
+  CHECK(plan_mixed == want_mixed, "chain %d: mixed %d, want %d", id, plan_mixed, want_mixed);
+  int e_at = 0;
+  size_t records = 0;
+  bool written[kSqueezeMaxLevels] = {};
+  for (int i = 0; i < P.n_prefix; i++) written[i] = true;
+  bool behind_cellwise = false;
   for (int i = 0; i < nl; i++) {
     if (i < P.n_prefix) { CHECK(need[i], "chain %d: prefix level %d is not needed", id, i); continue; }
     if (!need[i]) {
-      CHECK(e_at >= P.entry.size() || P.entry[e_at].level != i, "chain %d: an entry for dead level %d", id, i);
+      CHECK(e_at >= P.n || P.entry[e_at].level != i, "chain %d: an entry for dead level %d", id, i);
       continue;
     }
-    CHECK(e_at < P.entry.size() && P.entry[e_at].level == i, "chain %d: no entry for level %d", id, i);
-    if (e_at >= P.entry.size()) return;
-    const SqTilesEntry& e = P.entry[e_at++];
+    CHECK(e_at < P.n && P.entry[e_at].level == i, "chain %d: no entry for level %d", id, i);
+    if (e_at >= P.n || P.entry[e_at].level != i) return;  // (the checks below index by the level's own grid)
+    const PreviewEntry& e = P.entry[e_at++];
     const bool hz = lv[i].horizontal != 0;
     const uint32_t ow = lv[i].out_w, oh = lv[i].out_h;
     CHECK(e.dst.where == (i == nl - 1 ? (int)kSqOut : i) && e.src.where == (i == 0 ? (int)kSqBase : i - 1) &&
               e.src2.where == (i <= 1 ? (int)kSqBase : i - 2), "chain %d level %d: planes", id, i);
     CHECK(e.rct == (i == nl - 1 && in.with_rct), "chain %d level %d: rct", id, i);
-    uint8_t k0 = kinds[i][0];
-    bool uniform = !cellwise[i];
-    for (uint8_t k : kinds[i]) uniform = uniform && k == k0;
+    const uint8_t k0 = kinds[i][0];
+    const bool uniform = !cellwise[i];
     CHECK(e.kind == (uniform ? (int)k0 : -1), "chain %d level %d: kind %d", id, i, e.kind);
-    if (uniform) {
-      CHECK(e.smooth.empty() && e.runs.empty(), "chain %d level %d: lists of a whole level", id, i);
+    if (uniform) {  // a whole level: what a plan without grids is held to
+      check_whole_entry(id, in, e, P.n_prefix, written);
+      written[i] = true;
+      if (behind_cellwise) (k0 == JXLH_PREVIEW_REGULAR ? g_whole_regular : g_whole_smooth)++;
       continue;
     }
+    written[i] = true;
+    behind_cellwise = true;
     const SqTileGrid g = e.grid;
+    const SqTileGrid want_g = squeeze_tile_grid(lv[i], tl[i]);
+    CHECK(g.tw == want_g.tw && g.th == want_g.th && g.nx == want_g.nx && g.ny == want_g.ny, "chain %d level %d: grid", id, i);
+    CHECK(e.smooth_off + e.n_smooth == e.runs_off && e.runs_off + e.n_runs <= P.records.size(), "chain %d level %d: lists outside the records", id, i);
+    if (e.runs_off + e.n_runs > P.records.size() || e.smooth_off > e.runs_off) return;
     std::vector<int> covered(kinds[i].size(), 0);
-    for (const SqTileSmoothCell& c : e.smooth) {
+    for (uint32_t j = 0; j < e.n_smooth; j++) {
+      const SqTileSmoothCell& c = P.records[e.smooth_off + j].cell;
       const uint32_t tx = (uint32_t)c.x0 / g.tw, ty = (uint32_t)c.y0 / g.th;
       const int w_ = c.w, h_ = c.h_kind >> 2;
       CHECK((uint32_t)c.x0 == tx * g.tw && (uint32_t)c.y0 == ty * g.th && tx < g.nx && ty < g.ny, "chain %d level %d: a cell off the grid", id, i);
@@ -207,7 +239,8 @@ void one_chain(int id, uint32_t w, uint32_t h, int nl, bool finest_hz, uint32_t 
     const uint32_t len = hz ? ow : oh, lines = hz ? oh : ow, n_avg = len - len / 2;
     const size_t out_str = e.dst.stride, res_str = lv[i].res_stride, avg_str = e.src.stride;
     CHECK(out_str >= ow && avg_str >= (hz ? n_avg : ow), "chain %d level %d: strides", id, i);
-    for (const SqTileRun& r : e.runs) {
+    for (uint32_t j = 0; j < e.n_runs; j++) {
+      const SqTileRun& r = P.records[e.runs_off + j].run;
       const uint32_t n_lines = (uint32_t)r.n_lines_tail >> 1;
       const bool tail = r.n_lines_tail & 1;
       const uint32_t s0 = 2 * (uint32_t)r.pair0, s1 = s0 + 2 * (uint32_t)r.n_pairs + tail;
@@ -240,11 +273,10 @@ void one_chain(int id, uint32_t w, uint32_t h, int nl, bool finest_hz, uint32_t 
       g_runs++;
     }
     for (size_t c = 0; c < covered.size(); c++) CHECK(covered[c] == 1, "chain %d level %d: cell %zu is in %d lists", id, i, c, covered[c]);
-    CHECK(e.smooth_off == records && e.runs_off == records + e.smooth.size(), "chain %d level %d: list offsets", id, i);
-    records += e.smooth.size() + e.runs.size();
+    CHECK(e.smooth_off == records && e.runs_off == records + e.n_smooth, "chain %d level %d: list offsets", id, i);
+    records += (size_t)e.n_smooth + e.n_runs;
   }
-  CHECK(e_at == P.entry.size() && records == P.upload_records, "chain %d: entries %zu of %zu, records %zu of %zu", id, e_at, P.entry.size(), records,
-        P.upload_records);
+  CHECK(e_at == P.n && records == P.records.size(), "chain %d: entries %d of %d, records %zu of %zu", id, e_at, P.n, records, P.records.size());
 }
 
 }  // namespace
@@ -287,6 +319,7 @@ int main() {
     std::printf("%d failures\n", g_fail);
     return 1;
   }
-  std::printf("squeeze tile plans: ok (%d chains, %d mixed, %d smooth cells, %d runs)\n", id, g_mixed, g_smooth, g_runs);
-  return g_mixed > 1000 && g_runs > 1000 && g_smooth > 1000 ? 0 : 1;
+  std::printf("squeeze tile plans: ok (%d chains, %d mixed, %d smooth cells, %d runs; %d equal to the plan without grids; behind a cell-wise "
+              "level %d whole smooth and %d whole regular entries)\n", id, g_mixed, g_smooth, g_runs, g_equal, g_whole_smooth, g_whole_regular);
+  return g_mixed > 1000 && g_runs > 1000 && g_smooth > 1000 && g_equal >= 1000 && g_whole_smooth >= 1000 && g_whole_regular >= 1000 ? 0 : 1;
 }

@@ -1,6 +1,6 @@
 """Squeeze previews per grid cell, the host side (no GPU): tests/squeeze_tiles_ref.py against the oracle where the two
 overlap (every cell present: the regular steps; masks uniform per level: squeeze_preview_ref.preview_reference);
-jxlh_squeeze_tile_kinds -- the public face of jxl_rs_amd/csrc/squeeze_tiles_plan.h -- against the restated rule; what
+jxlh_squeeze_tile_kinds -- the public face of jxl_rs_amd/csrc/squeeze_preview_plan.h -- against the restated rule; what
 the GPU cases' masks exercise, as conditions on the reference alone; the bindings; the refusals that need no device."""
 import functools
 import os
