@@ -1,66 +1,20 @@
-// Host-side lowering of BlendingStage + ExtendToImageDimensionsStage (include/jxl_hip_pipeline.hpp): accepted at the
+// Host-side lowering of BlendingStage + ExtendToImageDimensionsStage (include/jxl_hip_lowering.hpp): accepted at the
 // reference's position -- behind the colour stage, the blending stage followed at once by the extend stage, in front of
 // the conversion / save stages (frame/render.rs:754-791) -- and lowered to a jxlh_blend_desc with the colour stage
 // moved into the blend call.  No GPU involved.
 #include <cstdio>
-#include <functional>
 #include <string>
 
-#include "jxl_hip_pipeline.hpp"
+#include "lowering_helpers.h"
 
 using namespace jxlh;
+using namespace lowering_helpers;
 
 namespace {
-int g_failed = 0;
-void expect(bool ok, const char* what) {
-  if (!ok) {
-    g_failed++;
-    fprintf(stderr, "FAILED: %s\n", what);
-  }
-}
-jxlh_status status_of(const std::function<void()>& f, std::string* msg = nullptr) {
-  try {
-    f();
-  } catch (const Error& e) {
-    if (msg) *msg = e.what();
-    return e.status;
-  }
-  return JXLH_OK;
-}
-jxlh_frame_params base(uint32_t w, uint32_t h) {
-  jxlh_frame_params p;
-  jxlh_default_frame_params(&p, w, h);
-  return p;
-}
 const jxlh_blending_info kColour{JXLH_BLEND_BLEND, 0, 1, 2};
 const jxlh_blending_info kAlpha{JXLH_BLEND_ALPHA_WEIGHTED_ADD, 0, 0, 1};
-BlendingStage blending(size_t num_ec) {
-  BlendingStage b;
-  b.x0 = -40;
-  b.y0 = 100;
-  b.image_w = 1280;
-  b.image_h = 1024;
-  b.blending_info = kColour;
-  b.ec_blending_info.assign(num_ec, kAlpha);
-  b.ec_flags.assign(num_ec, JXLH_EC_ALPHA);
-  return b;
-}
-ExtendToImageDimensionsStage extend(size_t num_ec) {
-  ExtendToImageDimensionsStage e;
-  e.x0 = -40;
-  e.y0 = 100;
-  e.image_w = 1280;
-  e.image_h = 1024;
-  e.blending_info = kColour;
-  e.ec_blending_info.assign(num_ec, kAlpha);
-  return e;
-}
-jxlh_xyb_params xyb() {
-  jxlh_xyb_params x{};
-  for (int i = 0; i < 9; i++) x.opsin_inverse_matrix[i] = 0.5f + (float)i;
-  x.intensity_scale = 0.75f;
-  return x;
-}
+BlendingStage blending(size_t num_ec) { return lowering_helpers::blending(-40, 100, 1280, 1024, kColour, num_ec, kAlpha); }
+ExtendToImageDimensionsStage extend(size_t num_ec) { return extend_of(blending(num_ec)); }
 RenderPipelineBuilder start(const jxlh_frame_params& p, size_t channels = 3) {
   return RenderPipelineBuilder(channels, {512, 384}, 0, 8, p)
       .add_inout_stage(GaborishStage{0, p.gab_w1[0], p.gab_w2[0]})

@@ -1,38 +1,17 @@
-// Host-side lowering of a Modular frame's stage list (include/jxl_hip_pipeline.hpp): lower_modular_frame() takes the
+// Host-side lowering of a Modular frame's stage list (include/jxl_hip_lowering.hpp): lower_modular_frame() takes the
 // reference's full Modular list (frame/render.rs:553-903) onto the LoweredPipeline fields a VarDCT list fills, under
 // the same order and consistency checks; lower() still rejects those lists exactly as before, naming the stage hooks.
 // No GPU involved.
 #include <cstdio>
-#include <functional>
 #include <string>
 
-#include "jxl_hip_pipeline.hpp"
+#include "lowering_helpers.h"
 
 using namespace jxlh;
+using namespace lowering_helpers;
 
 namespace {
-int g_failed = 0;
-void expect(bool ok, const char* what) {
-  if (!ok) {
-    g_failed++;
-    fprintf(stderr, "FAILED: %s\n", what);
-  }
-}
-jxlh_status status_of(const std::function<void()>& f, std::string* msg = nullptr) {
-  try {
-    f();
-  } catch (const Error& e) {
-    if (msg) *msg = e.what();
-    return e.status;
-  }
-  return JXLH_OK;
-}
 bool has(const std::string& s, const char* part) { return s.find(part) != std::string::npos; }
-jxlh_frame_params base(uint32_t w, uint32_t h) {
-  jxlh_frame_params p;
-  jxlh_default_frame_params(&p, w, h);
-  return p;
-}
 SplinesStage segs() {
   SplinesStage st;
   st.segments = {jxlh_spline_segment{10.0f, 20.0f, 3.5f, 1.25f, 0.1f, {0.5f, 0.6f, 0.7f}}};
@@ -51,35 +30,7 @@ RenderPipelineBuilder conversions(RenderPipelineBuilder b, uint8_t bits = 8) {
       .add_inout_stage(ConvertModularToF32Stage{1, bits})
       .add_inout_stage(ConvertModularToF32Stage{2, bits});
 }
-RenderPipelineBuilder filters(RenderPipelineBuilder b, const jxlh_frame_params& p) {
-  const std::array<float, 3> cs{p.epf_channel_scale[0], p.epf_channel_scale[1], p.epf_channel_scale[2]};
-  return std::move(b)
-      .add_inout_stage(GaborishStage{0, p.gab_w1[0], p.gab_w2[0]})
-      .add_inout_stage(GaborishStage{1, p.gab_w1[1], p.gab_w2[1]})
-      .add_inout_stage(GaborishStage{2, p.gab_w1[2], p.gab_w2[2]})
-      .add_inout_stage(Epf1Stage{1.0f, p.epf_border_sad_mul, cs});
-}
-BlendingStage blending() {
-  BlendingStage b{};
-  b.x0 = 5;
-  b.y0 = 3;
-  b.image_w = 1200;
-  b.image_h = 900;
-  b.blending_info = jxlh_blending_info{};
-  b.ec_blending_info.assign(1, jxlh_blending_info{});
-  b.ec_flags.assign(1, JXLH_EC_ALPHA);
-  return b;
-}
-ExtendToImageDimensionsStage extend_of(const BlendingStage& b) {
-  ExtendToImageDimensionsStage e{};
-  e.x0 = b.x0;
-  e.y0 = b.y0;
-  e.image_w = b.image_w;
-  e.image_h = b.image_h;
-  e.blending_info = b.blending_info;
-  e.ec_blending_info = b.ec_blending_info;
-  return e;
-}
+BlendingStage blending() { return lowering_helpers::blending(5, 3, 1200, 900, jxlh_blending_info{}, 1, jxlh_blending_info{}); }
 // the reference's full list of a 500 x 350 Modular frame shown at 1000 x 700: conversions, chroma upsampling, filters,
 // the alpha channel's conversion, patches, splines, frame upsampling (the alpha with it), noise, colour stages,
 // blending + extend, spot colour, premultiply, conversions, an RGBA8 save

@@ -1,49 +1,21 @@
-// Host-side lowering of PatchesStage (include/jxl_hip_pipeline.hpp): accepted at the reference's position -- after the
+// Host-side lowering of PatchesStage (include/jxl_hip_lowering.hpp): accepted at the reference's position -- after the
 // filters and the extra channels' own upsampling, before the colour upsampling, noise and the colour stage
 // (frame/render.rs:624-683) -- and only on a VarDCT frame.  No GPU involved.
 #include <cstdio>
-#include <functional>
 #include <string>
 
-#include "jxl_hip_pipeline.hpp"
+#include "lowering_helpers.h"
 
 using namespace jxlh;
+using namespace lowering_helpers;
 
 namespace {
-int g_failed = 0;
-void expect(bool ok, const char* what) {
-  if (!ok) {
-    g_failed++;
-    fprintf(stderr, "FAILED: %s\n", what);
-  }
-}
-jxlh_status status_of(const std::function<void()>& f, std::string* msg = nullptr) {
-  try {
-    f();
-  } catch (const Error& e) {
-    if (msg) *msg = e.what();
-    return e.status;
-  }
-  return JXLH_OK;
-}
 PatchesStage dict(size_t num_ec) {
   PatchesStage ps;
   ps.patches = {jxlh_patch{4, 5, 0, 0, 0, 16, 12}, jxlh_patch{40, 30, 1, 8, 2, 10, 20}};
   ps.blendings.assign(ps.patches.size() * (1 + num_ec), jxlh_patch_blending{JXLH_PATCH_BLEND_ABOVE, 0, 1});
   ps.ec_flags.assign(num_ec, JXLH_EC_ALPHA);
   return ps;
-}
-jxlh_frame_params base(uint32_t w, uint32_t h) {
-  jxlh_frame_params p;
-  jxlh_default_frame_params(&p, w, h);
-  return p;
-}
-RenderPipelineBuilder filters(RenderPipelineBuilder b, const jxlh_frame_params& p) {
-  return std::move(b)
-      .add_inout_stage(GaborishStage{0, p.gab_w1[0], p.gab_w2[0]})
-      .add_inout_stage(GaborishStage{1, p.gab_w1[1], p.gab_w2[1]})
-      .add_inout_stage(GaborishStage{2, p.gab_w1[2], p.gab_w2[2]})
-      .add_inout_stage(Epf1Stage{1.0f, p.epf_border_sad_mul, {p.epf_channel_scale[0], p.epf_channel_scale[1], p.epf_channel_scale[2]}});
 }
 }  // namespace
 

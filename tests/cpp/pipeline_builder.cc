@@ -9,78 +9,17 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 
 #include <hip/hip_runtime_api.h>
 
-#include "jxl_hip_pipeline.hpp"
+#include "lowering_helpers.h"
 #include "synth_frame.hpp"
 
 using namespace jxlh;
+using namespace lowering_helpers;
 
 namespace {
-int g_failed = 0;
-void expect(bool ok, const char* what) {
-  if (!ok) {
-    g_failed++;
-    fprintf(stderr, "FAILED: %s\n", what);
-  }
-}
-// the status build() / lower() fails with, or JXLH_OK
-jxlh_status status_of(const std::function<void()>& f, std::string* msg = nullptr) {
-  try {
-    f();
-  } catch (const Error& e) {
-    if (msg) *msg = e.what();
-    return e.status;
-  }
-  return JXLH_OK;
-}
-
-// RestorationFilter defaults as jxlh_default_frame_params holds them
-struct Rf {
-  float gab_w1[3], gab_w2[3], pass0, pass2, border_sad_mul;
-  std::array<float, 3> channel_scale;
-};
-Rf rf_of(const jxlh_frame_params& p) {
-  Rf r;
-  for (int c = 0; c < 3; c++) {
-    r.gab_w1[c] = p.gab_w1[c];
-    r.gab_w2[c] = p.gab_w2[c];
-    r.channel_scale[c] = p.epf_channel_scale[c];
-  }
-  r.pass0 = p.epf_pass0_sigma_scale;
-  r.pass2 = p.epf_pass2_sigma_scale;
-  r.border_sad_mul = p.epf_border_sad_mul;
-  return r;
-}
-
-// the filter part of Frame::build_render_pipeline (frame/render.rs:578-622)
-RenderPipelineBuilder add_filters(RenderPipelineBuilder b, const Rf& rf, bool gab, int epf_iters) {
-  if (gab) {
-    b = std::move(b)
-            .add_inout_stage(GaborishStage{0, rf.gab_w1[0], rf.gab_w2[0]})
-            .add_inout_stage(GaborishStage{1, rf.gab_w1[1], rf.gab_w2[1]})
-            .add_inout_stage(GaborishStage{2, rf.gab_w1[2], rf.gab_w2[2]});
-  }
-  if (epf_iters >= 3) b = std::move(b).add_inout_stage(Epf0Stage{rf.pass0, rf.border_sad_mul, rf.channel_scale});
-  if (epf_iters >= 1) b = std::move(b).add_inout_stage(Epf1Stage{1.0f, rf.border_sad_mul, rf.channel_scale});
-  if (epf_iters >= 2) b = std::move(b).add_inout_stage(Epf2Stage{rf.pass2, rf.border_sad_mul, rf.channel_scale});
-  return b;
-}
-
-jxlh_xyb_params some_xyb() {
-  jxlh_xyb_params x{};
-  for (int i = 0; i < 9; i++) x.opsin_inverse_matrix[i] = (i % 4 == 0) ? 1.0f : 0.01f * (float)i;
-  for (int i = 0; i < 3; i++) {
-    x.bias_cbrt[i] = -0.15f;
-    x.scaled_bias[i] = -0.0038f;
-  }
-  x.intensity_scale = 1.0f;
-  return x;
-}
-
 int host_checks() {
   const jxlh_frame_params base = VarDctFrame::default_params(1000, 700);
   const Rf rf = rf_of(base);

@@ -1,100 +1,22 @@
-// Host-side lowering of the save tail (include/jxl_hip_pipeline.hpp): SpotColorStage, PremultiplyAlphaStage, the
+// Host-side lowering of the save tail (include/jxl_hip_lowering.hpp): SpotColorStage, PremultiplyAlphaStage, the
 // conversions to u8 / u16 / f16 at any bit depth and on extra channels, and the six-argument save stage, in the order of
 // Frame::build_render_pipeline (frame/render.rs:793-903), lower to one jxlh_save_desc per output buffer; lists out of
 // that order fail naming the stage; lists without these stages lower to what they did.  No GPU involved.
 #include <cstdio>
-#include <functional>
 #include <string>
 
-#include "jxl_hip_pipeline.hpp"
+#include "lowering_helpers.h"
 
 using namespace jxlh;
+using namespace lowering_helpers;
 
 namespace {
-int g_failed = 0;
-void expect(bool ok, const char* what) {
-  if (!ok) {
-    g_failed++;
-    fprintf(stderr, "FAILED: %s\n", what);
-  }
-}
-jxlh_status status_of(const std::function<void()>& f, std::string* msg = nullptr) {
-  try {
-    f();
-  } catch (const Error& e) {
-    if (msg) *msg = e.what();
-    return e.status;
-  }
-  return JXLH_OK;
-}
-jxlh_xyb_params xyb() {
-  jxlh_xyb_params x{};
-  for (int i = 0; i < 9; i++) x.opsin_inverse_matrix[i] = 0.5f + (float)i;
-  x.intensity_scale = 0.75f;
-  return x;
-}
 const std::array<float, 3> kLum{0.2627f, 0.678f, 0.0593f};
 
-// the helpers of tests/cpp/pipeline_builder.cc, for its lists 1-4 below
-struct Rf {
-  float gab_w1[3], gab_w2[3], pass0, pass2, border_sad_mul;
-  std::array<float, 3> channel_scale;
-};
-Rf rf_of(const jxlh_frame_params& p) {
-  Rf r;
-  for (int c = 0; c < 3; c++) {
-    r.gab_w1[c] = p.gab_w1[c];
-    r.gab_w2[c] = p.gab_w2[c];
-    r.channel_scale[c] = p.epf_channel_scale[c];
-  }
-  r.pass0 = p.epf_pass0_sigma_scale;
-  r.pass2 = p.epf_pass2_sigma_scale;
-  r.border_sad_mul = p.epf_border_sad_mul;
-  return r;
-}
-RenderPipelineBuilder add_filters(RenderPipelineBuilder b, const Rf& rf, bool gab, int epf_iters) {
-  if (gab) {
-    b = std::move(b)
-            .add_inout_stage(GaborishStage{0, rf.gab_w1[0], rf.gab_w2[0]})
-            .add_inout_stage(GaborishStage{1, rf.gab_w1[1], rf.gab_w2[1]})
-            .add_inout_stage(GaborishStage{2, rf.gab_w1[2], rf.gab_w2[2]});
-  }
-  if (epf_iters >= 3) b = std::move(b).add_inout_stage(Epf0Stage{rf.pass0, rf.border_sad_mul, rf.channel_scale});
-  if (epf_iters >= 1) b = std::move(b).add_inout_stage(Epf1Stage{1.0f, rf.border_sad_mul, rf.channel_scale});
-  if (epf_iters >= 2) b = std::move(b).add_inout_stage(Epf2Stage{rf.pass2, rf.border_sad_mul, rf.channel_scale});
-  return b;
-}
-jxlh_xyb_params some_xyb() {
-  jxlh_xyb_params x{};
-  for (int i = 0; i < 9; i++) x.opsin_inverse_matrix[i] = (i % 4 == 0) ? 1.0f : 0.01f * (float)i;
-  for (int i = 0; i < 3; i++) {
-    x.bias_cbrt[i] = -0.15f;
-    x.scaled_bias[i] = -0.0038f;
-  }
-  x.intensity_scale = 1.0f;
-  return x;
-}
 BlendingStage blending(size_t num_ec) {
-  BlendingStage bl;
-  bl.x0 = -4;
-  bl.y0 = 9;
-  bl.image_w = 640;
-  bl.image_h = 480;
-  bl.blending_info = jxlh_blending_info{JXLH_BLEND_BLEND, 0, 1, 0};
-  bl.ec_blending_info.assign(num_ec, jxlh_blending_info{JXLH_BLEND_BLEND, 0, 0, 0});
-  bl.ec_flags.assign(num_ec, JXLH_EC_ALPHA);
-  return bl;
+  return lowering_helpers::blending(-4, 9, 640, 480, jxlh_blending_info{JXLH_BLEND_BLEND, 0, 1, 0}, num_ec, jxlh_blending_info{JXLH_BLEND_BLEND, 0, 0, 0});
 }
-ExtendToImageDimensionsStage extend(size_t num_ec) {
-  ExtendToImageDimensionsStage ex;
-  ex.x0 = -4;
-  ex.y0 = 9;
-  ex.image_w = 640;
-  ex.image_h = 480;
-  ex.blending_info = jxlh_blending_info{JXLH_BLEND_BLEND, 0, 1, 0};
-  ex.ec_blending_info.assign(num_ec, jxlh_blending_info{JXLH_BLEND_BLEND, 0, 0, 0});
-  return ex;
-}
+ExtendToImageDimensionsStage extend(size_t num_ec) { return extend_of(blending(num_ec)); }
 // a VarDCT frame with `num_ec` 16-bit extra channels, Gaborish, XYB + sRGB
 RenderPipelineBuilder start(const jxlh_frame_params& p, int num_ec, uint32_t tf = JXLH_TF_SRGB) {
   auto b = RenderPipelineBuilder(3 + num_ec, {512, 384}, 0, 8, p);

@@ -1,31 +1,15 @@
-// Host-side lowering of SplinesStage (include/jxl_hip_pipeline.hpp): accepted at the reference's position -- behind the
+// Host-side lowering of SplinesStage (include/jxl_hip_lowering.hpp): accepted at the reference's position -- behind the
 // patches stage (if any), before the colour upsampling, noise and the colour stage (frame/render.rs:644-683) -- and only
 // on a VarDCT frame.  No GPU involved.
 #include <cstdio>
-#include <functional>
 #include <string>
 
-#include "jxl_hip_pipeline.hpp"
+#include "lowering_helpers.h"
 
 using namespace jxlh;
+using namespace lowering_helpers;
 
 namespace {
-int g_failed = 0;
-void expect(bool ok, const char* what) {
-  if (!ok) {
-    g_failed++;
-    fprintf(stderr, "FAILED: %s\n", what);
-  }
-}
-jxlh_status status_of(const std::function<void()>& f, std::string* msg = nullptr) {
-  try {
-    f();
-  } catch (const Error& e) {
-    if (msg) *msg = e.what();
-    return e.status;
-  }
-  return JXLH_OK;
-}
 SplinesStage segs() {
   SplinesStage st;
   st.segments = {jxlh_spline_segment{10.0f, 20.0f, 3.5f, 1.25f, 0.1f, {0.5f, 0.6f, 0.7f}},
@@ -38,18 +22,6 @@ PatchesStage dict() {
   ps.patches = {jxlh_patch{4, 5, 0, 0, 0, 16, 12}};
   ps.blendings.assign(1, jxlh_patch_blending{JXLH_PATCH_ADD, 0, 0});
   return ps;
-}
-jxlh_frame_params base(uint32_t w, uint32_t h) {
-  jxlh_frame_params p;
-  jxlh_default_frame_params(&p, w, h);
-  return p;
-}
-RenderPipelineBuilder filters(RenderPipelineBuilder b, const jxlh_frame_params& p) {
-  return std::move(b)
-      .add_inout_stage(GaborishStage{0, p.gab_w1[0], p.gab_w2[0]})
-      .add_inout_stage(GaborishStage{1, p.gab_w1[1], p.gab_w2[1]})
-      .add_inout_stage(GaborishStage{2, p.gab_w1[2], p.gab_w2[2]})
-      .add_inout_stage(Epf1Stage{1.0f, p.epf_border_sad_mul, {p.epf_channel_scale[0], p.epf_channel_scale[1], p.epf_channel_scale[2]}});
 }
 RenderPipelineBuilder upsample2(RenderPipelineBuilder b) {
   return std::move(b).add_inout_stage(Upsample2x{nullptr, 0}).add_inout_stage(Upsample2x{nullptr, 1}).add_inout_stage(Upsample2x{nullptr, 2});

@@ -1,5 +1,5 @@
 """BlendingStage and ExtendToImageDimensionsStage in the C++ mirror of the reference's RenderPipelineBuilder
-(include/jxl_hip_pipeline.hpp): where a stage list may hold them and what they lower to, through
+(include/jxl_hip_lowering.hpp): where a stage list may hold them and what they lower to, through
 tests/cpp/blending_lowering.cc.  Host-only, no GPU."""
 import subprocess
 

@@ -1,8 +1,8 @@
 """The drop-in boundary from compiled code: tests/cpp/frame_parity.cc (C++17, g++) drives the C++ host side
 include/jxl_hip.hpp over the C ABI and checks the frame against the oracle library, no Python in the data path;
 tests/cpp/pipeline_builder.cc does the same through the mirror of the reference's stage traits and
-RenderPipelineBuilder (include/jxl_hip_pipeline.hpp), whose lowering / rejection logic is host-only and runs
-without a GPU."""
+RenderPipelineBuilder (include/jxl_hip_pipeline.hpp), whose lowering / rejection logic (include/jxl_hip_lowering.hpp)
+is host-only and runs without a GPU."""
 import os
 import subprocess
 

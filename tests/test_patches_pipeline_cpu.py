@@ -1,4 +1,4 @@
-"""PatchesStage in the C++ mirror of the reference's RenderPipelineBuilder (include/jxl_hip_pipeline.hpp): where a
+"""PatchesStage in the C++ mirror of the reference's RenderPipelineBuilder (include/jxl_hip_lowering.hpp): where a
 stage list may hold it and what it lowers to, through tests/cpp/patches_lowering.cc.  Host-only, no GPU."""
 import subprocess
 

@@ -1,4 +1,4 @@
-"""The save tail in the C++ mirror of the reference's RenderPipelineBuilder (include/jxl_hip_pipeline.hpp): the RGBA,
+"""The save tail in the C++ mirror of the reference's RenderPipelineBuilder (include/jxl_hip_lowering.hpp): the RGBA,
 gray + alpha, BGRA-premultiplied, spot-colour, f16-with-clamp, 10-bit-u16 and several-buffer lists of frame/render.rs
 lower to the expected jxlh_save_desc entries, lists out of the reference's order fail naming the stage, and lists without
 these stages lower to what they did -- through tests/cpp/save_lowering.cc.  Host-only, no GPU."""

@@ -1,4 +1,4 @@
-"""SplinesStage in the C++ mirror of the reference's RenderPipelineBuilder (include/jxl_hip_pipeline.hpp): where a
+"""SplinesStage in the C++ mirror of the reference's RenderPipelineBuilder (include/jxl_hip_lowering.hpp): where a
 stage list may hold it and what it lowers to, through tests/cpp/splines_lowering.cc.  Host-only, no GPU."""
 import subprocess
 
