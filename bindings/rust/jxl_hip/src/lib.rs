@@ -257,6 +257,21 @@ pub fn changed_rects(params: &sys::jxlh_frame_params, groups: &[u32]) -> Result<
     Ok(rects)
 }
 
+/// `jxlh_extra_channel_changed_rects` (host code, no context): for rects of new samples of a `w` x `h` extra channel with
+/// factor `ec_upsampling`, the rects of the finished channel (cut to `res_w` x `res_h`) outside which every sample is as
+/// it was -- one per input rect; what `VarDctFrame::save_rects` repaints, with `changed_rects`, after a pass.
+pub fn extra_channel_changed_rects(w: u32, h: u32, ec_upsampling: u32, res_w: u32, res_h: u32,
+                                   rects: &[sys::save_rects::jxlh_rect]) -> Result<Vec<sys::save_rects::jxlh_rect>> {
+    let mut n = 0u32;
+    let mut out = vec![sys::save_rects::jxlh_rect { x0: 0, y0: 0, w: 0, h: 0 }; rects.len()];
+    // SAFETY: `out` holds one entry per input rect, which is what the call writes
+    check(std::ptr::null(), unsafe {
+        sys::extra_rects::jxlh_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects.as_ptr(), rects.len() as u32,
+                                                           out.as_mut_ptr(), out.len() as u32, &mut n)
+    })?;
+    Ok(out)
+}
+
 /// A VarDCT frame on the device.  Call order = the reference's frame flow.
 pub struct VarDctFrame<'a> {
     ctx: &'a Context,
@@ -509,6 +524,23 @@ impl<'a> VarDctFrame<'a> {
         }
         self.ctx.ok(unsafe {
             sys::jxlh_frame_set_extra_channel(self.ctx.raw, ec, samples.as_ptr(), stride, w, h, bits_per_sample, ec_upsampling)
+        })
+    }
+    /// An extra channel that arrives group by group (`jxlh_frame_begin_extra_channel`): declared once per frame with
+    /// no samples yet -- every sample reads as zero until `set_extra_channel_rects` sets it.
+    pub fn begin_extra_channel(&self, ec: u32, w: u32, h: u32, bits_per_sample: u32, ec_upsampling: u32) -> Result<()> {
+        self.ctx.ok(unsafe { sys::extra_rects::jxlh_frame_begin_extra_channel(self.ctx.raw, ec, w, h, bits_per_sample, ec_upsampling) })
+    }
+    /// The samples of extra channels as their groups arrive (`jxlh_frame_set_extra_channel_rects`): every rect names
+    /// `h` rows of `w` samples of the host block `samples`, `stride` apart from `offset`, and where they go in channel
+    /// `ec`.  One copy and one launch per call; the next `finalize_and_render` / `rerender_groups` converts and
+    /// upsamples only what the rects can have changed.  The block is copied before the call returns; a refusal names
+    /// the rect in the context's last error.
+    pub fn set_extra_channel_rects(&self, samples: &[i32], rects: &[sys::extra_rects::jxlh_ec_rect]) -> Result<()> {
+        let mut bad = 0u32;
+        self.ctx.ok(unsafe {
+            sys::extra_rects::jxlh_frame_set_extra_channel_rects(self.ctx.raw, samples.as_ptr(), samples.len() as u64,
+                                                                 rects.as_ptr(), rects.len() as u32, &mut bad)
         })
     }
     /// the save stage of an extra channel: one f32 plane of the frame's output size

@@ -974,7 +974,10 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
 /* Save rectangles -- the same save for a LIST of rectangles of the source in one launch, so that a repaint moves only
  * the pixels a group re-render can have changed, and the host function that names those rectangles:
  * jxlh_frame_save_rects, jxlh_frame_save_rects_async, jxlh_stage_save_rects and jxlh_changed_rects (jxlh_rect,
- * JXLH_MAX_SAVE_RECTS), declared in jxl_hip_save_rects.h, which this header includes at its end. */
+ * JXLH_MAX_SAVE_RECTS), declared in jxl_hip_save_rects.h, which this header includes at its end.
+ * Extra channels by rect -- a channel declared once and fed rect by rect as its groups arrive, converted and upsampled
+ * only where a rect can have changed it: jxlh_frame_begin_extra_channel, jxlh_frame_set_extra_channel_rects (_async)
+ * and jxlh_extra_channel_changed_rects (jxlh_ec_rect, JXLH_MAX_EC_RECTS), declared in jxl_hip_extra_rects.h, likewise. */
 
 /* ---------------------------------------------------------------- LF frames
  * A frame with lf_level = L >= 1 (the layers of a progressive_dc file) is an ordinary frame of ceil(size / 8^L) pixels,
@@ -1299,5 +1302,6 @@ int32_t jxlh_quant_table_size(int32_t table);
 #include "jxl_hip_preview.h"
 #include "jxl_hip_save_rects.h"
 #include "jxl_hip_preview_tiles.h"
+#include "jxl_hip_extra_rects.h"
 
 #endif /* JXL_HIP_H_ */

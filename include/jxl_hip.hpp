@@ -137,6 +137,18 @@ inline std::vector<jxlh_rect> changed_rects(const jxlh_frame_params& p, const st
   return rects;
 }
 
+// the rectangles of a finished extra channel (w x h samples, factor ec_upsampling, cut to res_w x res_h) outside which
+// new samples in `rects` (source samples) change nothing (jxlh_extra_channel_changed_rects): host only
+inline std::vector<jxlh_rect> extra_channel_changed_rects(uint32_t w, uint32_t h, uint32_t ec_upsampling, uint32_t res_w,
+                                                          uint32_t res_h, const std::vector<jxlh_rect>& rects) {
+  uint32_t n = 0;
+  std::vector<jxlh_rect> out(rects.size());
+  const jxlh_status st = jxlh_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects.data(), (uint32_t)rects.size(),
+                                                          out.data(), (uint32_t)out.size(), &n);
+  if (st != JXLH_OK) throw Error(st, "jxlh_extra_channel_changed_rects", "");
+  return out;
+}
+
 // what each level of a preview chain runs (JXLH_PREVIEW_*) and whether the final planes depend on it: host only
 struct SqueezePreviewKinds {
   std::vector<uint8_t> kinds, live;
@@ -232,6 +244,23 @@ class VarDctFrame {
     ctx_.check(async ? jxlh_frame_set_modular_groups_async(ctx_.raw(), arena, arena_samples, groups, n, sample_format, &bad)
                      : jxlh_frame_set_modular_groups(ctx_.raw(), arena, arena_samples, groups, n, sample_format, &bad),
                "jxlh_frame_set_modular_groups");
+  }
+  // An extra channel that arrives group by group (jxl_hip_extra_rects.h): declared once per frame, all zero ...
+  void begin_extra_channel(uint32_t ec, uint32_t w, uint32_t h, uint32_t bits_per_sample, uint32_t ec_upsampling) {
+    ctx_.check(jxlh_frame_begin_extra_channel(ctx_.raw(), ec, w, h, bits_per_sample, ec_upsampling), "jxlh_frame_begin_extra_channel");
+  }
+  // ... then the rects of its samples as their groups arrive, many per call, out of one block (host or device memory);
+  // the next finalize_and_render() / rerender_groups() converts and upsamples only what they can have changed.  The
+  // block may be reused when the call returns; _async: after the next sync / mark.
+  void set_extra_channel_rects(const int32_t* samples, uint64_t n_samples, const std::vector<jxlh_ec_rect>& rects) {
+    uint32_t bad = 0;
+    ctx_.check(jxlh_frame_set_extra_channel_rects(ctx_.raw(), samples, n_samples, rects.data(), (uint32_t)rects.size(), &bad),
+               "jxlh_frame_set_extra_channel_rects");
+  }
+  void set_extra_channel_rects_async(const int32_t* samples, uint64_t n_samples, const std::vector<jxlh_ec_rect>& rects) {
+    uint32_t bad = 0;
+    ctx_.check(jxlh_frame_set_extra_channel_rects_async(ctx_.raw(), samples, n_samples, rects.data(), (uint32_t)rects.size(), &bad),
+               "jxlh_frame_set_extra_channel_rects_async");
   }
   // PatchesDictionary::read's result (decode_lf_global, frame/decode.rs:315-324), flattened: blendings holds
   // patches.size() * (1 + ec_flags.size()) entries, ec_flags the JXLH_EC_* of each extra channel

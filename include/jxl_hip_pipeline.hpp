@@ -79,6 +79,32 @@ class GpuFramePipeline {
     ctx_.check(jxlh_frame_set_extra_channel(ctx_.raw(), ec, samples, stride, w, h, lp_.extra[ec].bits, lp_.extra[ec].upsampling),
                "jxlh_frame_set_extra_channel");
   }
+  // ... or the channel declared without samples (w x h at its own resolution) and fed rect by rect as its groups
+  // arrive: the stage list names its bit depth and factor as above, and the next do_render() converts and upsamples only
+  // what the rects can have changed (jxl_hip_extra_rects.h).  samples: one block, host or device memory.
+  void begin_extra_channel(uint32_t ec, uint32_t w, uint32_t h) {
+    if (ec >= JXLH_MAX_EXTRA_CHANNELS || !lp_.extra[ec].bits)
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::begin_extra_channel", "the stage list does not name this extra channel");
+    frame_.begin_extra_channel(ec, w, h, lp_.extra[ec].bits, lp_.extra[ec].upsampling);
+  }
+  void set_extra_channel_rects(const int32_t* samples, uint64_t n_samples, const std::vector<jxlh_ec_rect>& rects) {
+    frame_.set_extra_channel_rects(samples, n_samples, rects);
+  }
+  void set_extra_channel_rects_async(const int32_t* samples, uint64_t n_samples, const std::vector<jxlh_ec_rect>& rects) {
+    frame_.set_extra_channel_rects_async(samples, n_samples, rects);
+  }
+  // The rectangles of finished extra channel `ec` (w x h source samples) that new samples in `rects` can change
+  // (jxlh_extra_channel_changed_rects): what save_rects repaints, with changed_rects(), after the do_render() of a pass
+  std::vector<jxlh_rect> extra_channel_changed_rects(uint32_t ec, uint32_t w, uint32_t h, const std::vector<jxlh_rect>& rects) const {
+    if (ec >= JXLH_MAX_EXTRA_CHANNELS || !lp_.extra[ec].bits)
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::extra_channel_changed_rects", "the stage list does not name this extra channel");
+    uint32_t n = 0;
+    std::vector<jxlh_rect> out(rects.size());
+    const jxlh_status st = jxlh_extra_channel_changed_rects(w, h, lp_.extra[ec].upsampling, frame_.out_width(), frame_.out_height(),
+                                                            rects.data(), (uint32_t)rects.size(), out.data(), (uint32_t)out.size(), &n);
+    if (st != JXLH_OK) throw Error(st, "jxlh_extra_channel_changed_rects", "");
+    return out;
+  }
   // the save stage of an extra channel: one f32 plane of the frame's output size (out_width() x out_height())
   void save_extra_channel(uint32_t ec, float* out, size_t stride) {
     jxlh_plane pl{out, (size_t)frame_.out_width() * sizeof(float), frame_.out_height(), stride * sizeof(float)};

@@ -32,7 +32,8 @@ void set_filter_params(FrameDev& f, const jxlh_frame_params& p) {
 // The per-frame state every jxlh_frame_begin starts from: FrameState's defaults, and the steps that are no plain value.
 static void start_frame(jxlh_ctx* ctx) {
   ctx->frame = FrameState{};
-  for (auto& e : ctx->extra) e.set = e.done = e.pat_ready = false;
+  for (auto& e : ctx->extra) e.set = e.done = e.pat_ready = e.rect = false;
+  for (auto& g : ctx->ec_plan.ch) g.clear();  // the rect state of the extra channels is per frame
   for (auto& s : ctx->slots) s.used = false;
   ctx->patch_desc_host.clear();  // the patch dictionary is per frame (the reference slots are not)
   ctx->spline_desc_host.clear();  // ... and so are the splines
@@ -402,6 +403,8 @@ jxlh_status jxlh_frame_set_extra_channel(jxlh_ctx* ctx, uint32_t ec, const int32
   e.up = ec_upsampling;
   e.set = true;
   e.done = false;
+  e.rect = false;  // a whole-plane channel (again): the next run converts all of it
+  ctx->ec_plan.ch[ec].clear();
   return JXLH_OK;
 }
 

@@ -376,7 +376,7 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
     // PatchesStage (frame/render.rs:644-650): after the extra channels' own upsampling, before the colour upsampling
     // and noise, at the coded size.  The extra channels must be converted before the patches read them.
     bool pending = whole_frame;
-    for (uint32_t i = 0; i < ctx->frame.patch_nec; i++) pending |= !ctx->extra[i].done;
+    for (uint32_t i = 0; i < ctx->frame.patch_nec; i++) pending |= !ctx->extra[i].done || extra_pending(ctx, i);
     if (ctx->frame.patch_nec > 0 && pending) {
       if (jxlh_status st = run_extra_channels(ctx)) return st;
       extra_run = true;
@@ -431,7 +431,7 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
   }
   // (a partial re-render still picks up a channel that was handed over after the last whole-frame run)
   bool pending_extra = false;
-  for (int i = 0; i < JXLH_MAX_EXTRA_CHANNELS; i++) pending_extra |= ctx->extra[i].set && !ctx->extra[i].done;
+  for (int i = 0; i < JXLH_MAX_EXTRA_CHANNELS; i++) pending_extra |= extra_pending(ctx, (uint32_t)i);
   if ((whole_frame || pending_extra) && !extra_run)
     if (jxlh_status st = run_extra_channels(ctx)) return st;
   HIPCHK(ctx, hipGetLastError());
@@ -441,9 +441,14 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
 // channels 3.. of the reference's pipeline: ConvertModularToF32Stage, then Upsample<N> by the channel's own factor
 // (frame/render.rs:564-567, :624-637 / :655-671)
 jxlh_status run_extra_channels(jxlh_ctx* ctx) {
+  bool rect_channels = false;
   for (int i = 0; i < JXLH_MAX_EXTRA_CHANNELS; i++) {
     jxlh_ctx::ExtraChannel& e = ctx->extra[i];
     if (!e.set) continue;
+    if (e.rect) {  // only its dirty tiles, below
+      rect_channels = true;
+      continue;
+    }
     const size_t n = (size_t)e.w * e.h;
     e.done = false;
     e.pat_ready = false;  // a new base: the patched copy is rebuilt by the next patches launch
@@ -473,6 +478,77 @@ jxlh_status run_extra_channels(jxlh_ctx* ctx) {
     }
     e.done = true;
   }
+  return rect_channels ? run_extra_channel_rects(ctx) : JXLH_OK;
+}
+
+// The channels with rect state (jxl_hip_extra_rects.h): the dirty tiles of all of them (ec_rects_plan.h) in at most one
+// k_ec_finish launch per factor -- ConvertModularToF32Stage, and Upsample<N> read from the i32 samples.  The buffers and
+// strides are the whole-plane path's, so every reader of a finished channel takes them as they are.
+jxlh_status run_extra_channel_rects(jxlh_ctx* ctx) {
+  const uint32_t full_w = (uint32_t)(ctx->res_w > 0 ? ctx->res_w : ctx->fd.xsize),
+                 full_h = (uint32_t)(ctx->res_h > 0 ? ctx->res_h : ctx->fd.ysize);
+  EcChannelDesc chans[JXLH_MAX_EXTRA_CHANNELS] = {};
+  size_t n_items = 0;
+  for (int i = 0; i < JXLH_MAX_EXTRA_CHANNELS; i++) {
+    jxlh_ctx::ExtraChannel& e = ctx->extra[i];
+    if (!e.set || !e.rect) continue;
+    const EcGrid& g = ctx->ec_plan.ch[i];
+    e.out_w = std::min(e.w * e.up, full_w);
+    e.out_h = std::min(e.h * e.up, full_h);
+    e.out_stride = e.up > 1 ? round_up((size_t)e.w * e.up, 64) : e.w;
+    DevBuf<float>& dst = e.up > 1 ? e.out : e.f32;
+    // (allocated by the first run after the begin, when every tile is dirty, or by the whole-plane run before the rects)
+    if (jxlh_status st = ensure(ctx, dst, e.up > 1 ? e.out_stride * (size_t)e.h * e.up : (size_t)e.w * e.h)) return st;
+    if (e.up > 1)  // on first use this uploads and waits: in front of the timed launches
+      if (jxlh_status st = upload_upsampling_kernels(ctx, (int)e.up)) return st;
+    n_items += g.n_dirty;
+    EcChannelDesc& c = chans[i];
+    c.raw = e.raw.p;
+    c.dst = dst.p;
+    c.dst_stride = e.out_stride;
+    c.w = e.w;
+    c.h = e.h;
+    c.ntx = g.ntx;
+    c.out_w = e.out_w;
+    c.out_h = e.out_h;
+    c.bits = e.bits & 0xffu;
+    c.exp_bits = e.bits >> 8;
+    c.scale = c.exp_bits ? 0.0f : 1.0f / (float)((1ull << c.bits) - 1);
+  }
+  if (n_items) {
+    // room first: once the plan has handed its tiles over (collect) they are issued
+    const size_t bytes = sizeof(chans) + n_items * sizeof(EcItem);
+    if (jxlh_status st = ensure(ctx, ctx->ec_finish_dev, bytes)) return st;
+    HIPCHK(ctx, ctx->ec_finish_copied.sync());  // the pinned block's previous list is on its way
+    ctx->ec_finish_copied.clear();
+    if (ctx->ec_finish_host.n < bytes) {
+      HIPCHK(ctx, ctx->ec_finish_host.reset());
+      HIPCHK(ctx, ctx->ec_finish_host.alloc(bytes + bytes / 2));
+    }
+    uint32_t first[5];
+    ctx->ec_plan.collect(ctx->ec_items, first);
+    std::memcpy(ctx->ec_finish_host.p, chans, sizeof(chans));
+    std::memcpy(ctx->ec_finish_host.p + sizeof(chans), ctx->ec_items.data(), n_items * sizeof(EcItem));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ec_finish_dev.p, ctx->ec_finish_host.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, ctx->ec_finish_copied.record(ctx->stream));
+    const EcChannelDesc* dchans = reinterpret_cast<const EcChannelDesc*>(ctx->ec_finish_dev.p);
+    const EcItem* ditems = reinterpret_cast<const EcItem*>(ctx->ec_finish_dev.p + sizeof(chans));
+    ScopedKernelTimer t(ctx, "k_ec_finish");
+    for (int k = 0; k < 4; k++) {
+      if (first[k + 1] == first[k]) continue;
+      const float* kernels = nullptr;
+      if (k > 0) {
+        if (jxlh_status st = upload_upsampling_kernels(ctx, 1 << k)) return st;  // (valid already: selects the set)
+        kernels = ctx->ups_kernels.p;
+      }
+      launch_ec_finish(ctx->stream, 1 << k, dchans, ditems + first[k], first[k + 1] - first[k], kernels);
+    }
+    // a new base: the patched copy is rebuilt (whole) by the next patches launch
+    ctx->frame.patch_ec_stale = true;
+    for (const EcItem& it : ctx->ec_items) ctx->extra[it.ec].pat_ready = false;
+  }
+  for (auto& e : ctx->extra)
+    if (e.set && e.rect) e.done = true;
   return JXLH_OK;
 }
 }  // namespace jxlh_host

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "device_owned.h"
+#include "ec_rects_plan.h"
 #include "frame_plan.h"
 #include "jxlh_internal.h"
 #include "run_plan.h"
@@ -212,8 +213,23 @@ struct jxlh_ctx {
     // result for the current conversion (read-outs then return it)
     DevBuf<float> pat;
     bool pat_ready = false;
+    // rect state (jxl_hip_extra_rects.h): the channel was begun without samples or touched by a rects call -- a run
+    // finishes only the dirty tiles of ec_plan.ch[i]
+    bool rect = false;
   };
   ExtraChannel extra[JXLH_MAX_EXTRA_CHANNELS];
+  // extra channels by rect: the channels' tile grids and dirty bitmaps (ec_rects_plan.h); the scatter descriptors of a
+  // rects call and the host block's span on the device; a run's channel descriptors + item list.  Both lists go up from
+  // a pinned block, reused once its fence (recorded behind the copy) has passed.
+  EcRectsPlan ec_plan;
+  DevBuf<int32_t> ec_block;
+  DevBuf<EcScatterDesc> ec_scatter_dev;
+  Pinned<EcScatterDesc> ec_scatter_host;
+  Fence ec_scatter_copied;
+  DevBuf<uint8_t> ec_finish_dev;
+  Pinned<uint8_t> ec_finish_host;
+  Fence ec_finish_copied;
+  std::vector<EcItem> ec_items;
   // reference frames (DecoderState::reference_frames): n_channels planes of w x h at `stride`, channel c at c * stride * h
   struct RefSlot {
     bool set = false;
@@ -381,6 +397,11 @@ jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan);
 jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& stages, int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame);
 jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsample of the channels handed over
+jxlh_status run_extra_channel_rects(jxlh_ctx* ctx);  // ... and of the dirty tiles of the channels with rect state
+// an extra channel a run still has to convert: handed over or touched since it was last finished
+inline bool extra_pending(const jxlh_ctx* ctx, uint32_t i) {
+  return ctx->extra[i].set && (!ctx->extra[i].done || (ctx->extra[i].rect && ctx->ec_plan.dirty(i)));
+}
 // abi_patches.hip: the patches stage on the colour planes `cur` (rows [y_lo, y_hi)) and, when stale, on every row of
 // the patched extra channels; the check a run makes before it launches anything
 jxlh_status run_patches(jxlh_ctx* ctx, float* const cur[3], size_t stride, int y_lo, int y_hi);

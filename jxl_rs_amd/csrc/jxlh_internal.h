@@ -558,6 +558,28 @@ void launch_save(hipStream_t s, const SaveLaunch& a);
 struct SaveRectWork;
 void launch_save_rects(hipStream_t s, const SaveLaunch& a, const SaveRectWork* work, uint32_t n, uint32_t groups);
 
+// extra channels by rect (k_extra_rects.hip; ec_rects_plan.h decides): the rects of one call from one block of samples
+// into the channels' sample planes, and the finish of a run's dirty tiles
+struct EcScatterDesc;
+struct EcItem;
+struct EcPlanes {
+  int32_t* raw[JXLH_MAX_EXTRA_CHANNELS];  // the channels' sample planes (w x h at stride w)
+};
+// a channel as k_ec_finish reads it (device memory, scalar loads): dst = its f32 plane (factor 1, stride w) or its
+// upsampled plane (stores beyond out_w x out_h are suppressed); integer samples scale by `scale`, float samples
+// (exp_bits != 0) widen exactly
+struct EcChannelDesc {
+  const int32_t* raw;
+  float* dst;
+  uint64_t dst_stride;
+  uint32_t w, h, ntx, out_w, out_h, bits, exp_bits;
+  float scale;
+};
+void launch_ec_scatter(hipStream_t s, const int32_t* src, const EcScatterDesc* descs, uint32_t n, uint64_t pieces,
+                       const EcPlanes& planes);
+void launch_ec_finish(hipStream_t s, int n, const EcChannelDesc* chans, const EcItem* items, uint32_t count,
+                      const float* kernels);
+
 // the LF-frame preview (k_lf_preview.hip): Upsample8x of a rect of an LF slot, the colour stage, the conversion at
 // pipeline position (channel 0, row 0) and the oriented interleaved store, one pass.  The kernel indexes the structure
 // with constants only, like SaveLaunch.

@@ -78,6 +78,55 @@ def changed_rects(params, group_ids):
     return rects
 
 
+def try_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects, cap=None):
+    """jxlh_extra_channel_changed_rects (host only), returning (status, rects [n, 4] as (x0, y0, w, h) or None, n needed).
+    cap: room offered (None: as many as needed -- asked for first, as a C caller would)"""
+    src, n_src = _rect_array(rects)
+    L, n = load(), C.c_uint32(0)
+    if cap is None:
+        st = L.jxlh_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, _addr(src), n_src, None, 0, C.byref(n))
+        if st != OK and n.value == 0:
+            return st, None, 0
+        cap = n.value
+    out = np.zeros((max(int(cap), 1), 4), dtype=np.uint32)
+    st = L.jxlh_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, _addr(src), n_src,
+                                            _addr(out) if cap else None, int(cap), C.byref(n))
+    return st, (out[:n.value].copy() if st == OK else None), n.value
+
+
+def extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects):
+    """the rectangles of the finished extra channel (w x h samples, factor ec_upsampling, cut to res_w x res_h) outside
+    which new samples in `rects` (source samples, rows (x0, y0, w, h)) change nothing: one per input rect"""
+    st, out, _ = try_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects)
+    if st != OK:
+        raise JxlHipError(st, "jxlh_extra_channel_changed_rects")
+    return out
+
+
+# jxlh_ec_rect as a numpy record (the C layout: `offset` is 8-byte aligned)
+EC_RECT_DTYPE = np.dtype([("ec", np.uint32), ("x0", np.uint32), ("y0", np.uint32), ("w", np.uint32), ("h", np.uint32),
+                          ("offset", np.uint64), ("stride", np.uint32)], align=True)
+
+
+def pack_ec_rects(rects, stride_pad=0, fill=0):
+    """(ec, x0, y0, samples [h, w]) rects -> (block, descs): one contiguous i32 block with every rect's rows `w +
+    stride_pad` samples apart (the padding holds `fill`), and the jxlh_ec_rect records (EC_RECT_DTYPE) that name them"""
+    descs = np.zeros(len(rects), dtype=EC_RECT_DTYPE)
+    parts, off = [], 0
+    for i, (ec, x0, y0, a) in enumerate(rects):
+        a = np.asarray(a, dtype=np.int32)
+        a = a.reshape(a.shape if a.ndim == 2 else (0, 0))
+        h, w = a.shape
+        stride = w + int(stride_pad)
+        blk = np.full((h, stride), fill, dtype=np.int32)
+        blk[:, :w] = a
+        descs[i] = (ec, x0, y0, w, h, off, stride)
+        parts.append(blk.reshape(-1))
+        off += blk.size
+    block = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    return np.ascontiguousarray(block, dtype=np.int32), descs
+
+
 class SaveDesc(_abi.SaveDesc):
     """jxlh_save_desc, with the sizes callers allocate by."""
 
@@ -903,6 +952,39 @@ class Context:
         self._chk(self.L.jxlh_frame_set_extra_channel(self._ctx, ec, _addr(a), w, w, h, bits_per_sample | exp_bits << 8,
                                                       ec_upsampling),
                   "frame_set_extra_channel")
+
+    def begin_extra_channel(self, ec, w, h, bits_per_sample, ec_upsampling=1, exp_bits=0):
+        """jxlh_frame_begin_extra_channel: declares extra channel `ec` of w x h samples, all zero until rects set them"""
+        self._chk(self.L.jxlh_frame_begin_extra_channel(self._ctx, ec, w, h, bits_per_sample | exp_bits << 8, ec_upsampling),
+                  "frame_begin_extra_channel")
+
+    def try_set_extra_channel_rects(self, block, descs, n_samples=None, n=None, wait=True):
+        """jxlh_frame_set_extra_channel_rects (wait=False: the _async form), returning (status, first_bad or None).  block: an
+        i32 array, or a DeviceArray / raw device pointer with n_samples; descs: EC_RECT_DTYPE records (or None with n)"""
+        if block is not None and not _is_pointer(block):
+            block = np.ascontiguousarray(block, dtype=np.int32)
+            n_samples = block.size if n_samples is None else n_samples
+            if not wait:
+                self._keep["ec_block"] = block
+        if descs is not None:
+            descs = np.ascontiguousarray(descs, dtype=EC_RECT_DTYPE)
+            n = len(descs) if n is None else n
+        bad = C.c_uint32(0xFFFFFFFF)
+        fn = self.L.jxlh_frame_set_extra_channel_rects if wait else self.L.jxlh_frame_set_extra_channel_rects_async
+        st = fn(self._ctx, None if block is None else _addr(block), int(n_samples or 0),
+                None if descs is None else _addr(descs), int(n or 0), C.byref(bad))
+        return st, (None if bad.value == 0xFFFFFFFF else bad.value)
+
+    def set_extra_channel_rects(self, rects, wait=True, block=None, n_samples=None, stride_pad=0):
+        """Samples of extra channels as they arrive: rects = (ec, x0, y0, samples [h, w]) tuples, packed into one block
+        and handed over in one call; converted by the next frame_run / rerender_groups.  With `block` (an i32 array, a
+        DeviceArray or a raw device pointer with n_samples) rects are EC_RECT_DTYPE records that name samples of it."""
+        if block is None:
+            block, descs = pack_ec_rects(rects, stride_pad=stride_pad)
+        else:
+            descs = rects
+        st, bad = self.try_set_extra_channel_rects(block, descs, n_samples=n_samples, wait=wait)
+        self._chk(st, "frame_set_extra_channel_rects" + ("" if bad is None else f" (rect {bad})"))
 
     def read_extra_channel(self, ec, out_w, out_h):
         out = np.zeros((out_h, out_w), dtype=np.float32)

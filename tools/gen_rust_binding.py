@@ -22,6 +22,8 @@ SAVE_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_save_rects.h")
 OUT_SAVE_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "save_rects.rs")
 PREVIEW_TILES_HEADER = os.path.join(ROOT, "include", "jxl_hip_preview_tiles.h")
 OUT_PREVIEW_TILES = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "preview_tiles.rs")
+EXTRA_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_extra_rects.h")
+OUT_EXTRA_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "extra_rects.rs")
 
 SCALARS = {"uint8_t": "u8", "int8_t": "i8", "uint16_t": "u16", "int16_t": "i16", "uint32_t": "u32", "int32_t": "i32",
            "uint64_t": "u64", "int64_t": "i64", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -158,17 +160,22 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod save_rects;")
     w("// include/jxl_hip_preview_tiles.h (... src/preview_tiles.rs)")
     w("pub mod preview_tiles;")
+    w("// include/jxl_hip_extra_rects.h (... src/extra_rects.rs)")
+    w("pub mod extra_rects;")
     return "\n".join(out) + "\n"
 
 
-def emit_extension(header_name, defines, enums, structs, opaque, funcs):
-    """a header that adds constants, plain structs and entry points, as a module on top of the crate's types"""
+def emit_extension(header_name, defines, enums, structs, opaque, funcs, uses=()):
+    """a header that adds constants, plain structs and entry points, as a module on top of the crate's types (uses: the
+    sibling modules whose structs its signatures name)"""
     assert not opaque, header_name
     out = []
     w = out.append
     w(f"// GENERATED by tools/gen_rust_binding.py from include/{header_name} -- do not edit.")
     w("#![allow(non_camel_case_types, non_upper_case_globals, dead_code)]")
     w("use super::*;")
+    for dep in uses:
+        w(f"use super::{dep}::*;")
     w("")
     for name, val in defines + enums:
         w(f"pub const {name}: u32 = {val};")
@@ -206,9 +213,14 @@ def generate_preview_tiles():
     return emit_extension(os.path.basename(PREVIEW_TILES_HEADER), *parse_header(open(PREVIEW_TILES_HEADER).read()))
 
 
+def generate_extra_rects():
+    return emit_extension(os.path.basename(EXTRA_RECTS_HEADER), *parse_header(open(EXTRA_RECTS_HEADER).read()),
+                          uses=("save_rects",))
+
+
 def main():
     for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
-                      (OUT_PREVIEW_TILES, generate_preview_tiles())):
+                      (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
             if cur != text:
