@@ -977,7 +977,10 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
  * JXLH_MAX_SAVE_RECTS), declared in jxl_hip_save_rects.h, which this header includes at its end.
  * Extra channels by rect -- a channel declared once and fed rect by rect as its groups arrive, converted and upsampled
  * only where a rect can have changed it: jxlh_frame_begin_extra_channel, jxlh_frame_set_extra_channel_rects (_async)
- * and jxlh_extra_channel_changed_rects (jxlh_ec_rect, JXLH_MAX_EC_RECTS), declared in jxl_hip_extra_rects.h, likewise. */
+ * and jxlh_extra_channel_changed_rects (jxlh_ec_rect, JXLH_MAX_EC_RECTS), declared in jxl_hip_extra_rects.h, likewise.
+ * Repaint -- the re-render of listed groups on every kind of unsharded frame, upsampled and Modular frames included, and
+ * the rectangles of the result it can change: jxlh_frame_repaint_groups and jxlh_repaint_changed_rects, declared in
+ * jxl_hip_repaint.h, likewise. */
 
 /* ---------------------------------------------------------------- LF frames
  * A frame with lf_level = L >= 1 (the layers of a progressive_dc file) is an ordinary frame of ceil(size / 8^L) pixels,
@@ -1303,5 +1306,6 @@ int32_t jxlh_quant_table_size(int32_t table);
 #include "jxl_hip_save_rects.h"
 #include "jxl_hip_preview_tiles.h"
 #include "jxl_hip_extra_rects.h"
+#include "jxl_hip_repaint.h"
 
 #endif /* JXL_HIP_H_ */

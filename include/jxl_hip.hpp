@@ -137,6 +137,17 @@ inline std::vector<jxlh_rect> changed_rects(const jxlh_frame_params& p, const st
   return rects;
 }
 
+// the rectangles of a frame's RESULT (upsampled size) that repainting `groups` can change, on any kind of frame
+// (jxlh_repaint_changed_rects): host only
+inline std::vector<jxlh_rect> repaint_changed_rects(const jxlh_frame_params& p, const std::vector<uint32_t>& groups) {
+  uint32_t n = 0;
+  jxlh_status st = jxlh_repaint_changed_rects(&p, groups.data(), (uint32_t)groups.size(), nullptr, 0, &n);
+  std::vector<jxlh_rect> rects(n);
+  if (n) st = jxlh_repaint_changed_rects(&p, groups.data(), (uint32_t)groups.size(), rects.data(), n, &n);
+  if (st != JXLH_OK) throw Error(st, "jxlh_repaint_changed_rects", "");
+  return rects;
+}
+
 // the rectangles of a finished extra channel (w x h samples, factor ec_upsampling, cut to res_w x res_h) outside which
 // new samples in `rects` (source samples) change nothing (jxlh_extra_channel_changed_rects): host only
 inline std::vector<jxlh_rect> extra_channel_changed_rects(uint32_t w, uint32_t h, uint32_t ec_upsampling, uint32_t res_w,
@@ -312,6 +323,12 @@ class VarDctFrame {
     blend_w_ = blend_h_ = 0;  // a render discards the composition
     ctx_.check(jxlh_frame_run(ctx_.raw(), group_row0, group_row1), "jxlh_frame_run");
   }
+  // The listed cells of the 256 grid over the coded size again, behind a whole finalize_and_render(), on every kind of
+  // unsharded frame -- upsampled and Modular frames included (jxlh_frame_repaint_groups); before any whole render it is one
+  void repaint_groups(const std::vector<uint32_t>& groups) {
+    if (!groups.empty()) blend_w_ = blend_h_ = 0;
+    ctx_.check(jxlh_frame_repaint_groups(ctx_.raw(), groups.data(), (uint32_t)groups.size()), "jxlh_frame_repaint_groups");
+  }
   // tight f32 planes X, Y, B of out_width() x out_height()
   void read_planes(float* x, float* y, float* b) {
     const size_t w = out_width(), h = out_height();
@@ -360,6 +377,10 @@ class VarDctFrame {
   }
   // the rectangles of this frame's result that re-rendering `groups` can change (before blend(): frame coordinates)
   std::vector<jxlh_rect> changed_rects(const std::vector<uint32_t>& groups) const { return jxlh::changed_rects(p_, groups); }
+  // ... and that repaint_groups(groups) can change: the result's coordinates, at the upsampled size
+  std::vector<jxlh_rect> repaint_changed_rects(const std::vector<uint32_t>& groups) const {
+    return jxlh::repaint_changed_rects(p_, groups);
+  }
   uint32_t out_width() const {
     if (blend_w_) return blend_w_;
     const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;

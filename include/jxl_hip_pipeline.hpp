@@ -145,6 +145,20 @@ class GpuRenderPipeline : public GpuFramePipeline {
   // repaints after the do_render() of a pass that touched them.  Frame coordinates: with a BlendingStage in the list,
   // shift them by the frame's origin and clip them to the image.
   std::vector<jxlh_rect> changed_rects(const std::vector<uint32_t>& groups) const { return frame_.changed_rects(groups); }
+  // do_render() for frames jxlh_frame_rerender_groups refuses as well (frame upsampling): the groups handed over or
+  // marked since the last render are repainted (jxlh_frame_repaint_groups), the whole frame before the first render.
+  // repaint_changed_rects: the rectangles of the result, at the upsampled size, that such a repaint can change.
+  void repaint() {
+    for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");
+    if (!rerender_.empty() && !dirty_first_) frame_.repaint_groups(rerender_);
+    else frame_.finalize_and_render();
+    blend_if_listed();
+    dirty_first_ = false;
+    rerender_.clear();
+  }
+  std::vector<jxlh_rect> repaint_changed_rects(const std::vector<uint32_t>& groups) const {
+    return frame_.repaint_changed_rects(groups);
+  }
   // A group that must be rendered while its HF has not arrived (force_render with DataStatus::Zero, frame/decode.rs:
   // 744-752): the reference hands the pipeline the LF image upsampled 8x as the group's buffers; here the group is marked
   // and the next do_render() fills it on the device.  set_buffer_for_group on the group later clears the mark.
@@ -194,6 +208,16 @@ class GpuModularFramePipeline : public GpuFramePipeline {
   void render() {
     frame_.finalize_and_render();
     blend_if_listed();
+  }
+  // The listed cells of the 256 grid over the coded size again, after set_channels / set_groups replaced samples in them
+  // and behind a whole render() (jxlh_frame_repaint_groups: frame upsampling included; before any render() it is one),
+  // then the list's blending; repaint_changed_rects: the rectangles of the result such a repaint can change
+  void repaint_groups(const std::vector<uint32_t>& groups) {
+    frame_.repaint_groups(groups);
+    blend_if_listed();
+  }
+  std::vector<jxlh_rect> repaint_changed_rects(const std::vector<uint32_t>& groups) const {
+    return frame_.repaint_changed_rects(groups);
   }
   // 256-row bands [band0, band1) (a list with blending or frame upsampling renders whole)
   void render_band(uint32_t band0, uint32_t band1) {

@@ -41,11 +41,15 @@ jxlh_status modular_frame_begin(jxlh_ctx* ctx, const FramePlan& pl) {
 
 // jxlh_frame_run of a Modular frame on 256-row bands [group_row0, group_row1) (clamped and checked by the caller)
 jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_row1) {
-  FrameDev& f = ctx->fd;
-  const jxlh_frame_params& p = ctx->params;
   if (jxlh_status st = patches_check_run(ctx)) return st;
   // (a band whose halo rows would undo the neighbouring band's finished rows is rendered whole: run_plan.h)
   const RunPlan plan = plan_run(run_inputs(ctx), (int)group_row0, (int)group_row1);
+  return modular_frame_issue(ctx, plan, plan.y_lo, plan.y_hi, nullptr);
+}
+
+jxlh_status modular_frame_issue(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_hi, const PostRepaint* repaint) {
+  FrameDev& f = ctx->fd;
+  const jxlh_frame_params& p = ctx->params;
   f.tiled = plan.tiled ? 1 : 0;  // the intake writes raster planes
   ctx->frame.strip_ran = false;
   ctx->frame.chroma_lazy = plan.chroma_lazy;
@@ -75,7 +79,7 @@ jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group
   }
   if (f.subsampled) run_chroma_upsample_rows(ctx, ya, yb);  // frame/render.rs:569-576, in front of the filters
   if (plan.whole) ctx->frame.rendered = true;
-  return run_stages_rows(ctx, plan.stages, plan.y_lo, plan.y_hi, plan.whole);
+  return run_stages_rows(ctx, plan.stages, y_lo, y_hi, plan.whole, repaint);
 }
 
 }  // namespace jxlh_host

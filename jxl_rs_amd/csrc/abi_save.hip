@@ -303,6 +303,18 @@ jxlh_status jxlh_changed_rects(const jxlh_frame_params* p, const uint32_t* group
   return JXLH_OK;
 }
 
+// pure host code (repaint_plan.h)
+jxlh_status jxlh_repaint_changed_rects(const jxlh_frame_params* p, const uint32_t* group_ids, uint32_t count,
+                                       jxlh_rect* rects, uint32_t cap, uint32_t* n) {
+  if (!p || !n || (count && !group_ids) || (cap && !rects)) return JXLH_ERR_INVALID_ARGUMENT;
+  std::vector<jxlh_rect> need;
+  if (jxlh_status st = plan_repaint_changed_rects(*p, group_ids, count, need)) return st;
+  *n = (uint32_t)need.size();
+  if (need.size() > cap) return JXLH_ERR_INVALID_ARGUMENT;
+  std::copy(need.begin(), need.end(), rects);
+  return JXLH_OK;
+}
+
 // jxlh_stage_save (rows [y0, y1)) and jxlh_stage_save_rects (by_rects: the list)
 static jxlh_status stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const jxlh_save_desc* d,
                               const float* const planes[], uint32_t n_planes, uint32_t w, uint32_t h, size_t stride,

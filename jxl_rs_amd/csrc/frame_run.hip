@@ -318,7 +318,8 @@ jxlh_status run_strip(jxlh_ctx* ctx) {
 }
 
 // the stage list on pixel rows [y_lo, y_hi), then upsampling and noise
-jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& sl, int y_lo, int y_hi, bool whole_frame) {
+jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& sl, int y_lo, int y_hi, bool whole_frame,
+                            const PostRepaint* repaint) {
   FrameDev& f = ctx->fd;
   // ---- stage list of frame/render.rs:569-622
   StageList::Stage stages[4];
@@ -360,11 +361,12 @@ jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& sl, int y_lo, int y_
     }
     std::swap(cur, oth);
   }
-  return run_post_stages(ctx, cur, y_lo, y_hi, whole_frame);
+  return run_post_stages(ctx, cur, y_lo, y_hi, whole_frame, repaint);
 }
 
 // what follows the filters: patches, splines, upsampling and noise on the finished planes `cur` (rows [y_lo, y_hi))
-jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame) {
+jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame,
+                            const PostRepaint* repaint) {
   FrameDev& f = ctx->fd;
   const jxlh_frame_params& p = ctx->params;
   for (int c = 0; c < 3; c++) ctx->frame.result[c] = cur[c];
@@ -388,8 +390,8 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
     if (jxlh_status st = run_splines(ctx, cur, f.plane_stride, f.xsize, f.ysize, y_lo, y_hi)) return st;
   if (p.upsampling > 1) {
     // Upsample2x/4x/8x on the three colour channels (frame/render.rs:655-671).  The 5x5 window crosses band
-    // edges, so an upsampled frame is run whole.
-    if (!whole_frame) return JXLH_ERR_UNSUPPORTED;
+    // edges, so an upsampled frame is run whole -- or, by a repaint behind a whole run, on the rows its plan names.
+    if (!whole_frame && !repaint) return JXLH_ERR_UNSUPPORTED;
     const int n = (int)p.upsampling;
     const int ow = p.xsize_upsampled ? (int)p.xsize_upsampled : f.xsize * n;
     const int oh = p.ysize_upsampled ? (int)p.ysize_upsampled : f.ysize * n;
@@ -397,12 +399,20 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
     if (jxlh_status st = upload_upsampling_kernels(ctx, n)) return st;
     for (int c = 0; c < 3; c++)
       if (jxlh_status st = ensure(ctx, ctx->ups[c], ostride * (size_t)f.ysize * n)) return st;
-    ScopedKernelTimer t(ctx, "k_upsample");
-    for (int c = 0; c < 3; c++) {
-      launch_upsample(ctx->stream, n, cur[c], f.plane_stride, f.xsize, f.ysize, ctx->ups_kernels.p, ctx->ups[c].p,
-                      ostride, ow, oh);
-      ctx->frame.result[c] = ctx->ups[c].p;
+    if (whole_frame) {
+      ScopedKernelTimer t(ctx, "k_upsample");
+      for (int c = 0; c < 3; c++)
+        launch_upsample(ctx->stream, n, cur[c], f.plane_stride, f.xsize, f.ysize, ctx->ups_kernels.p, ctx->ups[c].p,
+                        ostride, ow, oh);
+    } else if (!repaint->centre_rows->empty()) {
+      // (the buffers are the whole run's: ensure() at an unchanged size keeps them and what they hold)
+      float* const out[3] = {ctx->ups[0].p, ctx->ups[1].p, ctx->ups[2].p};
+      ScopedKernelTimer t(ctx, "k_upsample_rows");
+      for (const RowRange& r : *repaint->centre_rows)
+        launch_upsample_rows(ctx->stream, n, cur, f.plane_stride, f.xsize, f.ysize, r.lo, r.hi, ctx->ups_kernels.p, out,
+                             ostride, ow, oh);
     }
+    for (int c = 0; c < 3; c++) ctx->frame.result[c] = ctx->ups[c].p;
     ctx->res_w = ow;
     ctx->res_h = oh;
     ctx->res_stride = ostride;
@@ -411,23 +421,31 @@ jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_
     // render_noise_for_group + ConvolveNoise x3 + AddNoise (frame/decode.rs:578-668, frame/render.rs:673-683),
     // at the resolution of the result (after upsampling).  Random planes: the 256-row tile rows that cover
     // the band plus the convolution's 2-row border.
+    // An upsampled frame: all of it -- or, in a repaint, exactly the result rows that were just written again (every
+    // other row still carries the noise of the whole run: adding it there would add it twice).
     const int W = ctx->res_w, H = ctx->res_h;
-    const int ya = p.upsampling > 1 ? 0 : y_lo, yb = p.upsampling > 1 ? H : y_hi;
+    const RowRange own{p.upsampling > 1 ? 0 : y_lo, p.upsampling > 1 ? H : y_hi};
+    const bool listed = p.upsampling > 1 && !whole_frame;
+    const RowRange* rows = listed ? repaint->noise_rows->data() : &own;
+    const size_t n_rows = listed ? repaint->noise_rows->size() : 1;
     if (jxlh_status st = ensure_jump_table(ctx)) return st;
     for (int c = 0; c < 3; c++)
       if (jxlh_status st = ensure(ctx, ctx->noise[c], ctx->res_stride * (size_t)H)) return st;
     float* nz[3] = {ctx->noise[0].p, ctx->noise[1].p, ctx->noise[2].p};
-    const int ty0 = max(0, ya - 2) / 256, ty1 = (min(H, yb + 2) + 255) / 256;
-    {
-      ScopedKernelTimer t(ctx, "k_noise_generate");
-      launch_noise_generate(ctx->stream, nz, ctx->res_stride, W, H, ty0, ty1, p.visible_frame_index,
-                            p.nonvisible_frame_index, ctx->xs_jump.p);
-    }
     const float ytox = p.base_correlation_x + (float)p.ytox_lf / (float)p.color_factor;  // y_to_x_lf
     const float ytob = p.base_correlation_b + (float)p.ytob_lf / (float)p.color_factor;
-    ScopedKernelTimer t(ctx, "k_noise_apply");
-    launch_noise_apply(ctx->stream, nz, ctx->res_stride, ctx->frame.result, ctx->res_stride, W, H, ya, yb, p.noise_lut, ytox,
-                       ytob);
+    for (size_t i = 0; i < n_rows; i++) {
+      const int ya = rows[i].lo, yb = rows[i].hi;
+      const int ty0 = max(0, ya - 2) / 256, ty1 = (min(H, yb + 2) + 255) / 256;
+      {
+        ScopedKernelTimer t(ctx, "k_noise_generate");
+        launch_noise_generate(ctx->stream, nz, ctx->res_stride, W, H, ty0, ty1, p.visible_frame_index,
+                              p.nonvisible_frame_index, ctx->xs_jump.p);
+      }
+      ScopedKernelTimer t(ctx, "k_noise_apply");
+      launch_noise_apply(ctx->stream, nz, ctx->res_stride, ctx->frame.result, ctx->res_stride, W, H, ya, yb, p.noise_lut,
+                         ytox, ytob);
+    }
   }
   // (a partial re-render still picks up a channel that was handed over after the last whole-frame run)
   bool pending_extra = false;
@@ -551,6 +569,31 @@ jxlh_status run_extra_channel_rects(jxlh_ctx* ctx) {
     if (e.set && e.rect) e.done = true;
   return JXLH_OK;
 }
+
+// What jxlh_frame_rerender_groups and jxlh_frame_repaint_groups share once the plan says "bands": the transforms (or LF
+// fill) of exactly the groups of ctx->rerender_upload, then the stage list on every band.  rows: a repaint's upsampling
+// and noise rows, handed over with the last band (run_post_stages); null for a re-render.
+static jxlh_status rerender_listed(jxlh_ctx* ctx, const RunInputs& in, const std::vector<RowBand>& bands,
+                                   const PostRepaint* rows) {
+  bool sparse_k1 = false;
+  if (jxlh_status st = run_prologue(ctx, false, in.stages.fused(), &sparse_k1)) return st;
+  // ---- transforms of exactly the listed groups
+  // a listed group whose HF has not arrived (jxlh_frame_set_groups_lf_only) is filled from the LF image again, the
+  // others are transformed: the list goes up with the transforms' groups first
+  int n_k1 = 0, n_fill = 0;
+  if (jxlh_status st = lf_split_groups(ctx, ctx->rerender_upload, &n_k1, &n_fill)) return st;
+  if (jxlh_status st = run_transforms(ctx, sparse_k1, 0, 0, true, n_k1, n_fill)) return st;
+  // ---- the filters on every pixel row the listed groups influence
+  static const std::vector<RowRange> none;
+  const PostRepaint wait{&none, &none};
+  for (size_t i = 0; i < bands.size(); i++) {
+    const RowBand& b = bands[i];
+    if (jxlh_status st = run_stages_rows(ctx, in.stages, b.y_lo, b.y_hi, b.whole_frame,
+                                         !rows ? nullptr : i + 1 == bands.size() ? rows : &wait))
+      return st;
+  }
+  return JXLH_OK;
+}
 }  // namespace jxlh_host
 
 extern "C" {
@@ -597,17 +640,38 @@ jxlh_status jxlh_frame_rerender_groups(jxlh_ctx* ctx, const uint32_t* group_ids,
   const RerenderPlan plan = plan_rerender(in, ctx->rerender_upload);
   if (plan.route == RerenderPlan::kUnsupported) return JXLH_ERR_UNSUPPORTED;
   if (plan.route == RerenderPlan::kFullRun) return jxlh_frame_run(ctx, 0, UINT32_MAX);
-  bool sparse_k1 = false;
-  if (jxlh_status st = run_prologue(ctx, false, in.stages.fused(), &sparse_k1)) return st;
-  // ---- transforms of exactly the listed groups
-  // a listed group whose HF has not arrived (jxlh_frame_set_groups_lf_only) is filled from the LF image again, the
-  // others are transformed: the list goes up with the transforms' groups first
-  int n_k1 = 0, n_fill = 0;
-  if (jxlh_status st = lf_split_groups(ctx, ctx->rerender_upload, &n_k1, &n_fill)) return st;
-  if (jxlh_status st = run_transforms(ctx, sparse_k1, 0, 0, true, n_k1, n_fill)) return st;
-  // ---- the filters on every pixel row the listed groups influence
-  for (const RowBand& b : plan.bands)
-    if (jxlh_status st = run_stages_rows(ctx, in.stages, b.y_lo, b.y_hi, b.whole_frame)) return st;
+  return rerender_listed(ctx, in, plan.bands, nullptr);
+}
+
+jxlh_status jxlh_frame_repaint_groups(jxlh_ctx* ctx, const uint32_t* group_ids, uint32_t count) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || (count && !group_ids)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
+  if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
+  if (!ctx->modular && !ctx->tables_set) return JXLH_ERR_BAD_STATE;
+  const uint32_t ncells = (uint32_t)ctx->fd.xgroups * (uint32_t)ctx->fd.ygroups;
+  for (uint32_t i = 0; i < count; i++)
+    if (group_ids[i] >= ncells) return JXLH_ERR_INVALID_ARGUMENT;
+  if (count == 0) return JXLH_OK;
+  if (jxlh_status st = patches_check_run(ctx)) return st;
+  ctx->rerender_upload.assign(group_ids, group_ids + count);
+  std::sort(ctx->rerender_upload.begin(), ctx->rerender_upload.end());
+  ctx->rerender_upload.erase(std::unique(ctx->rerender_upload.begin(), ctx->rerender_upload.end()),
+                             ctx->rerender_upload.end());
+  const RunInputs in = run_inputs(ctx);
+  const jxlh_frame_params& p = ctx->params;
+  const int out_h = p.upsampling > 1 && p.ysize_upsampled ? (int)p.ysize_upsampled : in.ysize * std::max(1, in.upsampling);
+  const RepaintPlan plan = plan_repaint(in, ctx->rerender_upload, out_h);
+  if (plan.route == RepaintPlan::kWholeRun) return jxlh_frame_run(ctx, 0, UINT32_MAX);
+  const PostRepaint rows{&plan.centre_rows, &plan.noise_rows};
+  if (plan.route == RepaintPlan::kRerenderBands) return rerender_listed(ctx, in, plan.bands, &rows);
+  // a Modular frame: the intake of every run of listed group rows, the stage list on its rows and the stage list's reach
+  static const std::vector<RowRange> none;
+  const PostRepaint wait{&none, &none};
+  for (size_t i = 0; i < plan.runs.size(); i++)
+    if (jxlh_status st = modular_frame_issue(ctx, plan.runs[i], plan.bands[i].y_lo, plan.bands[i].y_hi,
+                                             i + 1 == plan.runs.size() ? &rows : &wait))
+      return st;
   return JXLH_OK;
 }
 

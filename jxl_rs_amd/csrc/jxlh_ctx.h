@@ -15,6 +15,7 @@
 #include "ec_rects_plan.h"
 #include "frame_plan.h"
 #include "jxlh_internal.h"
+#include "repaint_plan.h"
 #include "run_plan.h"
 #include "save_rects_plan.h"
 
@@ -394,8 +395,17 @@ StageList stage_list(const jxlh_ctx* ctx);
 RunInputs run_inputs(jxlh_ctx* ctx);
 jxlh_status run_prologue(jxlh_ctx* ctx, bool strip_candidate, bool tiled, bool* sparse_k1);
 jxlh_status run_k1(jxlh_ctx* ctx, const RunPlan& plan);
-jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& stages, int y_lo, int y_hi, bool whole_frame);
-jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame);
+// repaint (jxlh_frame_repaint_groups, else null): the band belongs to a repaint, whose plan names the coded rows to
+// upsample again and the result rows that then take their noise again (repaint_plan.h).  A repaint of several bands
+// hands the rows over with its LAST band, when every coded row is final, and empty lists with the others.
+struct PostRepaint {
+  const std::vector<RowRange>* centre_rows;
+  const std::vector<RowRange>* noise_rows;
+};
+jxlh_status run_stages_rows(jxlh_ctx* ctx, const StageList& stages, int y_lo, int y_hi, bool whole_frame,
+                            const PostRepaint* repaint = nullptr);
+jxlh_status run_post_stages(jxlh_ctx* ctx, float* const cur[3], int y_lo, int y_hi, bool whole_frame,
+                            const PostRepaint* repaint = nullptr);
 jxlh_status run_extra_channels(jxlh_ctx* ctx);  // ConvertModularToF32 + Upsample of the channels handed over
 jxlh_status run_extra_channel_rects(jxlh_ctx* ctx);  // ... and of the dirty tiles of the channels with rect state
 // an extra channel a run still has to convert: handed over or touched since it was last finished
@@ -460,6 +470,8 @@ jxlh_status choose_placement(jxlh_ctx* ctx, const FramePlan& pl);
 // abi_modular_frame.hip: the commit / jxlh_frame_run of a Modular frame
 jxlh_status modular_frame_begin(jxlh_ctx* ctx, const FramePlan& pl);
 jxlh_status modular_frame_run(jxlh_ctx* ctx, uint32_t group_row0, uint32_t group_row1);
+// ... and what it issues for a plan: the intake of the plan's rows, the stage list on rows [y_lo, y_hi)
+jxlh_status modular_frame_issue(jxlh_ctx* ctx, const RunPlan& plan, int y_lo, int y_hi, const PostRepaint* repaint);
 void run_chroma_upsample_rows(jxlh_ctx* ctx, int y0, int y1);  // frame_run.hip: ... of the rows that cover [y0, y1)
 // frame_run.hip: pieces of the frame pipeline the read-out and stage-hook entry points share
 bool noise_lut_is_zero(const float lut[8]);

@@ -218,6 +218,10 @@ void launch_chroma_upsample(hipStream_t s, const float* src, float* dst, const P
 // upsample.rs: n = 2, 4, 8; kernels = n*n*25 expanded taps on the device; writes are clipped to out_w x out_h
 void launch_upsample(hipStream_t s, int n, const float* in, size_t in_stride, int w, int h, const float* kernels,
                      float* out, size_t out_stride, int out_w, int out_h);
+// the same on input rows [iy0, iy1) of three planes in one launch: the window is mirrored at the image's edges (h), exactly
+// output rows [n * iy0, min(n * iy1, out_h)) are written
+void launch_upsample_rows(hipStream_t s, int n, const float* const in[3], size_t in_stride, int w, int h, int iy0, int iy1,
+                          const float* kernels, float* const out[3], size_t out_stride, int out_w, int out_h);
 // k_lf_fill.hip: the 8 x 8 patches of Upsample8x over f.lf[c] (the whole image, mirrored at its edges) for every block of
 // the n groups listed at `groups` (device), into f.planes[c] in the layout of pix_layout(f); kernels = the expanded
 // taps of factor 8

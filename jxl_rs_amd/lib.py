@@ -78,6 +78,31 @@ def changed_rects(params, group_ids):
     return rects
 
 
+def try_repaint_changed_rects(params, group_ids, cap=None):
+    """jxlh_repaint_changed_rects (host only), returning (status, rects [n, 4] as (x0, y0, w, h) or None, n needed), as
+    try_changed_rects does"""
+    ids = np.ascontiguousarray(group_ids, dtype=np.uint32)
+    L, n = load(), C.c_uint32(0)
+    if cap is None:
+        st = L.jxlh_repaint_changed_rects(C.byref(params), _addr(ids), len(ids), None, 0, C.byref(n))
+        if st != OK and n.value == 0:
+            return st, None, 0
+        cap = n.value
+    out = np.zeros((max(int(cap), 1), 4), dtype=np.uint32)
+    st = L.jxlh_repaint_changed_rects(C.byref(params), _addr(ids), len(ids), _addr(out) if cap else None, int(cap),
+                                      C.byref(n))
+    return st, (out[:n.value].copy() if st == OK else None), n.value
+
+
+def repaint_changed_rects(params, group_ids):
+    """the rectangles of the frame's result (upsampled size) that repainting `group_ids` can change, on any kind of
+    frame: [n, 4] rows (x0, y0, w, h)"""
+    st, rects, _ = try_repaint_changed_rects(params, group_ids)
+    if st != OK:
+        raise JxlHipError(st, "jxlh_repaint_changed_rects")
+    return rects
+
+
 def try_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects, cap=None):
     """jxlh_extra_channel_changed_rects (host only), returning (status, rects [n, 4] as (x0, y0, w, h) or None, n needed).
     cap: room offered (None: as many as needed -- asked for first, as a C caller would)"""
@@ -904,6 +929,20 @@ class Context:
             self._blend_size = None
         self._chk(self.L.jxlh_frame_rerender_groups(self._ctx, _addr(ids), len(ids)), "frame_rerender_groups")
 
+    def try_repaint_groups(self, group_ids):
+        """jxlh_frame_repaint_groups, returning the status: rerender_groups for every kind of unsharded frame (upsampled
+        and Modular frames included).  group_ids None: a null pointer with count 1 (the argument check)"""
+        if group_ids is None:
+            return self.L.jxlh_frame_repaint_groups(self._ctx, None, 1)
+        ids = np.ascontiguousarray(group_ids, dtype=np.uint32)
+        st = self.L.jxlh_frame_repaint_groups(self._ctx, _addr(ids), len(ids))
+        if st == OK and len(ids):
+            self._blend_size = None
+        return st
+
+    def repaint_groups(self, group_ids):
+        self._chk(self.try_repaint_groups(group_ids), "frame_repaint_groups")
+
     def try_set_groups_lf_only(self, group_ids):
         ids = np.ascontiguousarray(group_ids, dtype=np.uint32)
         return self.L.jxlh_frame_set_groups_lf_only(self._ctx, _addr(ids), len(ids))
@@ -1155,6 +1194,10 @@ class Context:
     def changed_rects(self, group_ids):
         """jxlh_changed_rects for the current frame's parameters"""
         return changed_rects(self.params, group_ids)
+
+    def repaint_changed_rects(self, group_ids):
+        """jxlh_repaint_changed_rects for the current frame's parameters"""
+        return repaint_changed_rects(self.params, group_ids)
 
     def try_frame_save_rects(self, desc, rects, colour=None, out=None, bytes_per_row=None, wait=True):
         """jxlh_frame_save_rects (_async when not `wait`), returning (status, out).  rects: rows (x0, y0, w, h) of the

@@ -24,6 +24,8 @@ PREVIEW_TILES_HEADER = os.path.join(ROOT, "include", "jxl_hip_preview_tiles.h")
 OUT_PREVIEW_TILES = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "preview_tiles.rs")
 EXTRA_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_extra_rects.h")
 OUT_EXTRA_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "extra_rects.rs")
+REPAINT_HEADER = os.path.join(ROOT, "include", "jxl_hip_repaint.h")
+OUT_REPAINT = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "repaint.rs")
 
 SCALARS = {"uint8_t": "u8", "int8_t": "i8", "uint16_t": "u16", "int16_t": "i16", "uint32_t": "u32", "int32_t": "i32",
            "uint64_t": "u64", "int64_t": "i64", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -162,6 +164,8 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod preview_tiles;")
     w("// include/jxl_hip_extra_rects.h (... src/extra_rects.rs)")
     w("pub mod extra_rects;")
+    w("// include/jxl_hip_repaint.h (... src/repaint.rs)")
+    w("pub mod repaint;")
     return "\n".join(out) + "\n"
 
 
@@ -218,9 +222,14 @@ def generate_extra_rects():
                           uses=("save_rects",))
 
 
+def generate_repaint():
+    return emit_extension(os.path.basename(REPAINT_HEADER), *parse_header(open(REPAINT_HEADER).read()), uses=("save_rects",))
+
+
 def main():
     for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
-                      (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects())):
+                      (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects()),
+                      (OUT_REPAINT, generate_repaint())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
             if cur != text:
