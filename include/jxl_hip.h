@@ -238,7 +238,8 @@ jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t
  * A lossless encoder picks an RCT per group and very often a per-group palette.  These calls take the channels of many
  * groups AS DECODED (before meta_apply_local_transforms' steps have run) plus each group's transform list, run every
  * group's inverse steps on the device and write the finished channels at the group's rect -- the whole batch in ONE
- * kernel launch (k_modular_local).
+ * kernel launch (k_modular_local).  (Palettes with delta entries or a predictor: the _general calls of
+ * jxl_hip_local_palette.h.)
  *
  *   arena    one block of i32 samples, host or device memory, that holds every group's coded channels and palettes;
  *            descriptors address it by sample offsets.

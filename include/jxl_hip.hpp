@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "jxl_hip.h"
+#include "jxl_hip_local_palette.h"
 
 namespace jxlh {
 
@@ -255,6 +256,15 @@ class VarDctFrame {
     ctx_.check(async ? jxlh_frame_set_modular_groups_async(ctx_.raw(), arena, arena_samples, groups, n, sample_format, &bad)
                      : jxlh_frame_set_modular_groups(ctx_.raw(), arena, arena_samples, groups, n, sample_format, &bad),
                "jxlh_frame_set_modular_groups");
+  }
+  // ... with EVERY local palette on the device (jxl_hip_local_palette.h): delta entries and all 14 predictors.  wp: one
+  // GroupHeader::wp_header per group, or null when no step has predictor 6; it is read before the call returns.
+  void set_modular_groups_general(const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
+                                  const jxlh_wp_header* wp, size_t n, uint32_t sample_format, bool async = false) {
+    size_t bad = 0;
+    ctx_.check(async ? jxlh_frame_set_modular_groups_general_async(ctx_.raw(), arena, arena_samples, groups, wp, n, sample_format, &bad)
+                     : jxlh_frame_set_modular_groups_general(ctx_.raw(), arena, arena_samples, groups, wp, n, sample_format, &bad),
+               "jxlh_frame_set_modular_groups_general");
   }
   // An extra channel that arrives group by group (jxl_hip_extra_rects.h): declared once per frame, all zero ...
   void begin_extra_channel(uint32_t ec, uint32_t w, uint32_t h, uint32_t bits_per_sample, uint32_t ec_upsampling) {

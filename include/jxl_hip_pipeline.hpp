@@ -204,6 +204,16 @@ class GpuModularFramePipeline : public GpuFramePipeline {
   void set_groups(const int32_t* arena, uint64_t arena_samples, const std::vector<jxlh_local_group>& groups, bool async = false) {
     frame_.set_modular_groups(arena, arena_samples, groups.data(), groups.size(), lp_.modular_sample_format, async);
   }
+  // the same with every local palette on the device (jxlh_frame_set_modular_groups_general): delta entries and all 14
+  // predictors, so that only a local squeeze is left to the host.  wp: empty when no step has predictor 6, else one
+  // GroupHeader::wp_header per group
+  void set_groups_general(const int32_t* arena, uint64_t arena_samples, const std::vector<jxlh_local_group>& groups,
+                          const std::vector<jxlh_wp_header>& wp, bool async = false) {
+    if (!wp.empty() && wp.size() != groups.size())
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuModularFramePipeline::set_groups_general", "one wp header per group, or none");
+    frame_.set_modular_groups_general(arena, arena_samples, groups.data(), wp.empty() ? nullptr : wp.data(), groups.size(),
+                                      lp_.modular_sample_format, async);
+  }
   // the whole frame, then the list's blending
   void render() {
     frame_.finalize_and_render();
@@ -243,6 +253,18 @@ class GpuModularPipeline {
     ctx_.check(jxlh_modular_local_transforms(ctx_.raw(), arena, arena_samples, groups.data(), groups.size(), bit_depth, planes,
                                              n_planes, lp_.frame.xsize, lp_.frame.ysize, stride, &bad),
                "jxlh_modular_local_transforms");
+  }
+  // ... with every local palette (jxlh_modular_local_transforms_general); wp as in set_groups_general
+  void local_transforms_general(const int32_t* arena, uint64_t arena_samples, const std::vector<jxlh_local_group>& groups,
+                                const std::vector<jxlh_wp_header>& wp, uint32_t bit_depth, int32_t* const planes[],
+                                uint32_t n_planes, size_t stride) {
+    if (!wp.empty() && wp.size() != groups.size())
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuModularPipeline::local_transforms_general", "one wp header per group, or none");
+    size_t bad = 0;
+    ctx_.check(jxlh_modular_local_transforms_general(ctx_.raw(), arena, arena_samples, groups.data(),
+                                                     wp.empty() ? nullptr : wp.data(), groups.size(), bit_depth, planes, n_planes,
+                                                     lp_.frame.xsize, lp_.frame.ysize, stride, &bad),
+               "jxlh_modular_local_transforms_general");
   }
   // ConvertI32ToU8Stage: interleaved bytes (3 or 4 per pixel) in one pass
   void render_u8(const int32_t* const planes[3], size_t stride, void* out, size_t bytes_per_row) {

@@ -1,8 +1,10 @@
 // C ABI, group-local Modular transforms (jxlh_modular_local_lower, jxlh_modular_local_transforms,
-// jxlh_frame_set_modular_groups*): every group's transform list is lowered on the host (modular_local_host.h), the
-// lowered programs and a flat (group, row chunk) work list go up in one copy from a pinned block, a host arena in one
-// more, and the whole batch is one launch of k_modular_local.  Everything that can refuse a call is checked before the
-// first copy is enqueued.
+// jxlh_frame_set_modular_groups* and their _general forms of jxl_hip_local_palette.h): every group's transform list is
+// lowered on the host (modular_local_host.h), the lowered programs and a flat (group, row chunk) work list go up in one
+// copy from a pinned block, a host arena in one more, and the whole batch is one launch of k_modular_local.  Groups with
+// GENERAL palettes (the _general calls only) follow phase by phase -- one launch per phase for all of them, their
+// descriptors in the same block and the same copy.  Everything that can refuse a call is checked before the first copy
+// is enqueued.
 #include <algorithm>
 
 #include "jxlh_ctx.h"
@@ -12,6 +14,7 @@ namespace jxlh_host {
 namespace {
 
 constexpr uint32_t kLocalItemSamples = 8192;  // samples of one channel a work item covers (32 rows of a 256-wide group)
+constexpr uint32_t kLpMaxPhases = 2 * JXLH_LOCAL_MAX_STEPS + 1;
 
 jxlh_status refuse_group(jxlh_ctx* ctx, jxlh_status st, size_t g, const char* why, size_t* first_bad) {
   if (first_bad) *first_bad = g;
@@ -26,25 +29,148 @@ struct LocalDest {
   bool frame = false;  // the frame's sample planes: 3 or 1 (fanned out) channels per group
 };
 
-// checks, lowering, upload, launch; nothing is enqueued unless every group passed
+// what the phases of the groups with general palettes launch: phase p's descriptors (LpPhaseDev for even p, LpJobDev for
+// odd p) and work items, and the scratch the batch needs
+struct GeneralBatch {
+  std::vector<LpPhaseDev> pointwise[kLpMaxPhases];
+  std::vector<LpJobDev> jobs[kLpMaxPhases];
+  std::vector<LocalItem> items[kLpMaxPhases];
+  bool weighted[kLpMaxPhases] = {}, lds_palette[kLpMaxPhases] = {};
+  uint64_t scratch = 0;  // samples
+  bool any() const {
+    for (const auto& v : items)
+      if (!v.empty()) return true;
+    return false;
+  }
+};
+
+// One group with general palettes, cut into phases (jxl_hip_local_palette.h).  Between phases a slot is in the arena
+// (a coded channel nothing has touched yet), in the destination rect, or -- the index channel of the next general
+// palette, which shares its slot with that palette's output channel 0 while the other channels' workgroups still read
+// it -- in scratch.  A point-wise phase loads every slot that is somewhere and stores what it changed (what the next
+// palette overwrites excepted); the last one leaves every channel in the destination rect.
+void plan_general_group(const jxlh_local_group& g, const jxlh_local_general_program& prog, const jxlh_wp_header* wp,
+                        bool fan, GeneralBatch& b) {
+  LpPlane loc[4] = {};
+  for (uint32_t k = 0; k < prog.n_coded; k++) loc[prog.coded_slot[k]] = LpPlane{g.coded_offset[k], g.coded_stride, kLpArena};
+  const uint32_t nvx = (g.w + 3) / 4, rows_per_item = std::max(1u, kLocalItemSamples / (4 * nvx));
+  bool have_copy = false;
+  uint64_t copy_off = 0;
+  auto index_copy = [&]() {  // one per group: a copy is dead once its palette has run
+    if (!have_copy) {
+      copy_off = b.scratch;
+      b.scratch += (uint64_t)g.w * g.h;
+      have_copy = true;
+    }
+    return LpPlane{copy_off, g.w, kLpScratch};
+  };
+  auto pointwise = [&](uint32_t phase, uint32_t op0, uint32_t op1, const jxlh_local_general_op* next) {
+    LpPhaseDev d{};
+    d.x0 = g.x0, d.y0 = g.y0, d.w = g.w, d.h = g.h;
+    d.rows_per_item = rows_per_item;
+    bool changed[4] = {};
+    for (uint32_t i = op0; i < op1; i++) {
+      const jxlh_local_general_op& p = prog.ops[i];
+      LocalOpDev& q = d.ops[d.n_ops++];
+      q.kind = p.kind, q.rct_op = p.rct_op, q.n_slots = p.n_slots, q.num_colors = p.num_colors, q.pal_off = p.palette_offset;
+      q.lds_off = kLocalNoLds;
+      for (int k = 0; k < 3; k++) q.in_slot[k] = p.in_slot[k];
+      for (int k = 0; k < 4; k++) q.out_slot[k] = p.out_slot[k];
+      for (uint32_t k = 0; k < p.n_slots; k++) changed[p.out_slot[k]] = true;
+    }
+    for (int t = 0; t < 4; t++) d.src[t] = loc[t];
+    bool any = false;
+    for (uint32_t t = 0; t < g.n_channels; t++) {
+      LpPlane to{0, 0, kLpNone};
+      if (!next) {
+        if (changed[t] || loc[t].space != kLpOut) to.space = kLpOut;
+      } else if (t == next->in_slot[0]) {
+        if (changed[t] || loc[t].space == kLpOut) to = index_copy();
+      } else if (changed[t]) {
+        bool overwritten = false;
+        for (uint32_t k = 0; k < next->n_slots; k++) overwritten = overwritten || next->out_slot[k] == t;
+        if (overwritten) loc[t] = LpPlane{0, 0, kLpNone};
+        else to.space = kLpOut;
+      }
+      if (to.space != kLpNone) {
+        d.dst[t] = loc[t] = to;
+        any = true;
+      }
+    }
+    if (!next && fan) d.fan = 1, any = true;
+    if (!any) return;
+    const uint32_t id = (uint32_t)b.pointwise[phase].size();
+    b.pointwise[phase].push_back(d);
+    for (uint64_t r = 0; r < g.h; r += rows_per_item) b.items[phase].push_back(LocalItem{id, (uint32_t)r});
+  };
+  uint32_t i = 0, phase = 0;
+  while (i < prog.n_ops) {
+    uint32_t e = i;
+    while (e < prog.n_ops && prog.ops[e].kind != JXLH_LOCAL_GENERAL_PALETTE) e++;
+    if (e == prog.n_ops) break;
+    const jxlh_local_general_op& p = prog.ops[e];
+    pointwise(p.phase - 1, i, e, &p);
+    LpJobDev j{};
+    j.x0 = g.x0, j.y0 = g.y0, j.w = g.w, j.h = g.h;
+    j.index = loc[p.in_slot[0]];  // the arena or scratch: pointwise() moved it out of the destination rect
+    j.pal_off = p.palette_offset;
+    j.palette_size = p.num_colors, j.num_deltas = p.num_deltas, j.predictor = p.predictor, j.n_slots = p.n_slots;
+    for (int k = 0; k < 4; k++) j.out_slot[k] = p.out_slot[k];
+    j.lds = p.num_colors <= kLpLdsEntries;
+    if (p.predictor == 6) {
+      j.wp.p1c = (int32_t)wp->p1c, j.wp.p2c = (int32_t)wp->p2c;
+      const uint32_t p3[5] = {wp->p3ca, wp->p3cb, wp->p3cc, wp->p3cd, wp->p3ce}, ww[4] = {wp->w0, wp->w1, wp->w2, wp->w3};
+      for (int k = 0; k < 5; k++) j.wp.p3c[k] = (int32_t)p3[k];
+      for (int k = 0; k < 4; k++) j.wp.w[k] = ww[k];
+      b.weighted[p.phase] = true;
+      if (g.h > (uint32_t)kLpRows) {  // state rows between the bands of a channel's workgroup: two sets of five
+        j.wp_rows_off = b.scratch;
+        b.scratch += (uint64_t)p.n_slots * 10 * g.w;
+      }
+    }
+    b.lds_palette[p.phase] = b.lds_palette[p.phase] || j.lds;
+    const uint32_t id = (uint32_t)b.jobs[p.phase].size();
+    b.jobs[p.phase].push_back(j);
+    for (uint32_t c = 0; c < p.n_slots; c++) b.items[p.phase].push_back(LocalItem{id, c});
+    for (uint32_t k = 0; k < p.n_slots; k++) loc[p.out_slot[k]] = LpPlane{0, 0, kLpOut};
+    phase = p.phase;
+    i = e + 1;
+  }
+  pointwise(phase + 1, i, prog.n_ops, nullptr);
+}
+
+// checks, lowering, upload, launch; nothing is enqueued unless every group passed.  general: the _general calls (wp: one
+// header per group, or null)
 jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
-                          size_t n, uint32_t bit_depth, const LocalDest& d, size_t* first_bad) {
+                          size_t n, uint32_t bit_depth, const LocalDest& d, size_t* first_bad, bool general = false,
+                          const jxlh_wp_header* wp = nullptr) {
   if (n > 0x7fffffffu || d.w > 0x7fffffffu || d.h > 0x7fffffffu) return JXLH_ERR_INVALID_ARGUMENT;
   std::vector<LocalGroupDev> dev(n);
   std::vector<LocalItem> items;
+  GeneralBatch gb;
   bool dst_aligned = (d.stride & 3) == 0 && (reinterpret_cast<uintptr_t>(arena) & 15) == 0;
   for (uint32_t c = 0; c < d.n_out; c++) dst_aligned = dst_aligned && (reinterpret_cast<uintptr_t>(d.out[c]) & 15) == 0;
   for (size_t gi = 0; gi < n; gi++) {
     const jxlh_local_group& g = groups[gi];
     jxlh_local_program prog;
+    jxlh_local_general_program gprog;
     const char* why = "";
-    if (jxlh_status st = local_lower_group(g, bit_depth, arena_samples, &prog, &why)) return refuse_group(ctx, st, gi, why, first_bad);
+    if (jxlh_status st = local_lower_core(g, bit_depth, arena_samples, general, wp ? &wp[gi] : nullptr, &prog, &gprog, &why))
+      return refuse_group(ctx, st, gi, why, first_bad);
     if (d.frame ? (g.n_channels != 3 && g.n_channels != 1) : g.n_channels > d.n_out)
       return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, d.frame ? "a frame's groups hold 3 channels, or 1 (grey)" : "more channels than out planes", first_bad);
     if ((uint64_t)g.x0 + g.w > d.w || (uint64_t)g.y0 + g.h > d.h)
       return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the rect leaves the planes", first_bad);
     LocalGroupDev& o = dev[gi];
     o = LocalGroupDev{};
+    if (gprog.n_phases > 1) {  // general palettes: this group runs phase by phase, behind the launch of the others
+      if (g.w > (1u << 30)) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "a predicted palette on a group wider than 2^30", first_bad);
+      if (g.w == 0 || g.h == 0) continue;
+      plan_general_group(g, gprog, wp ? &wp[gi] : nullptr, d.frame && g.n_channels == 1, gb);
+      for (const auto& v : gb.items)
+        if (v.size() > 0x7fffffffu) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the batch holds more than 2^31 - 1 work items", first_bad);
+      continue;
+    }
     o.x0 = g.x0, o.y0 = g.y0, o.w = g.w, o.h = g.h;
     o.n_channels = g.n_channels;
     o.n_ops = prog.n_ops;
@@ -82,9 +208,19 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     for (uint64_t r = 0; r < g.h; r += o.rows_per_item) items.push_back(LocalItem{(uint32_t)gi, (uint32_t)r});
     if (items.size() > 0x7fffffffu) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the batch holds more than 2^31 - 1 work items", first_bad);
   }
-  if (items.empty()) return JXLH_OK;
+  const bool have_general = gb.any();
+  if (items.empty() && !have_general) return JXLH_OK;
   // ---- from here on the call cannot be refused for its arguments
-  const size_t desc_bytes = round_up(n * sizeof(LocalGroupDev), 16), bytes = desc_bytes + items.size() * sizeof(LocalItem);
+  // the block: the plain groups' descriptors and items, then per phase its descriptors and items, each 16-byte aligned
+  const size_t desc_bytes = round_up(n * sizeof(LocalGroupDev), 16);
+  size_t bytes = desc_bytes + round_up(items.size() * sizeof(LocalItem), 16);
+  size_t phase_desc[kLpMaxPhases] = {}, phase_items[kLpMaxPhases] = {};
+  for (uint32_t p = 0; p < kLpMaxPhases && have_general; p++) {
+    phase_desc[p] = bytes;
+    bytes += round_up((p & 1) ? gb.jobs[p].size() * sizeof(LpJobDev) : gb.pointwise[p].size() * sizeof(LpPhaseDev), 16);
+    phase_items[p] = bytes;
+    bytes += round_up(gb.items[p].size() * sizeof(LocalItem), 16);
+  }
   HIPCHK(ctx, ctx->local_copied.sync());  // the pinned block's previous content is on its way
   ctx->local_copied.clear();
   if (ctx->local_desc_host.n < bytes) {
@@ -92,8 +228,15 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     HIPCHK(ctx, ctx->local_desc_host.alloc(bytes + bytes / 2));
   }
   if (jxlh_status st = ensure(ctx, ctx->local_desc, bytes)) return st;
+  if (gb.scratch > 0)
+    if (jxlh_status st = ensure(ctx, ctx->local_scratch, (size_t)gb.scratch)) return st;
   std::memcpy(ctx->local_desc_host.p, dev.data(), n * sizeof(LocalGroupDev));
   std::memcpy(ctx->local_desc_host.p + desc_bytes, items.data(), items.size() * sizeof(LocalItem));
+  for (uint32_t p = 0; p < kLpMaxPhases && have_general; p++) {
+    if (p & 1) std::memcpy(ctx->local_desc_host.p + phase_desc[p], gb.jobs[p].data(), gb.jobs[p].size() * sizeof(LpJobDev));
+    else std::memcpy(ctx->local_desc_host.p + phase_desc[p], gb.pointwise[p].data(), gb.pointwise[p].size() * sizeof(LpPhaseDev));
+    std::memcpy(ctx->local_desc_host.p + phase_items[p], gb.items[p].data(), gb.items[p].size() * sizeof(LocalItem));
+  }
   const int32_t* arena_dev = arena;
   if (!is_device_ptr(arena)) {
     // one copy; 16-byte alignment of the samples is kept (hipMalloc's and the caller's bases are both taken as they
@@ -103,26 +246,52 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
   }
   HIPCHK(ctx, hipMemcpyAsync(ctx->local_desc.p, ctx->local_desc_host.p, bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, ctx->local_copied.record(ctx->stream));
-  LocalLaunch a{};
-  a.arena = arena_dev;
-  a.groups = reinterpret_cast<const LocalGroupDev*>(ctx->local_desc.p);
-  a.items = reinterpret_cast<const LocalItem*>(ctx->local_desc.p + desc_bytes);
-  a.n_items = (uint32_t)items.size();
-  for (int c = 0; c < 4; c++) a.out[c] = d.out[c];
-  a.n_out = d.n_out;
-  a.fan_grey = d.frame ? 1 : 0;
-  a.out_stride = d.stride;
-  a.bit_depth = (int)std::min(bit_depth, 24u);  // do_palette_step_general: bits_per_sample().min(24), palette.rs:177
-  {
-    ScopedKernelTimer t(ctx, "k_modular_local");
-    launch_modular_local(ctx->stream, a);
+  const int depth = (int)std::min(bit_depth, 24u);  // do_palette_step_general: bits_per_sample().min(24), palette.rs:177
+  if (!items.empty()) {
+    LocalLaunch a{};
+    a.arena = arena_dev;
+    a.groups = reinterpret_cast<const LocalGroupDev*>(ctx->local_desc.p);
+    a.items = reinterpret_cast<const LocalItem*>(ctx->local_desc.p + desc_bytes);
+    a.n_items = (uint32_t)items.size();
+    for (int c = 0; c < 4; c++) a.out[c] = d.out[c];
+    a.n_out = d.n_out;
+    a.fan_grey = d.frame ? 1 : 0;
+    a.out_stride = d.stride;
+    a.bit_depth = depth;
+    {
+      ScopedKernelTimer t(ctx, "k_modular_local");
+      launch_modular_local(ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
   }
-  HIPCHK(ctx, hipGetLastError());
+  for (uint32_t p = 0; p < kLpMaxPhases && have_general; p++) {
+    if (gb.items[p].empty()) continue;
+    LpLaunch a{};
+    a.arena = arena_dev;
+    a.scratch = ctx->local_scratch.p;
+    for (int c = 0; c < 4; c++) a.out[c] = d.out[c];
+    a.out_stride = d.stride;
+    a.bit_depth = depth;
+    a.items = reinterpret_cast<const LocalItem*>(ctx->local_desc.p + phase_items[p]);
+    a.n_items = (uint32_t)gb.items[p].size();
+    if (p & 1) {
+      a.jobs = reinterpret_cast<const LpJobDev*>(ctx->local_desc.p + phase_desc[p]);
+      a.weighted = gb.weighted[p], a.lds_palette = gb.lds_palette[p];
+      ScopedKernelTimer t(ctx, "k_modular_local_palette");
+      launch_modular_local_palette(ctx->stream, a);
+    } else {
+      a.phases = reinterpret_cast<const LpPhaseDev*>(ctx->local_desc.p + phase_desc[p]);
+      ScopedKernelTimer t(ctx, "k_modular_local_phase");
+      launch_modular_local_phase(ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+  }
   return JXLH_OK;
 }
 
 jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
-                             size_t n, uint32_t sample_format, size_t* first_bad, bool wait) {
+                             size_t n, uint32_t sample_format, size_t* first_bad, bool wait, bool general = false,
+                             const jxlh_wp_header* wp = nullptr) {
   JXLH_ON_DEVICE(ctx);
   if (!ctx || !arena || (!groups && n > 0)) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame || !ctx->modular) return JXLH_ERR_BAD_STATE;
@@ -146,9 +315,32 @@ jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
   d.stride = f.plane_stride;
   d.frame = true;
   // the palettes' bit depth is the samples' (a palette on 32-bit float samples is refused: no bit depth of 1..31)
-  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, depth & 0xffu, d, first_bad)) return st;
+  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, depth & 0xffu, d, first_bad, general, wp)) return st;
   ctx->frame.mod_format = sample_format;
   if (wait) JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+jxlh_status stage_transforms(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
+                             size_t n, uint32_t bit_depth, int32_t* const out[], uint32_t n_out, uint32_t out_w,
+                             uint32_t out_h, size_t out_stride, size_t* first_bad, bool general, const jxlh_wp_header* wp) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !arena || (!groups && n > 0) || !out || n_out < 1 || n_out > JXLH_LOCAL_MAX_CHANNELS || out_stride < out_w)
+    return JXLH_ERR_INVALID_ARGUMENT;
+  LocalDest d;
+  for (uint32_t c = 0; c < n_out; c++) {
+    if (!out[c] || !is_device_ptr(out[c])) return JXLH_ERR_INVALID_ARGUMENT;
+    d.out[c] = out[c];
+  }
+  if (ctx->comm) {
+    ctx->last_error = "group-local transforms on a sharded context";
+    return JXLH_ERR_UNSUPPORTED;
+  }
+  d.n_out = n_out;
+  d.w = out_w, d.h = out_h;
+  d.stride = out_stride;
+  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, bit_depth, d, first_bad, general, wp)) return st;
+  JXLH_SYNC(ctx);
   return JXLH_OK;
 }
 
@@ -173,28 +365,36 @@ jxlh_status jxlh_modular_local_lower(const jxlh_local_group* groups, size_t n, u
   return JXLH_OK;
 }
 
+jxlh_status jxlh_modular_local_lower_general(const jxlh_local_group* groups, const jxlh_wp_header* wp, size_t n,
+                                             uint32_t bit_depth, uint64_t arena_samples,
+                                             jxlh_local_general_program* programs, size_t* first_bad) {
+  if (!groups && n > 0) return JXLH_ERR_INVALID_ARGUMENT;
+  for (int pass = 0; pass < (programs ? 2 : 1); pass++) {
+    for (size_t g = 0; g < n; g++) {
+      if (jxlh_status st = local_lower_core(groups[g], bit_depth, arena_samples, true, wp ? &wp[g] : nullptr, nullptr,
+                                            pass ? &programs[g] : nullptr, nullptr)) {
+        if (first_bad) *first_bad = g;
+        return st;
+      }
+    }
+  }
+  return JXLH_OK;
+}
+
 jxlh_status jxlh_modular_local_transforms(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
                                           const jxlh_local_group* groups, size_t n, uint32_t bit_depth, int32_t* const out[],
                                           uint32_t n_out, uint32_t out_w, uint32_t out_h, size_t out_stride,
                                           size_t* first_bad) {
-  JXLH_ON_DEVICE(ctx);
-  if (!ctx || !arena || (!groups && n > 0) || !out || n_out < 1 || n_out > JXLH_LOCAL_MAX_CHANNELS || out_stride < out_w)
-    return JXLH_ERR_INVALID_ARGUMENT;
-  LocalDest d;
-  for (uint32_t c = 0; c < n_out; c++) {
-    if (!out[c] || !is_device_ptr(out[c])) return JXLH_ERR_INVALID_ARGUMENT;
-    d.out[c] = out[c];
-  }
-  if (ctx->comm) {
-    ctx->last_error = "group-local transforms on a sharded context";
-    return JXLH_ERR_UNSUPPORTED;
-  }
-  d.n_out = n_out;
-  d.w = out_w, d.h = out_h;
-  d.stride = out_stride;
-  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, bit_depth, d, first_bad)) return st;
-  JXLH_SYNC(ctx);
-  return JXLH_OK;
+  return stage_transforms(ctx, arena, arena_samples, groups, n, bit_depth, out, n_out, out_w, out_h, out_stride, first_bad,
+                          false, nullptr);
+}
+
+jxlh_status jxlh_modular_local_transforms_general(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                  const jxlh_local_group* groups, const jxlh_wp_header* wp, size_t n,
+                                                  uint32_t bit_depth, int32_t* const out[], uint32_t n_out, uint32_t out_w,
+                                                  uint32_t out_h, size_t out_stride, size_t* first_bad) {
+  return stage_transforms(ctx, arena, arena_samples, groups, n, bit_depth, out, n_out, out_w, out_h, out_stride, first_bad,
+                          true, wp);
 }
 
 jxlh_status jxlh_frame_set_modular_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
@@ -207,6 +407,18 @@ jxlh_status jxlh_frame_set_modular_groups_async(jxlh_ctx* ctx, const int32_t* ar
                                                 const jxlh_local_group* groups, size_t n, uint32_t sample_format,
                                                 size_t* first_bad) {
   return frame_set_groups(ctx, arena, arena_samples, groups, n, sample_format, first_bad, false);
+}
+
+jxlh_status jxlh_frame_set_modular_groups_general(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                  const jxlh_local_group* groups, const jxlh_wp_header* wp, size_t n,
+                                                  uint32_t sample_format, size_t* first_bad) {
+  return frame_set_groups(ctx, arena, arena_samples, groups, n, sample_format, first_bad, true, true, wp);
+}
+
+jxlh_status jxlh_frame_set_modular_groups_general_async(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                        const jxlh_local_group* groups, const jxlh_wp_header* wp, size_t n,
+                                                        uint32_t sample_format, size_t* first_bad) {
+  return frame_set_groups(ctx, arena, arena_samples, groups, n, sample_format, first_bad, false, true, wp);
 }
 
 }  // extern "C"

@@ -114,6 +114,8 @@ struct jxlh_ctx {
   // group-local transforms (abi_modular_local.hip): device scratch of a host arena and of a batch's descriptors + work
   // list; the descriptors go up from a pinned block, reused once local_copied (recorded behind its copy) has passed
   DevBuf<int32_t> local_arena;
+  // groups with general palettes: index channels their palette would overwrite, and the weighted predictor's state rows
+  DevBuf<int32_t> local_scratch;
   DevBuf<uint8_t> local_desc;
   Pinned<uint8_t> local_desc_host;
   Fence local_copied;

@@ -426,6 +426,60 @@ struct LocalLaunch {
   int bit_depth;
 };
 void launch_modular_local(hipStream_t s, const LocalLaunch& a);
+// k_modular_local_palette.hip: groups with GENERAL palettes (delta entries under a predictor != 0: jxl_hip_local_palette.h)
+// run phase by phase.  A channel slot of such a group lives, between phases, in one of these places:
+enum : uint32_t { kLpNone = 0, kLpArena = 1, kLpOut = 2, kLpScratch = 3 };
+struct LpPlane {
+  uint64_t off;     // kLpArena / kLpScratch: samples into the arena / the scratch block, of the group's first sample
+  uint32_t stride;  // kLpArena / kLpScratch: samples between rows
+  uint32_t space;   // kLp*; kLpOut: plane `slot` of the launch at the group's rect
+};
+// the weighted predictor's header as the kernels take it (WpHeader, modular/predict.rs)
+struct WpParams {
+  uint32_t w[4];
+  int32_t p1c, p2c, p3c[5];
+};
+constexpr int kLpRows = 64;                // rows of a group one workgroup (ONE wavefront: a row per lane) walks at a time
+constexpr int kLpChunk = 32;               // wavefront steps between two visits to global memory
+constexpr uint32_t kLpLdsEntries = 2048;   // entries of ONE channel's palette row staged in LDS (8 KiB)
+// one general palette of one group; the workgroup of output channel c reads row c of the palette
+struct LpJobDev {
+  uint32_t x0, y0, w, h;
+  LpPlane index;           // kLpArena or kLpScratch: never a plane this job writes
+  uint64_t pal_off;        // samples into the arena; n_slots rows of palette_size values
+  uint32_t palette_size;   // num_colors + num_deltas
+  uint32_t num_deltas, predictor, n_slots;
+  uint32_t out_slot[4];
+  uint32_t lds;            // 1: the palette row is staged in LDS (palette_size <= kLpLdsEntries)
+  uint32_t pad;
+  uint64_t wp_rows_off;    // predictor 6, h > kLpRows: samples into scratch; per channel 2 x 5 rows of w (TE, E0..E3)
+  WpParams wp;
+};
+// one point-wise phase of one such group: k_modular_local's pass with a place per slot on either side
+struct LpPhaseDev {
+  uint32_t x0, y0, w, h;
+  uint32_t n_ops;
+  uint32_t fan;            // 1: slot 0 also goes to planes 1 and 2 (a grey group of a frame)
+  uint32_t rows_per_item, pad;
+  LpPlane src[4];          // kLpNone: the slot holds nothing yet (zero)
+  LpPlane dst[4];          // kLpNone: not stored; kLpOut or kLpScratch
+  LocalOpDev ops[4];       // lds_off unused: palettes are read from global memory
+};
+struct LpLaunch {
+  const int32_t* arena;
+  int32_t* scratch;
+  int32_t* out[4];
+  size_t out_stride;  // samples
+  int bit_depth;
+  const LpJobDev* jobs;       // palette launch: items are (job, output channel)
+  const LpPhaseDev* phases;   // point-wise launch: items are (phase descriptor, first row)
+  const LocalItem* items;
+  uint32_t n_items;
+  uint32_t weighted;          // palette launch: 1 if a job of it has predictor 6 (the larger LDS layout)
+  uint32_t lds_palette;       // palette launch: 1 if a job of it stages its palette row
+};
+void launch_modular_local_palette(hipStream_t s, const LpLaunch& a);
+void launch_modular_local_phase(hipStream_t s, const LpLaunch& a);
 void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
 void launch_modular_xyb_to_f32(hipStream_t s, const int32_t* y, const int32_t* x, const int32_t* b, size_t n,
                                const float scale[3], float* ox, float* oy, float* ob);

@@ -6,6 +6,7 @@
 #include "jxlh_internal.h"
 #include "modular_convert_device.h"
 #include "modular_ops_device.h"  // wadd / wsub, rct_op, rct_permute, kDeltaPalette, palette_value
+#include "modular_predict_device.h"  // predict_one, WpParams, kWpDivLookup, wp_pixel
 
 namespace jxlh {
 namespace {
@@ -78,35 +79,6 @@ __global__ void k4_rct_rows(int32_t* __restrict__ p0, int32_t* __restrict__ p1, 
 //    written).  A waiting band only depends on bands with a lower block index, which were dispatched earlier.
 constexpr int kDeltaRows = 256;
 constexpr int kDeltaPublish = 32;
-
-template <int predictor>
-__device__ __forceinline__ int64_t predict_one(int64_t left, int64_t top, int64_t toptop, int64_t topleft,
-                                               int64_t topright, int64_t leftleft, int64_t toprightright) {
-  switch (predictor) {  // Predictor::predict_one, modular/predict.rs:152-198 (i64, `/` truncates)
-    case 1: return left;
-    case 2: return top;
-    case 3: return (top + left) / 2;
-    case 4: {
-      const int64_t p = left + top - topleft;
-      const int64_t dl = p - left < 0 ? left - p : p - left, dt = p - top < 0 ? top - p : p - top;
-      return dl < dt ? left : top;
-    }
-    case 5: {
-      const int64_t mn = left < top ? left : top, mx = left < top ? top : left;
-      const int64_t grad = left + top - topleft;
-      const int64_t gmax = topleft < mn ? mx : grad;
-      return topleft > mx ? mn : gmax;
-    }
-    case 7: return topright;
-    case 8: return topleft;
-    case 9: return leftleft;
-    case 10: return (left + topleft) / 2;
-    case 11: return (top + topleft) / 2;
-    case 12: return (top + topright) / 2;
-    case 13: return (6 * top - 2 * toptop + 7 * left + leftleft + toprightright + 3 * topright + 8) / 16;
-    default: return 0;
-  }
-}
 
 // `out` already holds the palette entry of every pixel (the parallel gather kernel ran first): the wavefront only
 // adds the prediction where index < num_deltas.
@@ -280,17 +252,6 @@ __global__ __launch_bounds__(kDeltaRows) void k5_palette_delta(const int32_t* __
 // registers: err_n = E(x, y-1) + E(x-1, y), err_nw = E(x-1, y-1) + E(x-2, y), err_ne = E(x+1, y-1), with the
 // reference's edge rules (pos_nw = max(x-1, 0), pos_ne = min(x+1, w-1) index the SAME summed slots).  Same wavefront
 // as k5_palette_delta (x + 3y), same band pipeline; a band's last row also publishes its TE / E row for the band below.
-struct WpParams {
-  uint32_t w[4];
-  int32_t p1c, p2c, p3c[5];
-};
-__constant__ uint32_t kWpDivLookup[64] = {  // (1 << 24) / (i + 1), predict.rs:206-213
-    16777216, 8388608, 5592405, 4194304, 3355443, 2796202, 2396745, 2097152, 1864135, 1677721, 1525201, 1398101,
-    1290555,  1198372, 1118481, 1048576, 986895,  932067,  883011,  838860,  798915,  762600,  729444,  699050,
-    671088,   645277,  621378,  599186,  578524,  559240,  541200,  524288,  508400,  493447,  479349,  466033,
-    453438,   441505,  430185,  419430,  409200,  399457,  390167,  381300,  372827,  364722,  356962,  349525,
-    342392,   335544,  328965,  322638,  316551,  310689,  305040,  299593,  294337,  289262,  284359,  279620,
-    275036,   270600,  266305,  262144};
 
 // wp_rows: per channel and band, five rows of w ints (TE, E0..E3 of the band's last row).
 // Memory movement as in k5_palette_delta: chunks of 32 steps moved as coalesced row segments through LDS, neighbour and
@@ -428,60 +389,20 @@ __global__ __launch_bounds__(kDeltaRows) void k5_palette_wp(const int32_t* __res
         ea_0[q] = s_e[q][l + 1][c0];
         ea_p1[q] = s_e[q][l + 1][cp];
       }
-      const bool has_top = y > 0;
-      // PredictionData::get_rows, modular/predict.rs:96-128
-      const int32_t left = x > 0 ? left_v : (has_top ? t_0 : 0);
-      const int32_t top = has_top ? t_0 : left;
-      const int32_t topleft = (x > 0 && has_top) ? t_m1 : left;
-      const int32_t topright = (x + 1 < w && has_top) ? t_p1 : top;
-      const int32_t toptop = y > 1 ? tt_0 : top;
-      const bool at_right = !(x + 1 < w), at_left = !(x > 0);  // pos_ne == x, pos_nw == x
-      // weights from the error sums (:340-377)
-      uint32_t wk[4];
+      WpIn in;
+      in.x = x, in.w = w, in.has_top = y > 0, in.has_toptop = y > 1;
+      in.left_v = left_v, in.t_m1 = t_m1, in.t_0 = t_0, in.t_p1 = t_p1, in.tt_0 = tt_0;
+      in.ta_m1 = ta_m1, in.ta_0 = ta_0, in.ta_p1 = ta_p1, in.te1 = te1;
 #pragma unroll
       for (int q = 0; q < 4; q++) {
-        const uint32_t en = (has_top ? ea_0[q] : 0u) + (x > 0 ? e1[q] : 0u);
-        const uint32_t ene = at_right ? en : (has_top ? ea_p1[q] : 0u);
-        const uint32_t enw = at_left ? en : (has_top ? ea_m1[q] : 0u) + (x > 1 ? e2[q] : 0u);
-        const uint32_t err = en + ene + enw;
-        int shift = 63 - __clzll((unsigned long long)err + 1ull) - 5;
-        shift = shift < 0 ? 0 : shift;
-        wk[q] = 4u + ((P.w[q] * s_div[err >> shift]) >> shift);
+        in.ea_m1[q] = ea_m1[q], in.ea_0[q] = ea_0[q], in.ea_p1[q] = ea_p1[q];
+        in.e1[q] = e1[q], in.e2[q] = e2[q];
       }
-      const int64_t te_w = x > 0 ? (int64_t)te1 : 0;
-      const int64_t te_n = has_top ? (int64_t)ta_0 : 0;
-      const int64_t te_nw = has_top ? (int64_t)(at_left ? ta_0 : ta_m1) : 0;
-      const int64_t te_ne = has_top ? (int64_t)(at_right ? ta_0 : ta_p1) : 0;
-      const int64_t sum_wn = te_n + te_w;
-      const int64_t n = (int64_t)top << 3, wv = (int64_t)left << 3, ne = (int64_t)topright << 3;
-      const int64_t nw = (int64_t)topleft << 3, nn = (int64_t)toptop << 3;
-      int64_t pk[4];
-      pk[0] = wv + ne - n;
-      pk[1] = n - (((sum_wn + te_ne) * (int64_t)P.p1c) >> 5);
-      pk[2] = wv - (((sum_wn + te_nw) * (int64_t)P.p2c) >> 5);
-      pk[3] = n - ((te_nw * (int64_t)P.p3c[0] + te_n * (int64_t)P.p3c[1] + te_ne * (int64_t)P.p3c[2] +
-                    (nn - n) * (int64_t)P.p3c[3] + (nw - wv) * (int64_t)P.p3c[4]) >> 5);
-      const int log_weight = 63 - __clzll((unsigned long long)wk[0] + wk[1] + wk[2] + wk[3]);
-      const int64_t w0s = (int64_t)(wk[0] >> (log_weight - 4)), w1s = (int64_t)(wk[1] >> (log_weight - 4));
-      const int64_t w2s = (int64_t)(wk[2] >> (log_weight - 4)), w3s = (int64_t)(wk[3] >> (log_weight - 4));
-      const int64_t weight_sum = w0s + w1s + w2s + w3s;
-      const int64_t sum = (weight_sum >> 1) - 1 + w0s * pk[0] + w1s * pk[1] + w2s * pk[2] + w3s * pk[3];
-      int64_t pred = (sum * (int64_t)s_div[(weight_sum - 1) & 63]) >> 24;
-      if (((te_n ^ te_w) | (te_n ^ te_nw)) <= 0) {
-        const int64_t mx = max(wv, max(ne, n)), mn = min(wv, min(ne, n));
-        pred = max(mn, min(mx, pred));
-      }
-      const int64_t wp_pred = (pred + 3) >> 3;
-      const int32_t val = idx < num_deltas ? (int32_t)(uint32_t)(uint64_t)(wp_pred + (int64_t)entry) : entry;
-      // update_errors (:472-517)
-      const int64_t v = (int64_t)val << 3;
-      const int32_t te = (int32_t)(pred - v);
+      const WpOut px = wp_pixel(P, s_div, in, idx, num_deltas, entry);
+      const int32_t val = px.val, te = px.te;
       uint32_t e[4];
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int64_t dd = pk[q] - v;
-        e[q] = (uint32_t)(((dd < 0 ? -dd : dd) + 3) >> 3);
-      }
+      for (int q = 0; q < 4; q++) e[q] = px.e[q];
       if (active) {
         s_outc[l][j] = val;
         s_ring[l + 2][c0] = val;

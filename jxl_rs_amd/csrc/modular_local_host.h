@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/jxl_hip.h"
+#include "../../include/jxl_hip_local_palette.h"
 
 #if defined(__HIPCC__)
 #define JXLH_HOST_DEVICE __host__ __device__
@@ -42,9 +43,21 @@ inline bool local_fits(uint64_t offset, uint64_t extent, uint64_t arena_samples)
   return offset <= arena_samples && extent <= arena_samples - offset;
 }
 
-// One group.  *why names the rule that refused it (a literal).  `prog` may be null (checks only).
-inline jxlh_status local_lower_group(const jxlh_local_group& g, uint32_t bit_depth, uint64_t arena_samples,
-                                     jxlh_local_program* prog, const char** why) {
+// Bits(5) / Bits(4) fields of a weighted-predictor header (the rule of jxlh_palette_delta_wp)
+inline bool wp_header_ok(const jxlh_wp_header& h) {
+  const uint32_t f[11] = {h.p1c, h.p2c, h.p3ca, h.p3cb, h.p3cc, h.p3cd, h.p3ce, h.w0, h.w1, h.w2, h.w3};
+  for (int i = 0; i < 11; i++)
+    if (f[i] >= (i < 7 ? 32u : 16u)) return false;
+  return true;
+}
+
+// One group.  *why names the rule that refused it (a literal).  `prog` / `gprog` may be null (checks only).
+// general == false: the lowering of jxlh_modular_local_lower, which refuses delta / predicted palettes.
+// general == true: the lowering of jxlh_modular_local_lower_general (jxl_hip_local_palette.h); `wp` is the group's own
+// header, or null.  gprog receives what prog cannot say: per op num_deltas, predictor and the phase.
+inline jxlh_status local_lower_core(const jxlh_local_group& g, uint32_t bit_depth, uint64_t arena_samples, bool general,
+                                    const jxlh_wp_header* wp, jxlh_local_program* prog,
+                                    jxlh_local_general_program* gprog, const char** why) {
   const char* dummy;
   if (!why) why = &dummy;
   auto refuse = [&](jxlh_status st, const char* w) {
@@ -60,6 +73,7 @@ inline jxlh_status local_lower_group(const jxlh_local_group& g, uint32_t bit_dep
   uint32_t len = g.n_channels;
   for (uint32_t i = 0; i < len; i++) list[i] = (int)i;
   jxlh_local_op fwd[JXLH_LOCAL_MAX_STEPS] = {};
+  uint32_t fwd_deltas[JXLH_LOCAL_MAX_STEPS] = {}, fwd_pred[JXLH_LOCAL_MAX_STEPS] = {};  // general palettes only
   for (uint32_t i = 0; i < g.n_steps; i++) {
     const jxlh_local_step& s = g.steps[i];
     jxlh_local_op& op = fwd[i];
@@ -88,16 +102,25 @@ inline jxlh_status local_lower_group(const jxlh_local_group& g, uint32_t bit_dep
       if ((uint64_t)s.num_colors + s.num_deltas == 0) return refuse(JXLH_ERR_INVALID_ARGUMENT, "palette without entries");
       for (uint32_t k = 0; k < s.num_c; k++)
         if (list[s.begin_c + k] < 0) return refuse(JXLH_ERR_UNSUPPORTED, "palette of a palette meta channel");
-      if (s.num_deltas > 0 || s.predictor != 0) return refuse(JXLH_ERR_UNSUPPORTED, "delta / predicted local palette");
+      if (!general && (s.num_deltas > 0 || s.predictor != 0))
+        return refuse(JXLH_ERR_UNSUPPORTED, "delta / predicted local palette");
+      if (s.predictor > 13) return refuse(JXLH_ERR_INVALID_ARGUMENT, "predictor above 13");
+      if (s.predictor == 6 && !wp) return refuse(JXLH_ERR_INVALID_ARGUMENT, "weighted predictor without a wp header");
+      if (s.predictor == 6 && !wp_header_ok(*wp)) return refuse(JXLH_ERR_INVALID_ARGUMENT, "wp header field outside its width");
       if (bit_depth < 1 || bit_depth > 31) return refuse(JXLH_ERR_INVALID_ARGUMENT, "a palette needs a bit depth of 1..31");
-      if (s.num_colors > 0x7fffffffu) return refuse(JXLH_ERR_INVALID_ARGUMENT, "num_colors above 2^31 - 1");
+      const uint64_t palette_size = (uint64_t)s.num_colors + s.num_deltas;
+      if (palette_size > 0x7fffffffu) return refuse(JXLH_ERR_INVALID_ARGUMENT, "num_colors + num_deltas above 2^31 - 1");
       // the meta channel: num_c rows of num_colors + num_deltas values (meta_apply.rs:192-197)
-      if (!local_fits(s.palette_offset, (uint64_t)s.num_c * s.num_colors, arena_samples))
+      if (!local_fits(s.palette_offset, (uint64_t)s.num_c * palette_size, arena_samples))
         return refuse(JXLH_ERR_INVALID_ARGUMENT, "palette beyond the arena");
+      if (s.predictor != 0) {  // a negative index is predicted even without delta entries (palette.rs:239)
+        fwd_deltas[i] = s.num_deltas;
+        fwd_pred[i] = s.predictor;
+      }
       op.n_slots = s.num_c;  // <= 4: the range holds image channels only
       op.in_slot[0] = (uint32_t)list[s.begin_c];
       for (uint32_t k = 0; k < s.num_c; k++) op.out_slot[k] = (uint32_t)list[s.begin_c + k];
-      op.num_colors = s.num_colors;
+      op.num_colors = (uint32_t)palette_size;  // predictor 0: get_palette_value(.., num_colors + num_deltas) per pixel
       op.palette_offset = s.palette_offset;
       // channels.drain(begin + 1..begin + num); channels[begin] = index channel; channels.insert(0, meta) (:226-228)
       for (uint32_t k = s.begin_c + s.num_c; k < len; k++) list[k - (s.num_c - 1)] = list[k];
@@ -126,7 +149,39 @@ inline jxlh_status local_lower_group(const jxlh_local_group& g, uint32_t bit_dep
     prog->n_ops = g.n_steps;
     for (uint32_t i = 0; i < g.n_steps; i++) prog->ops[i] = fwd[g.n_steps - 1 - i];  // local_apply: last step first
   }
+  if (gprog) {
+    *gprog = jxlh_local_general_program{};
+    gprog->n_coded = n_coded;
+    for (uint32_t k = 0; k < n_coded; k++) gprog->coded_slot[k] = coded_slot[k];
+    gprog->n_ops = g.n_steps;
+    uint32_t phase = 0;
+    for (uint32_t i = 0; i < g.n_steps; i++) {
+      const uint32_t f = g.n_steps - 1 - i;
+      const jxlh_local_op& p = fwd[f];
+      jxlh_local_general_op& q = gprog->ops[i];
+      q.kind = p.kind, q.rct_op = p.rct_op, q.n_slots = p.n_slots, q.num_colors = p.num_colors, q.palette_offset = p.palette_offset;
+      for (int k = 0; k < 3; k++) q.in_slot[k] = p.in_slot[k];
+      for (int k = 0; k < 4; k++) q.out_slot[k] = p.out_slot[k];
+      if (fwd_pred[f] != 0) {
+        q.kind = JXLH_LOCAL_GENERAL_PALETTE;
+        q.num_deltas = fwd_deltas[f], q.predictor = fwd_pred[f];
+        phase += (phase & 1) ? 2 : 1;  // the next odd phase
+        q.phase = phase;
+      } else {
+        phase += phase & 1;  // point-wise ops behind a general palette: the even phase after it
+        q.phase = phase;
+      }
+    }
+    uint32_t generals = 0;
+    for (uint32_t i = 0; i < g.n_steps; i++) generals += fwd_pred[i] != 0;
+    gprog->n_phases = 1 + 2 * generals;
+  }
   return JXLH_OK;
+}
+
+inline jxlh_status local_lower_group(const jxlh_local_group& g, uint32_t bit_depth, uint64_t arena_samples,
+                                     jxlh_local_program* prog, const char** why) {
+  return local_lower_core(g, bit_depth, arena_samples, false, nullptr, prog, nullptr, why);
 }
 
 }  // namespace jxlh

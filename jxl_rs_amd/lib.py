@@ -253,6 +253,26 @@ def modular_local_lower(groups, bit_depth, arena_samples, n=None):
     return st, progs, (None if bad.value == 2 ** 64 - 1 else bad.value)
 
 
+def wp_headers(headers):
+    """a (WpHeader * n) array from n tuples (p1c, p2c, p3ca, p3cb, p3cc, p3cd, p3ce, w0, w1, w2, w3); None stays None"""
+    if headers is None or isinstance(headers, C.Array):
+        return headers
+    arr = (WpHeader * max(len(headers), 1))()
+    for dst, h in zip(arr, headers):
+        (dst.p1c, dst.p2c, dst.p3ca, dst.p3cb, dst.p3cc, dst.p3cd, dst.p3ce, dst.w0, dst.w1, dst.w2, dst.w3) = [int(v) for v in h]
+    return arr
+
+
+def modular_local_lower_general(groups, bit_depth, arena_samples, wp=None, n=None):
+    """jxlh_modular_local_lower_general: (status, programs, first_bad); wp: None, or one header per group (wp_headers)"""
+    L = _lib()
+    n = len(groups) if n is None else n
+    progs = (LocalGeneralProgram * max(n, 1))()
+    bad = C.c_size_t(2 ** 64 - 1)
+    st = L.jxlh_modular_local_lower_general(groups, wp_headers(wp), n, bit_depth, arena_samples, progs, C.byref(bad))
+    return st, progs, (None if bad.value == 2 ** 64 - 1 else bad.value)
+
+
 class JxlHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -771,6 +791,31 @@ class Context:
         ptrs = (C.c_void_p * len(out))(*[_addr(o) for o in out])
         self._chk(self.L.jxlh_modular_local_transforms(self._ctx, _addr(arena), arena_samples, groups, n, bit_depth, ptrs,
                                                        len(out), out_w, out_h, out_stride, None), "modular_local_transforms")
+
+    def set_modular_groups_general(self, arena, groups, sample_format, wp=None, n=None, arena_samples=None, wait=True):
+        """jxlh_frame_set_modular_groups_general[_async]: set_modular_groups with every local palette (delta entries, all
+        14 predictors); wp: None, or one weighted-predictor header per group (wp_headers)"""
+        n = len(groups) if n is None else n
+        if not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+            if not wait:
+                self._keep["local_arena"] = arena
+        fn = self.L.jxlh_frame_set_modular_groups_general if wait else self.L.jxlh_frame_set_modular_groups_general_async
+        self._chk(fn(self._ctx, _addr(arena), arena_samples, groups, wp_headers(wp), n, sample_format, None),
+                  "set_modular_groups_general")
+
+    def modular_local_transforms_general(self, arena, groups, bit_depth, out, out_w, out_h, out_stride, wp=None, n=None,
+                                         arena_samples=None):
+        """jxlh_modular_local_transforms_general: modular_local_transforms with every local palette"""
+        n = len(groups) if n is None else n
+        if not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+        ptrs = (C.c_void_p * len(out))(*[_addr(o) for o in out])
+        self._chk(self.L.jxlh_modular_local_transforms_general(self._ctx, _addr(arena), arena_samples, groups, wp_headers(wp), n,
+                                                               bit_depth, ptrs, len(out), out_w, out_h, out_stride, None),
+                  "modular_local_transforms_general")
 
     def set_dequant_tables(self, tables):
         tabs = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]

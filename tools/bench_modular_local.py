@@ -15,8 +15,22 @@ What the interface offered before, on the same data, same session:
   per_group       1024 x (jxlh_rct on the group's contiguous buffer + one rect call)
 Two contexts alternate between repetitions.
 
-  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only]
---kernel-only: a few launches of the rct case and nothing else, for a profiler run of its own."""
+  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general]
+--kernel-only: a few launches of the rct case and nothing else, for a profiler run of its own.
+
+--general: the group-local palettes with delta entries (jxlh_frame_set_modular_groups_general, k_modular_local_palette.hip)
+on the same frame and rects, device-resident arena, kernels alone from the library's event timers (median, min and max
+over `reps` of the mean of `steps`; --steps 20 --reps 5 for the recorded table):
+  delta_p5   every rect a three-channel delta palette (11 colours, 5 delta entries, the tests' index recipe), predictor 5
+  delta_p6   the same under the weighted predictor (default header)
+  mix16      1 rect in 16 a predictor-5 delta palette, the others RCTs -- the batch the old refusal made expensive
+against
+  whole_p5 / whole_p6   jxlh_palette_delta / jxlh_palette_delta_wp on ONE 8192 x 8192 plane set with the same palette and
+                        index statistics (k5_palette + k5_palette_delta / k5_palette_wp): the only device path for
+                        this arithmetic before
+  mix16_lookup          k_modular_local on the mix16 batch with the delta rects replaced by look-up palettes: the
+                        difference to mix16 is what the general groups cost
+With --kernel-only: a few launches of delta_p5 and nothing else."""
 import argparse
 import json
 import os
@@ -34,7 +48,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--general", action="store_true")
     a = ap.parse_args()
+    if a.general:
+        return general(a)
     import numpy as np
     import jxl_rs_amd
     from jxl_rs_amd import lib
@@ -120,6 +137,110 @@ def main():
         h_ms, h_mm, _, _ = measure(per_group, 2, "k4_rct")
         print(json.dumps({"case": "per_group", "call_ms": h_ms, "call_ms_min_max": h_mm}), flush=True)
         for d in planes + bufs:
+            d.free()
+    for c in ctxs:
+        c.close()
+
+
+def general(a):
+    import numpy as np
+    import jxl_rs_amd
+    from jxl_rs_amd import lib
+    n, g = a.size, 256
+    rng = np.random.default_rng(2)
+    num_colors, num_deltas = 11, 5
+    table = rng.integers(0, 256, size=(3, num_deltas + num_colors)).astype(np.int32)
+    table[:, :num_deltas] = rng.integers(-12, 13, size=(3, num_deltas))
+
+    def recipe_index(shape):
+        idx = rng.integers(-8, num_colors + num_deltas + 200, size=shape).astype(np.int32)
+        redraw = rng.random(shape) < 0.5
+        idx[redraw] = rng.integers(0, num_deltas, size=int(redraw.sum()))
+        return idx
+
+    index = recipe_index((g, g))
+    chan = [rng.integers(0, 64, size=(g, g)).astype(np.int32) for _ in range(3)]
+    WP_DEFAULT = (16, 10, 7, 7, 7, 0, 0, 13, 12, 12, 12)
+
+    def specs(kind):
+        out = []
+        for k, (gy, gx) in enumerate((y, x) for y in range(0, n, g) for x in range(0, n, g)):
+            if kind == "delta_p5" or (kind.startswith("mix16") and k % 16 == 0):
+                steps = [lib.local_palette(0, 3, table, *((0, 0) if kind == "mix16_lookup" else (num_deltas, 5)))]
+            elif kind == "delta_p6":
+                steps = [lib.local_palette(0, 3, table, num_deltas, 6)]
+            else:
+                steps = [lib.local_rct(0, k % 42)]
+            out.append({"x0": gx, "y0": gy, "n_channels": 3, "steps": steps, "coded": [index] if steps[0]["kind"] == lib.LOCAL_PALETTE else chan})
+        return out
+
+    ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(2)]
+    p = ctxs[0].default_params(n, n)
+    p.gab, p.epf_iters = 0, 0
+    for c in ctxs:
+        c.modular_frame_begin(p)
+
+    def timed(c, call, steps):
+        c.kernel_timing_reset()
+        c.kernel_timing(True)
+        for _ in range(steps):
+            call(c)
+        c.sync()
+        kt = c.kernel_times()
+        c.kernel_timing(False)
+        return {k: ms / steps for k, (ms, _) in kt.items()}, {k: cnt // steps for k, (_, cnt) in kt.items()}
+
+    def measure(call):
+        for c in ctxs:
+            call(c)
+            c.sync()
+        runs = [timed(ctxs[r % 2], call, a.steps) for r in range(a.reps)]
+        labels = sorted(runs[0][0])
+        row = {"launches_per_call": runs[0][1]}
+        for k in labels + ["total"]:
+            v = [sum(r[0].values()) if k == "total" else r[0][k] for r in runs]
+            row[k + "_ms"] = [statistics.median(v), min(v), max(v)]
+        return row
+
+    for kind in ("delta_p5", "delta_p6", "mix16", "mix16_lookup"):
+        sp = specs(kind)
+        arena, groups = lib.pack_local_groups(sp)
+        dev = lib.DeviceArray(arena)
+        wp = lib.wp_headers([WP_DEFAULT] * len(sp))
+        if kind == "mix16_lookup":
+            launch = lambda c: c.set_modular_groups(dev, groups, 8, n=len(sp), arena_samples=arena.size, wait=False)
+        else:
+            launch = lambda c: c.set_modular_groups_general(dev, groups, 8, wp=wp, n=len(sp), arena_samples=arena.size, wait=False)
+        if a.kernel_only:
+            for _ in range(3):
+                launch(ctxs[0])
+            ctxs[0].sync()
+            dev.free()
+            break
+        row = {"case": kind, "frame": f"{n}x{n}", "rects": len(sp), "median_min_max": True}
+        row.update(measure(launch))
+        print(json.dumps(row), flush=True)
+        dev.free()
+    if not a.kernel_only:
+        # the whole-plane kernels on one plane set of the frame's size
+        idx = lib.DeviceArray(recipe_index((n, n)))
+        pal = lib.DeviceArray(table)
+        out = lib.DeviceArray(nbytes=3 * n * n * 4)
+        hdr = lib.wp_headers([WP_DEFAULT])
+
+        def whole_p5(c):
+            c._chk(c.L.jxlh_palette_delta(c._ctx, idx.ptr, n, n, pal.ptr, num_colors, num_deltas, num_colors + num_deltas, 3, 8, 5,
+                                          out.ptr), "palette_delta")
+
+        def whole_p6(c):
+            c._chk(c.L.jxlh_palette_delta_wp(c._ctx, idx.ptr, n, n, pal.ptr, num_colors, num_deltas, num_colors + num_deltas, 3, 8,
+                                             hdr, out.ptr), "palette_delta_wp")
+
+        for name, call in (("whole_p5", whole_p5), ("whole_p6", whole_p6)):
+            row = {"case": name, "plane_set": f"3 x {n}x{n}", "median_min_max": True}
+            row.update(measure(call))
+            print(json.dumps(row), flush=True)
+        for d in (idx, pal, out):
             d.free()
     for c in ctxs:
         c.close()

@@ -26,6 +26,9 @@ EXTRA_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_extra_rects.h")
 OUT_EXTRA_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "extra_rects.rs")
 REPAINT_HEADER = os.path.join(ROOT, "include", "jxl_hip_repaint.h")
 OUT_REPAINT = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "repaint.rs")
+# ... and a header that includes jxl_hip.h rather than being included by it
+LOCAL_PALETTE_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_palette.h")
+OUT_LOCAL_PALETTE = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_palette.rs")
 
 SCALARS = {"uint8_t": "u8", "int8_t": "i8", "uint16_t": "u16", "int16_t": "i16", "uint32_t": "u32", "int32_t": "i32",
            "uint64_t": "u64", "int64_t": "i64", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -166,6 +169,8 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod extra_rects;")
     w("// include/jxl_hip_repaint.h (... src/repaint.rs)")
     w("pub mod repaint;")
+    w("// include/jxl_hip_local_palette.h (... src/local_palette.rs)")
+    w("pub mod local_palette;")
     return "\n".join(out) + "\n"
 
 
@@ -226,10 +231,14 @@ def generate_repaint():
     return emit_extension(os.path.basename(REPAINT_HEADER), *parse_header(open(REPAINT_HEADER).read()), uses=("save_rects",))
 
 
+def generate_local_palette():
+    return emit_extension(os.path.basename(LOCAL_PALETTE_HEADER), *parse_header(open(LOCAL_PALETTE_HEADER).read()))
+
+
 def main():
     for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
                       (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects()),
-                      (OUT_REPAINT, generate_repaint())):
+                      (OUT_REPAINT, generate_repaint()), (OUT_LOCAL_PALETTE, generate_local_palette())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
             if cur != text:
