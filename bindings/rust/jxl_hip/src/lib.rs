@@ -120,8 +120,8 @@ impl Context {
     /// every group's coded channels and palettes (host memory), `groups` each group's rect, transform list in bitstream
     /// order and offsets into the arena (what `decode_modular_section` leaves instead of running `local_apply`).  All
     /// groups run in one launch; the call returns when `arena` may be reused.  A group the device does not take
-    /// (`HipError::Unsupported`: delta palettes, local squeeze) stays on the host and goes in with
-    /// `jxlh_frame_set_modular_channels`.
+    /// (`HipError::Unsupported`: delta palettes, local squeeze -- see `set_modular_groups_squeeze`) stays on the host
+    /// and goes in with `jxlh_frame_set_modular_channels`.
     pub fn set_modular_groups(&self, arena: &[i32], groups: &[sys::jxlh_local_group], sample_format: u32) -> Result<()> {
         let mut first_bad = usize::MAX;
         // SAFETY: the library checks every offset + extent against arena.len() before it reads; the call waits
@@ -138,6 +138,44 @@ impl Context {
         let mut first_bad = usize::MAX;
         let st = unsafe {
             sys::jxlh_modular_local_lower(groups.as_ptr(), groups.len(), bit_depth, arena_samples, progs.as_mut_ptr(), &mut first_bad)
+        };
+        if st == sys::JXLH_OK { Ok(progs) } else { Err((st, first_bad)) }
+    }
+    /// `jxlh_frame_set_modular_groups_squeeze`: `set_modular_groups` for groups that carry a local squeeze
+    /// (`jxl_hip_local_squeeze.h`).  `groups` are self-contained: the steps in front of the squeeze, and ranges of `coded`
+    /// (the coded channels in the reference's list order, each with its own size and stride) and of `params` (the
+    /// squeeze's `SqueezeParams`; an empty range is `default_squeeze`).  `wp`: one weighted-predictor header per group,
+    /// or `None` when no step has predictor 6.  The launches do not grow with the number of groups; the call returns when
+    /// `arena` may be reused.
+    pub fn set_modular_groups_squeeze(&self, arena: &[i32], groups: &[sys::local_squeeze::jxlh_local_squeeze_group],
+                                      coded: &[sys::local_squeeze::jxlh_local_coded_channel],
+                                      params: &[sys::local_squeeze::jxlh_squeeze_params], wp: Option<&[sys::jxlh_wp_header]>,
+                                      sample_format: u32) -> Result<()> {
+        if wp.map_or(false, |w| w.len() != groups.len()) {
+            return Err(HipError::InvalidArgument);
+        }
+        let mut first_bad = usize::MAX;
+        // SAFETY: the library checks every range against coded.len() / params.len() and every offset + extent against
+        // arena.len() before it reads; the call waits
+        self.ok(unsafe {
+            sys::local_squeeze::jxlh_frame_set_modular_groups_squeeze(
+                self.raw, arena.as_ptr(), arena.len() as u64, groups.as_ptr(), groups.len(), coded.as_ptr(), coded.len(),
+                params.as_ptr(), params.len(), wp.map_or(std::ptr::null(), |w| w.as_ptr()), sample_format, &mut first_bad)
+        })
+    }
+    /// `jxlh_modular_local_lower_squeeze`: the host-side lowering and checks alone; `Err` carries the first refused group
+    pub fn lower_modular_squeeze_groups(groups: &[sys::local_squeeze::jxlh_local_squeeze_group],
+                                        coded: &[sys::local_squeeze::jxlh_local_coded_channel],
+                                        params: &[sys::local_squeeze::jxlh_squeeze_params], wp: Option<&[sys::jxlh_wp_header]>,
+                                        bit_depth: u32, arena_samples: u64)
+                                        -> std::result::Result<Vec<sys::local_squeeze::jxlh_local_squeeze_program>, (sys::jxlh_status, usize)> {
+        // SAFETY: plain-old-data structs, fully written by a successful call
+        let mut progs: Vec<sys::local_squeeze::jxlh_local_squeeze_program> = vec![unsafe { std::mem::zeroed() }; groups.len()];
+        let mut first_bad = usize::MAX;
+        let st = unsafe {
+            sys::local_squeeze::jxlh_modular_local_lower_squeeze(
+                groups.as_ptr(), groups.len(), coded.as_ptr(), coded.len(), params.as_ptr(), params.len(),
+                wp.map_or(std::ptr::null(), |w| w.as_ptr()), bit_depth, arena_samples, progs.as_mut_ptr(), &mut first_bad)
         };
         if st == sys::JXLH_OK { Ok(progs) } else { Err((st, first_bad)) }
     }

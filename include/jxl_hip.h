@@ -266,7 +266,7 @@ jxlh_status jxlh_frame_set_modular_channels(jxlh_ctx* ctx, uint32_t x0, uint32_t
  *                              a rect outside the frame / the out planes; a bad or changed sample_format.
  *   JXLH_ERR_UNSUPPORTED       (keep that group on the host and hand it over with jxlh_frame_set_modular_channels) a
  *                              palette with num_deltas > 0 or predictor != 0; a step whose range touches a palette meta
- *                              channel; any other transform kind (local squeeze); a chroma-subsampled frame; a sharded
+ *                              channel; any other transform kind (local squeeze: jxl_hip_local_squeeze.h); a chroma-subsampled frame; a sharded
  *                              context.
  *   JXLH_ERR_BAD_STATE         jxlh_frame_set_modular_groups* outside a frame or on a VarDCT frame. */
 #define JXLH_LOCAL_MAX_STEPS 4

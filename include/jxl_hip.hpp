@@ -21,6 +21,7 @@
 
 #include "jxl_hip.h"
 #include "jxl_hip_local_palette.h"
+#include "jxl_hip_local_squeeze.h"
 
 namespace jxlh {
 
@@ -265,6 +266,18 @@ class VarDctFrame {
     ctx_.check(async ? jxlh_frame_set_modular_groups_general_async(ctx_.raw(), arena, arena_samples, groups, wp, n, sample_format, &bad)
                      : jxlh_frame_set_modular_groups_general(ctx_.raw(), arena, arena_samples, groups, wp, n, sample_format, &bad),
                "jxlh_frame_set_modular_groups_general");
+  }
+  // ... and with local squeezes (jxl_hip_local_squeeze.h): self-contained groups whose coded channels and squeeze
+  // parameters are ranges of the call-wide `coded` and `params` arrays; all of them are read before the call returns.
+  void set_modular_groups_squeeze(const int32_t* arena, uint64_t arena_samples, const jxlh_local_squeeze_group* groups, size_t n,
+                                  const jxlh_local_coded_channel* coded, size_t n_coded, const jxlh_squeeze_params* params,
+                                  size_t n_params, const jxlh_wp_header* wp, uint32_t sample_format, bool async = false) {
+    size_t bad = 0;
+    ctx_.check(async ? jxlh_frame_set_modular_groups_squeeze_async(ctx_.raw(), arena, arena_samples, groups, n, coded, n_coded, params,
+                                                                   n_params, wp, sample_format, &bad)
+                     : jxlh_frame_set_modular_groups_squeeze(ctx_.raw(), arena, arena_samples, groups, n, coded, n_coded, params,
+                                                             n_params, wp, sample_format, &bad),
+               "jxlh_frame_set_modular_groups_squeeze");
   }
   // An extra channel that arrives group by group (jxl_hip_extra_rects.h): declared once per frame, all zero ...
   void begin_extra_channel(uint32_t ec, uint32_t w, uint32_t h, uint32_t bits_per_sample, uint32_t ec_upsampling) {

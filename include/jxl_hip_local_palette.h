@@ -44,8 +44,8 @@ extern "C" {
  * Statuses: as for the calls of jxl_hip.h (a refused call enqueues nothing, changes nothing and names the group in
  * *first_bad and jxlh_last_error), except
  *   JXLH_ERR_UNSUPPORTED       no longer: a palette with num_deltas > 0 or predictor != 0.  Still: a step whose range
- *                              touches a palette meta channel; any other transform kind (local squeeze -- the one
- *                              group-local transform left on the host); a chroma-subsampled frame; a sharded context.
+ *                              touches a palette meta channel; any other transform kind (local squeeze: the _squeeze
+ *                              calls of jxl_hip_local_squeeze.h); a chroma-subsampled frame; a sharded context.
  *   JXLH_ERR_INVALID_ARGUMENT  also: predictor > 13; predictor 6 with wp == NULL; a wp field outside its width (p1c, p2c,
  *                              p3ca..p3ce >= 32, w0..w3 >= 16: the rule of jxlh_palette_delta_wp) in a group that has a
  *                              predictor-6 step; a palette whose num_c * (num_colors + num_deltas) values leave the arena

@@ -21,6 +21,37 @@
 
 namespace jxlh {
 
+// A batch of groups for the squeeze calls (jxl_hip_local_squeeze.h): the groups, and the call-wide arrays their
+// coded_first / params_first ranges index.  wp: empty when no step has predictor 6, else one header per group.
+struct LocalSqueezeGroups {
+  std::vector<jxlh_local_squeeze_group> groups;
+  std::vector<jxlh_local_coded_channel> coded;
+  std::vector<jxlh_squeeze_params> params;
+  std::vector<jxlh_wp_header> wp;
+  // a group of w x h at (x0, y0) whose coded channels and squeeze parameters are appended to the arrays; squeeze ==
+  // nullptr: the group has none; an empty list: default_squeeze
+  jxlh_local_squeeze_group& add(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t n_channels,
+                                const std::vector<jxlh_local_step>& steps, const std::vector<jxlh_squeeze_params>* squeeze,
+                                const std::vector<jxlh_local_coded_channel>& channels) {
+    if (steps.size() > JXLH_LOCAL_MAX_STEPS) throw Error(JXLH_ERR_INVALID_ARGUMENT, "LocalSqueezeGroups::add", "at most 4 steps");
+    jxlh_local_squeeze_group g{};
+    g.x0 = x0, g.y0 = y0, g.w = w, g.h = h, g.n_channels = n_channels;
+    g.n_steps = (uint32_t)steps.size();
+    for (size_t i = 0; i < steps.size(); i++) g.steps[i] = steps[i];
+    g.has_squeeze = squeeze ? 1 : 0;
+    g.squeeze_pos = squeeze ? g.n_steps : 0;
+    g.params_first = (uint32_t)params.size(), g.n_params = squeeze ? (uint32_t)squeeze->size() : 0;
+    if (squeeze) params.insert(params.end(), squeeze->begin(), squeeze->end());
+    g.coded_first = (uint32_t)coded.size(), g.n_coded = (uint32_t)channels.size();
+    coded.insert(coded.end(), channels.begin(), channels.end());
+    groups.push_back(g);
+    return groups.back();
+  }
+  void check(const char* where) const {
+    if (!wp.empty() && wp.size() != groups.size()) throw Error(JXLH_ERR_INVALID_ARGUMENT, where, "one wp header per group, or none");
+  }
+};
+
 // What GpuRenderPipeline and GpuModularFramePipeline share: the frame begun on the context with the lowered parameters,
 // its dictionary and splines, the extra channels, and the output side -- blend, save, read.
 class GpuFramePipeline {
@@ -205,7 +236,7 @@ class GpuModularFramePipeline : public GpuFramePipeline {
     frame_.set_modular_groups(arena, arena_samples, groups.data(), groups.size(), lp_.modular_sample_format, async);
   }
   // the same with every local palette on the device (jxlh_frame_set_modular_groups_general): delta entries and all 14
-  // predictors, so that only a local squeeze is left to the host.  wp: empty when no step has predictor 6, else one
+  // predictors; a local squeeze goes through the LocalSqueezeGroups overload below.  wp: empty when no step has predictor 6, else one
   // GroupHeader::wp_header per group
   void set_groups_general(const int32_t* arena, uint64_t arena_samples, const std::vector<jxlh_local_group>& groups,
                           const std::vector<jxlh_wp_header>& wp, bool async = false) {
@@ -213,6 +244,14 @@ class GpuModularFramePipeline : public GpuFramePipeline {
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuModularFramePipeline::set_groups_general", "one wp header per group, or none");
     frame_.set_modular_groups_general(arena, arena_samples, groups.data(), wp.empty() ? nullptr : wp.data(), groups.size(),
                                       lp_.modular_sample_format, async);
+  }
+  // the same with local squeezes on the device too (jxlh_frame_set_modular_groups_squeeze): nothing group-local is left
+  // to the host but what the header lists as unsupported
+  void set_groups(const int32_t* arena, uint64_t arena_samples, const LocalSqueezeGroups& batch, bool async = false) {
+    batch.check("GpuModularFramePipeline::set_groups");
+    frame_.set_modular_groups_squeeze(arena, arena_samples, batch.groups.data(), batch.groups.size(), batch.coded.data(),
+                                      batch.coded.size(), batch.params.data(), batch.params.size(),
+                                      batch.wp.empty() ? nullptr : batch.wp.data(), lp_.modular_sample_format, async);
   }
   // the whole frame, then the list's blending
   void render() {
@@ -265,6 +304,17 @@ class GpuModularPipeline {
                                                      wp.empty() ? nullptr : wp.data(), groups.size(), bit_depth, planes, n_planes,
                                                      lp_.frame.xsize, lp_.frame.ysize, stride, &bad),
                "jxlh_modular_local_transforms_general");
+  }
+  // ... and with local squeezes (jxlh_modular_local_transforms_squeeze)
+  void local_transforms(const int32_t* arena, uint64_t arena_samples, const LocalSqueezeGroups& batch, uint32_t bit_depth,
+                        int32_t* const planes[], uint32_t n_planes, size_t stride) {
+    batch.check("GpuModularPipeline::local_transforms");
+    size_t bad = 0;
+    ctx_.check(jxlh_modular_local_transforms_squeeze(ctx_.raw(), arena, arena_samples, batch.groups.data(), batch.groups.size(),
+                                                     batch.coded.data(), batch.coded.size(), batch.params.data(),
+                                                     batch.params.size(), batch.wp.empty() ? nullptr : batch.wp.data(), bit_depth,
+                                                     planes, n_planes, lp_.frame.xsize, lp_.frame.ysize, stride, &bad),
+               "jxlh_modular_local_transforms_squeeze");
   }
   // ConvertI32ToU8Stage: interleaved bytes (3 or 4 per pixel) in one pass
   void render_u8(const int32_t* const planes[3], size_t stride, void* out, size_t bytes_per_row) {

@@ -3,12 +3,16 @@
 // lowered on the host (modular_local_host.h), the lowered programs and a flat (group, row chunk) work list go up in one
 // copy from a pinned block, a host arena in one more, and the whole batch is one launch of k_modular_local.  Groups with
 // GENERAL palettes (the _general calls only) follow phase by phase -- one launch per phase for all of them, their
-// descriptors in the same block and the same copy.  Everything that can refuse a call is checked before the first copy
-// is enqueued.
+// descriptors in the same block and the same copy.  Groups with a squeeze of their own (the _squeeze calls of
+// jxl_hip_local_squeeze.h, lowered by modular_local_squeeze_host.h) run their chains first -- one LDS launch and one
+// launch per streamed level index for the whole batch -- and then the same phases on their rects.  Everything that can
+// refuse a call is checked before the first copy is enqueued.
 #include <algorithm>
 
 #include "jxlh_ctx.h"
 #include "modular_local_host.h"
+#include "modular_local_squeeze_host.h"
+#include "squeeze_plan.h"
 
 namespace jxlh_host {
 namespace {
@@ -49,10 +53,14 @@ struct GeneralBatch {
 // palette, which shares its slot with that palette's output channel 0 while the other channels' workgroups still read
 // it -- in scratch.  A point-wise phase loads every slot that is somewhere and stores what it changed (what the next
 // palette overwrites excepted); the last one leaves every channel in the destination rect.
+// init (a group of the squeeze calls): where each slot is when the phases start -- a coded channel of its own stride, or
+// the destination rect, where the slot's squeeze chain ends.  Such a group may have no general palette at all: its one
+// point-wise phase is phase 0.
 void plan_general_group(const jxlh_local_group& g, const jxlh_local_general_program& prog, const jxlh_wp_header* wp,
-                        bool fan, GeneralBatch& b) {
+                        bool fan, GeneralBatch& b, const LpPlane* init = nullptr) {
   LpPlane loc[4] = {};
-  for (uint32_t k = 0; k < prog.n_coded; k++) loc[prog.coded_slot[k]] = LpPlane{g.coded_offset[k], g.coded_stride, kLpArena};
+  for (uint32_t k = 0; k < prog.n_coded; k++)
+    loc[prog.coded_slot[k]] = init ? init[prog.coded_slot[k]] : LpPlane{g.coded_offset[k], g.coded_stride, kLpArena};
   const uint32_t nvx = (g.w + 3) / 4, rows_per_item = std::max(1u, kLocalItemSamples / (4 * nvx));
   bool have_copy = false;
   uint64_t copy_off = 0;
@@ -104,6 +112,7 @@ void plan_general_group(const jxlh_local_group& g, const jxlh_local_general_prog
     for (uint64_t r = 0; r < g.h; r += rows_per_item) b.items[phase].push_back(LocalItem{id, (uint32_t)r});
   };
   uint32_t i = 0, phase = 0;
+  bool seen = false;
   while (i < prog.n_ops) {
     uint32_t e = i;
     while (e < prog.n_ops && prog.ops[e].kind != JXLH_LOCAL_GENERAL_PALETTE) e++;
@@ -134,35 +143,141 @@ void plan_general_group(const jxlh_local_group& g, const jxlh_local_general_prog
     for (uint32_t c = 0; c < p.n_slots; c++) b.items[p.phase].push_back(LocalItem{id, c});
     for (uint32_t k = 0; k < p.n_slots; k++) loc[p.out_slot[k]] = LpPlane{0, 0, kLpOut};
     phase = p.phase;
+    seen = true;
     i = e + 1;
   }
-  pointwise(phase + 1, i, prog.n_ops, nullptr);
+  pointwise(seen ? phase + 1 : 0, i, prog.n_ops, nullptr);
+}
+
+// the groups, coded channels and squeeze parameters of the squeeze calls (jxl_hip_local_squeeze.h)
+struct SqueezeIn {
+  const jxlh_local_squeeze_group* groups;
+  const jxlh_local_coded_channel* coded;
+  size_t n_coded;
+  const jxlh_squeeze_params* params;
+  size_t n_params;
+};
+// what the squeeze chains of a batch launch: the LDS launch's items (chain, 0) and streamed launch k's (chain, first line)
+struct SqueezeBatch {
+  std::vector<LsChainDev> chains;
+  std::vector<LocalItem> lds_items;
+  std::vector<LocalItem> level_items[kLsLevels];
+  bool any() const { return !chains.empty(); }
+};
+
+// One group of the squeeze calls that does not run as a plain / general group: every squeezed channel becomes a chain
+// that ends in the destination rect, every other one stays in the arena; the steps in front follow as phases.
+void plan_squeeze_group(const jxlh_local_group& g, const jxlh_local_squeeze_group& sg, const jxlh_local_squeeze_program& prog,
+                        const jxlh_local_coded_channel* coded, const jxlh_wp_header* wp, bool fan, GeneralBatch& gb,
+                        SqueezeBatch& sb) {
+  LpPlane init[4] = {};
+  for (uint32_t k = 0; k < prog.general.n_coded; k++) {
+    const uint32_t slot = prog.general.coded_slot[k];
+    const jxlh_local_squeeze_chain& ch = prog.chains[k];
+    const jxlh_local_coded_channel& bc = coded[sg.coded_first + ch.base];
+    if (ch.n_levels == 0) {
+      init[slot] = LpPlane{bc.offset, bc.stride, kLpArena};
+      continue;
+    }
+    LsChainDev c{};
+    c.x0 = g.x0, c.y0 = g.y0, c.slot = slot;
+    c.n_levels = ch.n_levels;
+    c.base_w = ch.base_w, c.base_h = ch.base_h, c.base_stride = bc.stride, c.base_off = bc.offset;
+    jxlh_squeeze_level fit[kLsLevels] = {};
+    for (uint32_t i = 0; i < ch.n_levels; i++) {
+      const jxlh_local_squeeze_level& lv = ch.levels[i];
+      const jxlh_local_coded_channel& rc = coded[sg.coded_first + lv.res];
+      const bool has_res = rc.w > 0 && rc.h > 0;
+      c.lv[i] = LsLevelDev{lv.horizontal, lv.out_w, lv.out_h, has_res ? rc.stride : 0u, has_res ? rc.offset : 0u};
+      fit[i].horizontal = lv.horizontal, fit[i].out_w = lv.out_w, fit[i].out_h = lv.out_h;
+    }
+    // the LDS launch takes the first levels while every plane fits its tiles (squeeze_plan.h)
+    uint32_t n_lds = 0;
+    while (n_lds < ch.n_levels && ch.levels[n_lds].out_w <= (uint32_t)kLsTile && ch.levels[n_lds].out_h <= (uint32_t)kLsTile) n_lds++;
+    while (n_lds >= 1 && !jxlh::squeeze_levels_fit((int)n_lds, fit, ch.base_w, ch.base_h)) n_lds--;
+    c.n_lds = n_lds;
+    // level i's output, unless it is the last, goes to the chain's scratch plane i & 1: each as large as the largest it holds
+    uint64_t need[2] = {0, 0};
+    for (uint32_t i = n_lds > 0 ? n_lds - 1 : 0; i + 1 < ch.n_levels; i++)
+      need[i & 1] = std::max(need[i & 1], (uint64_t)ch.levels[i].out_w * ch.levels[i].out_h);
+    for (int q = 0; q < 2; q++) {
+      c.scratch_off[q] = gb.scratch;
+      gb.scratch += need[q];
+    }
+    const uint32_t id = (uint32_t)sb.chains.size();
+    sb.chains.push_back(c);
+    if (n_lds > 0) sb.lds_items.push_back(LocalItem{id, 0});
+    for (uint32_t k2 = 0; n_lds + k2 < ch.n_levels; k2++) {
+      const jxlh_local_squeeze_level& lv = ch.levels[n_lds + k2];
+      const uint32_t n_lines = lv.horizontal ? lv.out_h : lv.out_w;
+      for (uint32_t l = 0; l < n_lines; l += (uint32_t)kLsLines) sb.level_items[k2].push_back(LocalItem{id, l});
+    }
+    init[slot] = LpPlane{0, 0, kLpOut};
+  }
+  plan_general_group(g, prog.general, wp, fan, gb, init);
 }
 
 // checks, lowering, upload, launch; nothing is enqueued unless every group passed.  general: the _general calls (wp: one
 // header per group, or null)
 jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
                           size_t n, uint32_t bit_depth, const LocalDest& d, size_t* first_bad, bool general = false,
-                          const jxlh_wp_header* wp = nullptr) {
+                          const jxlh_wp_header* wp = nullptr, const SqueezeIn* sq = nullptr) {
   if (n > 0x7fffffffu || d.w > 0x7fffffffu || d.h > 0x7fffffffu) return JXLH_ERR_INVALID_ARGUMENT;
   std::vector<LocalGroupDev> dev(n);
   std::vector<LocalItem> items;
   GeneralBatch gb;
+  SqueezeBatch sb;
   bool dst_aligned = (d.stride & 3) == 0 && (reinterpret_cast<uintptr_t>(arena) & 15) == 0;
   for (uint32_t c = 0; c < d.n_out; c++) dst_aligned = dst_aligned && (reinterpret_cast<uintptr_t>(d.out[c]) & 15) == 0;
   for (size_t gi = 0; gi < n; gi++) {
-    const jxlh_local_group& g = groups[gi];
     jxlh_local_program prog;
     jxlh_local_general_program gprog;
     const char* why = "";
-    if (jxlh_status st = local_lower_core(g, bit_depth, arena_samples, general, wp ? &wp[gi] : nullptr, &prog, &gprog, &why))
-      return refuse_group(ctx, st, gi, why, first_bad);
+    // a group of the squeeze calls: one without squeeze levels whose coded channels share a stride runs as a group of
+    // the _general calls does (gtmp says it in their terms); any other one as chains and phases
+    jxlh_local_group gtmp{};
+    jxlh_local_squeeze_program sprog;
+    bool chains = false;
+    if (sq) {
+      const jxlh_local_squeeze_group& sg = sq->groups[gi];
+      if (jxlh_status st = local_lower_squeeze_group(sg, sq->coded, sq->n_coded, sq->params, sq->n_params, wp ? &wp[gi] : nullptr,
+                                                     bit_depth, arena_samples, &sprog, &why))
+        return refuse_group(ctx, st, gi, why, first_bad);
+      gtmp.x0 = sg.x0, gtmp.y0 = sg.y0, gtmp.w = sg.w, gtmp.h = sg.h;
+      gtmp.n_channels = sg.n_channels, gtmp.n_steps = sg.n_steps;
+      for (uint32_t k = 0; k < sg.n_steps; k++) gtmp.steps[k] = sg.steps[k];
+      for (uint32_t k = 0; k < sprog.general.n_coded; k++) chains = chains || sprog.chains[k].n_levels > 0;
+      if (!chains) {  // the coded channels are the channels that reach the squeeze, full size
+        gtmp.n_coded = sprog.n_coded;
+        gtmp.coded_stride = sg.w;
+        for (uint32_t k = 0; k < sprog.n_coded && sg.w > 0 && sg.h > 0; k++) {
+          const jxlh_local_coded_channel& c = sq->coded[sg.coded_first + k];
+          gtmp.coded_offset[k] = c.offset;
+          if (k == 0) gtmp.coded_stride = c.stride;
+          chains = chains || c.stride != gtmp.coded_stride;
+        }
+      }
+      gprog = sprog.general;
+    }
+    const jxlh_local_group& g = sq ? gtmp : groups[gi];
+    if (!chains)
+      if (jxlh_status st = local_lower_core(g, bit_depth, arena_samples, general, wp ? &wp[gi] : nullptr, &prog, &gprog, &why))
+        return refuse_group(ctx, st, gi, why, first_bad);
     if (d.frame ? (g.n_channels != 3 && g.n_channels != 1) : g.n_channels > d.n_out)
       return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, d.frame ? "a frame's groups hold 3 channels, or 1 (grey)" : "more channels than out planes", first_bad);
     if ((uint64_t)g.x0 + g.w > d.w || (uint64_t)g.y0 + g.h > d.h)
       return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the rect leaves the planes", first_bad);
     LocalGroupDev& o = dev[gi];
     o = LocalGroupDev{};
+    if (chains) {
+      if (g.w == 0 || g.h == 0) continue;
+      plan_squeeze_group(g, sq->groups[gi], sprog, sq->coded, wp ? &wp[gi] : nullptr, d.frame && g.n_channels == 1, gb, sb);
+      size_t most = std::max(sb.chains.size(), sb.lds_items.size());
+      for (const auto& v : sb.level_items) most = std::max(most, v.size());
+      for (const auto& v : gb.items) most = std::max(most, v.size());
+      if (most > 0x7fffffffu) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the batch holds more than 2^31 - 1 work items", first_bad);
+      continue;
+    }
     if (gprog.n_phases > 1) {  // general palettes: this group runs phase by phase, behind the launch of the others
       if (g.w > (1u << 30)) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "a predicted palette on a group wider than 2^30", first_bad);
       if (g.w == 0 || g.h == 0) continue;
@@ -209,7 +324,7 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     if (items.size() > 0x7fffffffu) return refuse_group(ctx, JXLH_ERR_INVALID_ARGUMENT, gi, "the batch holds more than 2^31 - 1 work items", first_bad);
   }
   const bool have_general = gb.any();
-  if (items.empty() && !have_general) return JXLH_OK;
+  if (items.empty() && !have_general && !sb.any()) return JXLH_OK;
   // ---- from here on the call cannot be refused for its arguments
   // the block: the plain groups' descriptors and items, then per phase its descriptors and items, each 16-byte aligned
   const size_t desc_bytes = round_up(n * sizeof(LocalGroupDev), 16);
@@ -220,6 +335,18 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     bytes += round_up((p & 1) ? gb.jobs[p].size() * sizeof(LpJobDev) : gb.pointwise[p].size() * sizeof(LpPhaseDev), 16);
     phase_items[p] = bytes;
     bytes += round_up(gb.items[p].size() * sizeof(LocalItem), 16);
+  }
+  // ... then the squeeze chains, the LDS launch's items and each streamed launch's
+  size_t chain_desc = 0, lds_items_at = 0, level_items_at[kLsLevels] = {};
+  if (sb.any()) {
+    chain_desc = bytes;
+    bytes += round_up(sb.chains.size() * sizeof(LsChainDev), 16);
+    lds_items_at = bytes;
+    bytes += round_up(sb.lds_items.size() * sizeof(LocalItem), 16);
+    for (int k = 0; k < kLsLevels; k++) {
+      level_items_at[k] = bytes;
+      bytes += round_up(sb.level_items[k].size() * sizeof(LocalItem), 16);
+    }
   }
   HIPCHK(ctx, ctx->local_copied.sync());  // the pinned block's previous content is on its way
   ctx->local_copied.clear();
@@ -236,6 +363,12 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     if (p & 1) std::memcpy(ctx->local_desc_host.p + phase_desc[p], gb.jobs[p].data(), gb.jobs[p].size() * sizeof(LpJobDev));
     else std::memcpy(ctx->local_desc_host.p + phase_desc[p], gb.pointwise[p].data(), gb.pointwise[p].size() * sizeof(LpPhaseDev));
     std::memcpy(ctx->local_desc_host.p + phase_items[p], gb.items[p].data(), gb.items[p].size() * sizeof(LocalItem));
+  }
+  if (sb.any()) {
+    std::memcpy(ctx->local_desc_host.p + chain_desc, sb.chains.data(), sb.chains.size() * sizeof(LsChainDev));
+    std::memcpy(ctx->local_desc_host.p + lds_items_at, sb.lds_items.data(), sb.lds_items.size() * sizeof(LocalItem));
+    for (int k = 0; k < kLsLevels; k++)
+      std::memcpy(ctx->local_desc_host.p + level_items_at[k], sb.level_items[k].data(), sb.level_items[k].size() * sizeof(LocalItem));
   }
   const int32_t* arena_dev = arena;
   if (!is_device_ptr(arena)) {
@@ -261,6 +394,29 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
     {
       ScopedKernelTimer t(ctx, "k_modular_local");
       launch_modular_local(ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+  }
+  if (sb.any()) {  // every chain up to its destination rect, ahead of the phases that read it there
+    LsLaunch a{};
+    a.arena = arena_dev;
+    a.scratch = ctx->local_scratch.p;
+    for (int c = 0; c < 4; c++) a.out[c] = d.out[c];
+    a.out_stride = d.stride;
+    a.chains = reinterpret_cast<const LsChainDev*>(ctx->local_desc.p + chain_desc);
+    if (!sb.lds_items.empty()) {
+      a.items = reinterpret_cast<const LocalItem*>(ctx->local_desc.p + lds_items_at);
+      a.n_items = (uint32_t)sb.lds_items.size();
+      ScopedKernelTimer t(ctx, "k_modular_local_squeeze_lds");
+      launch_modular_local_squeeze_lds(ctx->stream, a);
+    }
+    for (int k = 0; k < kLsLevels; k++) {
+      if (sb.level_items[k].empty()) continue;
+      a.items = reinterpret_cast<const LocalItem*>(ctx->local_desc.p + level_items_at[k]);
+      a.n_items = (uint32_t)sb.level_items[k].size();
+      a.step = (uint32_t)k;
+      ScopedKernelTimer t(ctx, "k_modular_local_squeeze_level");
+      launch_modular_local_squeeze_level(ctx->stream, a);
     }
     HIPCHK(ctx, hipGetLastError());
   }
@@ -291,9 +447,9 @@ jxlh_status local_enqueue(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_sa
 
 jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
                              size_t n, uint32_t sample_format, size_t* first_bad, bool wait, bool general = false,
-                             const jxlh_wp_header* wp = nullptr) {
+                             const jxlh_wp_header* wp = nullptr, const SqueezeIn* sq = nullptr) {
   JXLH_ON_DEVICE(ctx);
-  if (!ctx || !arena || (!groups && n > 0)) return JXLH_ERR_INVALID_ARGUMENT;
+  if (!ctx || !arena || (!(sq ? (const void*)sq->groups : (const void*)groups) && n > 0)) return JXLH_ERR_INVALID_ARGUMENT;
   if (!ctx->in_frame || !ctx->modular) return JXLH_ERR_BAD_STATE;
   const FrameDev& f = ctx->fd;
   if (f.subsampled) {
@@ -315,7 +471,7 @@ jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
   d.stride = f.plane_stride;
   d.frame = true;
   // the palettes' bit depth is the samples' (a palette on 32-bit float samples is refused: no bit depth of 1..31)
-  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, depth & 0xffu, d, first_bad, general, wp)) return st;
+  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, depth & 0xffu, d, first_bad, general, wp, sq)) return st;
   ctx->frame.mod_format = sample_format;
   if (wait) JXLH_SYNC(ctx);
   return JXLH_OK;
@@ -323,9 +479,10 @@ jxlh_status frame_set_groups(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
 
 jxlh_status stage_transforms(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples, const jxlh_local_group* groups,
                              size_t n, uint32_t bit_depth, int32_t* const out[], uint32_t n_out, uint32_t out_w,
-                             uint32_t out_h, size_t out_stride, size_t* first_bad, bool general, const jxlh_wp_header* wp) {
+                             uint32_t out_h, size_t out_stride, size_t* first_bad, bool general, const jxlh_wp_header* wp,
+                             const SqueezeIn* sq = nullptr) {
   JXLH_ON_DEVICE(ctx);
-  if (!ctx || !arena || (!groups && n > 0) || !out || n_out < 1 || n_out > JXLH_LOCAL_MAX_CHANNELS || out_stride < out_w)
+  if (!ctx || !arena || (!(sq ? (const void*)sq->groups : (const void*)groups) && n > 0) || !out || n_out < 1 || n_out > JXLH_LOCAL_MAX_CHANNELS || out_stride < out_w)
     return JXLH_ERR_INVALID_ARGUMENT;
   LocalDest d;
   for (uint32_t c = 0; c < n_out; c++) {
@@ -339,7 +496,7 @@ jxlh_status stage_transforms(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena
   d.n_out = n_out;
   d.w = out_w, d.h = out_h;
   d.stride = out_stride;
-  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, bit_depth, d, first_bad, general, wp)) return st;
+  if (jxlh_status st = local_enqueue(ctx, arena, arena_samples, groups, n, bit_depth, d, first_bad, general, wp, sq)) return st;
   JXLH_SYNC(ctx);
   return JXLH_OK;
 }
@@ -419,6 +576,63 @@ jxlh_status jxlh_frame_set_modular_groups_general_async(jxlh_ctx* ctx, const int
                                                         const jxlh_local_group* groups, const jxlh_wp_header* wp, size_t n,
                                                         uint32_t sample_format, size_t* first_bad) {
   return frame_set_groups(ctx, arena, arena_samples, groups, n, sample_format, first_bad, false, true, wp);
+}
+
+jxlh_status jxlh_modular_local_default_squeeze(const uint32_t* w, const uint32_t* h, uint32_t n, uint32_t n_meta,
+                                               jxlh_squeeze_params* params, uint32_t cap, uint32_t* n_params) {
+  if (!w || !h || !n_params || n < 1 || n > JXLH_LOCAL_MAX_CHANNELS || (!params && cap > 0)) return JXLH_ERR_INVALID_ARGUMENT;
+  *n_params = jxlh::default_squeeze_list(w, h, n, n_meta, params, cap);
+  return *n_params > cap ? JXLH_ERR_INVALID_ARGUMENT : JXLH_OK;
+}
+
+jxlh_status jxlh_modular_local_lower_squeeze(const jxlh_local_squeeze_group* groups, size_t n,
+                                             const jxlh_local_coded_channel* coded, size_t n_coded,
+                                             const jxlh_squeeze_params* params, size_t n_params, const jxlh_wp_header* wp,
+                                             uint32_t bit_depth, uint64_t arena_samples,
+                                             jxlh_local_squeeze_program* programs, size_t* first_bad) {
+  if (!groups && n > 0) return JXLH_ERR_INVALID_ARGUMENT;
+  // two passes, so that a refused call leaves `programs` as it was
+  for (int pass = 0; pass < (programs ? 2 : 1); pass++) {
+    for (size_t g = 0; g < n; g++) {
+      if (jxlh_status st = jxlh::local_lower_squeeze_group(groups[g], coded, n_coded, params, n_params, wp ? &wp[g] : nullptr,
+                                                           bit_depth, arena_samples, pass ? &programs[g] : nullptr, nullptr)) {
+        if (first_bad) *first_bad = g;
+        return st;
+      }
+    }
+  }
+  return JXLH_OK;
+}
+
+jxlh_status jxlh_modular_local_transforms_squeeze(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                  const jxlh_local_squeeze_group* groups, size_t n,
+                                                  const jxlh_local_coded_channel* coded, size_t n_coded,
+                                                  const jxlh_squeeze_params* params, size_t n_params,
+                                                  const jxlh_wp_header* wp, uint32_t bit_depth, int32_t* const out[],
+                                                  uint32_t n_out, uint32_t out_w, uint32_t out_h, size_t out_stride,
+                                                  size_t* first_bad) {
+  const jxlh_host::SqueezeIn sq{groups, coded, n_coded, params, n_params};
+  return jxlh_host::stage_transforms(ctx, arena, arena_samples, nullptr, n, bit_depth, out, n_out, out_w, out_h, out_stride,
+                                     first_bad, true, wp, &sq);
+}
+
+jxlh_status jxlh_frame_set_modular_groups_squeeze(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                  const jxlh_local_squeeze_group* groups, size_t n,
+                                                  const jxlh_local_coded_channel* coded, size_t n_coded,
+                                                  const jxlh_squeeze_params* params, size_t n_params,
+                                                  const jxlh_wp_header* wp, uint32_t sample_format, size_t* first_bad) {
+  const jxlh_host::SqueezeIn sq{groups, coded, n_coded, params, n_params};
+  return jxlh_host::frame_set_groups(ctx, arena, arena_samples, nullptr, n, sample_format, first_bad, true, true, wp, &sq);
+}
+
+jxlh_status jxlh_frame_set_modular_groups_squeeze_async(jxlh_ctx* ctx, const int32_t* arena, uint64_t arena_samples,
+                                                        const jxlh_local_squeeze_group* groups, size_t n,
+                                                        const jxlh_local_coded_channel* coded, size_t n_coded,
+                                                        const jxlh_squeeze_params* params, size_t n_params,
+                                                        const jxlh_wp_header* wp, uint32_t sample_format,
+                                                        size_t* first_bad) {
+  const jxlh_host::SqueezeIn sq{groups, coded, n_coded, params, n_params};
+  return jxlh_host::frame_set_groups(ctx, arena, arena_samples, nullptr, n, sample_format, first_bad, false, true, wp, &sq);
 }
 
 }  // extern "C"

@@ -480,6 +480,39 @@ struct LpLaunch {
 };
 void launch_modular_local_palette(hipStream_t s, const LpLaunch& a);
 void launch_modular_local_phase(hipStream_t s, const LpLaunch& a);
+// k_modular_local_squeeze.hip: the inverse squeeze of a batch of groups (jxl_hip_local_squeeze.h).  A CHAIN is one image
+// channel of one group: its base plane and, level by level, a residual plane, all in the arena.  Levels [0, n_lds) run in
+// the LDS launch (one workgroup per chain), level n_lds + k in streamed launch k (64 lines per workgroup).  Level i's
+// output is the destination rect when it is the chain's last, else the chain's scratch plane i & 1, rows out_w apart.
+constexpr int kLsTile = 128;    // the LDS launch: largest plane side (= JXLH_SQL_MAX: squeeze_levels_fit decides)
+constexpr int kLsLevels = 16;   // = JXLH_LOCAL_SQUEEZE_MAX_LEVELS
+constexpr int kLsLines = 64;    // streamed launches: lines per workgroup, a lane each
+struct LsLevelDev {
+  uint32_t horizontal, out_w, out_h;
+  uint32_t res_stride;
+  uint64_t res_off;  // samples into the arena; never read when the level has no residuals
+};
+struct LsChainDev {
+  uint32_t x0, y0;   // the group's rect in the destination planes
+  uint32_t slot;     // the destination plane
+  uint32_t n_levels, n_lds;
+  uint32_t base_w, base_h, base_stride;
+  uint64_t base_off;        // samples into the arena
+  uint64_t scratch_off[2];  // samples into the scratch block
+  LsLevelDev lv[kLsLevels];
+};
+struct LsLaunch {
+  const int32_t* arena;
+  int32_t* scratch;
+  int32_t* out[4];
+  size_t out_stride;  // samples
+  const LsChainDev* chains;
+  const LocalItem* items;  // LDS launch: (chain, 0); streamed launch: (chain, first line)
+  uint32_t n_items;
+  uint32_t step;           // streamed launch k: the item's chain runs its level n_lds + k
+};
+void launch_modular_local_squeeze_lds(hipStream_t s, const LsLaunch& a);
+void launch_modular_local_squeeze_level(hipStream_t s, const LsLaunch& a);
 void launch_fill_f32(hipStream_t s, float* p, size_t n, float v);
 void launch_modular_xyb_to_f32(hipStream_t s, const int32_t* y, const int32_t* x, const int32_t* b, size_t n,
                                const float scale[3], float* ox, float* oy, float* ob);

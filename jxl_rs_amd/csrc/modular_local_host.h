@@ -55,9 +55,11 @@ inline bool wp_header_ok(const jxlh_wp_header& h) {
 // general == false: the lowering of jxlh_modular_local_lower, which refuses delta / predicted palettes.
 // general == true: the lowering of jxlh_modular_local_lower_general (jxl_hip_local_palette.h); `wp` is the group's own
 // header, or null.  gprog receives what prog cannot say: per op num_deltas, predictor and the phase.
+// check_coded == false (a squeeze stands behind the steps, modular_local_squeeze_host.h): what is left of the list is not
+// what the group brings, so n_coded, coded_offset and coded_stride are not read.
 inline jxlh_status local_lower_core(const jxlh_local_group& g, uint32_t bit_depth, uint64_t arena_samples, bool general,
                                     const jxlh_wp_header* wp, jxlh_local_program* prog,
-                                    jxlh_local_general_program* gprog, const char** why) {
+                                    jxlh_local_general_program* gprog, const char** why, bool check_coded = true) {
   const char* dummy;
   if (!why) why = &dummy;
   auto refuse = [&](jxlh_status st, const char* w) {
@@ -66,8 +68,8 @@ inline jxlh_status local_lower_core(const jxlh_local_group& g, uint32_t bit_dept
   };
   if (g.n_channels < 1 || g.n_channels > JXLH_LOCAL_MAX_CHANNELS) return refuse(JXLH_ERR_INVALID_ARGUMENT, "n_channels outside 1..4");
   if (g.n_steps > JXLH_LOCAL_MAX_STEPS) return refuse(JXLH_ERR_INVALID_ARGUMENT, "n_steps above 4");
-  if (g.n_coded < 1 || g.n_coded > JXLH_LOCAL_MAX_CHANNELS) return refuse(JXLH_ERR_INVALID_ARGUMENT, "n_coded outside 1..4");
-  if (g.coded_stride < g.w) return refuse(JXLH_ERR_INVALID_ARGUMENT, "coded_stride below w");
+  if (check_coded && (g.n_coded < 1 || g.n_coded > JXLH_LOCAL_MAX_CHANNELS)) return refuse(JXLH_ERR_INVALID_ARGUMENT, "n_coded outside 1..4");
+  if (check_coded && g.coded_stride < g.w) return refuse(JXLH_ERR_INVALID_ARGUMENT, "coded_stride below w");
   // the channel list: slot of an image channel, -1 for a palette's meta channel
   int list[JXLH_LOCAL_MAX_CHANNELS + JXLH_LOCAL_MAX_STEPS];
   uint32_t len = g.n_channels;
@@ -136,8 +138,8 @@ inline jxlh_status local_lower_core(const jxlh_local_group& g, uint32_t bit_dept
   uint32_t coded_slot[JXLH_LOCAL_MAX_CHANNELS] = {}, n_coded = 0;
   for (uint32_t k = 0; k < len; k++)
     if (list[k] >= 0) coded_slot[n_coded++] = (uint32_t)list[k];
-  if (n_coded != g.n_coded) return refuse(JXLH_ERR_INVALID_ARGUMENT, "n_coded is not what the steps leave");
-  if (g.w > 0 && g.h > 0) {
+  if (check_coded && n_coded != g.n_coded) return refuse(JXLH_ERR_INVALID_ARGUMENT, "n_coded is not what the steps leave");
+  if (check_coded && g.w > 0 && g.h > 0) {
     const uint64_t extent = (uint64_t)(g.h - 1) * g.coded_stride + g.w;
     for (uint32_t k = 0; k < n_coded; k++)
       if (!local_fits(g.coded_offset[k], extent, arena_samples)) return refuse(JXLH_ERR_INVALID_ARGUMENT, "coded channel beyond the arena");

@@ -273,6 +273,93 @@ def modular_local_lower_general(groups, bit_depth, arena_samples, wp=None, n=Non
     return st, progs, (None if bad.value == 2 ** 64 - 1 else bad.value)
 
 
+def local_squeeze(params=()):
+    """the squeeze of a group's transform list, for pack_local_squeeze_groups; params: (horizontal, in_place, begin_c,
+    num_c) tuples -- none: default_squeeze"""
+    return [tuple(int(v) for v in p) for p in params]
+
+
+def default_squeeze(sizes, n_meta=0):
+    """jxlh_modular_local_default_squeeze: the default list, as (horizontal, in_place, begin_c, num_c) tuples, for n_meta
+    palette meta channels followed by image channels of sizes[i] = (w, h)"""
+    L = _lib()
+    w = (C.c_uint32 * len(sizes))(*[int(s[0]) for s in sizes])
+    h = (C.c_uint32 * len(sizes))(*[int(s[1]) for s in sizes])
+    out = (SqueezeParams * 80)()
+    n = C.c_uint32(0)
+    st = L.jxlh_modular_local_default_squeeze(w, h, len(sizes), n_meta, out, 80, C.byref(n))
+    if st != OK:
+        raise JxlHipError(st, "jxlh_modular_local_default_squeeze")
+    return [(p.horizontal, p.in_place, p.begin_c, p.num_c) for p in list(out)[:n.value]]
+
+
+def pack_local_squeeze_groups(specs, align=4, skew=0, stride_pad=0, fill=0):
+    """pack_local_groups for the squeeze calls.  specs: dicts with x0, y0, w, h, n_channels, steps (local_rct /
+    local_palette in front of the squeeze), squeeze (None: the group has none; else local_squeeze(...)) and coded: the
+    2-D i32 channels as decoded, in list order, each of its own shape (a zero side: no samples).  Returns (arena, batch)
+    with batch = (groups, coded, params): a (LocalSqueezeGroup * n), a (LocalCodedChannel * m) and a (SqueezeParams * k)
+    array."""
+    groups = (LocalSqueezeGroup * max(len(specs), 1))()
+    n_coded = sum(len(sp["coded"]) for sp in specs)
+    n_params = sum(len(sp["squeeze"] or ()) for sp in specs)
+    coded = (LocalCodedChannel * max(n_coded, 1))()
+    params = (SqueezeParams * max(n_params, 1))()
+    blocks, pos, ci, pi = [], 0, 0, 0
+
+    def place(a):
+        nonlocal pos
+        pos = -(-pos // align) * align + skew
+        at = pos
+        blocks.append((at, a))
+        pos += a.size
+        return at
+
+    for g, sp in zip(groups, specs):
+        g.x0, g.y0, g.w, g.h = int(sp["x0"]), int(sp["y0"]), int(sp["w"]), int(sp["h"])
+        g.n_channels, g.n_steps = int(sp["n_channels"]), len(sp["steps"])
+        if g.n_steps > LOCAL_MAX_STEPS:
+            raise ValueError("a group holds at most 4 steps")
+        for st, d in zip(g.steps, sp["steps"]):
+            st.kind, st.begin_c, st.rct_type = d["kind"], d["begin_c"], d.get("rct_type", 0)
+            if d["kind"] == LOCAL_PALETTE:
+                st.num_c, st.num_colors, st.num_deltas, st.predictor = d["num_c"], d["num_colors"], d["num_deltas"], d["predictor"]
+                st.palette_offset = place(d["table"].reshape(-1))
+        sq = sp.get("squeeze")
+        g.has_squeeze = 0 if sq is None else 1
+        g.squeeze_pos = int(sp.get("squeeze_pos", g.n_steps)) if g.has_squeeze else 0
+        g.params_first, g.n_params = pi, len(sq or ())
+        for q in sq or ():
+            params[pi].horizontal, params[pi].in_place, params[pi].begin_c, params[pi].num_c = q
+            pi += 1
+        g.coded_first, g.n_coded = ci, len(sp["coded"])
+        for c in sp["coded"]:
+            c = np.asarray(c, dtype=np.int32)
+            h, w = c.shape
+            stride = -(-w // align) * align + stride_pad
+            coded[ci].w, coded[ci].h, coded[ci].stride = w, h, stride
+            if w > 0 and h > 0:
+                rows = np.full((h, stride), fill, dtype=np.int32)
+                rows[:, :w] = c
+                coded[ci].offset = place(rows.reshape(-1))
+            ci += 1
+    arena = np.full(max(pos, 1), fill, dtype=np.int32)
+    for at, a in blocks:
+        arena[at:at + a.size] = a
+    return arena, (groups, coded, params)
+
+
+def modular_local_lower_squeeze(batch, bit_depth, arena_samples, wp=None, n=None):
+    """jxlh_modular_local_lower_squeeze: (status, programs, first_bad); batch: pack_local_squeeze_groups'"""
+    L = _lib()
+    groups, coded, params = batch
+    n = len(groups) if n is None else n
+    progs = (LocalSqueezeProgram * max(n, 1))()
+    bad = C.c_size_t(2 ** 64 - 1)
+    st = L.jxlh_modular_local_lower_squeeze(groups, n, coded, len(coded), params, len(params), wp_headers(wp), bit_depth,
+                                            arena_samples, progs, C.byref(bad))
+    return st, progs, (None if bad.value == 2 ** 64 - 1 else bad.value)
+
+
 class JxlHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -816,6 +903,34 @@ class Context:
         self._chk(self.L.jxlh_modular_local_transforms_general(self._ctx, _addr(arena), arena_samples, groups, wp_headers(wp), n,
                                                                bit_depth, ptrs, len(out), out_w, out_h, out_stride, None),
                   "modular_local_transforms_general")
+
+    def set_modular_groups_squeeze(self, arena, batch, sample_format, wp=None, n=None, arena_samples=None, wait=True):
+        """jxlh_frame_set_modular_groups_squeeze[_async]: set_modular_groups_general for groups with a local squeeze;
+        batch: (groups, coded, params) of pack_local_squeeze_groups"""
+        groups, coded, params = batch
+        n = len(groups) if n is None else n
+        if not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+            if not wait:
+                self._keep["local_arena"] = arena
+        fn = self.L.jxlh_frame_set_modular_groups_squeeze if wait else self.L.jxlh_frame_set_modular_groups_squeeze_async
+        self._chk(fn(self._ctx, _addr(arena), arena_samples, groups, n, coded, len(coded), params, len(params), wp_headers(wp),
+                     sample_format, None), "set_modular_groups_squeeze")
+
+    def modular_local_transforms_squeeze(self, arena, batch, bit_depth, out, out_w, out_h, out_stride, wp=None, n=None,
+                                         arena_samples=None):
+        """jxlh_modular_local_transforms_squeeze: modular_local_transforms_general for groups with a local squeeze"""
+        groups, coded, params = batch
+        n = len(groups) if n is None else n
+        if not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+        ptrs = (C.c_void_p * len(out))(*[_addr(o) for o in out])
+        self._chk(self.L.jxlh_modular_local_transforms_squeeze(self._ctx, _addr(arena), arena_samples, groups, n, coded, len(coded),
+                                                               params, len(params), wp_headers(wp), bit_depth, ptrs, len(out),
+                                                               out_w, out_h, out_stride, None),
+                  "modular_local_transforms_squeeze")
 
     def set_dequant_tables(self, tables):
         tabs = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]

@@ -15,7 +15,7 @@ What the interface offered before, on the same data, same session:
   per_group       1024 x (jxlh_rct on the group's contiguous buffer + one rect call)
 Two contexts alternate between repetitions.
 
-  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general]
+  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general | --squeeze]
 --kernel-only: a few launches of the rct case and nothing else, for a profiler run of its own.
 
 --general: the group-local palettes with delta entries (jxlh_frame_set_modular_groups_general, k_modular_local_palette.hip)
@@ -30,7 +30,17 @@ against
                         this arithmetic before
   mix16_lookup          k_modular_local on the mix16 batch with the delta rects replaced by look-up palettes: the
                         difference to mix16 is what the general groups cost
-With --kernel-only: a few launches of delta_p5 and nothing else."""
+With --kernel-only: a few launches of delta_p5 and nothing else.
+
+--squeeze: group-local squeezes (jxlh_frame_set_modular_groups_squeeze_async, k_modular_local_squeeze.hip) on the same
+frame: 3 channels, every 256 x 256 rect a default squeeze (the 4:2:0-preview steps included) of its own coded channels,
+device-resident arena; median, min and max over `reps` of the mean of `steps`:
+  squeeze     kernel times per label with the launches per call (the LDS launch, the streamed level launches), the _async
+              call on the host clock, and the bytes moved: arena read, planes written, scratch written and read back
+  per_group   what the interface offered before for such a frame: per group one jxlh_unsqueeze_chain (three planes of one
+              geometry: the default squeeze without the preview steps) plus one rect intake
+              (jxlh_frame_set_modular_channels from device memory); kernels summed over all labels, and the host clock
+With --kernel-only: a few calls of the squeeze case and nothing else."""
 import argparse
 import json
 import os
@@ -49,9 +59,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--general", action="store_true")
+    ap.add_argument("--squeeze", action="store_true")
     a = ap.parse_args()
     if a.general:
         return general(a)
+    if a.squeeze:
+        return squeeze(a)
     import numpy as np
     import jxl_rs_amd
     from jxl_rs_amd import lib
@@ -242,6 +255,105 @@ def general(a):
             print(json.dumps(row), flush=True)
         for d in (idx, pal, out):
             d.free()
+    for c in ctxs:
+        c.close()
+
+
+def squeeze(a):
+    import ctypes as C
+    import numpy as np
+    import jxl_rs_amd
+    from jxl_rs_amd import lib
+    from jxl_rs_amd.modular import ModularChain
+    n, g = a.size, 256
+    rng = np.random.default_rng(3)
+    # one group's coded channels under the default squeeze, as the lowering derives them; every group gets a copy of its own
+    one = {"x0": 0, "y0": 0, "w": g, "h": g, "n_channels": 3, "steps": [], "squeeze": lib.local_squeeze(), "coded": []}
+    sizes = [(g, g)] * 3
+    for horizontal, in_place, begin_c, num_c in lib.default_squeeze(sizes):
+        at0 = begin_c + num_c if in_place else len(sizes)
+        for ic in range(num_c):
+            w, h = sizes[begin_c + ic]
+            sizes[begin_c + ic] = ((w + 1) // 2, h) if horizontal else (w, (h + 1) // 2)
+            sizes.insert(at0 + ic, (w // 2, h) if horizontal else (w, h // 2))
+    one["coded"] = [rng.integers(-40, 40, size=(h, w)).astype(np.int32) for w, h in sizes]
+    arena_one, (g1, c1, _) = lib.pack_local_squeeze_groups([one])
+    m, per = len(sizes), -(-arena_one.size // 64) * 64
+    rects = [(x, y) for y in range(0, n, g) for x in range(0, n, g)]
+    arena = np.zeros(per * len(rects), dtype=np.int32)
+    groups = (lib.LocalSqueezeGroup * len(rects))()
+    coded = (lib.LocalCodedChannel * (m * len(rects)))()
+    params = (lib.SqueezeParams * 1)()
+    for k, (x, y) in enumerate(rects):
+        arena[k * per:k * per + arena_one.size] = arena_one
+        C.memmove(C.byref(groups[k]), C.byref(g1[0]), C.sizeof(lib.LocalSqueezeGroup))
+        groups[k].x0, groups[k].y0, groups[k].coded_first = x, y, k * m
+        for j in range(m):
+            C.memmove(C.byref(coded[k * m + j]), C.byref(c1[j]), C.sizeof(lib.LocalCodedChannel))
+            coded[k * m + j].offset += k * per
+    batch = (groups, coded, params)
+    st, progs, bad = lib.modular_local_lower_squeeze(batch, 8, arena.size)
+    assert st == lib.OK, (st, bad)
+    scratch = 0  # samples written to scratch and read back: every level's output from the LDS launch's last on, but the chain's last
+    for ch in list(progs[0].chains)[:3]:
+        lv = list(ch.levels)[:ch.n_levels]
+        n_lds = sum(1 for q in lv if q.out_w <= 128 and q.out_h <= 128)
+        scratch += sum(q.out_w * q.out_h for q in lv[max(n_lds - 1, 0):-1])
+    ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(2)]
+    p = ctxs[0].default_params(n, n)
+    p.gab, p.epf_iters = 0, 0
+    for c in ctxs:
+        c.modular_frame_begin(p)
+    dev = lib.DeviceArray(arena)
+
+    def timed(c, call, steps):
+        c.kernel_timing_reset()
+        c.kernel_timing(True)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            call(c)
+        c.sync()
+        host = (time.perf_counter() - t0) * 1e3 / steps
+        kt = c.kernel_times()
+        c.kernel_timing(False)
+        return host, {k: ms / steps for k, (ms, _) in kt.items()}, {k: cnt // steps for k, (_, cnt) in kt.items()}
+
+    def measure(call, steps):
+        for c in ctxs:
+            call(c)
+            c.sync()
+        runs = [timed(ctxs[r % 2], call, steps) for r in range(a.reps)]
+        row = {"launches_per_call": runs[0][2], "call_ms": [statistics.median([r[0] for r in runs]), min(r[0] for r in runs), max(r[0] for r in runs)]}
+        for k in sorted(runs[0][1]) + ["total"]:
+            v = [sum(r[1].values()) if k == "total" else r[1][k] for r in runs]
+            row[k + "_ms"] = [statistics.median(v), min(v), max(v)]
+        return row
+
+    launch = lambda c: c.set_modular_groups_squeeze(dev, batch, 8, n=len(rects), arena_samples=arena.size, wait=False)
+    if a.kernel_only:
+        for _ in range(3):
+            launch(ctxs[0])
+        ctxs[0].sync()
+    else:
+        row = {"case": "squeeze", "frame": f"{n}x{n}", "rects": len(rects), "median_min_max": True,
+               "bytes": {"arena_read": 4 * sum(w * h for w, h in sizes) * len(rects), "planes_written": 12 * g * g * len(rects),
+                         "scratch_written_and_read": 8 * scratch * len(rects)}}
+        row.update(measure(launch, a.steps))
+        print(json.dumps(row), flush=True)
+        chains = [ModularChain(c, g, g, seed=5, rct=None) for c in ctxs]
+
+        def per_group(c):
+            ch = chains[ctxs.index(c)]
+            for x, y in rects:
+                ch.run_chain()
+                c.set_modular_channels(*[d.ptr for d in ch.d_out], 8, x0=x, y0=y, w=g, h=g, stride=g)
+
+        row = {"case": "per_group", "frame": f"{n}x{n}", "rects": len(rects), "median_min_max": True}
+        row.update(measure(per_group, max(1, a.steps // 5)))
+        print(json.dumps(row), flush=True)
+        for ch in chains:
+            ch.free()
+    dev.free()
     for c in ctxs:
         c.close()
 

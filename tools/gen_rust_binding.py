@@ -29,6 +29,8 @@ OUT_REPAINT = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "repa
 # ... and a header that includes jxl_hip.h rather than being included by it
 LOCAL_PALETTE_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_palette.h")
 OUT_LOCAL_PALETTE = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_palette.rs")
+LOCAL_SQUEEZE_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_squeeze.h")
+OUT_LOCAL_SQUEEZE = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_squeeze.rs")
 
 SCALARS = {"uint8_t": "u8", "int8_t": "i8", "uint16_t": "u16", "int16_t": "i16", "uint32_t": "u32", "int32_t": "i32",
            "uint64_t": "u64", "int64_t": "i64", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -171,6 +173,8 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod repaint;")
     w("// include/jxl_hip_local_palette.h (... src/local_palette.rs)")
     w("pub mod local_palette;")
+    w("// include/jxl_hip_local_squeeze.h (... src/local_squeeze.rs)")
+    w("pub mod local_squeeze;")
     return "\n".join(out) + "\n"
 
 
@@ -235,10 +239,16 @@ def generate_local_palette():
     return emit_extension(os.path.basename(LOCAL_PALETTE_HEADER), *parse_header(open(LOCAL_PALETTE_HEADER).read()))
 
 
+def generate_local_squeeze():
+    return emit_extension(os.path.basename(LOCAL_SQUEEZE_HEADER), *parse_header(open(LOCAL_SQUEEZE_HEADER).read()),
+                          uses=("local_palette",))
+
+
 def main():
     for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
                       (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects()),
-                      (OUT_REPAINT, generate_repaint()), (OUT_LOCAL_PALETTE, generate_local_palette())):
+                      (OUT_REPAINT, generate_repaint()), (OUT_LOCAL_PALETTE, generate_local_palette()),
+                      (OUT_LOCAL_SQUEEZE, generate_local_squeeze())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
             if cur != text:
