@@ -15,6 +15,7 @@
 //    (16 KiB: eight workgroups of 256 threads, the CU's full 32 waves, need 128 of its 160 KiB); a larger palette is read
 //    from global memory.  Implicit and negative indices never touch the table (palette_value).
 #include "jxlh_internal.h"
+#include "modular_local_desc.h"
 #include "modular_local_device.h"  // Slots, apply_rct, apply_palette, load_some / store_some
 #include "modular_ops_device.h"
 

@@ -27,6 +27,7 @@
 // k_modular_local_phase: k_modular_local's streaming pass for a group whose channels are, between phases, partly in the
 // arena, partly in its destination rect and partly (an index channel its palette is about to overwrite) in scratch.
 #include "jxlh_internal.h"
+#include "modular_local_desc.h"
 #include "modular_local_device.h"
 #include "modular_ops_device.h"
 #include "modular_predict_device.h"

@@ -9,6 +9,7 @@
 //                                  vertical steps are coalesced (lanes = adjacent columns), horizontal ones walk rows.
 // The arena is read with 4-byte accesses at any alignment.  A chain's last level writes the group's rect of its
 // destination plane, any other the chain's own scratch plane; nothing else is written.  No workgroup waits on another.
+#include "modular_local_desc.h"
 #include "squeeze_device.h"
 #include "squeeze_plan.h"  // JXLH_SQL_MAX: the host's fit rule is squeeze_levels_fit
 

@@ -15,7 +15,7 @@ What the interface offered before, on the same data, same session:
   per_group       1024 x (jxlh_rct on the group's contiguous buffer + one rect call)
 Two contexts alternate between repetitions.
 
-  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general | --squeeze]
+  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general | --squeeze | --host-side]
 --kernel-only: a few launches of the rct case and nothing else, for a profiler run of its own.
 
 --general: the group-local palettes with delta entries (jxlh_frame_set_modular_groups_general, k_modular_local_palette.hip)
@@ -40,7 +40,17 @@ device-resident arena; median, min and max over `reps` of the mean of `steps`:
   per_group   what the interface offered before for such a frame: per group one jxlh_unsqueeze_chain (three planes of one
               geometry: the default squeeze without the preview steps) plus one rect intake
               (jxlh_frame_set_modular_channels from device memory); kernels summed over all labels, and the host clock
-With --kernel-only: a few calls of the squeeze case and nothing else."""
+With --kernel-only: a few calls of the squeeze case and nothing else.
+
+--host-side [--only plain|mix16|squeeze]: what a 1024-rect batch costs on the host, one context, event timers off: rct of
+the first table (plain), mix16 of --general, squeeze of --squeeze.  Per case one JSON line, median, min and max over
+`reps` of the mean of `steps` calls (--steps 20 --reps 7 for the recorded table):
+  enqueue_ms              the _async call until it returns: lowering, planning, the block, one copy, the launches enqueued
+  call_plus_sync_ms       the call and one synchronise
+  kernels_ms              the k_modular_local* event timers, in a pass of their own
+  wall_minus_kernels_ms   median call_plus_sync_ms - median kernels_ms
+  minor_faults_per_call   page faults of the process inside the timed calls (getrusage): memory the allocator hands
+                          back and takes again on every call shows here"""
 import argparse
 import json
 import os
@@ -60,7 +70,11 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--general", action="store_true")
     ap.add_argument("--squeeze", action="store_true")
+    ap.add_argument("--host-side", action="store_true")
+    ap.add_argument("--only", choices=["plain", "mix16", "squeeze"])
     a = ap.parse_args()
+    if a.host_side:
+        return host_side(a)
     if a.general:
         return general(a)
     if a.squeeze:
@@ -259,14 +273,10 @@ def general(a):
         c.close()
 
 
-def squeeze(a):
+def _squeeze_batch(lib, rng, n, g):
+    """every g x g rect of an n x n frame a default squeeze of three channels -> (arena, batch, rects, coded sizes)"""
     import ctypes as C
     import numpy as np
-    import jxl_rs_amd
-    from jxl_rs_amd import lib
-    from jxl_rs_amd.modular import ModularChain
-    n, g = a.size, 256
-    rng = np.random.default_rng(3)
     # one group's coded channels under the default squeeze, as the lowering derives them; every group gets a copy of its own
     one = {"x0": 0, "y0": 0, "w": g, "h": g, "n_channels": 3, "steps": [], "squeeze": lib.local_squeeze(), "coded": []}
     sizes = [(g, g)] * 3
@@ -292,6 +302,17 @@ def squeeze(a):
             C.memmove(C.byref(coded[k * m + j]), C.byref(c1[j]), C.sizeof(lib.LocalCodedChannel))
             coded[k * m + j].offset += k * per
     batch = (groups, coded, params)
+    return arena, batch, rects, sizes
+
+
+def squeeze(a):
+    import numpy as np
+    import jxl_rs_amd
+    from jxl_rs_amd import lib
+    from jxl_rs_amd.modular import ModularChain
+    n, g = a.size, 256
+    rng = np.random.default_rng(3)
+    arena, batch, rects, sizes = _squeeze_batch(lib, rng, n, g)
     st, progs, bad = lib.modular_local_lower_squeeze(batch, 8, arena.size)
     assert st == lib.OK, (st, bad)
     scratch = 0  # samples written to scratch and read back: every level's output from the LDS launch's last on, but the chain's last
@@ -356,6 +377,82 @@ def squeeze(a):
     dev.free()
     for c in ctxs:
         c.close()
+
+
+def host_side(a):
+    import resource
+    import numpy as np
+    import jxl_rs_amd
+    from jxl_rs_amd import lib
+    n, g = a.size, 256
+    rng = np.random.default_rng(1)
+    rects = [(x, y) for y in range(0, n, g) for x in range(0, n, g)]
+    chan = [rng.integers(0, 64, size=(g, g)).astype(np.int32) for _ in range(3)]
+    table = rng.integers(0, 256, size=(3, 16)).astype(np.int32)
+    table[:, :5] = rng.integers(-12, 13, size=(3, 5))
+    index = rng.integers(0, 16, size=(g, g)).astype(np.int32)
+    ctx = jxl_rs_amd.Context(0, 1)
+    p = ctx.default_params(n, n)
+    p.gab, p.epf_iters = 0, 0
+    ctx.modular_frame_begin(p)
+
+    def groups_case(kind):
+        sp = []
+        for k, (x, y) in enumerate(rects):
+            pal = kind == "mix16" and k % 16 == 0
+            steps = [lib.local_palette(0, 3, table, 5, 5)] if pal else [lib.local_rct(0, k % 42)]
+            sp.append({"x0": x, "y0": y, "n_channels": 3, "steps": steps, "coded": [index] if pal else chan})
+        arena, groups = lib.pack_local_groups(sp)
+        dev = lib.DeviceArray(arena)
+        if kind == "plain":
+            return dev, lambda: ctx.set_modular_groups(dev, groups, 8, n=len(sp), arena_samples=arena.size, wait=False)
+        wp = lib.wp_headers([(16, 10, 7, 7, 7, 0, 0, 13, 12, 12, 12)] * len(sp))
+        return dev, lambda: ctx.set_modular_groups_general(dev, groups, 8, wp=wp, n=len(sp), arena_samples=arena.size, wait=False)
+
+    def squeeze_case(kind):
+        arena, batch, _, _ = _squeeze_batch(lib, rng, n, g)
+        dev = lib.DeviceArray(arena)
+        return dev, lambda: ctx.set_modular_groups_squeeze(dev, batch, 8, n=len(rects), arena_samples=arena.size, wait=False)
+
+    def mmm(v):
+        return [round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)]
+
+    for kind, make in (("plain", groups_case), ("mix16", groups_case), ("squeeze", squeeze_case)):
+        if a.only and a.only != kind:
+            continue
+        dev, call = make(kind)
+        for _ in range(5):
+            call()
+            ctx.sync()
+        enq, wall, kern, faults = [], [], [], []
+        for _ in range(a.reps):
+            e = w = 0.0
+            f0 = resource.getrusage(resource.RUSAGE_SELF).ru_minflt
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                call()
+                t1 = time.perf_counter()
+                ctx.sync()
+                e += t1 - t0
+                w += time.perf_counter() - t0
+            faults.append((resource.getrusage(resource.RUSAGE_SELF).ru_minflt - f0) / a.steps)
+            enq.append(e * 1e3 / a.steps)
+            wall.append(w * 1e3 / a.steps)
+        for _ in range(a.reps):
+            ctx.kernel_timing_reset()
+            ctx.kernel_timing(True)
+            for _ in range(a.steps):
+                call()
+            ctx.sync()
+            kt = ctx.kernel_times()
+            ctx.kernel_timing(False)
+            kern.append(sum(ms for k, (ms, _) in kt.items() if k.startswith("k_modular_local")) / a.steps)
+        print(json.dumps({"case": kind, "frame": f"{n}x{n}", "rects": len(rects), "median_min_max": True, "enqueue_ms": mmm(enq),
+                          "call_plus_sync_ms": mmm(wall), "kernels_ms": mmm(kern),
+                          "wall_minus_kernels_ms": round(statistics.median(wall) - statistics.median(kern), 4),
+                          "minor_faults_per_call": mmm(faults)}), flush=True)
+        dev.free()
+    ctx.close()
 
 
 if __name__ == "__main__":
