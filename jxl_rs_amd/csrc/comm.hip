@@ -182,27 +182,21 @@ jxlh_status comm_wait_stream(jxlh_ctx* ctx) {
 
 int comm_nranks(const jxlh_ctx* ctx) { return ctx->comm ? ctx->comm->nranks : 1; }
 
-// contiguous bands: ceil(ygroups / nranks) group rows per rank; trailing ranks may own nothing
-static void band_of(int ygroups, int nranks, int rank, int* r0, int* r1) {
-  const int per = rows_per_rank(ygroups, nranks);
-  *r0 = std::min(rank * per, ygroups);
-  *r1 = std::min((rank + 1) * per, ygroups);
-}
-int comm_rows_per_rank(const jxlh_ctx* ctx, int ygroups) { return rows_per_rank(ygroups, comm_nranks(ctx)); }
-
-// one block row (8 pixel rows) of plane c in the layout K1 just wrote: offset and length in floats
-static void block_row_span(const FrameDev& f, int by, size_t* off, size_t* count) {
-  if (f.tiled) {
-    *off = (size_t)by * f.xblocks * 64;
-    *count = (size_t)f.xblocks * 64;
-  } else {
-    *off = (size_t)by * 8 * f.plane_stride;
-    *count = 8 * f.plane_stride;
-  }
+// This rank's share of the protocol (shard_plan.h): the band, the edges to trade when the run exchanges them, and both
+// forms of the gather.  A gather passes exchange = false: the edges belong to the run.
+static ShardPlan shard_plan(const jxlh_ctx* ctx, bool exchange, size_t bytes_per_row = 0) {
+  const FrameDev& f = ctx->fd;
+  ShardIn in;
+  in.ygroups = f.ygroups, in.ysize = f.ysize, in.nranks = comm_nranks(ctx);
+  in.tiled = f.tiled != 0, in.xblocks = f.xblocks, in.plane_stride = f.plane_stride;
+  in.exchange = exchange;
+  in.result_in_tmp = stage_list(ctx).result_in_tmp();
+  in.bytes_per_row = bytes_per_row;
+  return plan_shard_rank(in, ctx->comm ? ctx->comm->rank : 0);
 }
 
 // transforms of the own band (plus recomputed halo group rows when the exchange does not apply: plan_shard)
-static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan) {
+static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan, ShardPlan* sp) {
   if (!ctx->in_frame || ctx->modular || !ctx->tables_set) return JXLH_ERR_BAD_STATE;
   if (ctx->params.upsampling > 1) return JXLH_ERR_UNSUPPORTED;  // the 5x5 upsampling window crosses bands: run whole
   const Comm* c = ctx->comm;
@@ -210,14 +204,25 @@ static jxlh_status shard_k1(jxlh_ctx* ctx, RunPlan* plan) {
   // (splines likewise: a segment crosses band edges)
   if (draws_in_place(ctx) && c->nranks > 1) return JXLH_ERR_UNSUPPORTED;
   if (jxlh_status st = patches_check_run(ctx)) return st;
-  int r0, r1;
-  band_of(ctx->fd.ygroups, c->nranks, c->rank, &r0, &r1);
-  *plan = plan_shard(run_inputs(ctx), r0, r1);
+  const ShardBand band = shard_band(ctx->fd.ygroups, ctx->fd.ysize, c->nranks, c->rank);
+  *plan = plan_shard(run_inputs(ctx), band.r0, band.r1);
   bool sparse_k1 = false;
   if (jxlh_status st = run_prologue(ctx, false, plan->tiled, &sparse_k1)) return st;
   *plan = resolve_strip(*plan, sparse_k1);
-  if (r0 >= r1) return JXLH_OK;
+  *sp = shard_plan(ctx, plan->exchange);  // (behind the prologue: it sets the layout the transforms write)
+  if (band.empty()) return JXLH_OK;
   return run_k1(ctx, *plan);
+}
+
+// the peers of an in-process call are the communicator's contexts in rank order: every loop below takes peers[i] for
+// rank i (a permuted list would gather other ranks' bands)
+static jxlh_status check_local_peers(jxlh_ctx* const peers[], int n, bool need_frame) {
+  for (int i = 0; i < n; i++) {
+    const jxlh_ctx* p = peers[i];
+    if (!p || !p->comm || p->comm->nccl || p->comm->nranks != n || p->comm->rank != i || (need_frame && !p->in_frame))
+      return JXLH_ERR_BAD_STATE;
+  }
+  return JXLH_OK;
 }
 
 }  // namespace jxlh_host
@@ -313,10 +318,9 @@ jxlh_status jxlh_comm_band(jxlh_ctx* ctx, int32_t* rank, int32_t* nranks, uint32
   if (nranks) *nranks = n;
   if (group_row0 || group_row1) {
     if (!ctx->in_frame) return JXLH_ERR_BAD_STATE;
-    int r0, r1;
-    band_of(ctx->fd.ygroups, n, r, &r0, &r1);
-    if (group_row0) *group_row0 = (uint32_t)r0;
-    if (group_row1) *group_row1 = (uint32_t)r1;
+    const ShardBand band = shard_band(ctx->fd.ygroups, ctx->fd.ysize, n, r);
+    if (group_row0) *group_row0 = (uint32_t)band.r0;
+    if (group_row1) *group_row1 = (uint32_t)band.r1;
   }
   return JXLH_OK;
 }
@@ -330,53 +334,32 @@ jxlh_status jxlh_frame_run_sharded(jxlh_ctx* ctx) {
   Comm* c = ctx->comm;
   RcclApi* api = rccl_api(nullptr);
   RunPlan plan;
-  if (jxlh_status st = shard_k1(ctx, &plan)) return st;
-  const int r0 = plan.group_row0, r1 = plan.group_row1;
+  ShardPlan sp;
+  if (jxlh_status st = shard_k1(ctx, &plan, &sp)) return st;
   const FrameDev& f = ctx->fd;
-  if (plan.exchange && c->nranks > 1) {
-    // neighbours = the adjacent NON-EMPTY bands (empty bands only trail)
-    int up0, up1, dn0, dn1;
-    const bool mine = r0 < r1;
-    bool has_up = false, has_dn = false;
-    if (mine && c->rank > 0) {
-      band_of(f.ygroups, c->nranks, c->rank - 1, &up0, &up1);
-      has_up = up0 < up1;
-    }
-    if (mine && c->rank + 1 < c->nranks) {
-      band_of(f.ygroups, c->nranks, c->rank + 1, &dn0, &dn1);
-      has_dn = dn0 < dn1;
-    }
-    if (has_up || has_dn) {
-      c->last_op = std::string("halo exchange of the band edges (ncclSend/ncclRecv with rank") + (has_up ? " " + std::to_string(c->rank - 1) : "") +
-                   (has_dn ? " " + std::to_string(c->rank + 1) : "") + ", group rows " + std::to_string(r0) + ".." + std::to_string(r1) + ")";
-      NCCLCHK(ctx, api, api->GroupStart());
-      for (int ch = 0; ch < 3; ch++) {
-        size_t off, cnt;
-        if (has_up) {  // my first block row goes up, the block row above my band comes down
-          block_row_span(f, r0 * kGroupBlocks, &off, &cnt);
-          NCCLCHK_IN_GROUP(ctx, api, api->Send(f.planes[ch] + off, cnt, ncclFloat32, c->rank - 1, c->nccl, ctx->stream));
-          block_row_span(f, r0 * kGroupBlocks - 1, &off, &cnt);
-          NCCLCHK_IN_GROUP(ctx, api, api->Recv(f.planes[ch] + off, cnt, ncclFloat32, c->rank - 1, c->nccl, ctx->stream));
-        }
-        if (has_dn) {
-          block_row_span(f, r1 * kGroupBlocks - 1, &off, &cnt);
-          NCCLCHK_IN_GROUP(ctx, api, api->Send(f.planes[ch] + off, cnt, ncclFloat32, c->rank + 1, c->nccl, ctx->stream));
-          block_row_span(f, r1 * kGroupBlocks, &off, &cnt);
-          NCCLCHK_IN_GROUP(ctx, api, api->Recv(f.planes[ch] + off, cnt, ncclFloat32, c->rank + 1, c->nccl, ctx->stream));
-        }
+  if (sp.n_edges > 0) {
+    c->last_op = "halo exchange of the band edges (ncclSend/ncclRecv with rank";
+    for (int e = 0; e < sp.n_edges; e++) c->last_op += " " + std::to_string(sp.edge[e].peer);
+    c->last_op += ", group rows " + std::to_string(sp.band.r0) + ".." + std::to_string(sp.band.r1) + ")";
+    NCCLCHK(ctx, api, api->GroupStart());
+    for (int ch = 0; ch < 3; ch++) {
+      for (int e = 0; e < sp.n_edges; e++) {  // my edge block row goes to the neighbour, the block row beyond the edge comes back
+        const ShardEdge& g = sp.edge[e];
+        NCCLCHK_IN_GROUP(ctx, api, api->Send(f.planes[ch] + g.send.off, g.send.n, ncclFloat32, g.peer, c->nccl, ctx->stream));
+        NCCLCHK_IN_GROUP(ctx, api, api->Recv(f.planes[ch] + g.recv.off, g.recv.n, ncclFloat32, g.peer, c->nccl, ctx->stream));
       }
-      NCCLCHK(ctx, api, api->GroupEnd());
     }
+    NCCLCHK(ctx, api, api->GroupEnd());
   }
-  if (r0 >= r1) return JXLH_OK;
+  if (sp.band.empty()) return JXLH_OK;
   return run_stages_rows(ctx, plan.stages, plan.y_lo, plan.y_hi, plan.whole);
 }
 
-// where a band run left the finished planes (a rank whose band is empty ran no stage: the frame's stage list says
-// where the result lives) + the geometry the read-out stages use
-static void set_band_result(jxlh_ctx* ctx) {
+// where a band run left the finished planes (a rank whose band is empty ran no stage: the plan says where the result
+// lives) + the geometry the read-out stages use
+static void set_band_result(jxlh_ctx* ctx, const ShardPlan& sp) {
   const FrameDev& f = ctx->fd;
-  for (int ch = 0; ch < 3; ch++) ctx->frame.result[ch] = stage_list(ctx).result_in_tmp() ? f.tmp[ch] : f.planes[ch];
+  for (int ch = 0; ch < 3; ch++) ctx->frame.result[ch] = sp.result_in_tmp ? f.tmp[ch] : f.planes[ch];
   ctx->res_w = f.xsize;
   ctx->res_h = f.ysize;
   ctx->res_stride = f.plane_stride;
@@ -389,13 +372,13 @@ jxlh_status jxlh_frame_allgather(jxlh_ctx* ctx) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Comm* c = ctx->comm;
   RcclApi* api = rccl_api(nullptr);
-  const FrameDev& f = ctx->fd;
-  set_band_result(ctx);
-  const size_t count = (size_t)comm_rows_per_rank(ctx, f.ygroups) * kGroupDim * f.plane_stride;
-  c->last_op = "ncclAllGather of the finished planes (" + std::to_string(count * 4) + " bytes per rank and plane)";
+  const ShardPlan sp = shard_plan(ctx, false);
+  set_band_result(ctx, sp);
+  const ShardSpan slot = sp.slot_planes;
+  c->last_op = "ncclAllGather of the finished planes (" + std::to_string(slot.n * 4) + " bytes per rank and plane)";
   NCCLCHK(ctx, api, api->GroupStart());
   for (int ch = 0; ch < 3; ch++)
-    NCCLCHK_IN_GROUP(ctx, api, api->AllGather(ctx->frame.result[ch] + (size_t)c->rank * count, ctx->frame.result[ch], count, ncclFloat32, c->nccl, ctx->stream));
+    NCCLCHK_IN_GROUP(ctx, api, api->AllGather(ctx->frame.result[ch] + slot.off, ctx->frame.result[ch], slot.n, ncclFloat32, c->nccl, ctx->stream));
   NCCLCHK(ctx, api, api->GroupEnd());
   return JXLH_OK;
 }
@@ -409,35 +392,30 @@ jxlh_status jxlh_frame_allgather_output(jxlh_ctx* ctx, const jxlh_output_desc* d
   RcclApi* api = rccl_api(nullptr);
   const FrameDev& f = ctx->fd;
   if (bytes_per_row < (size_t)f.xsize * d->channels * (d->bits / 8)) return JXLH_ERR_INVALID_ARGUMENT;
-  set_band_result(ctx);
-  int r0, r1;
-  band_of(f.ygroups, c->nranks, c->rank, &r0, &r1);
-  if (jxlh_status st = convert_band_to_output(ctx, d, (uint32_t)std::min(r0 * kGroupDim, f.ysize),
-                                              (uint32_t)std::min(r1 * kGroupDim, f.ysize), out, bytes_per_row))
-    return st;
-  const size_t count = (size_t)comm_rows_per_rank(ctx, f.ygroups) * kGroupDim * bytes_per_row;
-  c->last_op = "ncclAllGather of the converted image (" + std::to_string(count) + " bytes per rank)";
-  NCCLCHK(ctx, api, api->AllGather(static_cast<char*>(out) + (size_t)c->rank * count, out, count, ncclUint8, c->nccl, ctx->stream));
+  const ShardPlan sp = shard_plan(ctx, false, bytes_per_row);
+  set_band_result(ctx, sp);
+  if (jxlh_status st = convert_band_to_output(ctx, d, (uint32_t)sp.band.y0, (uint32_t)sp.band.y1, out, bytes_per_row)) return st;
+  const ShardSpan slot = sp.slot_image;
+  c->last_op = "ncclAllGather of the converted image (" + std::to_string(slot.n) + " bytes per rank)";
+  NCCLCHK(ctx, api, api->AllGather(static_cast<char*>(out) + slot.off, out, slot.n, ncclUint8, c->nccl, ctx->stream));
   return JXLH_OK;
 }
 
 jxlh_status jxlh_frames_allgather_output_local(jxlh_ctx* const peers[], int32_t n, const jxlh_output_desc* d,
                                                void* const outs[], size_t bytes_per_row) {
   if (!peers || !outs || !d || n < 1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_local_peers(peers, n, true)) return st;
   for (int i = 0; i < n; i++)
-    if (!peers[i] || !outs[i] || !peers[i]->comm || peers[i]->comm->nccl || peers[i]->comm->nranks != n || !peers[i]->in_frame)
-      return JXLH_ERR_BAD_STATE;
+    if (!outs[i]) return JXLH_ERR_BAD_STATE;
   // every rank converts its band into its own image buffer ...
+  std::vector<ShardPlan> sp(n);
   for (int i = 0; i < n; i++) {
     jxlh_ctx* c = peers[i];
     HIPCHK(c, hipSetDevice(c->device));
-    const FrameDev& f = c->fd;
-    if (bytes_per_row < (size_t)f.xsize * d->channels * (d->bits / 8)) return JXLH_ERR_INVALID_ARGUMENT;
-    set_band_result(c);
-    int r0, r1;
-    band_of(f.ygroups, n, i, &r0, &r1);
-    if (jxlh_status st = convert_band_to_output(c, d, (uint32_t)std::min(r0 * kGroupDim, f.ysize),
-                                                (uint32_t)std::min(r1 * kGroupDim, f.ysize), outs[i], bytes_per_row))
+    if (bytes_per_row < (size_t)c->fd.xsize * d->channels * (d->bits / 8)) return JXLH_ERR_INVALID_ARGUMENT;
+    sp[i] = shard_plan(c, false, bytes_per_row);
+    set_band_result(c, sp[i]);
+    if (jxlh_status st = convert_band_to_output(c, d, (uint32_t)sp[i].band.y0, (uint32_t)sp[i].band.y1, outs[i], bytes_per_row))
       return st;
     HIPCHK(c, hipEventRecord(c->comm->done_ev, c->stream));
   }
@@ -445,16 +423,10 @@ jxlh_status jxlh_frames_allgather_output_local(jxlh_ctx* const peers[], int32_t 
   for (int i = 0; i < n; i++) {
     jxlh_ctx* dst = peers[i];
     HIPCHK(dst, hipSetDevice(dst->device));
-    const FrameDev& f = dst->fd;
-    for (int k = 0; k < n; k++) {
-      if (k == i) continue;
-      int r0, r1;
-      band_of(f.ygroups, n, k, &r0, &r1);
-      const size_t y0 = (size_t)std::min(r0 * kGroupDim, f.ysize), y1 = (size_t)std::min(r1 * kGroupDim, f.ysize);
-      if (y0 >= y1) continue;
-      HIPCHK(dst, hipStreamWaitEvent(dst->stream, peers[k]->comm->done_ev, 0));
-      HIPCHK(dst, hipMemcpyAsync(static_cast<char*>(outs[i]) + y0 * bytes_per_row,
-                                 static_cast<const char*>(outs[k]) + y0 * bytes_per_row, (y1 - y0) * bytes_per_row,
+    for (const ShardPull& pull : sp[i].pulls) {
+      HIPCHK(dst, hipStreamWaitEvent(dst->stream, peers[pull.peer]->comm->done_ev, 0));
+      HIPCHK(dst, hipMemcpyAsync(static_cast<char*>(outs[i]) + pull.image.off,
+                                 static_cast<const char*>(outs[pull.peer]) + pull.image.off, pull.image.n,
                                  hipMemcpyDefault, dst->stream));
     }
   }
@@ -476,10 +448,9 @@ jxlh_status jxlh_comm_allgather(jxlh_ctx* ctx, void* buf, size_t bytes_per_rank)
 
 jxlh_status jxlh_comm_allgather_local(jxlh_ctx* const peers[], int32_t n, void* const bufs[], size_t bytes_per_rank) {
   if (!peers || !bufs || n < 1) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_local_peers(peers, n, false)) return st;
   for (int i = 0; i < n; i++)
-    if (!peers[i] || !bufs[i] || !peers[i]->comm || peers[i]->comm->nccl || peers[i]->comm->nranks != n ||
-        peers[i]->comm->rank != i)
-      return JXLH_ERR_BAD_STATE;
+    if (!bufs[i]) return JXLH_ERR_BAD_STATE;
   // every rank's part is final once its stream reaches this point ...
   for (int i = 0; i < n; i++) {
     HIPCHK(peers[i], hipSetDevice(peers[i]->device));
@@ -503,39 +474,32 @@ jxlh_status jxlh_comm_allgather_local(jxlh_ctx* const peers[], int32_t n, void* 
 // ---- local transport -----------------------------------------------------------------------------------------
 jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
   if (!peers || n < 1) return JXLH_ERR_INVALID_ARGUMENT;
-  for (int i = 0; i < n; i++)
-    if (!peers[i] || !peers[i]->comm || peers[i]->comm->nccl || peers[i]->comm->nranks != n || peers[i]->comm->rank != i)
-      return JXLH_ERR_BAD_STATE;
+  if (jxlh_status st = check_local_peers(peers, n, false)) return st;
   std::vector<RunPlan> plan(n);
+  std::vector<ShardPlan> sp(n);
   // phase 1: every rank's transforms
   for (int i = 0; i < n; i++) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (int k = 0; k < n; k++)  // the previous frame's gather may still be reading this rank's band
       if (k != i) HIPCHK(ctx, peers[k]->comm->gathered_ev.wait(ctx->stream));
-    if (jxlh_status st = shard_k1(ctx, &plan[i])) return st;
+    if (jxlh_status st = shard_k1(ctx, &plan[i], &sp[i])) return st;
     HIPCHK(ctx, hipEventRecord(ctx->comm->k1_ev, ctx->stream));
   }
+  for (int i = 0; i < n; i++)
+    for (int e = 0; e < sp[i].n_edges; e++)
+      if (!same_layout(sp[i], sp[sp[i].edge[e].peer])) return JXLH_ERR_BAD_STATE;  // the peers decode the same frame
   // phase 2: every rank pulls the edge block rows it reads across its band edges from the neighbours ...
   for (int i = 0; i < n; i++) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const FrameDev& f = ctx->fd;
-    if (plan[i].group_row0 < plan[i].group_row1 && plan[i].exchange) {
-      for (int side = 0; side < 2; side++) {
-        const int nb = side == 0 ? i - 1 : i + 1;
-        if (nb < 0 || nb >= n || plan[nb].group_row0 >= plan[nb].group_row1) continue;
-        jxlh_ctx* src = peers[nb];
-        if (src->fd.tiled != f.tiled || src->fd.xblocks != f.xblocks || src->fd.plane_stride != f.plane_stride)
-          return JXLH_ERR_BAD_STATE;  // the peers decode the same frame
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->comm->k1_ev, 0));
-        const int by = side == 0 ? plan[i].group_row0 * kGroupBlocks - 1 : plan[i].group_row1 * kGroupBlocks;
-        size_t off, cnt;
-        block_row_span(f, by, &off, &cnt);
-        for (int ch = 0; ch < 3; ch++)
-          HIPCHK(ctx, hipMemcpyAsync(f.planes[ch] + off, src->fd.planes[ch] + off, cnt * sizeof(float), hipMemcpyDefault,
-                                     ctx->stream));
-      }
+    for (int e = 0; e < sp[i].n_edges; e++) {
+      const ShardEdge& g = sp[i].edge[e];
+      jxlh_ctx* src = peers[g.peer];
+      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->comm->k1_ev, 0));
+      for (int ch = 0; ch < 3; ch++)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->fd.planes[ch] + g.recv.off, src->fd.planes[ch] + g.recv.off, g.recv.n * sizeof(float),
+                                   hipMemcpyDefault, ctx->stream));
     }
     HIPCHK(ctx, hipEventRecord(ctx->comm->pulled_ev, ctx->stream));
   }
@@ -544,7 +508,7 @@ jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
   for (int i = 0; i < n; i++) {
     jxlh_ctx* ctx = peers[i];
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (plan[i].group_row0 >= plan[i].group_row1) continue;
+    if (sp[i].band.empty()) continue;
     if (i > 0) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, peers[i - 1]->comm->pulled_ev, 0));
     if (i + 1 < n) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, peers[i + 1]->comm->pulled_ev, 0));
     if (jxlh_status st = run_stages_rows(ctx, plan[i].stages, plan[i].y_lo, plan[i].y_hi, plan[i].whole)) return st;
@@ -559,27 +523,18 @@ jxlh_status jxlh_frames_run_sharded_local(jxlh_ctx* const peers[], int32_t n) {
 
 jxlh_status jxlh_frames_allgather_local(jxlh_ctx* const peers[], int32_t n) {
   if (!peers || n < 1) return JXLH_ERR_INVALID_ARGUMENT;
-  for (int i = 0; i < n; i++)
-    if (!peers[i] || !peers[i]->comm || peers[i]->comm->nccl || peers[i]->comm->nranks != n || !peers[i]->in_frame)
-      return JXLH_ERR_BAD_STATE;
-  const int which = stage_list(peers[0]).result_in_tmp();  // a property of the stage list, identical on every peer
+  if (jxlh_status st = check_local_peers(peers, n, true)) return st;
   for (int i = 0; i < n; i++) {
     jxlh_ctx* dst = peers[i];
     HIPCHK(dst, hipSetDevice(dst->device));
-    const FrameDev& f = dst->fd;
-    set_band_result(dst);
-    for (int k = 0; k < n; k++) {
-      if (k == i) continue;
-      jxlh_ctx* src = peers[k];
-      int r0, r1;
-      band_of(f.ygroups, n, k, &r0, &r1);
-      if (r0 >= r1) continue;
+    const ShardPlan sp = shard_plan(dst, false);
+    set_band_result(dst, sp);
+    for (const ShardPull& pull : sp.pulls) {
+      jxlh_ctx* src = peers[pull.peer];
       HIPCHK(dst, hipStreamWaitEvent(dst->stream, src->comm->done_ev, 0));
-      const size_t off = (size_t)r0 * kGroupDim * f.plane_stride;
-      const size_t rows = (size_t)std::min(r1 * kGroupDim, f.ysize) - (size_t)r0 * kGroupDim;
-      for (int c = 0; c < 3; c++) {
-        const float* s = (which ? src->fd.tmp[c] : src->fd.planes[c]) + off;
-        HIPCHK(dst, hipMemcpyAsync(dst->frame.result[c] + off, s, rows * f.plane_stride * sizeof(float), hipMemcpyDefault,
+      for (int c = 0; c < 3; c++) {  // (the plane set is a property of the stage list, identical on every peer)
+        const float* s = (sp.result_in_tmp ? src->fd.tmp[c] : src->fd.planes[c]) + pull.planes.off;
+        HIPCHK(dst, hipMemcpyAsync(dst->frame.result[c] + pull.planes.off, s, pull.planes.n * sizeof(float), hipMemcpyDefault,
                                    dst->stream));
       }
     }

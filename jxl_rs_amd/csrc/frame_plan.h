@@ -10,14 +10,12 @@
 #include <cstdint>
 
 #include "../../include/jxl_hip.h"
+#include "shard_plan.h"  // rows_per_rank: the bands of a sharded frame
 
 namespace jxlh {
 
 constexpr uint32_t kPlanGroupDim = 256;               // pixels per group side (kGroupDim)
 constexpr size_t kPlanGroupCoeffs = 3 * 256 * 256;    // coefficients of a group, three channels (3 * kGroupArea)
-
-// contiguous bands of a sharded frame: ceil(ygroups / nranks) group rows per rank (comm.hip: band_of)
-inline int rows_per_rank(int ygroups, int nranks) { return (ygroups + nranks - 1) / nranks; }
 
 struct FramePlan {
   jxlh_status status = JXLH_ERR_INVALID_ARGUMENT;  // anything but JXLH_OK: nothing below is meaningful

@@ -509,7 +509,6 @@ jxlh_status stage_out(jxlh_ctx* ctx, T* dst, const T* src, size_t n) {
   JXLH_SYNC(ctx);
   return JXLH_OK;
 }
-int comm_rows_per_rank(const jxlh_ctx* ctx, int ygroups);
 
 // The one way interleaved samples leave the device.  `launch(origin, pitch)` writes the pixels of rectangle `r` of an
 // oriented output image whose pixel (0, 0) is at `origin`, rows `pitch` bytes apart; `dst` is where the rectangle's first

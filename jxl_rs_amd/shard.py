@@ -3,8 +3,9 @@
 K1 has no cross-group dependence; the filters need a 4..7 pixel halo.  The library (csrc/comm.hip) runs K1 on
 exactly the rank's band, exchanges one block row per band edge with the neighbour rank and all-gathers the
 finished planes (`jxlh_frame_run_sharded`, `jxlh_frame_allgather`); `jxlh_frame_run(row0, row1)` is the
-stand-alone form that recomputes a halo group row instead.  The helpers here mirror the library's partition for
-host code that distributes coefficient groups to ranks and for the CPU tests."""
+stand-alone form that recomputes a halo group row instead.  The helpers here mirror the library's partition
+(csrc/shard_plan.h: `shard_band`, `rows_per_rank`; tests/test_shard_plan_cpu.py holds them to it) for host code that
+distributes coefficient groups to ranks and for the CPU tests."""
 
 
 def band_for_rank(ygroups, rank, world):
@@ -16,7 +17,8 @@ def band_for_rank(ygroups, rank, world):
 
 
 def band_pixel_rows(row0, row1, ysize, group_dim=256):
-    return row0 * group_dim, min(row1 * group_dim, ysize)
+    """[y0, y1) pixel rows of group rows [row0, row1); an empty trailing band is (ysize, ysize), as in the library."""
+    return min(row0 * group_dim, ysize), min(row1 * group_dim, ysize)
 
 
 def assemble(gathered, ygroups, world, ysize, group_dim=256):

@@ -363,6 +363,84 @@ def test_local_sharded_output_gather(oracle, n, bits, channels):
             c.close()
 
 
+def test_local_short_last_band_then_an_empty_one(oracle):
+    """five group rows on four ranks: bands of 2, 2, 1 and 0 group rows, the last non-empty one shorter than the others
+    (and ending in the middle of a group) with an empty band behind it -- both forms of the gather"""
+    import jxl_rs_amd
+    from jxl_rs_amd import lib, synth
+    from jxl_rs_amd.lib import DeviceArray
+    n = 4
+    wl = synth.make_vardct(264, 1100, mix=synth.MIX_ALL, epf_iters=2)
+    assert wl.ygroups == 5
+    want, _ = run_oracle_frame(oracle, wl)
+    xp = _xyb_params(oracle)
+    want_rgb = oracle.xyb_to_rgb8(xp, want, wl.xsize, wl.ysize, 3)
+    bpr = wl.xsize * 3
+    ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(n)]
+    bufs = [DeviceArray(nbytes=n * 2 * 256 * bpr, device=0) for _ in range(n)]
+    try:
+        lib.comm_init_local(ctxs)
+        for r, c in enumerate(ctxs):
+            upload_band(c, wl, band_groups(wl, r, n))
+        assert [c.comm_band()[2:] for c in ctxs] == [(0, 2), (2, 4), (4, 5), (5, 5)]
+        lib.frames_run_sharded_local(ctxs)
+        lib.frames_allgather_local(ctxs)
+        for r, c in enumerate(ctxs):
+            c.sync()
+            got = c.read_planes()
+            for ch in range(3):
+                assert bit_equal(got[ch], want[ch]), f"rank {r} plane {ch}: {diff_report(got[ch], want[ch])}"
+        lib.frames_run_sharded_local(ctxs)
+        lib.frames_allgather_output_local(ctxs, jxl_rs_amd.Context.output_desc(xyb_params=xp), [b.ptr for b in bufs], bpr)
+        for r, c in enumerate(ctxs):
+            c.sync()
+            got = bufs[r].download(np.uint8, wl.ysize * bpr)
+            assert np.array_equal(got.reshape(want_rgb.shape), want_rgb), f"rank {r}: converted image"
+    finally:
+        for b in bufs:
+            b.free()
+        for c in ctxs:
+            c.close()
+
+
+def test_local_gathers_refuse_a_permuted_peer_list(oracle):
+    """the in-process calls take peers[i] for rank i: a list in another order is refused on the host, before anything
+    is enqueued, and the contexts go on working"""
+    import jxl_rs_amd
+    from jxl_rs_amd import lib, synth, JxlHipError
+    from jxl_rs_amd.lib import DeviceArray
+    wl = synth.make_vardct(300, 600, mix=synth.MIX_D1, seed=11, epf_iters=2)
+    want, _ = run_oracle_frame(oracle, wl)
+    bpr = wl.xsize * 3
+    ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(2)]
+    bufs = [DeviceArray(nbytes=2 * 2 * 256 * bpr, device=0) for _ in range(2)]
+    try:
+        lib.comm_init_local(ctxs)
+        for r, c in enumerate(ctxs):
+            upload_band(c, wl, band_groups(wl, r, 2))
+        lib.frames_run_sharded_local(ctxs)
+        swapped = ctxs[::-1]
+        with pytest.raises(JxlHipError) as e:
+            lib.frames_allgather_local(swapped)
+        assert e.value.status == lib.ERR_BAD_STATE
+        with pytest.raises(JxlHipError) as e:
+            lib.frames_allgather_output_local(swapped, jxl_rs_amd.Context.output_desc(xyb_params=_xyb_params(oracle)),
+                                              [b.ptr for b in bufs[::-1]], bpr)
+        assert e.value.status == lib.ERR_BAD_STATE
+        lib.frames_run_sharded_local(ctxs)
+        lib.frames_allgather_local(ctxs)
+        for r, c in enumerate(ctxs):
+            c.sync()
+            got = c.read_planes()
+            for ch in range(3):
+                assert bit_equal(got[ch], want[ch]), f"rank {r} plane {ch}: {diff_report(got[ch], want[ch])}"
+    finally:
+        for b in bufs:
+            b.free()
+        for c in ctxs:
+            c.close()
+
+
 def test_rccl_output_gather_single_rank(oracle):
     """the same through the library's RCCL communicator (one rank: what a 1-GPU box can run)"""
     import jxl_rs_amd
