@@ -310,6 +310,23 @@ pub fn extra_channel_changed_rects(w: u32, h: u32, ec_upsampling: u32, res_w: u3
     Ok(out)
 }
 
+/// `jxlh_blend_image_rects` (host code, no context): rects of a `frame_w` x `frame_h` result -- what `changed_rects`,
+/// `repaint_changed_rects` and `extra_channel_changed_rects` return -- as rects of the image `desc` composes the frame
+/// onto: shifted by the frame's origin, clipped to the image, empty ones dropped.  The list `VarDctFrame::blend_rects`
+/// and, after it, `VarDctFrame::save_rects` take.
+pub fn blend_image_rects(desc: &sys::jxlh_blend_desc, frame_w: u32, frame_h: u32,
+                         rects: &[sys::save_rects::jxlh_rect]) -> Result<Vec<sys::save_rects::jxlh_rect>> {
+    let mut n = 0u32;
+    let mut out = vec![sys::save_rects::jxlh_rect { x0: 0, y0: 0, w: 0, h: 0 }; rects.len()];
+    // SAFETY: `out` holds one entry per input rect, and the call never writes more than came in
+    check(std::ptr::null(), unsafe {
+        sys::blend_rects::jxlh_blend_image_rects(desc, frame_w, frame_h, rects.as_ptr(), rects.len() as u32, out.as_mut_ptr(),
+                                                 out.len() as u32, &mut n)
+    })?;
+    out.truncate(n as usize);
+    Ok(out)
+}
+
 /// A VarDCT frame on the device.  Call order = the reference's frame flow.
 pub struct VarDctFrame<'a> {
     ctx: &'a Context,
@@ -442,6 +459,20 @@ impl<'a> VarDctFrame<'a> {
     pub fn blend(&self, desc: &sys::jxlh_blend_desc, colour: Option<&sys::jxlh_output_desc>) -> Result<()> {
         let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
         self.ctx.ok(unsafe { sys::jxlh_frame_blend(self.ctx.raw, desc, colour) })?;
+        self.out_size.set((desc.image_w, desc.image_h));
+        Ok(())
+    }
+    /// After a re-render of a frame `blend` has composed: only the listed rectangles of the IMAGE (`blend_image_rects`)
+    /// are composed again, in the canvas `blend` left (`jxlh_frame_blend_rects`); the image is the frame's result again.
+    /// Same descriptor and colour stage as the `blend`.  The caller's contract: every image pixel an input of which
+    /// changed since the canvas was last written lies in a rect -- a pixel left out keeps its old value.
+    pub fn blend_rects(&self, desc: &sys::jxlh_blend_desc, colour: Option<&sys::jxlh_output_desc>,
+                       rects: &[sys::save_rects::jxlh_rect]) -> Result<()> {
+        let colour = colour.map_or(std::ptr::null(), |c| c as *const sys::jxlh_output_desc);
+        // SAFETY: `rects` is a live slice of rects.len() entries; the call reads it before it returns
+        self.ctx.ok(unsafe {
+            sys::blend_rects::jxlh_frame_blend_rects(self.ctx.raw, desc, colour, rects.as_ptr(), rects.len() as u32)
+        })?;
         self.out_size.set((desc.image_w, desc.image_h));
         Ok(())
     }

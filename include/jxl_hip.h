@@ -981,7 +981,10 @@ jxlh_status jxlh_stage_save(jxlh_ctx* ctx, const jxlh_output_desc* colour, const
  * and jxlh_extra_channel_changed_rects (jxlh_ec_rect, JXLH_MAX_EC_RECTS), declared in jxl_hip_extra_rects.h, likewise.
  * Repaint -- the re-render of listed groups on every kind of unsharded frame, upsampled and Modular frames included, and
  * the rectangles of the result it can change: jxlh_frame_repaint_groups and jxlh_repaint_changed_rects, declared in
- * jxl_hip_repaint.h, likewise. */
+ * jxl_hip_repaint.h, likewise.
+ * Blend rectangles -- after such a re-render of a blended frame, the recomposition of only the changed rectangles of the
+ * canvas jxlh_frame_blend wrote, and the mapping of a frame's changed rects to the image: jxlh_frame_blend_rects,
+ * jxlh_stage_blend_rects and jxlh_blend_image_rects, declared in jxl_hip_blend_rects.h, likewise. */
 
 /* ---------------------------------------------------------------- LF frames
  * A frame with lf_level = L >= 1 (the layers of a progressive_dc file) is an ordinary frame of ceil(size / 8^L) pixels,
@@ -1308,5 +1311,6 @@ int32_t jxlh_quant_table_size(int32_t table);
 #include "jxl_hip_preview_tiles.h"
 #include "jxl_hip_extra_rects.h"
 #include "jxl_hip_repaint.h"
+#include "jxl_hip_blend_rects.h"
 
 #endif /* JXL_HIP_H_ */

@@ -162,6 +162,20 @@ inline std::vector<jxlh_rect> extra_channel_changed_rects(uint32_t w, uint32_t h
   return out;
 }
 
+// rects of a frame_w x frame_h result (what the three *_changed_rects functions return) as rects of the image `desc`
+// composes the frame onto: shifted by the frame's origin, clipped to the image, empty ones dropped
+// (jxlh_blend_image_rects): host only.  The list VarDctFrame::blend_rects and, after it, save_rects take
+inline std::vector<jxlh_rect> blend_image_rects(const jxlh_blend_desc& desc, uint32_t frame_w, uint32_t frame_h,
+                                                const std::vector<jxlh_rect>& rects) {
+  uint32_t n = 0;
+  std::vector<jxlh_rect> out(rects.size());  // never more than came in
+  const jxlh_status st = jxlh_blend_image_rects(&desc, frame_w, frame_h, rects.data(), (uint32_t)rects.size(), out.data(),
+                                                (uint32_t)out.size(), &n);
+  if (st != JXLH_OK) throw Error(st, "jxlh_blend_image_rects", "");
+  out.resize(n);
+  return out;
+}
+
 // what each level of a preview chain runs (JXLH_PREVIEW_*) and whether the final planes depend on it: host only
 struct SqueezePreviewKinds {
   std::vector<uint8_t> kinds, live;
@@ -341,6 +355,14 @@ class VarDctFrame {
     blend_w_ = desc.image_w;
     blend_h_ = desc.image_h;
   }
+  // After a re-render of a frame blend() has composed: only the listed rectangles of the IMAGE (blend_image_rects) are
+  // composed again, in the canvas blend() left; the image is the frame's result again (jxlh_frame_blend_rects).  Same
+  // descriptor and colour stage as the blend(); every pixel an input of which changed must lie in a rect
+  void blend_rects(const jxlh_blend_desc& desc, const std::vector<jxlh_rect>& rects, const jxlh_output_desc* colour = nullptr) {
+    ctx_.check(jxlh_frame_blend_rects(ctx_.raw(), &desc, colour, rects.data(), (uint32_t)rects.size()), "jxlh_frame_blend_rects");
+    blend_w_ = desc.image_w;
+    blend_h_ = desc.image_h;
+  }
   // finalize_lf + SigmaSource::new + transforms + the frame's stage list, for group rows [row0, row1)
   void finalize_and_render(uint32_t group_row0 = 0, uint32_t group_row1 = 0xFFFFFFFFu) {
     blend_w_ = blend_h_ = 0;  // a render discards the composition
@@ -404,6 +426,16 @@ class VarDctFrame {
   std::vector<jxlh_rect> repaint_changed_rects(const std::vector<uint32_t>& groups) const {
     return jxlh::repaint_changed_rects(p_, groups);
   }
+  // the frame's own result, whether or not it has been blended onto an image: what the *_changed_rects speak about
+  uint32_t frame_width() const {
+    const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;
+    return p_.xsize_upsampled ? p_.xsize_upsampled : p_.xsize * n;
+  }
+  uint32_t frame_height() const {
+    const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;
+    return p_.ysize_upsampled ? p_.ysize_upsampled : p_.ysize * n;
+  }
+  bool blended() const { return blend_w_ != 0; }  // the image blend() / blend_rects() composed is the result
   uint32_t out_width() const {
     if (blend_w_) return blend_w_;
     const uint32_t n = p_.upsampling > 1 ? p_.upsampling : 1;

@@ -147,6 +147,20 @@ class GpuFramePipeline {
   void blend_if_listed() {
     if (lp_.has_blend) frame_.blend(lp_.blend, &lp_.blend_colour);
   }
+  // The *_rects forms of the render calls end here.  `changed`: rects of the frame's result a re-render can have changed.
+  // Without a BlendingStage they are what save_rects takes.  With one, only they are composed again, in the canvas the
+  // last blend left (jxlh_frame_blend_rects), and they come back in image coordinates (jxlh_blend_image_rects)
+  std::vector<jxlh_rect> blend_rects_if_listed(const std::vector<jxlh_rect>& changed) {
+    if (!lp_.has_blend) return changed;
+    const std::vector<jxlh_rect> image = blend_image_rects(lp_.blend, frame_.frame_width(), frame_.frame_height(), changed);
+    frame_.blend_rects(lp_.blend, image, &lp_.blend_colour);
+    return image;
+  }
+  // ... and a whole render here: the whole blend, one rect of the whole result
+  std::vector<jxlh_rect> blend_whole_if_listed() {
+    blend_if_listed();
+    return {jxlh_rect{0, 0, frame_.out_width(), frame_.out_height()}};
+  }
   const jxlh_save_desc& save_desc(size_t buffer_index) const {
     if (buffer_index >= lp_.saves.size())
       throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuRenderPipeline::save", "the stage list has no save stage for this buffer");
@@ -189,6 +203,44 @@ class GpuRenderPipeline : public GpuFramePipeline {
   }
   std::vector<jxlh_rect> repaint_changed_rects(const std::vector<uint32_t>& groups) const {
     return frame_.repaint_changed_rects(groups);
+  }
+  // do_render() / repaint() for a progressive repaint that stays rect-sized to the end: they render as their siblings
+  // do, but on a list with a BlendingStage only the changed rects are composed again (jxl_hip_blend_rects.h) instead of
+  // the whole image, and they return the rects to hand to save_rects -- image coordinates with a blend, the changed
+  // rects as they are without one; the first render does the whole blend and returns one rect of the whole result.
+  // also_changed: further rects of the frame's result whose inputs changed since the last render, e.g.
+  // extra_channel_changed_rects() of alpha samples that arrived by rect.
+  std::vector<jxlh_rect> do_render_rects(const std::vector<jxlh_rect>& also_changed = {}) {
+    for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");
+    std::vector<jxlh_rect> out;
+    if (!rerender_.empty() && !dirty_first_) {
+      std::vector<jxlh_rect> changed = frame_.changed_rects(rerender_);  // (refuses what jxlh_frame_rerender_groups refuses)
+      changed.insert(changed.end(), also_changed.begin(), also_changed.end());
+      ctx_.check(jxlh_frame_rerender_groups(ctx_.raw(), rerender_.data(), (uint32_t)rerender_.size()), "jxlh_frame_rerender_groups");
+      out = blend_rects_if_listed(changed);
+    } else {
+      frame_.finalize_and_render();
+      out = blend_whole_if_listed();
+    }
+    dirty_first_ = false;
+    rerender_.clear();
+    return out;
+  }
+  std::vector<jxlh_rect> repaint_rects(const std::vector<jxlh_rect>& also_changed = {}) {
+    for (int s = 0; s < ctx_.n_slots(); s++) ctx_.check(jxlh_slot_wait(ctx_.raw(), s), "jxlh_slot_wait");
+    std::vector<jxlh_rect> out;
+    if (!rerender_.empty() && !dirty_first_) {
+      std::vector<jxlh_rect> changed = frame_.repaint_changed_rects(rerender_);
+      changed.insert(changed.end(), also_changed.begin(), also_changed.end());
+      frame_.repaint_groups(rerender_);
+      out = blend_rects_if_listed(changed);
+    } else {
+      frame_.finalize_and_render();
+      out = blend_whole_if_listed();
+    }
+    dirty_first_ = false;
+    rerender_.clear();
+    return out;
   }
   // A group that must be rendered while its HF has not arrived (force_render with DataStatus::Zero, frame/decode.rs:
   // 744-752): the reference hands the pipeline the LF image upsampled 8x as the group's buffers; here the group is marked
@@ -267,6 +319,15 @@ class GpuModularFramePipeline : public GpuFramePipeline {
   }
   std::vector<jxlh_rect> repaint_changed_rects(const std::vector<uint32_t>& groups) const {
     return frame_.repaint_changed_rects(groups);
+  }
+  // repaint_groups() that stays rect-sized: on a list with a BlendingStage only repaint_changed_rects(groups) are composed
+  // again (jxl_hip_blend_rects.h) and come back in image coordinates, for save_rects; before the first render() -- no
+  // composition to patch -- it is the whole blend and one rect of the image.  Without a blend: the changed rects as they are
+  std::vector<jxlh_rect> repaint_groups_rects(const std::vector<uint32_t>& groups) {
+    const std::vector<jxlh_rect> changed = frame_.repaint_changed_rects(groups);
+    const bool patch = !lp_.has_blend || frame_.blended();
+    frame_.repaint_groups(groups);
+    return patch ? blend_rects_if_listed(changed) : blend_whole_if_listed();
   }
   // 256-row bands [band0, band1) (a list with blending or frame upsampling renders whole)
   void render_band(uint32_t band0, uint32_t band1) {

@@ -1,7 +1,8 @@
 // C ABI of frame blending: BlendingStage + ExtendToImageDimensionsStage (jxl/src/render/stages/blending.rs, extend.rs)
 // behind the frame's colour stage, as frame/render.rs:754-791 chains them.  jxlh_frame_blend composes the current frame's
 // result onto an image-sized canvas that becomes the frame's result; jxlh_stage_blend runs the same kernel (k_blend.hip)
-// on caller planes.
+// on caller planes.  jxlh_frame_blend_rects / jxlh_stage_blend_rects recompose only a list of image rectangles of a
+// canvas that holds a composition already (k_blend_rects.hip, blend_rects_plan.h); jxlh_blend_image_rects is host code.
 #include <algorithm>
 
 #include "blend_device.h"
@@ -61,14 +62,52 @@ bool sides_ok(const jxlh_blend_desc* d, uint32_t w, uint32_t h) {
   return d->image_w <= lim && d->image_h <= lim && w <= lim && h <= lim;
 }
 
-}  // namespace
+// the fields of two descriptors the blend reads (check_desc has passed both), equal: what map_blending and fill_desc
+// take from them
+bool same_composition(const jxlh_blend_desc& p, const jxlh_blend_desc& q) {
+  if (p.x0 != q.x0 || p.y0 != q.y0 || p.image_w != q.image_w || p.image_h != q.image_h || p.num_ec != q.num_ec) return false;
+  for (uint32_t k = 0; k <= p.num_ec; k++) {
+    const jxlh_blending_info& a = k == 0 ? p.color : p.ec[k - 1];
+    const jxlh_blending_info& b = k == 0 ? q.color : q.ec[k - 1];
+    if (a.mode != b.mode || (a.clamp != 0) != (b.clamp != 0) || a.source != b.source) return false;
+    const bool alpha_mode = a.mode == JXLH_BLEND_BLEND || a.mode == JXLH_BLEND_ALPHA_WEIGHTED_ADD;
+    if (alpha_mode && p.num_ec > 0 && a.alpha_channel != b.alpha_channel) return false;
+  }
+  const uint32_t bits = JXLH_EC_ALPHA | JXLH_EC_ALPHA_ASSOCIATED;
+  for (uint32_t i = 0; i < p.num_ec; i++)
+    if ((p.ec_flags[i] & bits) != (q.ec_flags[i] & bits)) return false;
+  return true;
+}
 
-}  // namespace jxlh_host
+// The rect-list tail (blend_rects_plan.h decides, this issues): the work list goes up on the stream from a pinned block
+// of the ring, ONE launch rewrites every rect in a.out.  An empty plan enqueues nothing.
+jxlh_status issue_blend_rects(jxlh_ctx* ctx, int nec, const BlendLaunch& a, const BlendRectsPlan& plan) {
+  if (plan.work.empty()) return JXLH_OK;
+  const uint32_t n = (uint32_t)plan.work.size();
+  if (jxlh_status st = ensure(ctx, ctx->blend_rects_dev, n)) return st;
+  Pinned<BlendRectWork>& host = ctx->blend_rects_host[ctx->blend_rects_next];
+  Fence& copied = ctx->blend_rects_copied[ctx->blend_rects_next];
+  ctx->blend_rects_next = (ctx->blend_rects_next + 1) % jxlh_ctx::kBlendRectsRing;
+  HIPCHK(ctx, copied.sync());  // the block's previous list is on the device
+  copied.clear();
+  if (host.n < n) {
+    HIPCHK(ctx, host.reset());
+    HIPCHK(ctx, host.alloc(n + n / 2));
+  }
+  std::memcpy(host.p, plan.work.data(), n * sizeof(BlendRectWork));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->blend_rects_dev.p, host.p, n * sizeof(BlendRectWork), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, copied.record(ctx->stream));
+  {
+    ScopedKernelTimer t(ctx, "k_blend_rects");
+    launch_blend_rects(ctx->stream, nec, a, ctx->blend_rects_dev.p, n, plan.groups);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return JXLH_OK;
+}
 
-extern "C" {
-
-jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh_output_desc* colour) {
-  JXLH_ON_DEVICE(ctx);
+// jxlh_frame_blend (by_rects false: the whole image) and jxlh_frame_blend_rects (the list, onto the kept composition)
+jxlh_status frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh_output_desc* colour, bool by_rects,
+                        const jxlh_rect* rects, uint32_t n_rects) {
   if (!ctx || !d) return JXLH_ERR_INVALID_ARGUMENT;
   if (comm_nranks(ctx) > 1) return JXLH_ERR_UNSUPPORTED;  // a rank holds only its band
   if (!ctx->in_frame || !ctx->frame.rendered || !ctx->frame.result[0]) return JXLH_ERR_BAD_STATE;
@@ -93,6 +132,22 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
     if (!e.done) return JXLH_ERR_BAD_STATE;
     if (e.out_w != (uint32_t)fw || e.out_h != (uint32_t)fh) return JXLH_ERR_UNSUPPORTED;
   }
+  const size_t ostride = round_up(d->image_w, 64), plane = ostride * d->image_h;
+  BlendRectsPlan plan;
+  if (by_rects) {
+    // the composition the rects are recomposed in: this frame's, of the same geometry, still in the canvas
+    const FrameState& f = ctx->frame;
+    if (!f.blend_kept || !ctx->blend_canvas.p) return JXLH_ERR_BAD_STATE;
+    if (!same_composition(f.blend_kept_desc, *d) || f.blend_kept_mode != a.mode) return JXLH_ERR_INVALID_ARGUMENT;
+    if (a.mode != kModeNone && (std::memcmp(&f.blend_kept_xyb, &a.xyb, sizeof(a.xyb)) != 0 ||
+                                std::memcmp(&f.blend_kept_tf, &a.tf, sizeof(a.tf)) != 0))
+      return JXLH_ERR_INVALID_ARGUMENT;
+    if (f.blend_fw != fw || f.blend_fh != fh || f.blend_nec != nec || ctx->blend_canvas.n < plane * (3 + nec))
+      return JXLH_ERR_BAD_STATE;  // (cannot happen inside one frame: the same descriptor met another result)
+    if (jxlh_status st = check_blend_rects(rects, n_rects, d->image_w, d->image_h)) return st;
+    plan = plan_blend_rects(rects, n_rects, d->image_w, d->image_h);
+    if (plan.status != JXLH_OK) return plan.status;
+  }
   // checked: from here on only the device can fail
   if (!again) materialise_chroma(ctx);
   fill_desc(ctx, d, a);
@@ -107,21 +162,28 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
     a.frame[3 + i] = e.pat_ready ? e.pat.p : e.up > 1 ? e.out.p : e.f32.p;
     a.frame_stride[3 + i] = (uint32_t)e.out_stride;
   }
-  const size_t ostride = round_up(d->image_w, 64), plane = ostride * d->image_h;
-  if (again && ctx->blend_canvas.n < plane * (3 + nec)) {  // the canvas is about to be replaced: un-blend first
-    for (int c = 0; c < 3; c++) ctx->frame.result[c] = fr[c];
-    ctx->res_w = fw;
-    ctx->res_h = fh;
-    ctx->res_stride = fstride;
+  if (!by_rects && ctx->blend_canvas.n < plane * (3 + nec)) {  // the canvas is about to be replaced
+    ctx->frame.blend_kept = false;
+    if (again) {  // un-blend first
+      for (int c = 0; c < 3; c++) ctx->frame.result[c] = fr[c];
+      ctx->res_w = fw;
+      ctx->res_h = fh;
+      ctx->res_stride = fstride;
+    }
   }
-  if (jxlh_status st = ensure(ctx, ctx->blend_canvas, plane * (3 + nec))) return st;
+  if (!by_rects)
+    if (jxlh_status st = ensure(ctx, ctx->blend_canvas, plane * (3 + nec))) return st;
   for (uint32_t c = 0; c < 3 + nec; c++) a.out[c] = ctx->blend_canvas.p + c * plane;
   a.out_stride = (uint32_t)ostride;
-  {
-    ScopedKernelTimer t(ctx, "k_blend");
-    launch_blend(ctx->stream, (int)nec, a);
+  if (by_rects) {
+    if (jxlh_status st = issue_blend_rects(ctx, (int)nec, a, plan)) return st;
+  } else {
+    {
+      ScopedKernelTimer t(ctx, "k_blend");
+      launch_blend(ctx->stream, (int)nec, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
   }
-  HIPCHK(ctx, hipGetLastError());
   for (int c = 0; c < 3; c++) {
     ctx->frame.blend_frame[c] = fr[c];
     ctx->frame.result[c] = a.out[c];
@@ -133,6 +195,42 @@ jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh
   ctx->res_w = (int)d->image_w;
   ctx->res_h = (int)d->image_h;
   ctx->res_stride = ostride;
+  if (!by_rects) {  // the record jxlh_frame_blend_rects asks for
+    ctx->frame.blend_kept = true;
+    ctx->frame.blend_kept_desc = *d;
+    ctx->frame.blend_kept_mode = a.mode;
+    ctx->frame.blend_kept_xyb = a.xyb;
+    ctx->frame.blend_kept_tf = a.tf;
+  }
+  return JXLH_OK;
+}
+
+}  // namespace
+
+}  // namespace jxlh_host
+
+extern "C" {
+
+jxlh_status jxlh_frame_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh_output_desc* colour) {
+  JXLH_ON_DEVICE(ctx);
+  return frame_blend(ctx, d, colour, /*by_rects=*/false, nullptr, 0);
+}
+
+jxlh_status jxlh_frame_blend_rects(jxlh_ctx* ctx, const jxlh_blend_desc* d, const jxlh_output_desc* colour,
+                                   const jxlh_rect* rects, uint32_t n) {
+  JXLH_ON_DEVICE(ctx);
+  return frame_blend(ctx, d, colour, /*by_rects=*/true, rects, n);
+}
+
+// pure host code (blend_rects_plan.h)
+jxlh_status jxlh_blend_image_rects(const jxlh_blend_desc* d, uint32_t frame_w, uint32_t frame_h, const jxlh_rect* frame_rects,
+                                   uint32_t n, jxlh_rect* image_rects, uint32_t cap, uint32_t* n_out) {
+  if (!d || !n_out || (n && !frame_rects) || (cap && !image_rects)) return JXLH_ERR_INVALID_ARGUMENT;
+  std::vector<jxlh_rect> need;
+  map_blend_image_rects(d->x0, d->y0, d->image_w, d->image_h, frame_w, frame_h, frame_rects, n, need);
+  *n_out = (uint32_t)need.size();
+  if (need.size() > cap) return JXLH_ERR_INVALID_ARGUMENT;
+  std::copy(need.begin(), need.end(), image_rects);
   return JXLH_OK;
 }
 
@@ -173,6 +271,58 @@ jxlh_status jxlh_stage_blend(jxlh_ctx* ctx, const jxlh_blend_desc* d, const floa
     if (jxlh_status st = copy2d(ctx, out[c], out_stride * sizeof(float), a.out[c], ostride * sizeof(float),
                                 (size_t)d->image_w * sizeof(float), d->image_h, ctx->stream))
       return st;
+  JXLH_SYNC(ctx);
+  return JXLH_OK;
+}
+
+jxlh_status jxlh_stage_blend_rects(jxlh_ctx* ctx, const jxlh_blend_desc* d, const float* const frame[], uint32_t n_channels,
+                                   uint32_t w, uint32_t h, size_t stride, const jxlh_rect* rects, uint32_t n,
+                                   float* const out[], size_t out_stride) {
+  JXLH_ON_DEVICE(ctx);
+  if (!ctx || !d || !frame || !out || w == 0 || h == 0 || stride < w) return JXLH_ERR_INVALID_ARGUMENT;
+  if (jxlh_status st = check_desc(ctx, d)) return st;
+  if (n_channels != 3 + d->num_ec || out_stride < d->image_w) return JXLH_ERR_INVALID_ARGUMENT;
+  for (uint32_t c = 0; c < n_channels; c++)
+    if (!frame[c] || !out[c]) return JXLH_ERR_INVALID_ARGUMENT;
+  if ((uint64_t)w * h >= (1ull << 31) || !sides_ok(d, w, h)) return JXLH_ERR_UNSUPPORTED;
+  if (jxlh_status st = check_blend_rects(rects, n, d->image_w, d->image_h)) return st;
+  const BlendRectsPlan plan = plan_blend_rects(rects, n, d->image_w, d->image_h);
+  if (plan.status != JXLH_OK) return plan.status;
+  if (plan.work.empty()) return JXLH_OK;  // nothing to rewrite: nothing enqueued
+  // device planes whose rows a lane's 16-byte store can address are rewritten where they are; others are staged whole
+  bool in_place = out_stride % 4 == 0 && out_stride <= 0xffffffffu;
+  for (uint32_t c = 0; c < n_channels; c++)
+    in_place = in_place && reinterpret_cast<uintptr_t>(out[c]) % 16 == 0 && is_device_ptr(out[c]);
+  const size_t fplane = (size_t)w * h;
+  const size_t ostride = round_up(d->image_w, 64), oplane = ostride * d->image_h;
+  if (jxlh_status st = ensure(ctx, ctx->blend_hook_in, fplane * n_channels)) return st;
+  if (!in_place)
+    if (jxlh_status st = ensure(ctx, ctx->blend_hook_out, oplane * n_channels)) return st;
+  BlendLaunch a{};
+  a.mode = kModeNone;
+  fill_desc(ctx, d, a);
+  a.fw = (int)w;
+  a.fh = (int)h;
+  a.out_stride = (uint32_t)(in_place ? out_stride : ostride);
+  for (uint32_t c = 0; c < n_channels; c++) {
+    float* in = ctx->blend_hook_in.p + c * fplane;
+    if (jxlh_status st = copy2d(ctx, in, (size_t)w * sizeof(float), frame[c], stride * sizeof(float),
+                                (size_t)w * sizeof(float), h, ctx->stream))
+      return st;
+    a.frame[c] = in;
+    a.frame_stride[c] = w;
+    a.out[c] = in_place ? out[c] : ctx->blend_hook_out.p + c * oplane;
+    if (!in_place)
+      if (jxlh_status st = copy2d(ctx, a.out[c], ostride * sizeof(float), out[c], out_stride * sizeof(float),
+                                  (size_t)d->image_w * sizeof(float), d->image_h, ctx->stream))
+        return st;
+  }
+  if (jxlh_status st = issue_blend_rects(ctx, (int)d->num_ec, a, plan)) return st;
+  if (!in_place)
+    for (uint32_t c = 0; c < n_channels; c++)
+      if (jxlh_status st = copy2d(ctx, out[c], out_stride * sizeof(float), a.out[c], ostride * sizeof(float),
+                                  (size_t)d->image_w * sizeof(float), d->image_h, ctx->stream))
+        return st;
   JXLH_SYNC(ctx);
   return JXLH_OK;
 }

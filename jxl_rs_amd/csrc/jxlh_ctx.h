@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "blend_rects_plan.h"
 #include "device_owned.h"
 #include "ec_rects_plan.h"
 #include "frame_plan.h"
@@ -96,6 +97,14 @@ struct FrameState {
   float* blend_frame[3] = {nullptr, nullptr, nullptr};
   int blend_fw = 0, blend_fh = 0;
   size_t blend_fstride = 0;
+  // jxlh_frame_blend_rects: the canvas holds a composition of this frame (written by jxlh_frame_blend, patched by
+  // jxlh_frame_blend_rects) made with blend_kept_desc behind the colour stage blend_kept_mode / _xyb / _tf.  A render
+  // points `result` away from the canvas and leaves this record: the stale composition is still in memory
+  bool blend_kept = false;
+  jxlh_blend_desc blend_kept_desc = {};
+  int blend_kept_mode = 0;
+  XybParamsDev blend_kept_xyb = {};
+  TfParamsDev blend_kept_tf = {};
 };
 
 struct jxlh_ctx {
@@ -277,6 +286,14 @@ struct jxlh_ctx {
   // c * res_stride * res_h
   DevBuf<float> blend_canvas;
   DevBuf<float> blend_hook_in, blend_hook_out;  // jxlh_stage_blend staging
+  // jxlh_frame_blend_rects: the work list on the device; it goes up from a ring of pinned blocks, each reused once its
+  // fence (recorded behind the copy) has passed -- the call returns while the copy is queued, and a caller recomposes
+  // again at once: a call waits for the copy of the fourth call before it
+  static constexpr int kBlendRectsRing = 4;
+  DevBuf<BlendRectWork> blend_rects_dev;
+  Pinned<BlendRectWork> blend_rects_host[kBlendRectsRing];
+  Fence blend_rects_copied[kBlendRectsRing];
+  int blend_rects_next = 0;
   DevBuf<float> save_hook_in;                   // jxlh_stage_save staging of host planes (abi_save.hip)
   // strip path (k_strip.hip): block descriptors / tile modes written by k1_scan, the strips' edge-column exchange
   // buffer, progress flags + ticket

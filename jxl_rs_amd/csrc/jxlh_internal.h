@@ -534,6 +534,11 @@ struct BlendLaunch {
   TfParamsDev tf;
 };
 void launch_blend(hipStream_t s, int num_ec, const BlendLaunch& a);
+// k_blend_rects.hip: the same per-pixel work on the n rects of the device-resident work list (blend_rects_plan.h), one
+// launch of `groups` workgroups; only samples inside a rect are stored.  a.out rows must be 16-byte aligned
+struct BlendRectWork;
+void launch_blend_rects(hipStream_t s, int num_ec, const BlendLaunch& a, const BlendRectWork* work, uint32_t n,
+                        uint32_t groups);
 
 // the save tail (k_save.hip): colour stage, spot colours, premultiply, conversion, opaque fill and orientation of source
 // rows [y0, y0 + rows) of w x h planes into the interleaved, oriented image at `out`.  Pipeline channel c = 0..2 is

@@ -103,6 +103,33 @@ def repaint_changed_rects(params, group_ids):
     return rects
 
 
+def try_blend_image_rects(desc, frame_w, frame_h, rects, cap=None):
+    """jxlh_blend_image_rects (host only), returning (status, rects [n, 4] as (x0, y0, w, h) or None, n needed).  rects:
+    rows (x0, y0, w, h) of the frame_w x frame_h result; cap: room offered (None: as many as needed -- asked for first)"""
+    r, n_in = _rect_array(rects)
+    L, n = load(), C.c_uint32(0)
+    src = _addr(r) if n_in else None
+    if cap is None:
+        st = L.jxlh_blend_image_rects(C.byref(desc), int(frame_w), int(frame_h), src, n_in, None, 0, C.byref(n))
+        if st != OK and n.value == 0:
+            return st, None, 0
+        cap = n.value
+    out = np.zeros((max(int(cap), 1), 4), dtype=np.uint32)
+    st = L.jxlh_blend_image_rects(C.byref(desc), int(frame_w), int(frame_h), src, n_in, _addr(out) if cap else None, int(cap),
+                                  C.byref(n))
+    return st, (out[:n.value].copy() if st == OK else None), n.value
+
+
+def blend_image_rects(desc, frame_w, frame_h, rects):
+    """rects of a frame's result (what the *_changed_rects functions return) as rects of the image `desc` composes the
+    frame onto: shifted by the frame's origin, clipped to the image, empty ones dropped -- the list blend_rects and,
+    after it, frame_save_rects take"""
+    st, out, _ = try_blend_image_rects(desc, frame_w, frame_h, rects)
+    if st != OK:
+        raise JxlHipError(st, "jxlh_blend_image_rects")
+    return out
+
+
 def try_extra_channel_changed_rects(w, h, ec_upsampling, res_w, res_h, rects, cap=None):
     """jxlh_extra_channel_changed_rects (host only), returning (status, rects [n, 4] as (x0, y0, w, h) or None, n needed).
     cap: room offered (None: as many as needed -- asked for first, as a C caller would)"""
@@ -1289,6 +1316,40 @@ class Context:
         """jxlh_stage_blend: the 3 + num_ec f32 planes [h, w] blended onto the image; returns the image's planes"""
         st, out = self.try_stage_blend(desc, planes)
         self._chk(st, "stage_blend")
+        return out
+
+    # ---- blend rectangles ----
+    def try_blend_rects(self, desc, rects, colour=None):
+        """jxlh_frame_blend_rects, returning the status.  rects: rows (x0, y0, w, h) of the IMAGE (blend_image_rects)"""
+        r, n = _rect_array(rects)
+        st = self.L.jxlh_frame_blend_rects(self._ctx, C.byref(desc), None if colour is None else C.byref(colour),
+                                           _addr(r) if n else None, n)
+        if st == OK:
+            self._blend_size = (desc.image_w, desc.image_h)
+        return st
+
+    def blend_rects(self, desc, rects, colour=None):
+        """jxlh_frame_blend_rects: after a re-render, only the pixels of `rects` of the composition blend() left are
+        composed again; the image is the frame's result again, as after blend()"""
+        self._chk(self.try_blend_rects(desc, rects, colour), "frame_blend_rects")
+
+    def try_stage_blend_rects(self, desc, planes, rects, out, out_stride=None):
+        """jxlh_stage_blend_rects, returning the status.  planes: the 3 + num_ec f32 frame planes [h, w]; out: as many
+        image planes that hold a composition -- float32 arrays [image_h, image_w], rewritten in the rects, or device
+        pointers with out_stride (floats)"""
+        pl = [np.ascontiguousarray(a, dtype=np.float32) for a in planes]
+        h, w = pl[0].shape
+        r, n = _rect_array(rects)
+        if out_stride is None:
+            out_stride = out[0].strides[0] // 4
+        pp = (C.c_void_p * len(pl))(*[a.ctypes.data for a in pl])
+        po = (C.c_void_p * len(out))(*[_addr(a).value for a in out])
+        return self.L.jxlh_stage_blend_rects(self._ctx, C.byref(desc), pp, len(pl), w, h, w, _addr(r) if n else None, n, po,
+                                             int(out_stride))
+
+    def stage_blend_rects(self, desc, planes, rects, out, out_stride=None):
+        """jxlh_stage_blend_rects: the rects of the image planes `out` composed again, in place; returns `out`"""
+        self._chk(self.try_stage_blend_rects(desc, planes, rects, out, out_stride), "stage_blend_rects")
         return out
 
     # ---- the save tail ----

@@ -14,8 +14,17 @@ Each row of the table, one JSON line each:
                process, timed the same number of times: the yardstick
   frame_ms / frame_blend_ms   jxlh_frame_run alone and followed by jxlh_frame_blend, host clock around `steps` calls
 
-  python tools/bench_blend.py [--size 8192] [--steps 20] [--reps 5] [--kernel-only CASE]
---kernel-only CASE (e.g. crop25_ec1): that composition a few times and nothing else, for a profiler run of its own."""
+  python tools/bench_blend.py [--size 8192] [--steps 20] [--reps 5] [--kernel-only CASE] [--rects]
+--kernel-only CASE (e.g. crop25_ec1): that composition a few times and nothing else, for a profiler run of its own.
+--rects: blend rectangles (k_blend_rects.hip, jxlh_frame_blend_rects) instead.  For the full frame and the crop, 0 and 1
+extra channels, three lists recomposed in the canvas a whole blend left:
+  group     the changed rects of one re-rendered group in the middle of the frame (jxlh_changed_rects, mapped by
+            jxlh_blend_image_rects)
+  row       ... of one whole group row
+  image     one image-sized rect: the whole blend's work through the rect kernel
+One JSON line each: k_blend_rects_ms (as k_blend_ms above), the bytes of the rects by the same model, and the two
+yardsticks timed alternately in the same process: k_blend_ms, the whole jxlh_frame_blend that was the only route, and
+k_save_rects_ms, jxlh_frame_save_rects of the same list as RGB8 into device memory."""
 import argparse
 import ctypes as C
 import json
@@ -34,6 +43,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kernel-only")
+    ap.add_argument("--rects", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import jxl_rs_amd
@@ -76,6 +86,50 @@ def main():
         dst.free()
         return ms
 
+    def timed(ctx, label, call):
+        """mean kernel ms of `steps` calls, from the library's event timers"""
+        ctx.kernel_timing_reset()
+        ctx.kernel_timing(True)
+        for _ in range(a.steps):
+            call()
+        ctx.sync()
+        kt = ctx.kernel_times()
+        ctx.kernel_timing(False)
+        return kt[label][0] / kt[label][1]
+
+    def bench_rects(ctx, tag, n, x0, y0, d, nch):
+        wl = frame(n)
+        xg, yg = wl.xgroups, wl.ygroups
+        mid = (yg // 2) * xg + xg // 2
+        whole = np.array([[0, 0, size, size]], dtype=np.uint32)
+        lists = [("group", lib.blend_image_rects(d, n, n, ctx.changed_rects([mid]))),
+                 ("row", lib.blend_image_rects(d, n, n, ctx.changed_rects(list(range((yg // 2) * xg, (yg // 2 + 1) * xg))))),
+                 ("image", whole)]
+        sd = lib.save_desc([0, 1, 2], lib.SAVE_U8)
+        paint = lib.DeviceArray(nbytes=size * size * 3)
+        for name, rects in lists:
+            px = inside = 0
+            for rx, ry, rw, rh in rects.tolist():
+                px += rw * rh
+                inside += max(0, min(rx + rw, x0 + n) - max(rx, x0)) * max(0, min(ry + rh, y0 + n) - max(ry, y0))
+            nbytes = nch * 4 * (3 * inside + 2 * (px - inside))
+            r_ms, b_ms, s_ms = [], [], []
+            ctx.blend_rects(d, rects)
+            ctx.sync()
+            for _ in range(a.reps):  # the rect kernel and its two yardsticks alternate
+                r_ms.append(timed(ctx, "k_blend_rects", lambda: ctx.blend_rects(d, rects)))
+                b_ms.append(timed(ctx, "k_blend", lambda: ctx.blend(d)))
+                s_ms.append(timed(ctx, "k_save_rects", lambda: ctx.frame_save_rects_async(sd, rects, out=paint, bytes_per_row=size * 3)))
+            rm = statistics.median(r_ms)
+            print(json.dumps({
+                "case": f"{tag}_{name}", "image": f"{size}x{size}", "frame": f"{n}x{n} at ({x0}, {y0})", "channels": nch,
+                "rects": len(rects), "pixels": px, "bytes": nbytes, "k_blend_rects_ms": rm,
+                "k_blend_rects_ms_min_max": [min(r_ms), max(r_ms)], "TBps": nbytes / rm * 1e-9,
+                "k_blend_ms": statistics.median(b_ms), "k_blend_ms_min_max": [min(b_ms), max(b_ms)],
+                "k_save_rects_ms": statistics.median(s_ms), "k_save_rects_ms_min_max": [min(s_ms), max(s_ms)],
+            }), flush=True)
+        paint.free()
+
     cases = [("full", size, 0, 0, lib.BLEND_BLEND), ("crop25", half, half // 2 + 1, half // 2 + 3, lib.BLEND_BLEND),
              ("extend", half, half // 2 + 1, half // 2 + 3, lib.BLEND_REPLACE)]
     for num_ec in (0, 1):
@@ -95,6 +149,10 @@ def main():
                 for _ in range(5):
                     ctx.blend(d)
                 ctx.sync()
+                continue
+            if a.rects:
+                if name != "extend":
+                    bench_rects(ctx, tag, n, x0, y0, d, nch)
                 continue
             inside = n * n
             nbytes = nch * 4 * (3 * inside + 2 * (size * size - inside))

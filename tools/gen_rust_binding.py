@@ -26,6 +26,8 @@ EXTRA_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_extra_rects.h")
 OUT_EXTRA_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "extra_rects.rs")
 REPAINT_HEADER = os.path.join(ROOT, "include", "jxl_hip_repaint.h")
 OUT_REPAINT = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "repaint.rs")
+BLEND_RECTS_HEADER = os.path.join(ROOT, "include", "jxl_hip_blend_rects.h")
+OUT_BLEND_RECTS = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "blend_rects.rs")
 # ... and a header that includes jxl_hip.h rather than being included by it
 LOCAL_PALETTE_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_palette.h")
 OUT_LOCAL_PALETTE = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_palette.rs")
@@ -171,6 +173,8 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod extra_rects;")
     w("// include/jxl_hip_repaint.h (... src/repaint.rs)")
     w("pub mod repaint;")
+    w("// include/jxl_hip_blend_rects.h (... src/blend_rects.rs)")
+    w("pub mod blend_rects;")
     w("// include/jxl_hip_local_palette.h (... src/local_palette.rs)")
     w("pub mod local_palette;")
     w("// include/jxl_hip_local_squeeze.h (... src/local_squeeze.rs)")
@@ -235,6 +239,11 @@ def generate_repaint():
     return emit_extension(os.path.basename(REPAINT_HEADER), *parse_header(open(REPAINT_HEADER).read()), uses=("save_rects",))
 
 
+def generate_blend_rects():
+    return emit_extension(os.path.basename(BLEND_RECTS_HEADER), *parse_header(open(BLEND_RECTS_HEADER).read()),
+                          uses=("save_rects",))
+
+
 def generate_local_palette():
     return emit_extension(os.path.basename(LOCAL_PALETTE_HEADER), *parse_header(open(LOCAL_PALETTE_HEADER).read()))
 
@@ -247,7 +256,8 @@ def generate_local_squeeze():
 def main():
     for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
                       (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects()),
-                      (OUT_REPAINT, generate_repaint()), (OUT_LOCAL_PALETTE, generate_local_palette()),
+                      (OUT_REPAINT, generate_repaint()), (OUT_BLEND_RECTS, generate_blend_rects()),
+                      (OUT_LOCAL_PALETTE, generate_local_palette()),
                       (OUT_LOCAL_SQUEEZE, generate_local_squeeze())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
