@@ -163,6 +163,29 @@ impl Context {
                 params.as_ptr(), params.len(), wp.map_or(std::ptr::null(), |w| w.as_ptr()), sample_format, &mut first_bad)
         })
     }
+    /// `jxlh_frame_set_modular_groups_extra`: `set_modular_groups_squeeze` for groups whose channels are the frame's
+    /// colour channels followed by extra channels, or extra channels only (`jxl_hip_local_extra.h`): an RGBA or grey +
+    /// alpha image, the alpha / depth / spot channels of a VarDCT frame.  Every finished channel is stored where the
+    /// frame keeps it -- colour in the sample planes, channel `n_colour + k` in the sample store of extra channel
+    /// `dest.ec[k]`, which must be begun or set -- with the launches of `set_modular_groups_squeeze` and nothing else.
+    /// The named extra channels are not rendered until the next run, rerender or repaint.  With `dest.n_colour == 0`
+    /// pass `sample_format` 0.  The call returns when `arena` may be reused.
+    pub fn set_modular_groups_extra(&self, arena: &[i32], groups: &[sys::local_squeeze::jxlh_local_squeeze_group],
+                                    coded: &[sys::local_squeeze::jxlh_local_coded_channel],
+                                    params: &[sys::local_squeeze::jxlh_squeeze_params], wp: Option<&[sys::jxlh_wp_header]>,
+                                    sample_format: u32, dest: &sys::local_extra::jxlh_local_dest) -> Result<()> {
+        if wp.map_or(false, |w| w.len() != groups.len()) {
+            return Err(HipError::InvalidArgument);
+        }
+        let mut first_bad = usize::MAX;
+        // SAFETY: as for set_modular_groups_squeeze; `dest` is read before the call returns, and the library checks its
+        // channel indices against the frame's extra channels before it stores anything
+        self.ok(unsafe {
+            sys::local_extra::jxlh_frame_set_modular_groups_extra(
+                self.raw, arena.as_ptr(), arena.len() as u64, groups.as_ptr(), groups.len(), coded.as_ptr(), coded.len(),
+                params.as_ptr(), params.len(), wp.map_or(std::ptr::null(), |w| w.as_ptr()), sample_format, dest, &mut first_bad)
+        })
+    }
     /// `jxlh_modular_local_lower_squeeze`: the host-side lowering and checks alone; `Err` carries the first refused group
     pub fn lower_modular_squeeze_groups(groups: &[sys::local_squeeze::jxlh_local_squeeze_group],
                                         coded: &[sys::local_squeeze::jxlh_local_coded_channel],

@@ -1312,5 +1312,8 @@ int32_t jxlh_quant_table_size(int32_t table);
 #include "jxl_hip_extra_rects.h"
 #include "jxl_hip_repaint.h"
 #include "jxl_hip_blend_rects.h"
+/* ... and this one brings jxl_hip_local_squeeze.h and jxl_hip_local_palette.h, whose group form it takes: whichever of the
+ * four a translation unit names first, it gets the whole interface */
+#include "jxl_hip_local_extra.h"
 
 #endif /* JXL_HIP_H_ */

@@ -22,6 +22,7 @@
 #include "jxl_hip.h"
 #include "jxl_hip_local_palette.h"
 #include "jxl_hip_local_squeeze.h"
+#include "jxl_hip_local_extra.h"
 
 namespace jxlh {
 
@@ -292,6 +293,21 @@ class VarDctFrame {
                      : jxlh_frame_set_modular_groups_squeeze(ctx_.raw(), arena, arena_samples, groups, n, coded, n_coded, params,
                                                              n_params, wp, sample_format, &bad),
                "jxlh_frame_set_modular_groups_squeeze");
+  }
+  // ... and for groups that hold extra channels behind (or instead of) the colour (jxl_hip_local_extra.h): RGBA, grey +
+  // alpha, the alpha / depth / spot channels of a VarDCT frame.  Every finished channel goes where the frame keeps it;
+  // the named extra channels are "not rendered" until the next run, rerender or repaint.  dest is read before the call
+  // returns.
+  void set_modular_groups_extra(const int32_t* arena, uint64_t arena_samples, const jxlh_local_squeeze_group* groups, size_t n,
+                                const jxlh_local_coded_channel* coded, size_t n_coded, const jxlh_squeeze_params* params,
+                                size_t n_params, const jxlh_wp_header* wp, uint32_t sample_format, const jxlh_local_dest& dest,
+                                bool async = false) {
+    size_t bad = 0;
+    ctx_.check(async ? jxlh_frame_set_modular_groups_extra_async(ctx_.raw(), arena, arena_samples, groups, n, coded, n_coded, params,
+                                                                 n_params, wp, sample_format, &dest, &bad)
+                     : jxlh_frame_set_modular_groups_extra(ctx_.raw(), arena, arena_samples, groups, n, coded, n_coded, params,
+                                                           n_params, wp, sample_format, &dest, &bad),
+               "jxlh_frame_set_modular_groups_extra");
   }
   // An extra channel that arrives group by group (jxl_hip_extra_rects.h): declared once per frame, all zero ...
   void begin_extra_channel(uint32_t ec, uint32_t w, uint32_t h, uint32_t bits_per_sample, uint32_t ec_upsampling) {

@@ -6,10 +6,12 @@
  * jxl_hip.h refuse exactly what they refused.  tools/gen_py_binding.py and tools/gen_rust_binding.py read this header as
  * they read jxl_hip.h (LOCAL_PALETTE_SYMBOLS in jxl_rs_amd/_abi.py, bindings/rust/jxl_hip_sys/src/local_palette.rs).
  */
+/* (in front of the guard: jxl_hip.h ends by including jxl_hip_local_extra.h, which needs this header's declarations --
+ * when this header is the first one a translation unit names, they are made on that way in, and skipped below) */
+#include "jxl_hip.h"
+
 #ifndef JXL_HIP_LOCAL_PALETTE_H_
 #define JXL_HIP_LOCAL_PALETTE_H_
-
-#include "jxl_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -7,10 +7,11 @@
  * did.  tools/gen_py_binding.py and tools/gen_rust_binding.py read this header as they read jxl_hip.h
  * (LOCAL_SQUEEZE_SYMBOLS in jxl_rs_amd/_abi.py, bindings/rust/jxl_hip_sys/src/local_squeeze.rs).
  */
+/* (in front of the guard, for the reason jxl_hip_local_palette.h gives) */
+#include "jxl_hip_local_palette.h"
+
 #ifndef JXL_HIP_LOCAL_SQUEEZE_H_
 #define JXL_HIP_LOCAL_SQUEEZE_H_
-
-#include "jxl_hip_local_palette.h"
 
 #ifdef __cplusplus
 extern "C" {

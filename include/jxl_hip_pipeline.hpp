@@ -124,6 +124,18 @@ class GpuFramePipeline {
   void set_extra_channel_rects_async(const int32_t* samples, uint64_t n_samples, const std::vector<jxlh_ec_rect>& rects) {
     frame_.set_extra_channel_rects_async(samples, n_samples, rects);
   }
+  // ... or many groups of extra channels AS DECODED, each with its local transform list (jxl_hip_local_extra.h, the
+  // n_colour == 0 form): the channels dest.ec names share one size, the groups' rects are in that resolution, and the
+  // finished samples land in the channels' sample stores without a plane in between.  VarDCT and Modular lists alike.
+  void set_extra_groups(const int32_t* arena, uint64_t arena_samples, const LocalSqueezeGroups& batch, const jxlh_local_dest& dest,
+                        bool async = false) {
+    if (dest.n_colour != 0)
+      throw Error(JXLH_ERR_INVALID_ARGUMENT, "GpuFramePipeline::set_extra_groups", "colour channels go through GpuModularFramePipeline::set_groups");
+    batch.check("GpuFramePipeline::set_extra_groups");
+    frame_.set_modular_groups_extra(arena, arena_samples, batch.groups.data(), batch.groups.size(), batch.coded.data(),
+                                    batch.coded.size(), batch.params.data(), batch.params.size(),
+                                    batch.wp.empty() ? nullptr : batch.wp.data(), 0u, dest, async);
+  }
   // The rectangles of finished extra channel `ec` (w x h source samples) that new samples in `rects` can change
   // (jxlh_extra_channel_changed_rects): what save_rects repaints, with changed_rects(), after the do_render() of a pass
   std::vector<jxlh_rect> extra_channel_changed_rects(uint32_t ec, uint32_t w, uint32_t h, const std::vector<jxlh_rect>& rects) const {
@@ -304,6 +316,17 @@ class GpuModularFramePipeline : public GpuFramePipeline {
     frame_.set_modular_groups_squeeze(arena, arena_samples, batch.groups.data(), batch.groups.size(), batch.coded.data(),
                                       batch.coded.size(), batch.params.data(), batch.params.size(),
                                       batch.wp.empty() ? nullptr : batch.wp.data(), lp_.modular_sample_format, async);
+  }
+  // ... into the colour planes AND extra channels (jxlh_frame_set_modular_groups_extra): the groups' leading
+  // dest.n_colour channels are the frame's colour, the others the extra channels dest.ec names (begun or set before).
+  // dest.n_colour == 0 is GpuFramePipeline::set_extra_groups
+  void set_groups(const int32_t* arena, uint64_t arena_samples, const LocalSqueezeGroups& batch, const jxlh_local_dest& dest,
+                  bool async = false) {
+    batch.check("GpuModularFramePipeline::set_groups");
+    frame_.set_modular_groups_extra(arena, arena_samples, batch.groups.data(), batch.groups.size(), batch.coded.data(),
+                                    batch.coded.size(), batch.params.data(), batch.params.size(),
+                                    batch.wp.empty() ? nullptr : batch.wp.data(), dest.n_colour ? lp_.modular_sample_format : 0u,
+                                    dest, async);
   }
   // the whole frame, then the list's blending
   void render() {

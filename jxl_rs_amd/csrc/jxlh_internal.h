@@ -414,13 +414,21 @@ struct LocalLaunch {
   uint32_t fan_grey;  // 1: a group of one channel writes it to planes 0..2
   size_t out_stride;  // samples
   int bit_depth;
+  // mixed (jxl_hip_local_extra.h): plane c's rows are slot_stride[c] samples apart and a grey slot 0 (fan_grey: every
+  // group of the launch) also goes to fan[0..1], planes of slot 0's stride; otherwise all planes share out_stride
+  uint32_t mixed;
+  size_t slot_stride[4];
+  int32_t* fan[2];
 };
 void launch_modular_local(hipStream_t s, const LocalLaunch& a);
 struct LpLaunch {
   const int32_t* arena;
   int32_t* scratch;
   int32_t* out[4];
-  size_t out_stride;  // samples
+  size_t out_stride;  // samples: slot 0's plane, and every plane's unless mixed
+  size_t slot_stride[4];  // plane c's rows (always filled)
+  int32_t* fan[2];        // where a phase descriptor's `fan` sends slot 0 besides out[0]: planes of out_stride
+  uint32_t mixed;         // point-wise launch: the planes' strides differ
   int bit_depth;
   const LpJobDev* jobs;       // palette launch: items are (job, output channel)
   const LpPhaseDev* phases;   // point-wise launch: items are (phase descriptor, first row)
@@ -435,7 +443,7 @@ struct LsLaunch {
   const int32_t* arena;
   int32_t* scratch;
   int32_t* out[4];
-  size_t out_stride;  // samples
+  size_t slot_stride[4];  // samples: plane c's rows
   const LsChainDev* chains;
   const LocalItem* items;  // LDS launch: (chain, 0); streamed launch: (chain, first line)
   uint32_t n_items;

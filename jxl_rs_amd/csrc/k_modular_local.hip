@@ -22,6 +22,10 @@
 namespace jxlh {
 namespace {
 
+//  * kMixed (jxl_hip_local_extra.h): the slots' planes have strides of their own -- a frame's colour planes beside extra
+//    channels' sample stores -- and a grey slot 0 fans out to a.fan, not to the planes of slots 1 and 2.  An
+//    instantiation of its own: the other keeps one row offset for all planes.
+template <bool kMixed>
 __global__ __launch_bounds__(256) void k_modular_local(const LocalLaunch a) {
   __shared__ int32_t s_pal[kLocalLdsEntries];
   const LocalItem item = a.items[blockIdx.x];
@@ -74,6 +78,23 @@ __global__ __launch_bounds__(256) void k_modular_local(const LocalLaunch a) {
           apply_palette(s, op, arena + op.pal_off, a.bit_depth);
         }
       }
+      if constexpr (kMixed) {
+        const size_t gy = (size_t)g.y0 + y, gx = (size_t)g.x0 + x;
+        auto put_at = [&](int32_t* plane, size_t stride, int4 v) {
+          int32_t* p = plane + gy * stride + gx;
+          if (full) gstore_i4<true>(p, v);
+          else store_some(p, v, cnt);
+        };
+        if (g.n_channels > 0) put_at(a.out[0], a.slot_stride[0], s.r0);
+        if (g.n_channels > 1) put_at(a.out[1], a.slot_stride[1], s.r1);
+        if (g.n_channels > 2) put_at(a.out[2], a.slot_stride[2], s.r2);
+        if (g.n_channels > 3) put_at(a.out[3], a.slot_stride[3], s.r3);
+        if (a.fan_grey) {
+          put_at(a.fan[0], a.slot_stride[0], s.r0);
+          put_at(a.fan[1], a.slot_stride[0], s.r0);
+        }
+        continue;
+      }
       auto put = [&](uint32_t c, int4 v) {
         if (c >= n_store) return;
         int32_t* p = a.out[c] + dst_row + x;
@@ -92,7 +113,8 @@ __global__ __launch_bounds__(256) void k_modular_local(const LocalLaunch a) {
 
 void launch_modular_local(hipStream_t s, const LocalLaunch& a) {
   if (a.n_items == 0) return;
-  hipLaunchKernelGGL(k_modular_local, dim3(a.n_items), dim3(256), 0, s, a);
+  if (a.mixed) hipLaunchKernelGGL(k_modular_local<true>, dim3(a.n_items), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_modular_local<false>, dim3(a.n_items), dim3(256), 0, s, a);
 }
 
 }  // namespace jxlh

@@ -57,8 +57,8 @@ __device__ __forceinline__ int32_t wg_load(const int32_t* p) {
 }
 
 template <bool WP>
-__device__ __forceinline__ void lp_run(const LpLaunch& a, const LpJobDev& job, const int c, int32_t* out, int32_t* sm,
-                                       int32_t* s_pal) {
+__device__ __forceinline__ void lp_run(const LpLaunch& a, const LpJobDev& job, const int c, int32_t* out,
+                                       const size_t ostride, int32_t* sm, int32_t* s_pal) {
   const int l = (int)threadIdx.x;
   const int w = (int)job.w, h = (int)job.h;
   int32_t(*s_ring)[9] = reinterpret_cast<int32_t(*)[9]>(sm + kOffRing);
@@ -72,7 +72,7 @@ __device__ __forceinline__ void lp_run(const LpLaunch& a, const LpJobDev& job, c
   uint32_t(*s_above_e)[128] = reinterpret_cast<uint32_t(*)[128]>(sm + kOffAboveE);
   uint32_t* s_div = reinterpret_cast<uint32_t*>(sm + kOffDiv);
   const int32_t* __restrict__ index = (job.index.space == kLpArena ? a.arena : a.scratch) + job.index.off;
-  const size_t istride = job.index.stride, ostride = a.out_stride;
+  const size_t istride = job.index.stride;
   const int32_t* __restrict__ pal_g = a.arena + job.pal_off + (size_t)c * job.palette_size;
   const bool lds = job.lds != 0;
   const int ps = (int)job.palette_size, nd = (int)job.num_deltas, bd = a.bit_depth, predictor = (int)job.predictor;
@@ -263,12 +263,17 @@ __global__ __launch_bounds__(kLpRows) void k_modular_local_palette(const LpLaunc
   const uint32_t slot = job.out_slot[c];
   // (a select chain: indexing the kernel argument dynamically would copy it to scratch)
   int32_t* plane = slot == 0 ? a.out[0] : slot == 1 ? a.out[1] : slot == 2 ? a.out[2] : a.out[3];
-  int32_t* out = plane + (size_t)job.y0 * a.out_stride + job.x0;  // no __restrict__: rows are read back
+  // ... and its row stride: a frame plane's and an extra channel's sample store differ (jxl_hip_local_extra.h)
+  const size_t ostride = slot == 0 ? a.slot_stride[0] : slot == 1 ? a.slot_stride[1] : slot == 2 ? a.slot_stride[2] : a.slot_stride[3];
+  int32_t* out = plane + (size_t)job.y0 * ostride + job.x0;  // no __restrict__: rows are read back
   int32_t* s_pal = lp_sm + (a.weighted ? kWpEnd : kDeltaEnd);
-  if (job.predictor == 6) lp_run<true>(a, job, c, out, lp_sm, s_pal);
-  else lp_run<false>(a, job, c, out, lp_sm, s_pal);
+  if (job.predictor == 6) lp_run<true>(a, job, c, out, ostride, lp_sm, s_pal);
+  else lp_run<false>(a, job, c, out, ostride, lp_sm, s_pal);
 }
 
+// kMixed: the slots' planes have strides of their own (slot_stride: colour planes beside extra channels); otherwise all
+// share out_stride and one row offset serves the four
+template <bool kMixed>
 __global__ __launch_bounds__(256) void k_modular_local_phase(const LpLaunch a) {
   const LocalItem item = a.items[blockIdx.x];
   const LpPhaseDev& g = a.phases[item.group];
@@ -278,10 +283,14 @@ __global__ __launch_bounds__(256) void k_modular_local_phase(const LpLaunch a) {
     const uint32_t y = item.row0 + i / nvx, x = (i % nvx) * 4;
     const uint32_t cnt = min(4u, w - x);
     const size_t out_at = (size_t)(g.y0 + y) * a.out_stride + g.x0 + x;
+    auto at = [&](int t) {
+      if constexpr (kMixed) return (size_t)(g.y0 + y) * a.slot_stride[t] + g.x0 + x;
+      else return out_at;
+    };
     auto fetch = [&](int t) {
       const LpPlane& p = g.src[t];
       if (p.space == kLpNone) return make_int4(0, 0, 0, 0);
-      if (p.space == kLpOut) return load_some(a.out[t] + out_at, cnt);
+      if (p.space == kLpOut) return load_some(a.out[t] + at(t), cnt);
       return load_some((p.space == kLpArena ? a.arena : a.scratch) + p.off + (size_t)y * p.stride + x, cnt);
     };
     Slots s;
@@ -296,7 +305,7 @@ __global__ __launch_bounds__(256) void k_modular_local_phase(const LpLaunch a) {
     }
     auto put = [&](int t, int4 v) {
       const LpPlane& p = g.dst[t];
-      if (p.space == kLpOut) store_some(a.out[t] + out_at, v, cnt);
+      if (p.space == kLpOut) store_some(a.out[t] + at(t), v, cnt);
       else if (p.space == kLpScratch) store_some(a.scratch + p.off + (size_t)y * p.stride + x, v, cnt);
     };
     put(0, s.r0);
@@ -304,8 +313,8 @@ __global__ __launch_bounds__(256) void k_modular_local_phase(const LpLaunch a) {
     put(2, s.r2);
     put(3, s.r3);
     if (g.fan) {
-      store_some(a.out[1] + out_at, s.r0, cnt);
-      store_some(a.out[2] + out_at, s.r0, cnt);
+      store_some(a.fan[0] + out_at, s.r0, cnt);  // (planes of slot 0's stride: out_stride)
+      store_some(a.fan[1] + out_at, s.r0, cnt);
     }
   }
 }
@@ -324,7 +333,8 @@ void launch_modular_local_palette(hipStream_t s, const LpLaunch& a) {
 
 void launch_modular_local_phase(hipStream_t s, const LpLaunch& a) {
   if (a.n_items == 0) return;
-  hipLaunchKernelGGL(k_modular_local_phase, dim3(a.n_items), dim3(256), 0, s, a);
+  if (a.mixed) hipLaunchKernelGGL(k_modular_local_phase<true>, dim3(a.n_items), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_modular_local_phase<false>, dim3(a.n_items), dim3(256), 0, s, a);
 }
 
 }  // namespace jxlh

@@ -20,6 +20,10 @@ __device__ __forceinline__ int32_t* ls_plane(const LsLaunch& a, uint32_t slot) {
   // (a select chain: indexing the kernel argument dynamically would copy it to scratch)
   return slot == 0 ? a.out[0] : slot == 1 ? a.out[1] : slot == 2 ? a.out[2] : a.out[3];
 }
+// ... and its row stride: a frame plane's and an extra channel's sample store differ (jxl_hip_local_extra.h)
+__device__ __forceinline__ size_t ls_stride(const LsLaunch& a, uint32_t slot) {
+  return slot == 0 ? a.slot_stride[0] : slot == 1 ? a.slot_stride[1] : slot == 2 ? a.slot_stride[2] : a.slot_stride[3];
+}
 
 // one line: n_out outputs from n_out - n_out / 2 averages and n_out / 2 residuals (hsqueeze_scalar / vsqueeze_scalar,
 // squeeze.rs:389-437, :576-644, with out_prev = in_next_avg = None).  Element i of the line is at p[i * ep].
@@ -144,8 +148,8 @@ __global__ __launch_bounds__(256) void k_modular_local_squeeze_lds(const LsLaunc
     int32_t* __restrict__ out;
     size_t ostride;
     if ((uint32_t)n == C.n_levels) {
-      out = ls_plane(A, C.slot) + (size_t)C.y0 * A.out_stride + C.x0;
-      ostride = A.out_stride;
+      ostride = ls_stride(A, C.slot);
+      out = ls_plane(A, C.slot) + (size_t)C.y0 * ostride + C.x0;
     } else {
       out = A.scratch + C.scratch_off[(n - 1) & 1];
       ostride = (size_t)cw;
@@ -177,8 +181,8 @@ __global__ __launch_bounds__(kLsLines) void k_modular_local_squeeze_level(const 
   int32_t* __restrict__ out;
   size_t ostride;
   if (i + 1 == C.n_levels) {
-    out = ls_plane(A, C.slot) + (size_t)C.y0 * A.out_stride + C.x0;
-    ostride = A.out_stride;
+    ostride = ls_stride(A, C.slot);
+    out = ls_plane(A, C.slot) + (size_t)C.y0 * ostride + C.x0;
   } else {
     out = A.scratch + C.scratch_off[i & 1];
     ostride = L.out_w;

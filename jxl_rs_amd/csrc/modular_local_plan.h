@@ -17,6 +17,90 @@
 
 namespace jxlh {
 
+// ---- a mixed destination (jxl_hip_local_extra.h): the frame's colour planes followed by extra channels' sample stores,
+// or extra channels only.  The plan sees no pointer: a plane is named by what it is, and whoever issues the plan maps
+// the names to addresses.
+enum : uint32_t { kLocalPlaneColour = 0 /* + c, c in 0..2 */, kLocalPlaneExtra = 3 /* + the extra channel's index */ };
+// what such a call meets: the frame and its extra channels
+struct LocalDestState {
+  bool in_frame = false, modular = false, subsampled = false, sharded = false;
+  uint32_t w = 0, h = 0;       // a Modular frame's coded size ...
+  uint32_t plane_stride = 0;   // ... and its sample planes' row stride
+  uint32_t mod_format = 0;     // the sample_format of the frame's earlier group calls; 0: none yet
+  struct Ec {
+    bool set = false;
+    uint32_t w = 0, h = 0;
+  } ec[JXLH_MAX_EXTRA_CHANNELS];
+};
+// The destination as a table: per channel slot of a group, which plane it is and that plane's row stride.  A grey slot
+// 0 (fan) keeps its two further planes, colour planes 1 and 2 of the frame's stride.
+struct LocalDestTable {
+  jxlh_status status = JXLH_OK;
+  const char* why = nullptr;  // a refusal's rule (a literal)
+  uint32_t n_slots = 0;
+  struct Slot {
+    uint32_t plane, stride;
+  } slot[4] = {};
+  bool fan = false;
+  uint32_t w = 0, h = 0;      // the planes' size: rects are checked against it
+  uint32_t bit_depth = 0;     // the palettes'
+  uint32_t n_colour = 0, n_ec = 0;
+  bool mixed() const { return n_colour > 0 && n_ec > 0; }  // planes of two kinds: strides may differ, the fan is apart
+};
+namespace local_plan_detail {
+inline LocalDestTable dest_refused(jxlh_status st, const char* why) {
+  LocalDestTable t;
+  t.status = st, t.why = why;
+  return t;
+}
+}  // namespace local_plan_detail
+// The rules of jxl_hip_local_extra.h that do not depend on a group, in the header's order (checks 2 to 7).
+inline LocalDestTable plan_local_dest(const jxlh_local_dest& d, uint32_t sample_format, const LocalDestState& s) {
+  using local_plan_detail::dest_refused;
+  const jxlh_status INV = JXLH_ERR_INVALID_ARGUMENT, BAD = JXLH_ERR_BAD_STATE, UNS = JXLH_ERR_UNSUPPORTED;
+  if (d.n_colour != 0 && d.n_colour != 1 && d.n_colour != 3) return dest_refused(INV, "n_colour is 0, 1 or 3");
+  if (d.n_ec > JXLH_LOCAL_MAX_CHANNELS || d.n_colour + d.n_ec < 1 || d.n_colour + d.n_ec > JXLH_LOCAL_MAX_CHANNELS)
+    return dest_refused(INV, "n_colour + n_ec is 1..4");
+  for (uint32_t k = 0; k < d.n_ec; k++) {
+    if (d.ec[k] >= JXLH_MAX_EXTRA_CHANNELS) return dest_refused(INV, "an extra channel index out of range");
+    for (uint32_t j = 0; j < k; j++)
+      if (d.ec[j] == d.ec[k]) return dest_refused(INV, "an extra channel named twice");
+  }
+  if (d.n_colour > 0 && d.bit_depth != 0) return dest_refused(INV, "bit_depth with colour channels: the depth is sample_format's");
+  if (d.bit_depth > 31) return dest_refused(INV, "a bit depth above 31");
+  if (d.n_colour == 0 && sample_format != 0) return dest_refused(INV, "a sample_format without colour channels");
+  const bool xyb = (sample_format & JXLH_MODULAR_XYB) != 0;
+  const uint32_t depth = sample_format & ~(uint32_t)JXLH_MODULAR_XYB;
+  if (d.n_colour > 0) {  // the rule of the other frame calls (bit_depth_ok(depth, 31), jxlh_internal.h)
+    const uint32_t bits = depth & 0xffu, eb = depth >> 8;
+    const bool ok = eb == 0 ? bits >= 1 && bits <= 31
+                            : (depth >> 16) == 0 && bits <= 32 && eb >= 2 && eb <= 8 && bits >= eb + 2 && bits - eb - 1 <= 23;
+    if (!(xyb && depth == 0) && !ok) return dest_refused(INV, "a sample_format that names no sample type");
+  }
+  if (!s.in_frame) return dest_refused(BAD, "outside a frame");
+  if (d.n_colour > 0 && !s.modular) return dest_refused(BAD, "colour channels on a VarDCT frame");
+  if (s.sharded) return dest_refused(UNS, "group-local transforms on a sharded context");
+  if (d.n_colour > 0 && s.subsampled) return dest_refused(UNS, "group-local transforms on a chroma-subsampled frame");
+  for (uint32_t k = 0; k < d.n_ec; k++)
+    if (!s.ec[d.ec[k]].set) return dest_refused(BAD, "a named extra channel is not set");
+  LocalDestTable t;
+  t.n_colour = d.n_colour, t.n_ec = d.n_ec;
+  t.w = d.n_colour > 0 ? s.w : s.ec[d.ec[0]].w;
+  t.h = d.n_colour > 0 ? s.h : s.ec[d.ec[0]].h;
+  for (uint32_t k = 0; k < d.n_ec; k++)
+    if (s.ec[d.ec[k]].w != t.w || s.ec[d.ec[k]].h != t.h)
+      return dest_refused(UNS, "a named extra channel of another size than the call's planes");
+  if (d.n_colour > 0 && s.mod_format && s.mod_format != sample_format)
+    return dest_refused(INV, "another sample_format than the frame's earlier groups");
+  t.n_slots = d.n_colour + d.n_ec;
+  for (uint32_t c = 0; c < d.n_colour; c++) t.slot[c] = {kLocalPlaneColour + c, s.plane_stride};
+  for (uint32_t k = 0; k < d.n_ec; k++) t.slot[d.n_colour + k] = {kLocalPlaneExtra + d.ec[k], t.w};  // a store's rows are w apart
+  t.fan = d.n_colour == 1;
+  // the palettes' bit depth is the samples' (a palette on 32-bit float samples is refused: no bit depth of 1..31)
+  t.bit_depth = d.n_colour > 0 ? (depth & 0xffu) : d.bit_depth;
+  return t;
+}
+
 // ---- what a call brings: "group gi of this call" in one form.  The plain and _general calls bring `groups`; the
 // _squeeze calls bring `sgroups` and the call-wide tables `coded` / `params`.  No sample pointer: what the vector path
 // needs of them is plan_local_batch's `aligned`.
@@ -35,6 +119,10 @@ struct LocalBatchIn {
   // the destination: n_out planes of w x h; frame: the frame's sample planes, 3 or 1 (fanned out) channels per group
   uint32_t n_out = 0, w = 0, h = 0;
   bool frame = false;
+  // ... or a table (jxl_hip_local_extra.h): slot c of every group is dest->slot[c]; n_out, w, h and frame are unused.
+  // plane_aligned[c]: slot c's plane starts 16-byte aligned, fan_aligned: so do the two planes a grey slot 0 fans out to
+  const LocalDestTable* dest = nullptr;
+  bool plane_aligned[4] = {false, false, false, false}, fan_aligned = false;
   bool has_groups() const { return form == kSqueeze ? sgroups != nullptr : groups != nullptr; }
 };
 
@@ -401,7 +489,8 @@ inline void lay_out(const LocalBatchIn& in, LocalPlan& plan) {
   L.lds_items = section(sb.lds_items.size(), sizeof(LocalItem));
   for (int k = 0; k < kLsLevels; k++) L.level_items[k] = section(sb.level_items[k].size(), sizeof(LocalItem));
   L.total = at;
-  if (!plan.items.empty()) step(LocalKernel::kLocal, L.groups, L.items, plan.items.size())->fan_grey = in.frame ? 1 : 0;
+  if (!plan.items.empty())
+    step(LocalKernel::kLocal, L.groups, L.items, plan.items.size())->fan_grey = in.dest ? (in.dest->fan ? 1 : 0) : in.frame ? 1 : 0;
   // every chain up to its destination rect, ahead of the phases that read it there
   if (!sb.lds_items.empty()) step(LocalKernel::kSqueezeLds, L.chains, L.lds_items, sb.lds_items.size());
   for (int k = 0; k < kLsLevels; k++)
@@ -420,9 +509,17 @@ inline void lay_out(const LocalBatchIn& in, LocalPlan& plan) {
 // launch; so does an accepted one whose groups are all empty (steps.empty()).
 // Per group, in this order: the lowering's refusals; the channel count against the destination; the rect against the
 // planes; the width cap of predicted palettes; the item cap.
+// A table destination (in.dest, accepted by plan_local_dest): `aligned` speaks of the arena alone, and alignment is a
+// per-plane fact -- a plane allows the 16-byte path when it starts 16-byte aligned and its stride is a multiple of 4
+// samples; a group takes that path when every plane it writes allows it (a group writes all of the table's planes).
 inline LocalPlan plan_local_batch(const LocalBatchIn& in, bool aligned) {
   using namespace local_plan_detail;
-  if (in.n > 0x7fffffffu || in.w > 0x7fffffffu || in.h > 0x7fffffffu) return refused(JXLH_ERR_INVALID_ARGUMENT, 0, nullptr);
+  const uint32_t dest_w = in.dest ? in.dest->w : in.w, dest_h = in.dest ? in.dest->h : in.h;
+  if (in.n > 0x7fffffffu || dest_w > 0x7fffffffu || dest_h > 0x7fffffffu) return refused(JXLH_ERR_INVALID_ARGUMENT, 0, nullptr);
+  if (in.dest) {
+    for (uint32_t c = 0; c < in.dest->n_slots; c++) aligned = aligned && in.plane_aligned[c] && (in.dest->slot[c].stride & 3) == 0;
+    if (in.dest->fan) aligned = aligned && in.fan_aligned;
+  }
   LocalPlan plan;
   plan.groups.assign(in.n, LocalGroupDev{});
   for (size_t gi = 0; gi < in.n; gi++) {
@@ -451,13 +548,17 @@ inline LocalPlan plan_local_batch(const LocalBatchIn& in, bool aligned) {
           return refused(st, gi, why);
     }
     const jxlh_local_group& g = sg ? as_general : in.groups[gi];
-    if (in.frame ? (g.n_channels != 3 && g.n_channels != 1) : g.n_channels > in.n_out)
+    if (in.dest) {
+      if (g.n_channels != in.dest->n_slots)
+        return refused(JXLH_ERR_INVALID_ARGUMENT, gi, "the group's channels are not the destination's n_colour + n_ec");
+    } else if (in.frame ? (g.n_channels != 3 && g.n_channels != 1) : g.n_channels > in.n_out) {
       return refused(JXLH_ERR_INVALID_ARGUMENT, gi, in.frame ? "a frame's groups hold 3 channels, or 1 (grey)" : "more channels than out planes");
-    if ((uint64_t)g.x0 + g.w > in.w || (uint64_t)g.y0 + g.h > in.h)
+    }
+    if ((uint64_t)g.x0 + g.w > dest_w || (uint64_t)g.y0 + g.h > dest_h)
       return refused(JXLH_ERR_INVALID_ARGUMENT, gi, "the rect leaves the planes");
     if (route == LocalRoute::kPhases && g.w > (1u << 30))
       return refused(JXLH_ERR_INVALID_ARGUMENT, gi, "a predicted palette on a group wider than 2^30");
-    const bool fan = in.frame && g.n_channels == 1, empty = g.w == 0 || g.h == 0;
+    const bool fan = in.dest ? in.dest->fan : in.frame && g.n_channels == 1, empty = g.w == 0 || g.h == 0;
     // an empty group is checked, never planned (the plain route still writes its descriptor: no item names it)
     if (route == LocalRoute::kPlain) plan_plain_group(g, prog, aligned, gi, plan);
     else if (empty) continue;

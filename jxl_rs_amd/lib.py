@@ -387,6 +387,17 @@ def modular_local_lower_squeeze(batch, bit_depth, arena_samples, wp=None, n=None
     return st, progs, (None if bad.value == 2 ** 64 - 1 else bad.value)
 
 
+def local_dest(n_colour, ec=(), bit_depth=0, n_ec=None):
+    """jxlh_local_dest: the leading n_colour (0, 1 or 3) channels of every group are the frame's colour channels, channel
+    n_colour + k is extra channel ec[k]; bit_depth: the palettes', without colour only"""
+    d = LocalDest()
+    ec = [int(e) for e in ec]
+    d.n_colour, d.n_ec, d.bit_depth = int(n_colour), len(ec) if n_ec is None else int(n_ec), int(bit_depth)
+    for k, e in enumerate(ec[:4]):
+        d.ec[k] = e
+    return d
+
+
 class JxlHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -944,6 +955,33 @@ class Context:
         fn = self.L.jxlh_frame_set_modular_groups_squeeze if wait else self.L.jxlh_frame_set_modular_groups_squeeze_async
         self._chk(fn(self._ctx, _addr(arena), arena_samples, groups, n, coded, len(coded), params, len(params), wp_headers(wp),
                      sample_format, None), "set_modular_groups_squeeze")
+
+    def try_set_modular_groups_extra(self, arena, batch, sample_format, dest, wp=None, n=None, arena_samples=None, wait=True):
+        """jxlh_frame_set_modular_groups_extra[_async], returning (status, first_bad); first_bad is None unless the
+        refusal names a group"""
+        if not hasattr(self.L, "jxlh_frame_set_modular_groups_extra"):
+            raise JxlHipError(ERR_UNSUPPORTED, "set_modular_groups_extra",
+                              f"{LIB_PATH} predates group-local transforms with extra channels")
+        groups, coded, params = batch
+        n = len(groups) if n is None else n
+        if arena is not None and not _is_pointer(arena):
+            arena = np.ascontiguousarray(arena, dtype=np.int32)
+            arena_samples = arena.size if arena_samples is None else arena_samples
+            if not wait:
+                self._keep["local_arena"] = arena
+        bad = C.c_size_t(2 ** 64 - 1)
+        fn = self.L.jxlh_frame_set_modular_groups_extra if wait else self.L.jxlh_frame_set_modular_groups_extra_async
+        st = fn(self._ctx, None if arena is None else _addr(arena), arena_samples or 0, groups, n, coded, len(coded), params,
+                len(params), wp_headers(wp), sample_format, None if dest is None else C.byref(dest), C.byref(bad))
+        return st, (None if bad.value == 2 ** 64 - 1 else bad.value)
+
+    def set_modular_groups_extra(self, arena, batch, sample_format, dest, wp=None, n=None, arena_samples=None, wait=True):
+        """jxlh_frame_set_modular_groups_extra[_async]: set_modular_groups_squeeze for groups whose channels are the
+        frame's colour channels followed by extra channels, or extra channels only (dest: local_dest(...)).  Every
+        finished channel goes straight where the frame keeps it: colour into the sample planes, the others into the
+        extra channels' sample stores, which are then "not rendered" until the next run, rerender or repaint."""
+        st, _ = self.try_set_modular_groups_extra(arena, batch, sample_format, dest, wp, n, arena_samples, wait)
+        self._chk(st, "set_modular_groups_extra")
 
     def modular_local_transforms_squeeze(self, arena, batch, bit_depth, out, out_w, out_h, out_stride, wp=None, n=None,
                                          arena_samples=None):

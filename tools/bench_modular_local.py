@@ -15,7 +15,7 @@ What the interface offered before, on the same data, same session:
   per_group       1024 x (jxlh_rct on the group's contiguous buffer + one rect call)
 Two contexts alternate between repetitions.
 
-  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general | --squeeze | --host-side]
+  python tools/bench_modular_local.py [--size 8192] [--steps 10] [--reps 5] [--kernel-only] [--general | --squeeze | --rgba | --host-side]
 --kernel-only: a few launches of the rct case and nothing else, for a profiler run of its own.
 
 --general: the group-local palettes with delta entries (jxlh_frame_set_modular_groups_general, k_modular_local_palette.hip)
@@ -41,6 +41,19 @@ device-resident arena; median, min and max over `reps` of the mean of `steps`:
               geometry: the default squeeze without the preview steps) plus one rect intake
               (jxlh_frame_set_modular_channels from device memory); kernels summed over all labels, and the host clock
 With --kernel-only: a few calls of the squeeze case and nothing else.
+
+--rgba: groups with an extra channel (jxlh_frame_set_modular_groups_extra_async, jxl_hip_local_extra.h) on an 8-bit RGBA
+frame of the same size and rects, device-resident arena, extra channel 0 begun at the frame's size.  Cases: rct = every
+rect an RCT on channels 0..2, types cycling, the alpha as coded; palette = every rect a 256-colour palette over all four
+channels.  Per case and route one JSON line, median, min and max over `reps` of the mean of `steps`:
+  direct       the one _async call: kernels_ms from the library's event timers (all labels, listed), call_ms by the host
+               clock (`steps` calls and one synchronise); absent when the library predates the call (JXLH_LIBRARY: A/B runs)
+  three_calls  what the interface offered before: jxlh_modular_local_transforms_squeeze into four caller planes (it
+               waits), jxlh_frame_set_modular_channels of three of them, jxlh_frame_set_extra_channel_rects_async of the
+               fourth; the same two clocks
+  bytes / TBps the route's own traffic over kernels_ms: the coded channels read and four channels written, plus -- three
+               calls -- three channels copied and one scattered, read and written again
+With --kernel-only: a few direct calls of the rct case and nothing else.
 
 --host-side [--only plain|mix16|squeeze]: what a 1024-rect batch costs on the host, one context, event timers off: rct of
 the first table (plain), mix16 of --general, squeeze of --squeeze.  Per case one JSON line, median, min and max over
@@ -70,6 +83,7 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--general", action="store_true")
     ap.add_argument("--squeeze", action="store_true")
+    ap.add_argument("--rgba", action="store_true")
     ap.add_argument("--host-side", action="store_true")
     ap.add_argument("--only", choices=["plain", "mix16", "squeeze"])
     a = ap.parse_args()
@@ -79,6 +93,8 @@ def main():
         return general(a)
     if a.squeeze:
         return squeeze(a)
+    if a.rgba:
+        return rgba(a)
     import numpy as np
     import jxl_rs_amd
     from jxl_rs_amd import lib
@@ -165,6 +181,87 @@ def main():
         print(json.dumps({"case": "per_group", "call_ms": h_ms, "call_ms_min_max": h_mm}), flush=True)
         for d in planes + bufs:
             d.free()
+    for c in ctxs:
+        c.close()
+
+
+def rgba(a):
+    import numpy as np
+    import jxl_rs_amd
+    from jxl_rs_amd import lib
+    n, g = a.size, 256
+    rng = np.random.default_rng(4)
+    chan = [rng.integers(0, 64, size=(g, g)).astype(np.int32) for _ in range(4)]
+    index = rng.integers(0, 256, size=(g, g)).astype(np.int32)
+    table = rng.integers(0, 256, size=(4, 256)).astype(np.int32)
+    cells = [(x, y) for y in range(0, n, g) for x in range(0, n, g)]
+    have_direct = hasattr(lib.load(), "jxlh_frame_set_modular_groups_extra_async")
+    ctxs = [jxl_rs_amd.Context(0, 1) for _ in range(2)]
+    p = ctxs[0].default_params(n, n)
+    p.gab, p.epf_iters = 0, 0
+    for c in ctxs:
+        c.modular_frame_begin(p)
+        c.begin_extra_channel(0, n, n, 8, 1)
+    outs = [lib.DeviceArray(nbytes=n * n * 4) for _ in range(4)]
+    descs = np.zeros(len(cells), dtype=lib.EC_RECT_DTYPE)
+    for d, (x, y) in zip(descs, cells):
+        d["ec"], d["x0"], d["y0"], d["w"], d["h"], d["offset"], d["stride"] = 0, x, y, g, g, y * n + x, n
+
+    def timed(c, call, steps):
+        c.kernel_timing_reset()
+        c.kernel_timing(True)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            call(c)
+        c.sync()
+        host = (time.perf_counter() - t0) * 1e3 / steps
+        kt = {k: (ms / steps, cnt // steps) for k, (ms, cnt) in c.kernel_times().items() if cnt}
+        c.kernel_timing(False)
+        return host, sum(ms for ms, _ in kt.values()), kt
+
+    def measure(call):
+        for c in ctxs:
+            call(c)
+            c.sync()
+        rows = [timed(ctxs[r % 2], call, a.steps) for r in range(a.reps)]
+        h, k = [r[0] for r in rows], [r[1] for r in rows]
+        labels = {name: [round(statistics.median(r[2][name][0] for r in rows), 4), rows[0][2][name][1]] for name in rows[0][2]}
+        return statistics.median(h), [min(h), max(h)], statistics.median(k), [min(k), max(k)], labels
+
+    for kind in ("rct", "palette"):
+        pal = kind == "palette"
+        sp = [{"x0": x, "y0": y, "w": g, "h": g, "n_channels": 4, "squeeze": None,
+               "steps": [lib.local_palette(0, 4, table)] if pal else [lib.local_rct(0, k % 42)],
+               "coded": [index] if pal else chan} for k, (x, y) in enumerate(cells)]
+        arena, batch = lib.pack_local_squeeze_groups(sp)
+        dev = lib.DeviceArray(arena)
+        dest = lib.local_dest(3, [0]) if have_direct else None
+        direct = lambda c: c.set_modular_groups_extra(dev, batch, 8, dest, n=len(sp), arena_samples=arena.size, wait=False)
+
+        def three(c):
+            c.modular_local_transforms_squeeze(dev, batch, 8, outs, n, n, n, n=len(sp), arena_samples=arena.size)
+            c.set_modular_channels(outs[0].ptr, outs[1].ptr, outs[2].ptr, 8, w=n, h=n, stride=n)
+            c.set_extra_channel_rects(descs, block=outs[3], n_samples=n * n, wait=False)
+
+        if a.kernel_only:
+            for _ in range(5):
+                (direct if have_direct else three)(ctxs[0])
+            ctxs[0].sync()
+            dev.free()
+            break
+        samples = (1 if pal else 4) + 4  # per pixel: coded channels read, four written
+        for route, call, per_px in (("direct", direct, samples), ("three_calls", three, samples + 8)):
+            if route == "direct" and not have_direct:
+                continue
+            call_ms, call_mm, k_ms, k_mm, labels = measure(call)
+            nbytes = per_px * 4 * n * n
+            print(json.dumps({"case": kind, "route": route, "library": os.environ.get("JXLH_LIBRARY", "tree"), "frame": f"{n}x{n}",
+                              "rects": len(sp), "bytes": nbytes, "kernels_ms": k_ms, "kernels_ms_min_max": k_mm,
+                              "TBps": nbytes / k_ms * 1e-9, "call_ms": call_ms, "call_ms_min_max": call_mm, "kernels": labels}),
+                  flush=True)
+        dev.free()
+    for o in outs:
+        o.free()
     for c in ctxs:
         c.close()
 

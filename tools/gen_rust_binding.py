@@ -33,6 +33,9 @@ LOCAL_PALETTE_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_palette.h")
 OUT_LOCAL_PALETTE = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_palette.rs")
 LOCAL_SQUEEZE_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_squeeze.h")
 OUT_LOCAL_SQUEEZE = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_squeeze.rs")
+# ... and one that jxl_hip.h includes and that includes those two
+LOCAL_EXTRA_HEADER = os.path.join(ROOT, "include", "jxl_hip_local_extra.h")
+OUT_LOCAL_EXTRA = os.path.join(ROOT, "bindings", "rust", "jxl_hip_sys", "src", "local_extra.rs")
 
 SCALARS = {"uint8_t": "u8", "int8_t": "i8", "uint16_t": "u16", "int16_t": "i16", "uint32_t": "u32", "int32_t": "i32",
            "uint64_t": "u64", "int64_t": "i64", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
@@ -179,6 +182,8 @@ def emit(defines, enums, structs, opaque, funcs):
     w("pub mod local_palette;")
     w("// include/jxl_hip_local_squeeze.h (... src/local_squeeze.rs)")
     w("pub mod local_squeeze;")
+    w("// include/jxl_hip_local_extra.h (... src/local_extra.rs)")
+    w("pub mod local_extra;")
     return "\n".join(out) + "\n"
 
 
@@ -253,12 +258,17 @@ def generate_local_squeeze():
                           uses=("local_palette",))
 
 
+def generate_local_extra():
+    return emit_extension(os.path.basename(LOCAL_EXTRA_HEADER), *parse_header(open(LOCAL_EXTRA_HEADER).read()),
+                          uses=("local_palette", "local_squeeze"))
+
+
 def main():
     for out, text in ((OUT, generate()), (OUT_PREVIEW, generate_preview()), (OUT_SAVE_RECTS, generate_save_rects()),
                       (OUT_PREVIEW_TILES, generate_preview_tiles()), (OUT_EXTRA_RECTS, generate_extra_rects()),
                       (OUT_REPAINT, generate_repaint()), (OUT_BLEND_RECTS, generate_blend_rects()),
                       (OUT_LOCAL_PALETTE, generate_local_palette()),
-                      (OUT_LOCAL_SQUEEZE, generate_local_squeeze())):
+                      (OUT_LOCAL_SQUEEZE, generate_local_squeeze()), (OUT_LOCAL_EXTRA, generate_local_extra())):
         if "--check" in sys.argv:
             cur = open(out).read() if os.path.exists(out) else ""
             if cur != text:
